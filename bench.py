@@ -10,6 +10,12 @@ with the next clip's upload queued beside this clip's steps.
 N > 1: one process per GPU (torch.distributed, RCCL); the clip is ONE job split over the ranks (strong scaling), see
 tiler_amd/distributed.py.  `python bench.py --gpus N` with no launcher around it starts the N ranks itself (torch.distributed.run as a
 child process, before this process touches a GPU) and relays rank 0's line.  Prints one JSON line.
+
+A plain run sets up, warms up, times the --steps steps and prints the line (`value`, `ms_per_step`, and what the timed steps' own counters
+give: stage times, the KNN roofline, the collectives).  Everything that takes GPU or CPU time of its own -- the parity gate, the host-memory
+clips, the measured peaks, the per-stage rooflines, the dense launch, the extra configurations, the CPU baseline -- runs only with --full
+(the --no-*-extra switches then leave out single parts of it).  --dump-outputs DIR writes what the last timed step computed (see
+dump_outputs) before anything else runs.
 """
 import argparse
 import ctypes
@@ -48,6 +54,68 @@ def _traffic_from_profiles(kernel_build):
 
 
 _traffic_from_profiles.extra = {}
+
+
+def synth_clip(out, freeze):
+    """tiler_amd.synth.frame(f, W, H, rng, freeze=freeze) for f = 0 .. F-1 on one PCG64(synth.SEED) stream, written into `out` (int32
+    [F][H][W]): the same draws in the same order and the same pixels (tests/test_bench_clip.py), in int32 with the position terms computed
+    once -- a quarter of the time of calling synth.frame per frame"""
+    from tiler_amd import synth
+    F, H, W = out.shape
+    rng = np.random.Generator(np.random.PCG64(synth.SEED))
+    y, x = np.mgrid[0:H, 0:W].astype(np.int64)
+    xr = (x[:1] * 255 // W).astype(np.int32)
+    yg = (y[:, :1] * 255 // H).astype(np.int32)
+    xb = ((x + y) * 255 // (W + H)).astype(np.int32)
+    still = ((np.arange(W) >> 3) % 3 == 0)[None, :]
+    th, tw = (H + 7) // 8, (W + 7) // 8
+    alpha = np.int32(-16777216)  # 0xFF000000
+    for f in range(F):
+        drift = np.where(still, 0, f).astype(np.int32) if freeze else np.int32(f)
+        rgb = [(xr + 2 * drift) & 255, (yg + drift) & 255, (xb + 3 * drift) & 255]  # (all terms >= 0)
+        noisy = rng.random((th, tw)) < 0.25
+        mask = np.repeat(np.repeat(noisy, 8, axis=0), 8, axis=1)[:H, :W]
+        n = rng.integers(-8, 8 + 1, size=(3, H, W)).astype(np.int32)
+        r, g, b = [np.clip(c + n[i] * mask, 0, 255) for i, c in enumerate(rgb)]
+        rot = (f // 100) % 3
+        if rot == 1:
+            r, g, b = g, b, r
+        elif rot == 2:
+            r, g, b = b, r, g
+        np.bitwise_or((r << 16) | (g << 8) | b, alpha, out=out[f])
+    return out
+
+
+def dump_outputs(enc, path, max_tilemap_items=1 << 18, max_tiles=49152, seed=20261016):
+    """What a caller of Run() reads after the last timed step, as DIR/<name>.npy (float64; the palette-index pixels float32), for comparing
+    two builds output for output: Tiles() as `tiles_header` (UseCount, TmpIndex, MergeIndex, PalIdx_Initial, Flags), `tiles_pal_px` and
+    `tiles_rgb`; `palettes`; `keyframes`; every frame's TileMap as `tilemap` (TileIdx, PalIdx, PredictedX, PredictedY, PSNR, Flags).  Past
+    `max_tiles` tiles / `max_tilemap_items` items a fixed seeded sample of rows is written, its row numbers beside it (`*_rows`); 64 MB at most."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(seed)
+
+    def rows(n, cap):
+        return None if n <= cap else np.sort(rng.choice(n, cap, replace=False))
+    arrays = {}
+    hdr, pal, rgb = enc.Tiles()
+    pick = rows(hdr.shape[0], max_tiles)
+    if pick is not None:
+        hdr, pal, rgb, arrays["tiles_rows"] = hdr[pick], pal[pick], rgb[pick], pick.astype(np.float64)
+    arrays["tiles_header"] = np.stack([hdr[k].astype(np.float64) for k in hdr.dtype.names], axis=1)
+    arrays["tiles_pal_px"] = pal.astype(np.float32)
+    arrays["tiles_rgb"] = rgb.astype(np.float64)
+    arrays["palettes"] = enc.Palettes().astype(np.float64)
+    arrays["keyframes"] = enc.KeyFrames().astype(np.float64)
+    tm = enc.TileMaps().reshape(-1)
+    pick = rows(tm.shape[0], max_tilemap_items)
+    if pick is not None:
+        tm, arrays["tilemap_rows"] = tm[pick], pick.astype(np.float64)
+    arrays["tilemap"] = np.stack([tm[k].astype(np.float64) for k in ("TileIdx", "PalIdx", "PredictedX", "PredictedY", "PSNR", "Flags")], axis=1)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, "outputs of %d bytes" % total
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
 
 
 def _host_threads(visible):
@@ -271,8 +339,13 @@ def parity_gate(enc, frames, nframes, tm_w, tm_h, oracle_so):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the parity gate, host-memory clips, measured peaks, per-stage rooflines, dense launch, extra "
+                         "configurations and CPU baseline (each of them can be left out with its --no-*-extra / --no-cpu-baseline switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=720)
     ap.add_argument("--frames", type=int, default=300)
@@ -292,12 +365,14 @@ def main():
     ap.add_argument("--no-dense-extra", action="store_true",
                     help="skip the dense diagnostic launch of the KNN kernel (under rocprofv3 --stats it would share the kernel's row with the pruned launches)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_spawn_ranks(args.gpus))
 
     import torch
     import torch.distributed as dist
-    from tiler_amd import synth, distributed, stages
+    from tiler_amd import distributed, stages
     from tiler_amd import lib as _lib_fn
     from tiler_amd._lib import check as _check
     from tiler_amd.encoder import TilingEncoder, TEncoderStep
@@ -323,10 +398,7 @@ def main():
     W, H, F = args.width, args.height, args.frames
     # synthetic clip, generated on the host into page-locked memory, then parked in HBM before any timing
     host_frames = torch.empty((F, H, W), dtype=torch.int32, pin_memory=True)
-    rng = np.random.Generator(np.random.PCG64(synth.SEED))
-    hv = host_frames.numpy()
-    for f in range(F):
-        hv[f] = synth.frame(f, W, H, rng, freeze=args.frozen_columns).view(np.int32)
+    hv = synth_clip(host_frames.numpy(), freeze=args.frozen_columns)
     frames = host_frames.cuda()
     torch.cuda.synchronize()
 
@@ -400,6 +472,8 @@ def main():
     for _ in range(args.warmup):
         step()
     dt, knn, stage_ms = timed(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(enc, args.dump_outputs)
 
     c = enc.counts()
     ks = enc.KnnStats()
@@ -478,8 +552,9 @@ def main():
                 if not os.path.exists(oracle_so):
                     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "libtm_oracle.so"])
             gate_box.update(parity_gate(enc, frames, F, c["tm_w"], c["tm_h"], oracle_so))
-    distributed.run_all(enc, F, rank, world, before_reindex=_gate)
-    if rank == 0:
+    if args.full:
+        distributed.run_all(enc, F, rank, world, before_reindex=_gate)
+    if rank == 0 and args.full:
         if args.motion_radius != 0:
             out["parity_gate"] = "not run: the gate checks the KNN-only pipeline of the headline (MotionPredictRadius=0)"
         else:
@@ -489,7 +564,7 @@ def main():
                 print(json.dumps(out), flush=True)
                 print("[bench] PARITY GATE FAILED: %r" % (gate_box,), file=sys.stderr)
                 raise SystemExit(3)
-    if world == 1 and not args.no_h2d_extra:
+    if args.full and world == 1 and not args.no_h2d_extra:
         # SURVEY.md 8(d)'s metric as it is defined, "H2D/D2H included": the same K steps with the clip in page-locked host memory -- every
         # step is handed the clip anew (tm_set_frames_host lends it until that step's Load has returned) and its Load moves 4*W*H*F bytes
         # across PCIe, chunks beside its own kernel -- and with what the reference's consumers read after Run (tilingencoder.pas:486-568:
@@ -548,7 +623,7 @@ def main():
         torch.cuda.synchronize()
         enc.SetFramesDevice(frames)
         del tm_host, hdr_host, pal_host, rgb_host
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         # the peaks measured on this very device: a bare loop of the kernel's MFMA instruction and an HBM stream triad
         tops, gbs = ctypes.c_double(), ctypes.c_double()
         _check(_lib_fn().tm_probe_mfma_i8(0.3, ctypes.byref(tops)))
@@ -558,7 +633,7 @@ def main():
                                          "roofline.frac stays against the 5000 TOP/s vendor figure"}
         out["roofline"]["frac_of_measured_peak"] = achieved / tops.value if tops.value > 0 else None
         out["roofline"]["mfma_pipe_frac_of_measured_peak"] = mfma_tops / tops.value if tops.value > 0 else None
-    if world == 1:
+    if args.full and world == 1:
         # per-stage rooflines: the streaming kernels timed on their own (torch events on the stream the stage seam
         # launches on) on the clip's own data; Dither and the k-means stage from the step's wall time
         def ev_time(fn, reps=5):  # the median of `reps` separately timed calls (a first call's allocations and a stray stall stay out of it)
@@ -645,7 +720,7 @@ def main():
             del rows_k
         sr["knn"] = {k: out["roofline"][k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "launch_ms", "scan")}
         out["stage_rooflines"] = sr
-    if world == 1 and not args.no_dense_extra:
+    if args.full and world == 1 and not args.no_dense_extra:
         # diagnostic, outside the timed region: the same kernel with pruning off = a dense Q x T_distinct distance GEMM (BASELINE config 3)
         os.environ["TM_KNN_NOPRUNE"] = "1"
         for s_ in (TEncoderStep.esLoad, TEncoderStep.esPredictMotion, TEncoderStep.esReduce, TEncoderStep.esPreparePalettes,
@@ -661,7 +736,7 @@ def main():
                                  "launch_ms": kd["kernel_ms"] / max(kd["launches"], 1), "pairs_per_launch": kd["pairs"] / max(kd["launches"], 1),
                                  "pairs_expected": float(kd.get("queries", q_total)) * float(kd["db_rows"]),
                                  "note": "same kernel, pruning disabled (TM_KNN_NOPRUNE=1): every (query, distinct row) pair evaluated; parity-tested in tests/test_gpu_parity.py::test_knn_dense_mode*"}
-    psnr = enc.PSNR() if hasattr(enc, "PSNR") else None
+    psnr = enc.PSNR() if args.full and hasattr(enc, "PSNR") else None
     if psnr:
         out["quality"] = psnr
 
@@ -686,22 +761,20 @@ def main():
             setattr(enc, k, v)
         return r
 
-    if world == 1 and args.motion_radius == 0 and not args.no_motion_extra:
+    if args.full and world == 1 and args.motion_radius == 0 and not args.no_motion_extra:
         r = extra("with_motion_prediction", warm=False, MotionPredictRadius=32)
         r["note"] = "the headline settings plus MotionPredictRadius=32 (PredictMotion + the motion branch of Reconstruct); not part of `value`"
-    if world == 1 and args.motion_radius == 0 and not args.no_defaults_extra:
+    if args.full and world == 1 and args.motion_radius == 0 and not args.no_defaults_extra:
         r = extra("with_extended_palette_usage", FrameTilingExtendedPaletteUsage=True)
         r["tiles_matched_per_sec"] = q_total / (r["stage_ms"]["reconstruct"] * 1e-3) if r["stage_ms"]["reconstruct"] > 0 else None
         r["note"] = "SURVEY.md 8d's second number: k = 64 nearest rows + the tile x palette re-rank, motion prediction excluded"
         r = extra("with_motion_and_extended_palette_usage", MotionPredictRadius=32, FrameTilingExtendedPaletteUsage=True)
         r["note"] = ("the reference's default code paths (motion prediction radius 32 + extended palette usage) at the benchmark's %d palettes; "
                      "the reference's default PaletteCount is 1024 (tilingencoder.pas:3826)" % args.palettes)
-    if world == 1 and args.motion_radius == 0 and not args.no_frozen_extra and not args.frozen_columns:
+    if args.full and world == 1 and args.motion_radius == 0 and not args.no_frozen_extra and not args.frozen_columns:
         # the clip rounds 1-3 were quoted on: the generator plus frozen tile columns (exact inter-frame duplicates, so Reconstruct searches
         # once per DISTINCT frame tile: 3.24 M of 4.32 M)
-        rng2 = np.random.Generator(np.random.PCG64(synth.SEED))
-        for f in range(F):
-            hv[f] = synth.frame(f, W, H, rng2, freeze=True).view(np.int32)
+        synth_clip(hv, freeze=True)
         frames.copy_(host_frames)
         torch.cuda.synchronize()
         enc.SetFramesDevice(frames)
@@ -725,7 +798,7 @@ def main():
                                       "final_tiles_after_reindex": int(enc.counts()["tiles"]),
                                       "note": "the headline step on the generator PLUS this repo's frozen tile columns (tiler_amd.synth.frame(freeze=True)), the clip "
                                               "rounds 1-3 quoted `value` on: device-resident like `value`, not part of it"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(W, H, F, args.palettes, T, int(ks["db_rows"]))
         visible = out["cpu_baseline"]["host_cpus_visible"]
         t32 = min(visible, 32)

@@ -30,7 +30,7 @@ def _bench(args, env=None, launcher=None):
 
 
 def test_two_ranks_on_one_device_equal_the_single_process():
-    small = ["--width", "640", "--height", "360", "--frames", "120", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-motion-extra",
+    small = ["--full", "--width", "640", "--height", "360", "--frames", "120", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-motion-extra",
              "--no-defaults-extra", "--no-dense-extra", "--no-h2d-extra", "--no-frozen-extra", "--no-kmodes-extra", "--frozen-columns"]
     one = _bench(["--gpus", "1"] + small)
     # no launcher around it: `bench.py --gpus 2` starts its two ranks itself, as the driver's command form needs it to
@@ -55,7 +55,7 @@ def test_two_ranks_on_the_literal_clip_and_the_data_parallel_clustering():
     """the same on SURVEY.md 8(d)'s generator as written (the clip `value` is quoted on: no duplicate frame tiles, a tile -> palette clustering
     that runs to its iteration cap), with the clustering replicated (the default: <= 120 collectives per step asked for, ~15 taken) and with
     TM_PP_SHARDED=1 (the data-parallel Lloyd: an int64 all-reduce per iteration) -- both equal the single process"""
-    small = ["--width", "640", "--height", "360", "--frames", "120", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-motion-extra",
+    small = ["--full", "--width", "640", "--height", "360", "--frames", "120", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-motion-extra",
              "--no-defaults-extra", "--no-dense-extra", "--no-h2d-extra", "--no-frozen-extra", "--no-kmodes-extra"]
     one = _bench(["--gpus", "1"] + small)
     assert one["parity_gate"] == "passed"

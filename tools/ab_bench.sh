@@ -1,7 +1,7 @@
 #!/bin/bash
 # runs the headline bench (no extras) for the default build and each named variant; prints value / reconstruct / knn launch ms
 for v in "" "$@"; do
-  out=$(TM_LIB_VARIANT=$v timeout -k 10 300 python bench.py --no-cpu-baseline --no-motion-extra --no-defaults-extra ${AB_ARGS:-} 2>&1 | tail -1)
+  out=$(TM_LIB_VARIANT=$v timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-motion-extra --no-defaults-extra ${AB_ARGS:-} 2>&1 | tail -1)
   python - "$v" "$out" <<'PY'
 import json, sys
 try:

@@ -2,7 +2,7 @@
 # development aid: the headline bench (no extras) once per named variant build (no base run).   bash tools/ab_one.sh v1 v2 ...
 set -o pipefail
 mkdir -p gpurun_out
-ARGS="--steps ${AB_STEPS:-3} --warmup 1 --no-cpu-baseline --no-motion-extra --no-defaults-extra --no-dense-extra --no-h2d-extra --no-kmodes-extra --no-frozen-extra ${AB_ARGS:-}"
+ARGS="--full --steps ${AB_STEPS:-3} --warmup 1 --no-cpu-baseline --no-motion-extra --no-defaults-extra --no-dense-extra --no-h2d-extra --no-kmodes-extra --no-frozen-extra ${AB_ARGS:-}"
 for v in "$@"; do
   if [ $v = base ]; then unset TM_LIB_VARIANT; else export TM_LIB_VARIANT=$v; fi
   TM_KNN_DEBUG=1 timeout -k 10 300 python bench.py $ARGS > gpurun_out/ab_$v.json 2> gpurun_out/ab_$v.err || { tail -5 gpurun_out/ab_$v.err; exit 1; }

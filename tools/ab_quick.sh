@@ -4,7 +4,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 PMC=0; [ "$1" = "--pmc" ] && { PMC=1; shift; }
-ARGS="--steps ${AB_STEPS:-5} --warmup 1 --no-cpu-baseline --no-motion-extra --no-defaults-extra --no-dense-extra --no-h2d-extra --no-kmodes-extra ${AB_ARGS:---no-frozen-extra}"
+ARGS="--full --steps ${AB_STEPS:-5} --warmup 1 --no-cpu-baseline --no-motion-extra --no-defaults-extra --no-dense-extra --no-h2d-extra --no-kmodes-extra ${AB_ARGS:---no-frozen-extra}"
 for rep in 1 2; do
 for v in base "$@"; do
   if [ $v = base ]; then unset TM_LIB_VARIANT; else export TM_LIB_VARIANT=$v; fi
@@ -25,7 +25,7 @@ if [ $PMC = 1 ]; then
   for v in base "$@"; do
     if [ $v = base ]; then unset TM_LIB_VARIANT; else export TM_LIB_VARIANT=$v; fi
     OUT=gpurun_out/pmcq_$v; mkdir -p $OUT
-    B="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-motion-extra --no-defaults-extra --no-dense-extra --no-h2d-extra --no-frozen-extra --no-kmodes-extra"
+    B="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-motion-extra --no-defaults-extra --no-dense-extra --no-h2d-extra --no-frozen-extra --no-kmodes-extra"
     timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "k_knn" --output-format csv -d $OUT/fetch -- $B > $OUT/fetch.json 2> $OUT/fetch.err || { tail -5 $OUT/fetch.err; exit 1; }
     timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --kernel-include-regex "k_knn" --output-format csv -d $OUT/write -- $B > $OUT/write.json 2> $OUT/write.err || { tail -5 $OUT/write.err; exit 1; }
     python3 - $OUT <<'PY'

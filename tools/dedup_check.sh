@@ -6,7 +6,7 @@ timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_encod
 rc=$?
 tail -4 gpurun_out/dedup_tests.log
 [ $rc -ne 0 ] && { grep -n "Error\|error\|assert" gpurun_out/dedup_tests.log | tail -20; exit $rc; }
-ARGS="--steps 5 --warmup 1 --no-cpu-baseline --no-motion-extra --no-defaults-extra --no-dense-extra --no-h2d-extra --no-kmodes-extra"
+ARGS="--full --steps 5 --warmup 1 --no-cpu-baseline --no-motion-extra --no-defaults-extra --no-dense-extra --no-h2d-extra --no-kmodes-extra"
 for rep in 1 2; do
 for v in table sort; do
   unset TM_DEDUP_SORT

@@ -6,7 +6,7 @@ timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fulls
 rc=$?
 tail -5 gpurun_out/knn_tests.log
 [ $rc -ne 0 ] && { grep -n "Error\|error\|assert" gpurun_out/knn_tests.log | tail -20; exit $rc; }
-ARGS="--steps ${AB_STEPS:-5} --warmup 1 --no-cpu-baseline --no-motion-extra --no-defaults-extra --no-dense-extra --no-h2d-extra --no-kmodes-extra ${AB_ARGS:-}"
+ARGS="--full --steps ${AB_STEPS:-5} --warmup 1 --no-cpu-baseline --no-motion-extra --no-defaults-extra --no-dense-extra --no-h2d-extra --no-kmodes-extra ${AB_ARGS:-}"
 for rep in 1 2; do
 for v in v3 "$@"; do
   unset TM_LIB_VARIANT
