@@ -292,7 +292,9 @@ TM_API int tm_stage_features_rgb(const void *tiles, int64_t n, const void *mirro
  * palettes i32 [npal][pal_size]. */
 TM_API int tm_stage_features_pal(const void *pal_px, const void *pal_idx, int64_t n, const void *palettes, int pal_size,
                                  int mode, void *out_i16, void *stream);
-/* A6 as used by DoPalettization (:4126,:4160): double DCT with UseLAB, Round()ed to int32 [n][192]. */
+/* A6 as used by DoPalettization (:4126,:4160): double DCT with UseLAB, Round()ed to int32 [n][192].
+ * mode TM_PVS_WAVELETS: the double path's Haar branch instead (WaveletGS, :2727-2764, depth 2), Round()ed the same way.
+ * (The int16 entry points above reject TM_PVS_WAVELETS, as the reference asserts at :3111.) */
 TM_API int tm_stage_features_cluster(const void *tiles, int64_t n, int mode, void *out_i32, void *stream);
 
 /* FrameTilingExtendedPaletteUsage (:1559-1610).

@@ -689,19 +689,27 @@ static int step_reduce_motion(tm_encoder *e) {
   // The search runs on per-group maxima of the prediction error (a group = one distinct tile content): PSNR is a
   // non-increasing function of the error, so "some member has PSNR <= x" is "the group's largest error exceeds the
   // largest error still predicted at x".  The state kept is the last probe's, as in the reference.
+  // GlobalTilingUseTargetPSNR (1916-1919): no search, one STCGREval probe at GlobalTilingTargetPSNR; the tile count is what it leaves.
   const int64_t per = e->tm_size();
-  DevBuf remap, order, use, kfmask, keep, sel, pos;
-  TM_TRY(remap.alloc((size_t)e->q * 4)); TM_TRY(order.alloc((size_t)e->q * 4)); TM_TRY(use.alloc((size_t)e->q * 4));
-  int64_t ngroups = 0;
-  TM_TRY(run_dedup(e->ftiles.p, e->q, 256, nullptr, remap.p, order.p, use.p, &ngroups, e->stream));
+  DevBuf kfmask, keep, sel, pos;
   std::vector<uint8_t> hk((size_t)e->nframes, 0);
   for (int32_t k : e->kf_start) hk[(size_t)k] = 1;
   TM_TRY(kfmask.alloc(hk.size()));
   TM_HIP(hipMemcpyAsync(kfmask.p, hk.data(), hk.size(), hipMemcpyHostToDevice, e->stream));
   TM_TRY(keep.alloc((size_t)e->q * 4)); TM_TRY(sel.alloc((size_t)e->q * 4)); TM_TRY(pos.alloc((size_t)e->q * 4));
-  const double target = e->s.GlobalTilingTileCount > 0 ? (double)e->s.GlobalTilingTileCount : (double)ngroups;
-  TM_TRY(solve_tile_count(remap.p, ngroups, e->pm_err.p, kfmask.p, (int)per, e->q, target, e->tm_pred.p, keep.p, &e->reduce_threshold,
-                          &e->reduce_probes, e->stream));
+  if (e->s.GlobalTilingUseTargetPSNR) {
+    e->reduce_threshold = e->s.GlobalTilingTargetPSNR;
+    e->reduce_probes = 1;
+    TM_TRY(mark_at_threshold(e->pm_err.p, kfmask.p, (int)per, e->q, e->reduce_threshold, e->tm_pred.p, keep.p, e->stream));
+  } else {
+    DevBuf remap, order, use;
+    TM_TRY(remap.alloc((size_t)e->q * 4)); TM_TRY(order.alloc((size_t)e->q * 4)); TM_TRY(use.alloc((size_t)e->q * 4));
+    int64_t ngroups = 0;
+    TM_TRY(run_dedup(e->ftiles.p, e->q, 256, nullptr, remap.p, order.p, use.p, &ngroups, e->stream));
+    const double target = e->s.GlobalTilingTileCount > 0 ? (double)e->s.GlobalTilingTileCount : (double)ngroups;
+    TM_TRY(solve_tile_count(remap.p, ngroups, e->pm_err.p, kfmask.p, (int)per, e->q, target, e->tm_pred.p, keep.p, &e->reduce_threshold,
+                            &e->reduce_probes, e->stream));
+  }
   progress(e, TM_STEP_REDUCE, 1, 2);
   int64_t nkeep = 0;
   TM_TRY(compact_kept(keep.p, e->q, sel.p, pos.p, &nkeep, e->stream));
@@ -733,6 +741,13 @@ static int step_reduce_motion(tm_encoder *e) {
   return TM_OK;
 }
 
+// the Reduce tile budget without motion prediction, 0 = none.  With GlobalTilingUseTargetPSNR no item has a motion PSNR to exceed the
+// target, so STCGREval predicts nothing and every distinct tile stays (GlobalTilingTileCount plays no part, 1916-1919).
+static int64_t tile_budget(const tm_encoder *e) {
+  if (e->s.GlobalTilingUseTargetPSNR) return 0;
+  return e->s.GlobalTilingTileCount > 0 ? (int64_t)e->s.GlobalTilingTileCount : 0;
+}
+
 static int step_reduce(tm_encoder *e) {
   // Reduce, tilingencoder.pas:1909-1926 = SolveTileCount (4043) + ReindexTiles(True).  After PredictMotion the threshold
   // search of step_reduce_motion runs.  With motion prediction switched off (MotionPredictRadius = 0, the benchmark's headline
@@ -758,7 +773,7 @@ static int step_reduce(tm_encoder *e) {
     // What travels: only the tiles that can be among the first GlobalTilingTileCount of the merged order, chosen on 16-byte keys every
     // process exchanges first (tm_dedup.hip, "Reduce over several processes"; gathering every distinct tile of every process, as the
     // first two rounds did, moved 857 MB on the bench clip).
-    const int64_t budget = e->s.GlobalTilingTileCount > 0 ? (int64_t)e->s.GlobalTilingTileCount : 0;  // 0: no budget, everything stays
+    const int64_t budget = tile_budget(e);  // 0: no budget, everything stays
     DevBuf lkeys, allkeys, in_s, sel, spos, sidx, suse;
     int64_t nsel = lnu, key_off = 0;
     {
@@ -797,7 +812,7 @@ static int step_reduce(tm_encoder *e) {
     int64_t nu = 0;
     TM_TRY(run_dedup(utiles.p, nun, 256, uuse.p, gremap.p, gorder.p, guse2.p, &nu, e->stream));
     progress(e, TM_STEP_REDUCE, 1, 2);
-    const int64_t target = e->s.GlobalTilingTileCount > 0 ? e->s.GlobalTilingTileCount : nu;
+    const int64_t target = tile_budget(e) > 0 ? tile_budget(e) : nu;
     e->t = std::min<int64_t>(nu, target);
     e->pair_keys_n = 0;
   TM_TRY(e->gtiles.alloc((size_t)e->t * 256));
@@ -823,9 +838,9 @@ static int step_reduce(tm_encoder *e) {
   TM_TRY(use.alloc((size_t)e->q * 4));
   int64_t nu = 0;
   // (only the first GlobalTilingTileCount tiles of the order stay: the rows behind them are counted and numbered, not ordered)
-  TM_TRY(run_dedup(e->ftiles.p, e->q, 256, nullptr, remap.p, order.p, use.p, &nu, e->stream, e->s.GlobalTilingTileCount > 0 ? (int64_t)e->s.GlobalTilingTileCount : 0));
+  TM_TRY(run_dedup(e->ftiles.p, e->q, 256, nullptr, remap.p, order.p, use.p, &nu, e->stream, tile_budget(e)));
   progress(e, TM_STEP_REDUCE, 1, 2);
-  int64_t target = e->s.GlobalTilingTileCount > 0 ? e->s.GlobalTilingTileCount : nu;
+  int64_t target = tile_budget(e) > 0 ? tile_budget(e) : nu;
   e->t = std::min<int64_t>(nu, target);
   e->pair_keys_n = 0;
   TM_TRY(e->gtiles.alloc((size_t)e->t * 256));

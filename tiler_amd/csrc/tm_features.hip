@@ -356,6 +356,40 @@ __global__ __launch_bounds__(256) void k_features_cluster_i32(const uint32_t *__
   }
 }
 
+// The same with Mode = pvsWavelets: WaveletGS<Double>(plane, out, 8, 8, 2) per channel (tilingencoder.pas:2727-2764, 3150-3157),
+// i.e. normalised Haar levels on the 8x8, then the top-left 4x4, then the top-left 2x2.  A level maps rows into tempX (low half
+// (a[2x] + a[2x+1]) f, high half (a[2x] - a[2x+1]) f), then the columns of tempX into tempY the same way, and copies the level's
+// square back; entries outside it keep their value.  One wave per tile, one lane per coefficient (v, u), the pairs fetched by
+// cross-lane reads.  Each step is one rounded add / subtract and one rounded multiply, as in the reference (no contraction).
+// f = 1.0 / sqrt(2.0) in double steps = 0.7071067811865475, one ulp below the correctly rounded 1/sqrt(2).
+__global__ __launch_bounds__(256) void k_features_cluster_wavelet_i32(const uint32_t *__restrict__ tiles, int64_t n, const uint8_t *__restrict__ snake,
+                                                                      const float *__restrict__ srgb_lut, int32_t *__restrict__ out) {
+  constexpr double f = 0.7071067811865475;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int u = lane & 7, v = lane >> 3;
+  const int zz = snake[lane];
+  for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < n; t += (int64_t)gridDim.x * 4) {  // (uniform in the wave)
+    const uint32_t col = tiles[t * 64 + lane];
+    float pl[3];
+    rgb_to_lab_det(col & 0xff, (col >> 8) & 0xff, (col >> 16) & 0xff, srgb_lut, pl[0], pl[1], pl[2]);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      double a = (double)pl[c];
+#pragma unroll
+      for (int d = 8; d >= 2; d >>= 1) {
+        const int h = d >> 1;
+        const int xs = u < h ? u : u - h, ys = v < h ? v : v - h;  // (source indices of lanes outside the level stay inside the tile)
+        const double r0 = __shfl(a, (v * 8 + 2 * xs) & 63), r1 = __shfl(a, (v * 8 + 2 * xs + 1) & 63);
+        const double tx = u < h ? __dmul_rn(__dadd_rn(r0, r1), f) : __dmul_rn(__dsub_rn(r0, r1), f);  // tempX[v][u]
+        const double c0 = __shfl(tx, (2 * ys * 8 + u) & 63), c1 = __shfl(tx, ((2 * ys + 1) * 8 + u) & 63);
+        const double ty = v < h ? __dmul_rn(__dadd_rn(c0, c1), f) : __dmul_rn(__dsub_rn(c0, c1), f);  // tempY[v][u]
+        if (u < d && v < d) a = ty;
+      }
+      out[t * 192 + c * 64 + zz] = (int32_t)__double2ll_rn(a);  // Round() (banker's), |a| <= 8 x the plane's largest magnitude
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // PearsonCorrelation (tilingencoder.pas:2201-2228) of consecutive frames' Lab tile means: one thread per frame, the
 // reference's exact sequence (Math.mean sums in double; everything else sequential Single), so the sums are bit
@@ -985,8 +1019,14 @@ int launch_window_dcts(const void *fb, int w, int h, void *out, hipStream_t stre
 int launch_features_cluster(const void *tiles, int64_t n, int mode, void *out, hipStream_t stream) {
   const DeviceTables *tab;
   TM_TRY(get_tables(&tab));
-  TM_CHECK(mode != TM_PVS_WAVELETS && mode >= 0 && mode <= 4, TM_E_INVAL, "bad TPsyVisMode %d", mode);
+  TM_CHECK(mode >= 0 && mode <= 4, TM_E_INVAL, "bad TPsyVisMode %d", mode);
   if (n <= 0) return TM_OK;
+  if (mode == TM_PVS_WAVELETS) {  // the double path has the Haar branch (3150-3157); only the int16 one asserts
+    hipLaunchKernelGGL(k_features_cluster_wavelet_i32, dim3(grid_for(n, 4)), dim3(256), 0, stream, (const uint32_t *)tiles, n, tab->snake, tab->srgb_lut,
+                       (int32_t *)out);
+    TM_HIP(hipGetLastError());
+    return TM_OK;
+  }
   hipLaunchKernelGGL(k_features_cluster_i32, dim3(grid_for(n, 4)), dim3(256), 0, stream, (const uint32_t *)tiles, n,
                      mode_weighted(mode) ? 1 : 0, tab->dct_lut_f64[mode_special(mode)], tab->weights, tab->snake, tab->srgb_lut,
                      (int32_t *)out, tab->dct_cos_f64[mode_special(mode)], knobs().features_plain ? 1 : 0);

@@ -86,6 +86,8 @@ int launch_recon_decide(int tm_w, int per, int pal_from_map, const void *mp_err,
                         const void *px, const void *py, void *pred, hipStream_t stream);
 int solve_tile_count(const void *group, int64_t ngroups, const void *pm_err, const void *frame_is_kf, int per, int64_t q, double target,
                      void *pred, void *keep, double *x_out, int *probes_out, hipStream_t stream);
+// STCGREval's marking at one threshold x (4024-4031): pred / keep of every item, as after the search's last probe
+int mark_at_threshold(const void *pm_err, const void *frame_is_kf, int per, int64_t q, double x, void *pred, void *keep, hipStream_t stream);
 float euclidean_to_psnr(uint32_t e);
 
 // One process per GPU: the collectives a step needs between its kernels, handed in by the host (tm_set_collective).  The calls

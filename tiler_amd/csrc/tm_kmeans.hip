@@ -63,7 +63,8 @@ __device__ __forceinline__ int find_seg(const Seg *__restrict__ segs, int &bx, i
 }
 
 // ---- farthest-first ------------------------------------------------------------------------------------------
-// best key: larger mindist wins, then lower index.  mindist can reach 2^38 (D=192), indices 2^31: two words.
+// best key: larger mindist wins, then lower index.  mindist can reach 2^38 (D=192), indices 2^31: two words.  (Wavelet features,
+// DitheringMode = pvsWavelets, stay far below: |coefficient| <= 8 x the largest Lab plane magnitude, 8 x 331 < 2 650, so mindist < 2^33.)
 struct BestKey { long long dist; long long negidx; };
 struct FfCandOut { long long *dist, *gidx; int32_t *row; };  // where a process writes its candidate (FfCand's fields)
 __device__ __forceinline__ bool better(const BestKey &a, const BestKey &b) {

@@ -623,11 +623,19 @@ int solve_tile_count(const void *group, int64_t ngroups, const void *pm_err, con
     if (y < target) mn = x; else mx = x;
   }
   TM_CHECK(n > 0, TM_E_INVAL, "tile-count search made no probe");
+  TM_TRY(mark_at_threshold(pm_err, frame_is_kf, per, q, last, pred, keep, stream));
+  if (x_out) *x_out = last;
+  if (probes_out) *probes_out = n;
+  return TM_OK;
+}
+
+int mark_at_threshold(const void *pm_err, const void *frame_is_kf, int per, int64_t q, double x, void *pred, void *keep, hipStream_t stream) {
+  // an item stays predicted when its PSNR -- divided by 10 on the first frame of a key frame's group -- exceeds x
+  uint32_t ep = 0, ek = 0;
+  const bool hp = largest_predicted_err(x, 1.0, &ep), hk = largest_predicted_err(x, 10.0, &ek);
   hipLaunchKernelGGL(k_mark_predicted, dim3(gridn(q)), dim3(256), 0, stream, (const uint32_t *)pm_err, (const uint8_t *)frame_is_kf, per, q, ep, ek,
                      hp ? 1 : 0, hk ? 1 : 0, (uint8_t *)pred, (int32_t *)keep);
   TM_HIP(hipGetLastError());
-  if (x_out) *x_out = last;
-  if (probes_out) *probes_out = n;
   return TM_OK;
 }
 

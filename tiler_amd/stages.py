@@ -56,7 +56,8 @@ def features_pal(pal_px, pal_idx, palettes, mode=1):
 
 
 def features_cluster(tiles, mode=4):
-    """ComputeTilePsyVisFeatures as DoPalettization calls it (tilingencoder.pas:4126), Round()ed -> int32 [n][192]"""
+    """ComputeTilePsyVisFeatures as DoPalettization calls it (tilingencoder.pas:4126), Round()ed -> int32 [n][192]; mode 2 =
+    pvsWavelets, the Haar branch of its double path (3150-3157)"""
     n = tiles.shape[0]
     out = torch.empty((n, 192), dtype=torch.int32, device=tiles.device)
     check(lib().tm_stage_features_cluster(_p(tiles), n, mode, _p(out), _stream()))
