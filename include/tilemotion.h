@@ -192,6 +192,21 @@ TM_API int tm_lz_decompress_host(const uint8_t *src, size_t n, uint8_t *dst, siz
  * palettes, one 'FFBBGGRR' line per colour.  Host code (export tooling). */
 TM_API int tm_generate_y4m(tm_encoder *, const char *path, int input);
 TM_API int tm_generate_pngs(tm_encoder *, int input);
+/* The same pictures rendered on the device (Render :3455-3640, Output tab with the constructor's defaults; or the Input tab: input != 0):
+ * frames [first_frame, first_frame+frame_count) as [frame_count][tm_h*8][tm_w*8] uint32 0x00RRGGBB (the format frames are pushed in; the
+ * input render is every pushed frame cropped to tm_w*8 x tm_h*8 with alpha 0).  A predicted item is frame f-1's output at its offset,
+ * clamped to the picture; a range starting inside a key frame's group gives what the whole clip gives.  out: a device pointer on the
+ * encoder's device (out_on_device != 0) or host memory (one DMA when page-locked).  Blocking.  TM_E_INVAL when the output has not been
+ * reconstructed or reloaded, when the source frames are not in memory (input: after ReloadGTM without Load, or frames a sharded Load
+ * did not keep), or when the range is out of bounds. */
+TM_API int tm_render_frames(tm_encoder *, int first_frame, int frame_count, int input, void *out, int out_on_device);
+/* Pixel-domain quality of the decoded output against the source, frames [first_frame, first_frame+frame_count), over tm_w*8 x tm_h*8:
+ * sse [count][3] exact squared errors of R, G, B; psnr [count] = 10 log10(3 W H 255^2 / (SSE_R+SSE_G+SSE_B)), +inf for SSE 0;
+ * ssim_y [count] = mean SSIM of the 8x8 windows on a 4-pixel grid of GenerateY4M's Y plane (c1 = (64*0.01*255)^2, c2 = (64*0.03*255)^2 on
+ * the windows' integer sums); clip_psnr from the range's summed SSE, clip_ssim_y the mean of the frames'.  The render is fused with the
+ * sums: no frame is materialised.  Any pointer may be NULL.  Errors as tm_render_frames (both renders are needed). */
+TM_API int tm_get_frame_quality(tm_encoder *, int first_frame, int frame_count, uint64_t *sse /* [count][3] */, double *psnr /* [count] */,
+                                double *ssim_y /* [count] */, double *clip_psnr, double *clip_ssim_y);
 /* ReloadGTM, :2059 -> LoadStream, :4880-5175: replaces the encoder's tiles (palette indices only), palettes, tile maps and key
  * frames with the file's; the video set with tm_set_video must match the file's header (:5021-5032) or TM_E_INVAL comes back.
  * Afterwards the read-back views and tm_save_gtm work on the loaded state. */
@@ -336,6 +351,16 @@ TM_API int tm_knn_index_last_stats(tm_knn_index *, double *kernel_ms, int *k_byt
  * side, 0..6 each, and whether it was the k-nearest collection: together they name the instantiation of the scan's kernels that ran -- and
  * how often a scan of this process has been repeated with a larger tile-list arena (TM_KNN_ARENA_ENTRIES sets the first size) */
 TM_API int tm_knn_last_plan(int *ht, int *hq, int *topk, int64_t *arena_retries);
+
+/* Render (:3455-3640) of nframes frames from their tile maps, on device pointers: tile_idx / pal_idx i32 [nframes][tm_h*tm_w],
+ * item_flags u8 (bit 0 H mirror, bit 1 V mirror, bit 2 predicted), px / py int8 (PredictedX / PredictedY), pal_px u8 [ntiles][64],
+ * palettes i32 [npal][pal_size] 0x00BBGGRR -> out u32 [nframes][tm_h*8][tm_w*8] 0x00RRGGBB, as tm_render_frames draws them. */
+TM_API int tm_stage_render(const void *tile_idx, const void *pal_idx, const void *item_flags, const void *px, const void *py, int tm_w, int tm_h,
+                           int nframes, const void *pal_px, int64_t ntiles, const void *palettes, int npal, int pal_size, void *out, void *stream);
+/* The sums behind tm_get_frame_quality for two stacks of frames a (source) and b (decoded), u32 0x00RRGGBB [nframes][h][stride_px]
+ * (w, h multiples of 4, at least 8): sse_u64 [nframes][3] (R, G, B), ssim_f64 [nframes], both device pointers. */
+TM_API int tm_stage_frame_quality(const void *a, const void *b, int nframes, int w, int h, int64_t stride_px, void *sse_u64, void *ssim_f64,
+                                  void *stream);
 
 /* A12: Dither (:1873) = PreparePlan (:2268) + DitherTile (:2688) for every tile.  tiles/flags as above,
  * pal_idx i32 [n], palettes i32 [npal][pal_size] -> pal_px u8 [n][64] (canonical orientation). */

@@ -162,4 +162,21 @@ int tm_stage_palettize(const void *feat_i32, const void *use, int64_t n, int npa
   return run_palettize(feat_i32, use, n, npal, max_iter, out_pal_idx, (hipStream_t)stream);
 }
 
+int tm_stage_render(const void *tile_idx, const void *pal_idx, const void *item_flags, const void *px, const void *py, int tm_w, int tm_h,
+                    int nframes, const void *pal_px, int64_t ntiles, const void *palettes, int npal, int pal_size, void *out, void *stream) {
+  knobs_reload();
+  TM_TRY(require_device());
+  TM_CHECK(tile_idx && pal_idx && item_flags && px && py && out && tm_w > 0 && tm_h > 0 && nframes >= 0 && ntiles >= 0 && npal >= 0 && pal_size > 0 &&
+               (pal_px || ntiles == 0) && (palettes || npal == 0), TM_E_INVAL, "render: bad arguments");
+  const RenderMap m{(const int32_t *)tile_idx, (const int32_t *)pal_idx, (const uint8_t *)item_flags, (const uint8_t *)item_flags, 4,
+                    (const int8_t *)px, (const int8_t *)py, (const uint8_t *)pal_px, ntiles, (const int32_t *)palettes, npal, pal_size, tm_w, tm_h};
+  return launch_render_output(m, 0, nframes, out, (hipStream_t)stream);
+}
+
+int tm_stage_frame_quality(const void *a, const void *b, int nframes, int w, int h, int64_t stride_px, void *sse_u64, void *ssim_f64, void *stream) {
+  knobs_reload();
+  TM_TRY(require_device());
+  return launch_quality_frames(a, b, nframes, w, h, stride_px, sse_u64, ssim_f64, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -219,6 +219,7 @@ struct tm_encoder {
   bool coll_stream_ordered = false;  // the callback enqueues on e->stream (tm_set_collective_mode): no drain before, no wait after
   Collectives co;
   bool load_sharded = false;     // Load only filled the frame tiles of this process's frames (and of the frame before them)
+  bool src_tiles = false;        // the frame tiles are the current video's source (Load ran; ReloadGTM clears it): the input render's data
   int load_first = 0, load_count = 0;
   // the native communicator (tm_comm_init): RCCL linked into the library, the collectives queued on the encoder's stream
   int64_t coll_calls[4] = {0, 0, 0, 0}, coll_bytes = 0;  // per kind, and the bytes this process put through them (tm_get_collective_stats)
@@ -587,6 +588,7 @@ static int step_load(tm_encoder *e) {  // Load, tilingencoder.pas:1741-1841 (dec
   } else
   TM_TRY(launch_load(e->frames, e->nframes, e->width, e->height, e->tm_w, e->tm_h, e->ftiles.p, e->fflags.p, e->flab.p, e->stream));
   progress(e, TM_STEP_LOAD, 1, 3);
+  e->src_tiles = true;
   // inter-frame correlation: one GPU thread per frame runs the reference's sequential Single sums (order matters)
   const int per = (int)e->tm_size() * 3;
   DevBuf &dcorrel = e->dcorrel;
@@ -1688,6 +1690,7 @@ int tm_set_video(tm_encoder *e, int width, int height, double fps, int frame_cou
   for (tm_encoder::HostClip &c : e->hclip) { c.buf.release(); c.pending = false; c.host = nullptr; }
   e->hclip_cur = -1;
   e->steps_done = 0;
+  e->src_tiles = false;
   if (e->auto_tile_count) recompute_auto_tile_count(e);
   return TM_OK;
 }
@@ -2140,6 +2143,7 @@ int tm_reload_gtm(tm_encoder *e, const char *path) {  // ReloadGTM, tilingencode
   e->has_pm = true;
   e->has_pal_px = true;
   e->reconstructed = false;  // PSNR is not in the stream
+  e->src_tiles = false;      // (the mirror flags are the stream's now; the source frames need a Load)
   e->gtiles_have_rgb = false;
   e->drop_prefetch();
   // every step's product the stream holds is in place: Save, Reindex and the read-back views work.  Steps that compute from the frame
@@ -2161,6 +2165,91 @@ int tm_generate_pngs(tm_encoder *e, int input) {
 int tm_save_gtm(tm_encoder *e, const char *path) {
   TM_CHECK(e && path, TM_E_INVAL, "null argument");
   return save_to(e, path);
+}
+
+// ---- the decoded frames and their quality on the device (tm_render.hip): the pictures FrameRenderer draws, without the host
+static int render_range_ok(tm_encoder *e, int first, int count) {
+  TM_CHECK(e->nframes > 0 && first >= 0 && count >= 0 && (int64_t)first + count <= e->nframes, TM_E_INVAL, "frame range [%d,+%d) outside 0..%d",
+           first, count, e->nframes);
+  return TM_OK;
+}
+static int render_output_map(tm_encoder *e, RenderMap *m) {  // same rule as FrameRenderer::init
+  TM_CHECK(e->has_pal_px && (e->steps_done & (1 << TM_STEP_RECONSTRUCT)) && e->tm_tile.p && e->tm_pal.p && e->fflags.p && e->palettes_dev.p, TM_E_INVAL,
+           "output frames: Reconstruct (or ReloadGTM) has not been run");
+  const bool pm = e->has_pm && e->tm_pred.p && e->tm_px.p && e->tm_py.p;
+  // (the palettes as made: a PaletteCount set since then does not reach past them)
+  const int npal = (int)std::min<int64_t>(e->s.PaletteCount, (int64_t)e->palettes_host.size() / std::max(1, e->s.PaletteSize));
+  *m = RenderMap{e->tm_tile.as<int32_t>(), e->tm_pal.as<int32_t>(), e->fflags.as<uint8_t>(), pm ? e->tm_pred.as<uint8_t>() : nullptr, 0xff,
+                 pm ? e->tm_px.as<int8_t>() : nullptr, pm ? e->tm_py.as<int8_t>() : nullptr, e->gpal_px.as<uint8_t>(), e->t,
+                 e->palettes_dev.as<int32_t>(), npal, e->s.PaletteSize, e->tm_w, e->tm_h};
+  return TM_OK;
+}
+static int render_input_src(tm_encoder *e, int first, int count, RenderInput *in) {
+  TM_CHECK(e->src_tiles && (e->steps_done & (1 << TM_STEP_LOAD)) && e->ftiles.p && e->fflags.p, TM_E_INVAL,
+           "source frames: the frame tiles are not in memory (run Load; ReloadGTM does not bring them)");
+  TM_CHECK(!e->load_sharded || (first >= e->load_first && first + count <= e->load_first + e->load_count), TM_E_INVAL,
+           "source frames: this process's Load kept frames [%d,+%d) only, not [%d,+%d)", e->load_first, e->load_count, first, count);
+  *in = RenderInput{e->ftiles.as<uint32_t>(), e->fflags.as<uint8_t>(), e->tm_w, e->tm_h};
+  return TM_OK;
+}
+
+int tm_render_frames(tm_encoder *e, int first_frame, int frame_count, int input, void *out, int out_on_device) {
+  TM_CHECK(e && out, TM_E_INVAL, "null argument");
+  TM_TRY(render_range_ok(e, first_frame, frame_count));
+  TM_HIP(hipSetDevice(e->device));
+  RenderMap m{};
+  RenderInput in{};
+  if (input) TM_TRY(render_input_src(e, first_frame, frame_count, &in));
+  else TM_TRY(render_output_map(e, &m));
+  if (frame_count == 0) return TM_OK;
+  const size_t bytes = (size_t)frame_count * e->tm_w * 8 * e->tm_h * 8 * 4;
+  DevBuf tmp;
+  void *dst = out;
+  if (!out_on_device) {
+    TM_TRY(tmp.alloc(bytes));
+    dst = tmp.p;
+  }
+  TM_TRY(input ? launch_render_input(in, first_frame, frame_count, dst, e->stream) : launch_render_output(m, first_frame, frame_count, dst, e->stream));
+  if (!out_on_device) TM_HIP(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, e->stream));  // page-locked destination: one DMA
+  TM_HIP(hipStreamSynchronize(e->stream));
+  return TM_OK;
+}
+
+int tm_get_frame_quality(tm_encoder *e, int first_frame, int frame_count, uint64_t *sse, double *psnr, double *ssim_y, double *clip_psnr,
+                         double *clip_ssim_y) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_TRY(render_range_ok(e, first_frame, frame_count));
+  TM_CHECK(frame_count > 0, TM_E_INVAL, "frame quality: no frames");
+  TM_HIP(hipSetDevice(e->device));
+  RenderMap m{};
+  RenderInput in{};
+  TM_TRY(render_output_map(e, &m));
+  TM_TRY(render_input_src(e, first_frame, frame_count, &in));
+  DevBuf d_sse, d_ssim;
+  TM_TRY(d_sse.alloc((size_t)frame_count * 3 * 8));
+  TM_TRY(d_ssim.alloc((size_t)frame_count * 8));
+  TM_TRY(launch_quality_render(in, m, first_frame, frame_count, d_sse.p, d_ssim.p, e->stream));
+  std::vector<uint64_t> h_sse((size_t)frame_count * 3);
+  std::vector<double> h_ssim((size_t)frame_count);
+  TM_HIP(hipMemcpyAsync(h_sse.data(), d_sse.p, h_sse.size() * 8, hipMemcpyDeviceToHost, e->stream));
+  TM_HIP(hipMemcpyAsync(h_ssim.data(), d_ssim.p, h_ssim.size() * 8, hipMemcpyDeviceToHost, e->stream));
+  TM_HIP(hipStreamSynchronize(e->stream));
+  // PSNR = 10 log10(3 W H 255^2 / SSE) over the three channels; the clip's from the summed SSE, its SSIM the mean of the frames'
+  const double peak = 3.0 * (e->tm_w * 8) * (e->tm_h * 8) * 255.0 * 255.0;
+  auto to_psnr = [](double top, uint64_t err) { return err ? 10.0 * std::log10(top / (double)err) : HUGE_VAL; };
+  uint64_t total = 0;
+  double ssum = 0.0;
+  for (int f = 0; f < frame_count; f++) {
+    const uint64_t fe = h_sse[(size_t)f * 3] + h_sse[(size_t)f * 3 + 1] + h_sse[(size_t)f * 3 + 2];
+    total += fe;
+    ssum += h_ssim[(size_t)f];
+    if (psnr) psnr[f] = to_psnr(peak, fe);
+  }
+  if (sse) memcpy(sse, h_sse.data(), h_sse.size() * 8);
+  if (ssim_y) memcpy(ssim_y, h_ssim.data(), h_ssim.size() * 8);
+  if (clip_psnr) *clip_psnr = to_psnr(peak * frame_count, total);
+  if (clip_ssim_y) *clip_ssim_y = ssum / frame_count;
+  return TM_OK;
 }
 
 }  // extern "C"

@@ -90,6 +90,31 @@ int solve_tile_count(const void *group, int64_t ngroups, const void *pm_err, con
 int mark_at_threshold(const void *pm_err, const void *frame_is_kf, int per, int64_t q, double x, void *pred, void *keep, hipStream_t stream);
 float euclidean_to_psnr(uint32_t e);
 
+// tm_render.hip: the decoded frames (Render, tilingencoder.pas:3455-3640, the constructor's defaults) and their quality against the source
+struct RenderMap {  // the output picture: tile maps [frames][tm_h * tm_w] from frame 0, tiles, palettes (0x00BBGGRR)
+  const int32_t *tile, *pal;
+  const uint8_t *mir;                 // bit 0 H mirror, bit 1 V mirror
+  const uint8_t *pred;                // predicted where pred[i] & pred_mask (null: none is)
+  int pred_mask;
+  const int8_t *px, *py;
+  const uint8_t *pal_px;              // [ntiles][64]
+  int64_t ntiles;
+  const int32_t *palettes;            // [npal][pal_size]
+  int npal, pal_size, tm_w, tm_h;
+};
+struct RenderInput {  // the source picture: frame tiles (canonical orientation, 0x00BBGGRR) and their mirror flags, from frame 0
+  const uint32_t *tiles;
+  const uint8_t *flags;
+  int tm_w, tm_h;
+};
+// frames [first, first + count) as [count][tm_h * 8][tm_w * 8] 0x00RRGGBB
+int launch_render_output(const RenderMap &m, int first, int count, void *out, hipStream_t stream);
+int launch_render_input(const RenderInput &in, int first, int count, void *out, hipStream_t stream);
+// per frame of [first, first + count): SSE of R, G, B (uint64 [count][3]) and the SSIM of GenerateY4M's luma (double [count]), output against source
+int launch_quality_render(const RenderInput &in, const RenderMap &m, int first, int count, void *sse, void *ssim, hipStream_t stream);
+// the same for two stacks of 0x00RRGGBB frames [n][h][stride_px] (w, h: multiples of 4, at least 8)
+int launch_quality_frames(const void *a, const void *b, int n, int w, int h, int64_t stride_px, void *sse, void *ssim, hipStream_t stream);
+
 // One process per GPU: the collectives a step needs between its kernels, handed in by the host (tm_set_collective).  The calls
 // are made on the caller's thread with the encoder's stream idle, and return with the result in place.
 struct Collectives {

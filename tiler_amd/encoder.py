@@ -71,6 +71,8 @@ _ENC_SIGS = {
     "tm_reload_gtm": (c_int, [c_void_p, c_char_p]),
     "tm_generate_y4m": (c_int, [c_void_p, c_char_p, c_int]),
     "tm_generate_pngs": (c_int, [c_void_p, c_int]),
+    "tm_render_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int]),
+    "tm_get_frame_quality": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
     "tm_set_query_shard": (c_int, [c_void_p, c_int, c_int]),
     "tm_set_dither_shard": (c_int, [c_void_p, c_int, c_int]),
     "tm_set_collective": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -340,6 +342,35 @@ class TilingEncoder:
     def GeneratePNGs(self, input=False):
         """GeneratePNGs (tilingencoder.pas:2075): <OutputFileName>_NNNN.png per frame + the palettes as <OutputFileName>.txt"""
         check(self._L.tm_generate_pngs(c_void_p(self._h), int(bool(input))))
+
+    def RenderFrames(self, first=0, count=None, input=False, device=True):
+        """The decoded frames [first, first+count) as Render (tilingencoder.pas:3455-3640) draws them with the constructor's defaults -- or
+        the source frames (input=True) -- rendered on the device: [count][tm_h*8][tm_w*8] 0x00RRGGBB (the pushed frames' format, alpha 0),
+        as a torch int32 CUDA tensor (device=True) or a numpy uint32 array"""
+        c = self.counts()
+        count = c["frames"] - first if count is None else count
+        shape = (max(count, 0), c["tm_h"] * 8, c["tm_w"] * 8)
+        if device:
+            import torch
+            out = torch.empty(shape, dtype=torch.int32, device="cuda")
+            check(self._L.tm_render_frames(c_void_p(self._h), first, count, int(bool(input)), c_void_p(out.data_ptr()), 1))
+            return out
+        out = np.empty(shape, np.uint32)
+        check(self._L.tm_render_frames(c_void_p(self._h), first, count, int(bool(input)), out.ctypes.data_as(c_void_p), 0))
+        return out
+
+    def FrameQuality(self, first=0, count=None):
+        """Pixel-domain quality of the decoded frames [first, first+count) against the source (tm_get_frame_quality): sse uint64 [count][3]
+        (R, G, B), psnr [count] (dB, inf where SSE is 0), ssim_y [count] (SSIM of the .y4m luma, 8x8 windows on a 4-pixel grid), clip_psnr
+        (from the summed SSE), clip_ssim_y (mean of the frames')"""
+        count = self.counts()["frames"] - first if count is None else count
+        sse = np.zeros((max(count, 0), 3), np.uint64)
+        psnr = np.zeros(max(count, 0), np.float64)
+        ssim = np.zeros(max(count, 0), np.float64)
+        cp, cs = c_double(), c_double()
+        check(self._L.tm_get_frame_quality(c_void_p(self._h), first, count, sse.ctypes.data_as(c_void_p), psnr.ctypes.data_as(c_void_p),
+                                           ssim.ctypes.data_as(c_void_p), ctypes.byref(cp), ctypes.byref(cs)))
+        return dict(sse=sse, psnr=psnr, ssim_y=ssim, clip_psnr=cp.value, clip_ssim_y=cs.value)
 
     def ReloadGTM(self, path):
         """ReloadGTM (tilingencoder.pas:2059) -> LoadStream (:4880): tiles, palettes, tile maps, key frames from a .gtm"""

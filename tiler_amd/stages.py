@@ -256,3 +256,49 @@ def kmodes_dev(rows, num_clusters, num_init=0, num_modalities=256, max_iter=-1):
     check(L.tm_stage_kmodes_dev(ctypes.c_void_p(rows.data_ptr()), rows.shape[0], num_clusters, num_init, num_modalities, max_iter, ctypes.c_void_p(labels.data_ptr()),
                                 ctypes.c_void_p(cent.data_ptr()), ctypes.byref(cost), ctypes.byref(iters), ctypes.byref(pit), _stream()))
     return labels, cent, cost.value, iters.value, pit.value
+
+
+def render(tile_idx, pal_idx, item_flags, px, py, tm_w, tm_h, pal_px, palettes):
+    """Render (tilingencoder.pas:3455-3640, the constructor's defaults) of F frames from their tile maps: tile_idx / pal_idx int32 [F][tm_h*tm_w],
+    item_flags uint8 (bit 0 H mirror, bit 1 V mirror, bit 2 predicted), px / py int8 (PredictedX / PredictedY), pal_px uint8 [T][64],
+    palettes int32 [npal][pal_size] 0x00BBGGRR -> int32 [F][tm_h*8][tm_w*8] 0x00RRGGBB; predicted items copy frame f-1's output (black before frame 0)"""
+    per = tm_w * tm_h
+    for t, dt in ((tile_idx, torch.int32), (pal_idx, torch.int32), (item_flags, torch.uint8), (px, torch.int8), (py, torch.int8), (pal_px, torch.uint8),
+                  (palettes, torch.int32)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous()
+    n = tile_idx.numel()
+    assert n % per == 0 and all(t.numel() == n for t in (pal_idx, item_flags, px, py))
+    nf = n // per
+    out = torch.empty((nf, tm_h * 8, tm_w * 8), dtype=torch.int32, device=tile_idx.device)
+    check(lib().tm_stage_render(_p(tile_idx), _p(pal_idx), _p(item_flags), _p(px), _p(py), tm_w, tm_h, nf, _p(pal_px), pal_px.numel() // 64, _p(palettes),
+                                palettes.shape[0], palettes.shape[1], _p(out), _stream()))
+    return out
+
+
+def _mean_in_order(v):
+    acc = 0.0
+    for x in v.tolist():  # frame order, as tm_get_frame_quality sums
+        acc += x
+    return acc / len(v) if len(v) else float("nan")
+
+
+def frame_quality(a, b):
+    """Quality of frames b (decoded) against a (source), int32 [F][H][W] 0x00RRGGBB (H, W multiples of 4, rows may be padded): the sums of
+    tm_get_frame_quality.  -> dict: sse int64 [F][3] (R, G, B) and ssim_y float64 [F] on the device; psnr (numpy [F], inf where SSE is 0),
+    clip_psnr (from the summed SSE) and clip_ssim_y (mean of the frames') on the host"""
+    import numpy as np
+    assert a.is_cuda and b.is_cuda and a.dtype == torch.int32 and b.dtype == torch.int32 and a.shape == b.shape and a.dim() == 3
+    assert a.stride() == b.stride() and a.stride(2) == 1 and a.stride(0) == a.shape[1] * a.stride(1)
+    f, h, w = a.shape
+    sse = torch.empty((f, 3), dtype=torch.int64, device=a.device)
+    ssim = torch.empty((f,), dtype=torch.float64, device=a.device)
+    check(lib().tm_stage_frame_quality(_p(a), _p(b), f, w, h, a.stride(1), _p(sse), _p(ssim), _stream()))
+    e = sse.cpu().numpy().astype(np.uint64)
+    s = ssim.cpu().numpy()
+    peak = 3.0 * w * h * 255.0 * 255.0
+    tot = e.sum(axis=1)
+    with np.errstate(divide="ignore"):
+        psnr = np.where(tot > 0, 10.0 * np.log10(peak / np.maximum(tot, 1).astype(np.float64)), np.inf)
+    allsum = int(tot.sum())
+    clip_psnr = 10.0 * np.log10(peak * f / allsum) if allsum else float("inf")
+    return dict(sse=sse, ssim_y=ssim, psnr=psnr, clip_psnr=float(clip_psnr), clip_ssim_y=_mean_in_order(s))
