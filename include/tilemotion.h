@@ -17,13 +17,14 @@
  *   3. Fine seam    ann_kdtree_* / yakmo_* / bico_*  == the DLL imports of extern.pas:178-223, same
  *      per-call semantics, plus *_batch twins (per-call GPU use is latency bound; kept for compatibility).
  *
- * Several GPUs: ONE PROCESS PER GPU, and only that.  The surveyed boundary sketched a tm_set_device_mask for one process driving 1/2/4/8
- * devices; it is not built and will not be: an encoder is bound to one device (tm_set_device) and one host thread, N encoders become one
- * job through tm_comm_init (RCCL inside the library) or tm_set_collective (the host's own communicator), and the reference's single
- * control thread (tiler.lpr:64-70) starts N copies of itself with a rank each.  One process per device is what
- * RCCL and the driver's launcher (torch.distributed.run) assume, it keeps a fault or an out-of-memory on one device from taking the
- * other seven encoders with it, and the steps' host tails (OptimizePalettes, the key-frame logic, LZMA) run N times in parallel
- * instead of queueing on one thread.
+ * Several GPUs, two ways.  (a) One process, several devices: tm_set_device_mask / tm_set_devices right after tm_create make the encoder a
+ * group of shards, one per listed device, and Run(step) shards and merges inside the library; the reference's single control thread
+ * (tiler.lpr:64-70) needs that one call and nothing else.  The surveyed objections, answered: the group does
+ * not use RCCL, which assumes a process per device -- its collectives are the library's own in-process ones (host barriers, peer copies
+ * and a reduce kernel); the steps' host tails (OptimizePalettes, the key-frame logic, LZMA) do not queue on one thread -- every device
+ * gets a host thread of its own; a fault or an out-of-memory on one device still takes the other shards with it -- that is the caller's
+ * choice to make.  (b) One process per device, for those who want that isolation: N encoders become one job through tm_comm_init (RCCL
+ * inside the library) or tm_set_collective (the host's own communicator), each process with a rank.
  *
  * Environment switches.  All are optional; they are sampled at the API boundary (tm_create, tm_run, every tm_stage_* and fine-seam entry)
  * and never read inside a step.  Set and not "0" = on.
@@ -64,7 +65,10 @@
  *                           every process could run it whole in one resident launch (tests, A/B)
  *   TM_PP_DEBUG             PreparePalettes prints its sub-steps' wall times (adds synchronisations)
  *   TM_COMM_FORCE_DIST      a one-process communicator still walks the sharded code paths (tests on a one-GPU box)
- *   TM_COMM_TIMEOUT_S=<s>   how long tm_comm_init (and a collective of the library's own communicator) waits for the other processes (120)
+ *   TM_COMM_TIMEOUT_S=<s>   how long tm_comm_init (and a collective of the library's own communicator, or of a device group) waits for the
+ *                           other processes or shards (120)
+ *   TM_GROUP_FAIL_SHARD=<r> shard r of a device group fails with TM_E_INVAL ("forced") at the start of its next step, before it queues any work
+ *                           (tests: the other shards must leave their collectives at once)
  *   TM_POOL_GIB=<x>         cap of the device-memory pool a thread keeps (96); TM_HOST_THREADS=<n>: OptimizePalettes' helper threads
  *                           (both read once per process)
  */
@@ -115,6 +119,9 @@ TM_API const char *tm_version(void);
  * arrays of `bytes_per_array` in GB/s.  Diagnostics for bench.py; nothing in the product path calls them. */
 TM_API int tm_probe_mfma_i8(double seconds_hint, double *tops);
 TM_API int tm_probe_hbm_triad(int64_t bytes_per_array, double *gb_per_s);
+/* The all-reduce of a device group (tm_set_devices): mean wall time in us of `iters` int32 sum all-reduces of `bytes` between n shards
+ * on `devices` (one host thread each, the stream drained before and after, as a step sees it).  A diagnostic for tools/group_bench.py. */
+TM_API int tm_probe_group_allreduce(const int *devices, int n, int64_t bytes, int iters, double *us_per_call);
 
 /* ======================================================================================= coarse seam */
 typedef struct tm_encoder tm_encoder;
@@ -123,6 +130,14 @@ typedef void (*tm_progress_cb)(void *user, int step, int position, int max, int 
 TM_API tm_encoder *tm_create(void);                 /* TTilingEncoder.Create, :5484; NULL on failure */
 TM_API void tm_destroy(tm_encoder *);               /* Destroy, :5516 */
 TM_API int tm_set_device(tm_encoder *, int device); /* which HIP device this encoder (process) drives */
+/* One process, several devices: the encoder becomes a group of shards, one per listed device, each with its own host thread; Run(step)
+ * shards and merges inside the library exactly as N processes under tm_comm_init do, and ends every step with the single encoder's state.
+ * Only before tm_set_video; settings already made carry over to every shard.  A list of one device is tm_set_device.  TM_E_INVAL: mask 0, a
+ * device outside 0 .. tm_device_count()-1, n < 1 or n > 32, an encoder with video, tm_set_collective or tm_comm_init; those two calls,
+ * tm_set_query_shard and tm_set_dither_shard then refuse the group (it owns the sharding).  TM_E_UNSUPPORTED: two listed devices cannot
+ * reach each other's memory.  The group is used from one host thread like any encoder; progress callbacks come from shard 0 only, on it. */
+TM_API int tm_set_device_mask(tm_encoder *, uint32_t mask);              /* bit d = HIP device d */
+TM_API int tm_set_devices(tm_encoder *, const int *devices, int n);     /* a device may repeat: several shards on one device */
 /* Settings: keys are the INI names of SaveSettings (:3745-3770); setters clamp like :2919-3047. */
 TM_API int tm_load_default_settings(tm_encoder *);  /* LoadDefaultSettings, :3817-3845 */
 TM_API int tm_load_settings_ini(tm_encoder *, const char *path); /* LoadSettings, :3777 */

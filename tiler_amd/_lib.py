@@ -29,6 +29,9 @@ SIGNATURES = {
     "tm_version": (c_char_p, []),
     "tm_probe_mfma_i8": (c_int, [c_double, ctypes.POINTER(c_double)]),
     "tm_probe_hbm_triad": (c_int, [c_int64, ctypes.POINTER(c_double)]),
+    "tm_probe_group_allreduce": (c_int, [ctypes.POINTER(c_int), c_int, c_int64, c_int, ctypes.POINTER(c_double)]),
+    "tm_set_device_mask": (c_int, [c_void_p, ctypes.c_uint32]),
+    "tm_set_devices": (c_int, [c_void_p, ctypes.POINTER(c_int), c_int]),
     "tm_stage_load": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tm_stage_features_rgb": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "tm_stage_features_pal": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),

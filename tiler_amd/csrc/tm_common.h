@@ -52,9 +52,11 @@ struct Knobs {
   int topk_estimate = -1;  // TM_TOPK_ESTIMATE: the k-nearest search's first thresholds from a sample of the database: -1 by size, 0 never, 1 whenever possible
   double epu_table_gib = 6.0, comm_timeout_s = 120.0;
   long long knn_arena_entries = 0, dedup_radix_min = 1ll << 20;
+  int group_fail_shard = -1;  // TM_GROUP_FAIL_SHARD: that shard of a device group fails at the start of its next step (tests)
 };
 const Knobs &knobs();
 void knobs_reload();
+void knobs_set(const Knobs &k);  // a device group's worker thread takes the set its caller sampled
 
 // Device memory pool: hipMalloc / hipFree of the pipeline's multi-GB temporaries cost ~16 ms per 720p clip (and hipFree
 // synchronises the device), so freed blocks are kept per host thread and handed out again.  A thread drives its encoder on

@@ -7,6 +7,9 @@
 // re-rank, OptimizePalettes, the .gtm writer and reader included); what stays outside the path is listed in DESIGN.md "Scope".
 #include <algorithm>
 #include <chrono>
+#include <condition_variable>
+#include <memory>
+#include <mutex>
 #include <thread>
 #include <cmath>
 #include <fstream>
@@ -229,7 +232,14 @@ struct tm_encoder {
   }
   ncclComm_t comm = nullptr;
   bool force_dist = false;  // a one-rank communicator walks the sharded paths too (TM_COMM_FORCE_DIST=1: tests on a one-GPU box)
-  bool dist() const { return (coll_cb != nullptr || comm != nullptr) && (co.world > 1 || force_dist); }
+  // One process, several devices (tm_set_devices): the front encoder is shard 0 and owns the group; every shard's collectives go through
+  // the group's in-process communicator (tm_group.hip), co.rank / co.world are its place in the group.
+  struct Group *grp = nullptr;
+  GroupComm *gcomm = nullptr;
+  int pp_whole = -1;                // PreparePalettes' branch as the group decided it for all shards (-1: this encoder decides)
+  const void *frames_peer = nullptr;  // tm_set_frames_device of a group whose clip lives on another device: Load pulls what it reads
+  int frames_peer_dev = -1;
+  bool dist() const { return (coll_cb != nullptr || comm != nullptr || gcomm != nullptr) && (co.world > 1 || force_dist); }
   // Query features of Reconstruct's first chunk, computed AHEAD on a second (non-blocking) stream: they depend on the frame tiles only.
   // Launched when PreparePalettes hands over to the host (OptimizePalettes' 2-5 ms search, then Dither's start), the one stretch where
   // the GPU idles; launched earlier they only trade time with the k-means kernels (measured: +3.8 ms there for -3.7 ms here).
@@ -524,6 +534,19 @@ static int step_load(tm_encoder *e) {  // Load, tilingencoder.pas:1741-1841 (dec
   e->q_groups = 0;
   e->load_sharded = false;
   TM_CHECK(e->nframes > 0 && e->width > 0, TM_E_INVAL, "tm_set_video has not been called");
+  if (e->frames_peer) {
+    // a device group's clip on another device (tm_set_frames_device): this shard pulls the frames its Load reads into its own memory
+    const size_t fbytes = (size_t)e->width * e->height * 4;
+    int64_t a = 0, b = e->nframes;
+    if (e->dist() && e->s.MotionPredictRadius <= 0) {
+      share_of(e->nframes, e->co.rank, e->co.world, &a, &b);
+      a = std::max<int64_t>(a - 1, 0);
+    }
+    TM_TRY(e->frames_owned.alloc(fbytes * e->nframes));
+    if (b > a) TM_HIP(hipMemcpyPeerAsync(e->frames_owned.as<uint8_t>() + fbytes * a, e->device, (const uint8_t *)e->frames_peer + fbytes * a, e->frames_peer_dev,
+                                         fbytes * (b - a), e->stream));
+    e->frames = e->frames_owned.p;
+  }
   TM_CHECK(e->frames != nullptr || e->frames_host != nullptr, TM_E_INVAL, "no frames: call tm_push_frame_rgb32 / tm_set_frames_device / tm_set_frames_host first");
   e->q = (int64_t)e->nframes * e->tm_size();
   TM_CHECK(e->q < (1ll << 31), TM_E_UNSUPPORTED, "%lld tile-map items: the index arrays are 32-bit (TileIdx is an Integer, tilingencoder.pas:179)", (long long)e->q);
@@ -672,6 +695,9 @@ static int step_predict_motion(tm_encoder *e) {
                                    e->tm_px.as<int8_t>() + off, e->tm_py.as<int8_t>() + off, e->stream));
     if ((f & 15) == 15) progress(e, TM_STEP_PREDICT_MOTION, f, e->nframes);
   }
+  if (e->gcomm && sf == 0)  // a device group reports from shard 0 only: the other shards' frames too, so that the sequence is the single run's
+    for (int f = sn; f < e->nframes; f++)
+      if ((f & 15) == 15) progress(e, TM_STEP_PREDICT_MOTION, f, e->nframes);
   if (e->dist()) {  // owner holds the value, everyone else 0
     TM_TRY(e->co.allreduce_sum_i32(e->pm_err.p, e->q));
     TM_TRY(e->co.allreduce_sum_i32(e->tm_px.p, (e->q + 3) / 4));
@@ -947,7 +973,8 @@ static int step_prepare_palettes(tm_encoder *e) {  // PreparePalettes, tilingenc
     // of the exact integer sums (run_palettize_dist), then the palette indices of all shares are all-gathered.  Palette colours:
     // the palettes are independent tasks (one thread per palette in the reference, 1864): process r quantises the palettes
     // p = r (mod world), an all-reduce(SUM) assembles the set.
-    if (!knobs().pp_sharded && palettize_resident(e->t, e->s.PaletteCount)) {
+    const bool whole = e->pp_whole >= 0 ? e->pp_whole != 0 : !knobs().pp_sharded && palettize_resident(e->t, e->s.PaletteCount);
+    if (whole) {
       // Up to 16 palettes and half a million tiles the single-GPU clustering is ONE resident launch of a few milliseconds (k_h_resident), and every
       // process holds all the global tiles: each runs it whole.  Sharded, a Lloyd iteration is an all-reduce of 25 KB -- 300 latency-bound
       // collectives on the bench clip, more than the whole clustering takes here -- plus two all-gathers per seeding pick; replicated there is none.
@@ -1532,6 +1559,7 @@ static int generate_pngs(tm_encoder *e, bool input) {  // GeneratePNGs, tilingen
 }
 
 static int run_step(tm_encoder *e, int step) {
+  TM_CHECK(!(e->gcomm && knobs().group_fail_shard == e->co.rank), TM_E_INVAL, "forced failure of shard %d (TM_GROUP_FAIL_SHARD)", e->co.rank);
   TM_HIP(hipSetDevice(e->device));
   const auto t0 = std::chrono::steady_clock::now();
   int rc = TM_OK;
@@ -1554,6 +1582,239 @@ static int run_step(tm_encoder *e, int step) {
   return rc;
 }
 
+static void set_query_shard(tm_encoder *e, int first_frame, int frame_count) {
+  if (first_frame != e->shard_first || frame_count != e->shard_count) e->qf_valid = false;  // prefetched for the old range (freed with the next Load / Reconstruct)
+  e->shard_first = first_frame;
+  e->shard_count = frame_count;
+}
+
+// ---- one process, several devices (tm_set_devices) ---------------------------------------------------------------------------
+// Shard 0 is the front encoder, driven on the caller's thread; shards 1 .. N-1 are encoders that live on persistent worker threads, one
+// each: a thread's device pool, page-locked area, knobs and error text are its own (tm_tables.hip), so a shard's memory is allocated and
+// freed on its thread from its creation to tm_destroy.  A call reaches every shard at once and returns the first error.
+struct ShardWorker {
+  int rank = 0, device = 0;
+  tm_encoder *enc = nullptr;
+  std::thread th;
+  std::mutex mu;
+  std::condition_variable cv;
+  std::function<int(tm_encoder *)> job;
+  Knobs kn;                // the caller's sampled switches, taken with the job
+  bool pending = true, quit = false;
+  int rc = TM_OK;
+  std::string err;
+};
+
+struct Group {
+  std::vector<int> devices;
+  std::vector<std::unique_ptr<ShardWorker>> workers;  // shards 1 .. N-1
+  GroupComm *comm = nullptr;
+};
+
+static void shard_main(ShardWorker *w, Settings s, bool auto_tile_count) {
+  std::unique_lock<std::mutex> lk(w->mu);
+  if (hipSetDevice(w->device) != hipSuccess) {
+    w->rc = TM_E_HIP;
+    w->err = std::string("hipSetDevice failed: ") + hipGetErrorString(hipGetLastError());
+  } else {
+    w->enc = new tm_encoder();
+    w->enc->device = w->device;
+    w->enc->s = s;  // settings made before the group was formed carry over
+    w->enc->auto_tile_count = auto_tile_count;
+  }
+  w->pending = false;
+  w->cv.notify_all();
+  for (;;) {
+    w->cv.wait(lk, [w] { return (bool)w->job || w->quit; });
+    if (!w->job) break;
+    std::function<int(tm_encoder *)> job = std::move(w->job);
+    w->job = nullptr;
+    knobs_set(w->kn);
+    lk.unlock();
+    const int rc = w->enc ? job(w->enc) : TM_E_INVAL;
+    const std::string err = rc == TM_OK ? std::string() : w->enc ? std::string(get_error()) : std::string("shard not created");
+    if (rc != TM_OK && w->enc && w->enc->gcomm) group_comm_abort(w->enc->gcomm, w->rank);  // the other shards stop waiting for this one
+    lk.lock();
+    w->rc = rc;
+    w->err = err;
+    w->pending = false;
+    w->cv.notify_all();
+  }
+  lk.unlock();
+  if (w->enc) {
+    delete w->enc;
+    pool_trim();  // the shard's device blocks go back to the driver from the thread that holds them
+  }
+}
+
+static void group_teardown(tm_encoder *e) {
+  Group *g = e->grp;
+  for (auto &w : g->workers) {
+    { std::lock_guard<std::mutex> lk(w->mu); w->quit = true; }
+    w->cv.notify_all();
+    if (w->th.joinable()) w->th.join();
+  }
+  if (g->comm) group_comm_destroy(g->comm);
+  delete g;
+  e->grp = nullptr;
+  e->gcomm = nullptr;
+}
+
+// fn on every shard at once (shard 0 on the caller's thread); the error of the shard that broke the group first, else of the lowest failing shard
+static int group_each(tm_encoder *e, const std::function<int(tm_encoder *)> &fn) {
+  Group *g = e->grp;
+  const Knobs kn = knobs();
+  for (auto &w : g->workers) {
+    { std::lock_guard<std::mutex> lk(w->mu); w->job = fn; w->kn = kn; w->pending = true; }
+    w->cv.notify_all();
+  }
+  e->grp = nullptr;  // shard 0 is the front encoder itself: while its share runs it is a plain encoder
+  const int rc0 = fn(e);
+  e->grp = g;
+  const std::string err0 = rc0 == TM_OK ? std::string() : std::string(get_error());
+  if (rc0 != TM_OK && e->gcomm) group_comm_abort(e->gcomm, 0);
+  const int n = (int)g->devices.size();
+  std::vector<int> rcs((size_t)n, TM_OK);
+  std::vector<std::string> errs((size_t)n);
+  rcs[0] = rc0;
+  errs[0] = err0;
+  for (auto &w : g->workers) {
+    std::unique_lock<std::mutex> lk(w->mu);
+    w->cv.wait(lk, [&] { return !w->pending; });
+    rcs[(size_t)w->rank] = w->rc;
+    errs[(size_t)w->rank] = w->err;
+  }
+  int pick = e->gcomm ? group_comm_broken_by(e->gcomm) : -1;
+  if (pick < 0 || rcs[(size_t)pick] == TM_OK) {
+    pick = -1;
+    for (int r = 0; r < n && pick < 0; r++)
+      if (rcs[(size_t)r] != TM_OK) pick = r;
+  }
+  if (pick < 0) return TM_OK;
+  if (pick == 0) set_error("%s", err0.c_str());
+  else set_error("shard %d (device %d): %s", pick, g->devices[(size_t)pick], errs[(size_t)pick].c_str());
+  return rcs[(size_t)pick];
+}
+
+static void bind_group_collectives(tm_encoder *e) {
+  e->co.allreduce_sum_i32 = [e](void *b, int64_t n) { e->coll_count(TM_COLL_ALLREDUCE_SUM_I32, n); return group_allreduce(e->gcomm, e->co.rank, TM_COLL_ALLREDUCE_SUM_I32, b, n, e->stream); };
+  e->co.allreduce_max_i32 = [e](void *b, int64_t n) { e->coll_count(TM_COLL_ALLREDUCE_MAX_I32, n); return group_allreduce(e->gcomm, e->co.rank, TM_COLL_ALLREDUCE_MAX_I32, b, n, e->stream); };
+  e->co.allreduce_sum_i64 = [e](void *b, int64_t n) { e->coll_count(TM_COLL_ALLREDUCE_SUM_I64, n); return group_allreduce(e->gcomm, e->co.rank, TM_COLL_ALLREDUCE_SUM_I64, b, n, e->stream); };
+  e->co.allgather = [e](const void *snd, void *rcv, int64_t bytes) {
+    e->coll_count(TM_COLL_ALLGATHER_BYTES, bytes);
+    return group_allgather(e->gcomm, e->co.rank, snd, rcv, bytes, e->stream);
+  };
+}
+
+// tiler_amd.distributed.keyframe_shard: the frame shares' borders snapped to the nearest key-frame start (ties: the earlier one)
+static void keyframe_shard(const std::vector<int32_t> &kf, int nframes, int rank, int world, int *first, int *count) {
+  std::vector<int64_t> cuts{0};
+  for (int r = 1; r < world; r++) {
+    int64_t ideal, hi;
+    share_of(nframes, r, world, &ideal, &hi);
+    int64_t snap = kf.empty() ? 0 : kf[0];
+    for (int32_t k : kf)
+      if (std::llabs(k - ideal) < std::llabs(snap - ideal) || (std::llabs(k - ideal) == std::llabs(snap - ideal) && k < snap)) snap = k;
+    cuts.push_back(std::max(snap, cuts.back()));
+  }
+  cuts.push_back(nframes);
+  *first = (int)cuts[(size_t)rank];
+  *count = (int)(cuts[(size_t)rank + 1] - cuts[(size_t)rank]);
+}
+
+// one step on every shard, with the query frames tiler_amd.distributed.run_all would give each: the Load share (motion prediction off: what
+// Reconstruct requires of a sharded Load), the key-frame-snapped share for Reconstruct with motion prediction
+static int group_run_step(tm_encoder *e, int step) {
+  Group *g = e->grp;
+  const int n = (int)g->devices.size();
+  group_comm_reset(g->comm);
+  std::vector<int> qf((size_t)n), qc((size_t)n);
+  for (int r = 0; r < n; r++) {
+    int64_t lo, hi;
+    share_of(e->nframes, r, n, &lo, &hi);
+    qf[(size_t)r] = (int)lo;
+    qc[(size_t)r] = (int)(hi - lo);
+  }
+  TM_HIP(hipSetDevice(e->device));
+  if (step == TM_STEP_RECONSTRUCT && e->s.MotionPredictRadius > 0) {
+    TM_TRY(load_tail(e));
+    for (int r = 0; r < n; r++) keyframe_shard(e->kf_start, e->nframes, r, n, &qf[(size_t)r], &qc[(size_t)r]);
+  }
+  // PreparePalettes' branch is taken once for the group, from shard 0's state, so that the shards cannot disagree
+  const int whole = step == TM_STEP_PREPARE_PALETTES ? (!knobs().pp_sharded && palettize_resident(e->t, e->s.PaletteCount) ? 1 : 0) : -1;
+  return group_each(e, [&](tm_encoder *s) {
+    set_query_shard(s, qf[(size_t)s->co.rank], qc[(size_t)s->co.rank]);
+    s->pp_whole = whole;
+    return run_step(s, step);
+  });
+}
+
+static int group_form(tm_encoder *e, const std::vector<int> &devices) {
+  const int n = (int)devices.size();
+  for (int a : devices)  // every pair of distinct devices must reach each other's memory (the shards pull across)
+    for (int b : devices) {
+      if (a == b) continue;
+      int can = 0;
+      TM_HIP(hipDeviceCanAccessPeer(&can, a, b));
+      TM_CHECK(can, TM_E_UNSUPPORTED, "device group: device %d cannot reach the memory of device %d", a, b);
+      TM_HIP(hipSetDevice(a));
+      const hipError_t pe = hipDeviceEnablePeerAccess(b, 0);
+      if (pe == hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
+      else TM_HIP(pe);
+    }
+  e->device = devices[0];
+  TM_HIP(hipSetDevice(e->device));
+  Group *g = new Group();
+  g->devices = devices;
+  g->comm = group_comm_create(devices);
+  e->grp = g;
+  e->gcomm = g->comm;
+  int rc = TM_OK;
+  std::string err;
+  for (int r = 1; r < n; r++) {
+    g->workers.emplace_back(new ShardWorker());
+    ShardWorker *w = g->workers.back().get();
+    w->rank = r;
+    w->device = devices[(size_t)r];
+    w->th = std::thread(shard_main, w, e->s, e->auto_tile_count);
+    std::unique_lock<std::mutex> lk(w->mu);
+    w->cv.wait(lk, [w] { return !w->pending; });
+    if (w->rc != TM_OK && rc == TM_OK) { rc = w->rc; err = w->err; }
+  }
+  if (rc != TM_OK) {
+    group_teardown(e);
+    set_error("device group: shard on device %s", err.c_str());
+    return rc;
+  }
+  std::vector<tm_encoder *> shards{e};
+  for (auto &w : g->workers) shards.push_back(w->enc);  // (the workers are idle: the next job's hand-over publishes these fields)
+  for (int r = 0; r < n; r++) {
+    tm_encoder *s = shards[(size_t)r];
+    s->gcomm = g->comm;
+    s->co.rank = r;
+    s->co.world = n;
+    bind_group_collectives(s);
+    s->dither_rank = r;
+    s->dither_world = n;
+    s->qf_valid = false;
+  }
+  return TM_OK;
+}
+
+// tm_get_frame_quality / tm_render_frames(input) of a group whose Load was sharded: each shard holds the source frames of its own Load range, so
+// the range is cut at those borders and every piece is computed on its shard
+struct Piece { int first = 0, count = 0; };
+static std::vector<Piece> group_pieces(tm_encoder *e, int first, int count) {
+  std::vector<Piece> out(e->grp->devices.size());
+  for (size_t r = 0; r < out.size(); r++) {
+    int64_t lo, hi;
+    share_of(e->nframes, (int)r, (int)out.size(), &lo, &hi);
+    const int64_t a = std::max<int64_t>(lo, first), b = std::min<int64_t>(hi, (int64_t)first + count);
+    if (b > a) out[r] = Piece{(int)a, (int)(b - a)};
+  }
+  return out;
+}
+
 extern "C" {
 
 tm_encoder *tm_create(void) {
@@ -1564,12 +1825,14 @@ tm_encoder *tm_create(void) {
 }
 
 void tm_destroy(tm_encoder *e) {
+  if (e && e->grp) group_teardown(e);  // every shard frees its memory on its own thread
   delete e;
   pool_trim();  // the calling thread's cached device blocks go back to the driver with the encoder
 }
 
 int tm_set_device(tm_encoder *e, int device) {
   TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_CHECK(!e->grp, TM_E_INVAL, "tm_set_device: the encoder is a device group (tm_set_devices)");
   TM_HIP(hipSetDevice(device));
   e->device = device;
   return TM_OK;
@@ -1577,6 +1840,7 @@ int tm_set_device(tm_encoder *e, int device) {
 
 int tm_load_default_settings(tm_encoder *e) {
   TM_CHECK(e, TM_E_INVAL, "null encoder");
+  if (e->grp) return group_each(e, [](tm_encoder *s) { return tm_load_default_settings(s); });
   e->s = Settings();
   e->auto_tile_count = true;
   return TM_OK;
@@ -1613,6 +1877,7 @@ static int load_settings_from(tm_encoder *e, std::istream &in) {  // LoadSetting
 
 int tm_load_settings_ini(tm_encoder *e, const char *path) {
   TM_CHECK(e && path, TM_E_INVAL, "null argument");
+  if (e->grp) return group_each(e, [path](tm_encoder *s) { return tm_load_settings_ini(s, path); });
   std::ifstream in(path);
   TM_CHECK(in.good(), TM_E_IO, "cannot open %s", path);
   return load_settings_from(e, in);
@@ -1648,11 +1913,25 @@ int tm_settings_text_host(const char *ini_text, char *out, int64_t cap, int64_t 
   return TM_OK;
 }
 
-int tm_set_int(tm_encoder *e, const char *key, int64_t v) { TM_CHECK(e && key, TM_E_INVAL, "null argument"); return set_number(e, key, (double)v, true); }
-int tm_set_float(tm_encoder *e, const char *key, double v) { TM_CHECK(e && key, TM_E_INVAL, "null argument"); return set_number(e, key, v, false); }
-int tm_set_bool(tm_encoder *e, const char *key, int v) { TM_CHECK(e && key, TM_E_INVAL, "null argument"); return set_number(e, key, v ? 1 : 0, true); }
+// (a device group: every setter reaches every shard)
+int tm_set_int(tm_encoder *e, const char *key, int64_t v) {
+  TM_CHECK(e && key, TM_E_INVAL, "null argument");
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return set_number(s, key, (double)v, true); });
+  return set_number(e, key, (double)v, true);
+}
+int tm_set_float(tm_encoder *e, const char *key, double v) {
+  TM_CHECK(e && key, TM_E_INVAL, "null argument");
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return set_number(s, key, v, false); });
+  return set_number(e, key, v, false);
+}
+int tm_set_bool(tm_encoder *e, const char *key, int v) {
+  TM_CHECK(e && key, TM_E_INVAL, "null argument");
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return set_number(s, key, v ? 1 : 0, true); });
+  return set_number(e, key, v ? 1 : 0, true);
+}
 int tm_set_str(tm_encoder *e, const char *key, const char *v) {
   TM_CHECK(e && key && v, TM_E_INVAL, "null argument");
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_set_str(s, key, v); });
   if (!strcmp(key, "InputFileName")) e->s.InputFileName = v;
   else if (!strcmp(key, "OutputFileName")) e->s.OutputFileName = v;
   else { set_error("unknown string setting '%s'", key); return TM_E_INVAL; }
@@ -1677,7 +1956,9 @@ int tm_set_progress_cb(tm_encoder *e, tm_progress_cb cb, void *user) {
 int tm_set_video(tm_encoder *e, int width, int height, double fps, int frame_count) {
   TM_CHECK(e, TM_E_INVAL, "null encoder");
   TM_CHECK(width > 0 && height > 0 && frame_count > 0 && fps >= 0, TM_E_INVAL, "bad video geometry %dx%d x%d", width, height, frame_count);
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_set_video(s, width, height, fps, frame_count); });
   TM_HIP(hipSetDevice(e->device));
+  e->frames_peer = nullptr;
   e->width = width; e->height = height; e->fps = fps; e->nframes = frame_count;
   e->tm_w = (width - 1) / 8 + 1;   // ReframeUI((DstWidth - 1) div cTileWidth + 1, ...), tilingencoder.pas:1776
   e->tm_h = (height - 1) / 8 + 1;
@@ -1699,9 +1980,11 @@ int tm_push_frame_rgb32(tm_encoder *e, int index, const uint32_t *pixels, int st
   TM_CHECK(e && pixels, TM_E_INVAL, "null argument");
   TM_CHECK(e->nframes > 0, TM_E_INVAL, "tm_set_video has not been called");
   TM_CHECK(index >= 0 && index < e->nframes && stride_px >= e->width, TM_E_INVAL, "bad frame index/stride");
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_push_frame_rgb32(s, index, pixels, stride_px); });
   TM_HIP(hipSetDevice(e->device));
   const size_t fbytes = (size_t)e->width * e->height * 4;
   e->frames_host = nullptr;
+  e->frames_peer = nullptr;
   e->hclip_cur = -1;
   if (!e->frames_owned.p || e->frames != e->frames_owned.p) {
     TM_TRY(e->frames_owned.alloc(fbytes * e->nframes));
@@ -1717,9 +2000,18 @@ int tm_push_frame_rgb32(tm_encoder *e, int index, const uint32_t *pixels, int st
 int tm_set_frames_device(tm_encoder *e, const void *dev_frames) {
   TM_CHECK(e && dev_frames, TM_E_INVAL, "null argument");
   TM_CHECK(e->nframes > 0, TM_E_INVAL, "tm_set_video has not been called");
+  if (e->grp) {  // the clip lives on the first listed device: shards there read it, shards elsewhere pull what their Load reads
+    const int home = e->grp->devices[0];
+    return group_each(e, [=](tm_encoder *s) -> int {
+      TM_TRY(tm_set_frames_device(s, dev_frames));
+      if (s->device != home) { s->frames = nullptr; s->frames_peer = dev_frames; s->frames_peer_dev = home; }
+      return (int)TM_OK;
+    });
+  }
   e->frames_owned.release();
   e->frames = dev_frames;
   e->frames_host = nullptr;
+  e->frames_peer = nullptr;
   e->hclip_cur = -1;
   return TM_OK;
 }
@@ -1727,6 +2019,8 @@ int tm_set_frames_device(tm_encoder *e, const void *dev_frames) {
 int tm_set_frames_host(tm_encoder *e, const uint32_t *host_frames) {
   TM_CHECK(e && host_frames, TM_E_INVAL, "null argument");
   TM_CHECK(e->nframes > 0, TM_E_INVAL, "tm_set_video has not been called");
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_set_frames_host(s, host_frames); });  // every shard loads the whole clip
+  e->frames_peer = nullptr;
   e->frames_host = host_frames;
   e->frames = nullptr;
   e->hclip_cur = -1;
@@ -1736,6 +2030,7 @@ int tm_set_frames_host(tm_encoder *e, const uint32_t *host_frames) {
 int tm_prefetch_frames_host(tm_encoder *e, const uint32_t *host_frames) {
   TM_CHECK(e && host_frames, TM_E_INVAL, "null argument");
   TM_CHECK(e->nframes > 0, TM_E_INVAL, "tm_set_video has not been called");
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_prefetch_frames_host(s, host_frames); });
   TM_HIP(hipSetDevice(e->device));
   // the buffer to fill: one that neither holds a clip waiting for its Load nor the clip the steps in flight may still read from --
   // unless both are taken, in which case the clip of the last Load gives way (its steps have returned: tm_run blocks)
@@ -1755,6 +2050,16 @@ int tm_prefetch_frames_host(tm_encoder *e, const uint32_t *host_frames) {
 int tm_run(tm_encoder *e, int step) {
   TM_CHECK(e, TM_E_INVAL, "null encoder");
   knobs_reload();  // the environment switches are sampled here, once per Run; the steps read the sampled set
+  if (e->grp) {  // every step on every shard at once; Save is shard 0's (every shard holds the merged state)
+    if (step == TM_STEP_ALL) {
+      for (int s = TM_STEP_LOAD; s <= TM_STEP_REINDEX; s++) TM_TRY(group_run_step(e, s));
+      if (!e->s.OutputFileName.empty()) TM_TRY(run_step(e, TM_STEP_SAVE));
+      return TM_OK;
+    }
+    if (step == TM_STEP_SAVE) return run_step(e, step);
+    TM_CHECK(step >= TM_STEP_LOAD && step < TM_STEP_SAVE, TM_E_INVAL, "bad step %d", step);
+    return group_run_step(e, step);
+  }
   if (step == TM_STEP_ALL) {  // Run(esAll): every step in order (5535-5553); Save only once an output name is set
     for (int s = TM_STEP_LOAD; s <= TM_STEP_REINDEX; s++) TM_TRY(run_step(e, s));
     if (!e->s.OutputFileName.empty()) TM_TRY(run_step(e, TM_STEP_SAVE));
@@ -1911,10 +2216,9 @@ int tm_get_stage_ms(tm_encoder *e, double ms[8]) {
 
 int tm_set_query_shard(tm_encoder *e, int first_frame, int frame_count) {
   TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_CHECK(!e->grp, TM_E_INVAL, "tm_set_query_shard: a device group shards by itself");
   TM_CHECK(first_frame >= 0, TM_E_INVAL, "bad shard");
-  if (first_frame != e->shard_first || frame_count != e->shard_count) e->qf_valid = false;  // prefetched for the old range (freed with the next Load / Reconstruct)
-  e->shard_first = first_frame;
-  e->shard_count = frame_count;
+  set_query_shard(e, first_frame, frame_count);
   return TM_OK;
 }
 
@@ -1939,6 +2243,7 @@ int tm_comm_init(tm_encoder *e, const uint8_t id[TM_COMM_ID_BYTES], int rank, in
   TM_CHECK(e && id, TM_E_INVAL, "null argument");
   TM_CHECK(world >= 1 && rank >= 0 && rank < world, TM_E_INVAL, "bad process %d of %d", rank, world);
   TM_CHECK(e->comm == nullptr, TM_E_INVAL, "tm_comm_init: this encoder already has a communicator (tm_comm_destroy first)");
+  TM_CHECK(!e->grp, TM_E_INVAL, "tm_comm_init: the encoder is a device group (tm_set_devices), which carries its own collectives");
   knobs_reload();
   TM_HIP(hipSetDevice(e->device));
   ncclUniqueId u;
@@ -2007,6 +2312,7 @@ int tm_set_collective(tm_encoder *e, int rank, int world, tm_collective_cb cb, v
   TM_CHECK(e, TM_E_INVAL, "null encoder");
   TM_CHECK(world >= 1 && rank >= 0 && rank < world && (cb != nullptr || world == 1), TM_E_INVAL, "bad process %d of %d", rank, world);
   TM_CHECK(e->comm == nullptr, TM_E_INVAL, "tm_set_collective: the encoder has a native communicator (tm_comm_destroy first)");
+  TM_CHECK(!e->grp, TM_E_INVAL, "tm_set_collective: the encoder is a device group (tm_set_devices), which carries its own collectives");
   e->coll_stream_ordered = false;  // mode 0 until tm_set_collective_mode says otherwise
   e->coll_cb = world > 1 ? cb : nullptr;
   e->coll_user = user;
@@ -2021,6 +2327,7 @@ int tm_set_collective(tm_encoder *e, int rank, int world, tm_collective_cb cb, v
 
 int tm_set_dither_shard(tm_encoder *e, int rank, int world) {
   TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_CHECK(!e->grp, TM_E_INVAL, "tm_set_dither_shard: a device group shards by itself");
   TM_CHECK(world >= 1 && rank >= 0 && rank < world, TM_E_INVAL, "bad dither shard %d of %d", rank, world);
   e->dither_rank = rank;
   e->dither_world = world;
@@ -2089,6 +2396,7 @@ int tm_get_knn_stats(tm_encoder *e, double *kernel_ms, int64_t *pairs, int *laun
 int tm_reload_gtm(tm_encoder *e, const char *path) {  // ReloadGTM, tilingencoder.pas:2059 -> LoadStream, 4880-5175
   TM_CHECK(e && path, TM_E_INVAL, "null argument");
   TM_CHECK(e->nframes > 0 && e->width > 0, TM_E_INVAL, "tm_set_video has not been called");
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_reload_gtm(s, path); });
   GtmLoaded g;
   TM_TRY(read_gtm(path, &g));
   // "Mismatch between GTM and loaded video!" (5021-5032)
@@ -2196,6 +2504,23 @@ static int render_input_src(tm_encoder *e, int first, int count, RenderInput *in
 int tm_render_frames(tm_encoder *e, int first_frame, int frame_count, int input, void *out, int out_on_device) {
   TM_CHECK(e && out, TM_E_INVAL, "null argument");
   TM_TRY(render_range_ok(e, first_frame, frame_count));
+  if (e->grp && input && e->load_sharded && frame_count > 0) {
+    // the source frames of a sharded Load: every shard draws the piece of the range it loaded
+    const std::vector<Piece> pc = group_pieces(e, first_frame, frame_count);
+    const size_t fb = (size_t)e->tm_w * 8 * e->tm_h * 8 * 4;
+    const int home = e->device;
+    return group_each(e, [&](tm_encoder *s) -> int {
+      const Piece p = pc[(size_t)s->co.rank];
+      if (p.count == 0) return TM_OK;
+      uint8_t *dst = (uint8_t *)out + fb * (size_t)(p.first - first_frame);
+      if (!out_on_device || s->device == home) return tm_render_frames(s, p.first, p.count, 1, dst, out_on_device);
+      DevBuf tmp;  // another device: drawn here, then copied to the caller's device
+      TM_TRY(tmp.alloc(fb * p.count));
+      TM_TRY(tm_render_frames(s, p.first, p.count, 1, tmp.p, 1));
+      TM_HIP(hipMemcpyPeer(dst, home, tmp.p, s->device, fb * p.count));
+      return TM_OK;
+    });
+  }
   TM_HIP(hipSetDevice(e->device));
   RenderMap m{};
   RenderInput in{};
@@ -2220,6 +2545,18 @@ int tm_get_frame_quality(tm_encoder *e, int first_frame, int frame_count, uint64
   TM_CHECK(e, TM_E_INVAL, "null encoder");
   TM_TRY(render_range_ok(e, first_frame, frame_count));
   TM_CHECK(frame_count > 0, TM_E_INVAL, "frame quality: no frames");
+  std::vector<uint64_t> h_sse((size_t)frame_count * 3);
+  std::vector<double> h_ssim((size_t)frame_count);
+  if (e->grp && e->load_sharded) {
+    // a sharded Load: every shard measures the piece of the range it loaded, the frames' sums are combined below in frame order
+    const std::vector<Piece> pc = group_pieces(e, first_frame, frame_count);
+    TM_TRY(group_each(e, [&](tm_encoder *s) {
+      const Piece p = pc[(size_t)s->co.rank];
+      if (p.count == 0) return (int)TM_OK;
+      const size_t off = (size_t)(p.first - first_frame);
+      return tm_get_frame_quality(s, p.first, p.count, h_sse.data() + off * 3, nullptr, h_ssim.data() + off, nullptr, nullptr);
+    }));
+  } else {
   TM_HIP(hipSetDevice(e->device));
   RenderMap m{};
   RenderInput in{};
@@ -2229,11 +2566,10 @@ int tm_get_frame_quality(tm_encoder *e, int first_frame, int frame_count, uint64
   TM_TRY(d_sse.alloc((size_t)frame_count * 3 * 8));
   TM_TRY(d_ssim.alloc((size_t)frame_count * 8));
   TM_TRY(launch_quality_render(in, m, first_frame, frame_count, d_sse.p, d_ssim.p, e->stream));
-  std::vector<uint64_t> h_sse((size_t)frame_count * 3);
-  std::vector<double> h_ssim((size_t)frame_count);
   TM_HIP(hipMemcpyAsync(h_sse.data(), d_sse.p, h_sse.size() * 8, hipMemcpyDeviceToHost, e->stream));
   TM_HIP(hipMemcpyAsync(h_ssim.data(), d_ssim.p, h_ssim.size() * 8, hipMemcpyDeviceToHost, e->stream));
   TM_HIP(hipStreamSynchronize(e->stream));
+  }
   // PSNR = 10 log10(3 W H 255^2 / SSE) over the three channels; the clip's from the summed SSE, its SSIM the mean of the frames'
   const double peak = 3.0 * (e->tm_w * 8) * (e->tm_h * 8) * 255.0 * 255.0;
   auto to_psnr = [](double top, uint64_t err) { return err ? 10.0 * std::log10(top / (double)err) : HUGE_VAL; };
@@ -2250,6 +2586,27 @@ int tm_get_frame_quality(tm_encoder *e, int first_frame, int frame_count, uint64
   if (clip_psnr) *clip_psnr = to_psnr(peak * frame_count, total);
   if (clip_ssim_y) *clip_ssim_y = ssum / frame_count;
   return TM_OK;
+}
+
+int tm_set_devices(tm_encoder *e, const int *devices, int n) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_CHECK(devices && n >= 1 && n <= GROUP_MAX, TM_E_INVAL, "tm_set_devices: %d devices (1 .. %d)", n, GROUP_MAX);
+  const int nd = tm_device_count();
+  for (int i = 0; i < n; i++) TM_CHECK(devices[i] >= 0 && devices[i] < nd, TM_E_INVAL, "tm_set_devices: device %d outside 0 .. %d", devices[i], nd - 1);
+  TM_CHECK(e->nframes == 0, TM_E_INVAL, "tm_set_devices: call it before tm_set_video");
+  TM_CHECK(!e->grp, TM_E_INVAL, "tm_set_devices: the encoder is already a device group");
+  TM_CHECK(e->coll_cb == nullptr && e->comm == nullptr, TM_E_INVAL, "tm_set_devices: the encoder has a communicator (tm_set_collective / tm_comm_init)");
+  if (n == 1) return tm_set_device(e, devices[0]);
+  return group_form(e, std::vector<int>(devices, devices + n));
+}
+
+int tm_set_device_mask(tm_encoder *e, uint32_t mask) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_CHECK(mask != 0, TM_E_INVAL, "tm_set_device_mask: empty mask");
+  std::vector<int> devs;
+  for (int d = 0; d < 32; d++)
+    if (mask & (1u << d)) devs.push_back(d);
+  return tm_set_devices(e, devs.data(), (int)devs.size());
 }
 
 }  // extern "C"

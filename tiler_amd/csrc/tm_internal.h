@@ -123,6 +123,20 @@ struct Collectives {
   std::function<int(const void *send, void *recv, int64_t bytes_per_rank)> allgather;  // recv: world x bytes_per_rank, rank order
 };
 
+// tm_group.hip: the in-process communicator of a device group (tm_set_devices).  Shard `rank` calls these from its own host thread with
+// its own stream; they drain the stream, wait for the other shards at host barriers and return with the result in place.
+constexpr int GROUP_MAX = 32;
+struct GroupComm;
+GroupComm *group_comm_create(const std::vector<int> &devices);
+void group_comm_destroy(GroupComm *g);
+void group_comm_reset(GroupComm *g);            // before a step, every shard idle: forget a failure of the last one
+void group_comm_abort(GroupComm *g, int rank);  // shard `rank` failed: every barrier of the group gives up at once
+int group_comm_broken_by(GroupComm *g);         // the shard that broke the group first, -1 if none
+int group_allreduce(GroupComm *g, int rank, int kind, void *buf, int64_t count, hipStream_t stream);   // kind: TM_COLL_ALLREDUCE_*
+int group_allgather(GroupComm *g, int rank, const void *send, void *recv, int64_t bytes, hipStream_t stream);
+// dst[i] = sum / max over the nsrc sources' element i (TM_COLL_ALLREDUCE_* kinds; int32 sums wrap around); dst may be one of the sources
+int launch_group_reduce(int kind, const void *const *srcs, int nsrc, int64_t n_elem, void *dst, hipStream_t stream);
+
 // tm_kmeans.hip
 // DoPalettization over `world` processes: every process holds the points of its own tile range (global index of the first:
 // global_begin); the farthest-first picks are settled by an all-gather of one candidate per process, the Lloyd iterations by

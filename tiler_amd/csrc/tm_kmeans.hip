@@ -36,7 +36,14 @@ typedef unsigned long long u64;
 // together, and two of them started from two host threads could each be dealt part of the CUs and wait for the rest for ever (until their
 // barriers give up).  Held from the launch to the read-back that ends it.  (Two PROCESSES on one device are not covered: there the barrier's
 // time limit and the launches-per-iteration path are the answer -- a development set-up, one process per device is the deployment.)
-static std::mutex g_resident_launch;
+// Keyed by device: a device group's shards on different devices run their replicated clusterings at the same time, shards on one device
+// take turns.
+static std::mutex g_resident_launch_dev[64];
+static std::mutex &resident_launch_lock() {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  return g_resident_launch_dev[dev & 63];
+}
 
 struct Seg {      // per segment state, device resident
   int64_t begin;  // first point
@@ -1973,7 +1980,7 @@ static int kmeans3_persistent(const int32_t *pts, const uint32_t *w, const std::
   TM_HIP(hipMemsetAsync(dstate.p, 0, sizeof(Seg3State) * hs.size(), stream));
   TM_HIP(hipMemsetAsync(dcent.p, 0, sizeof(double) * hs.size() * k * 3, stream));
   TM_CHECK(nblk >= 1 && k >= 1 && k <= P3_MAXK, TM_E_INVAL, "k-means: resident launch of %d workgroups for %d centres (at most %d)", nblk, k, P3_MAXK);
-  std::unique_lock<std::mutex> resident_lock(g_resident_launch);
+  std::unique_lock<std::mutex> resident_lock(resident_launch_lock());
   for (const auto &b : batches) {
     int grid = 0;
     for (size_t i = b.first; i < b.second; i++) grid += hs[i].blk_count;
@@ -2167,7 +2174,7 @@ static int kmeans_batched(const int32_t *pts, const uint32_t *w, int d, const st
       DevBuf hstate;
       TM_TRY(hstate.alloc(sizeof(HrState)));
       TM_HIP(hipMemsetAsync(hstate.p, 0, sizeof(HrState), stream));
-      std::unique_lock<std::mutex> resident_lock(g_resident_launch);
+      std::unique_lock<std::mutex> resident_lock(resident_launch_lock());
       auto kres = rounds == 1 ? &k_h_resident<1> : &k_h_resident<2>;
       static_assert(HR_MAXR == 2, "one instantiation per number of rounds");
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kres), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r_lds);

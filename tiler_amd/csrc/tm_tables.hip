@@ -157,8 +157,10 @@ void knobs_reload() {
   if (const char *v = getenv("TM_COMM_TIMEOUT_S")) k.comm_timeout_s = std::max(1.0, atof(v));
   if (const char *v = getenv("TM_DEDUP_RADIX_MIN")) k.dedup_radix_min = std::max(0ll, atoll(v));
   if (const char *v = getenv("TM_KNN_ARENA_ENTRIES")) k.knn_arena_entries = std::max(0ll, atoll(v));
+  if (const char *v = getenv("TM_GROUP_FAIL_SHARD")) k.group_fail_shard = atoi(v);
   t_knobs = k;
 }
+void knobs_set(const Knobs &k) { t_knobs = k; }
 
 int require_device() {
   knobs_reload();  // every compute entry point of the C ABI comes through here first

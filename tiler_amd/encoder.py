@@ -42,6 +42,8 @@ _ENC_SIGS = {
     "tm_create": (c_void_p, []),
     "tm_destroy": (None, [c_void_p]),
     "tm_set_device": (c_int, [c_void_p, c_int]),
+    "tm_set_device_mask": (c_int, [c_void_p, ctypes.c_uint32]),
+    "tm_set_devices": (c_int, [c_void_p, ctypes.POINTER(c_int), c_int]),
     "tm_load_default_settings": (c_int, [c_void_p]),
     "tm_load_settings_ini": (c_int, [c_void_p, c_char_p]),
     "tm_set_int": (c_int, [c_void_p, c_char_p, c_int64]),
@@ -158,6 +160,16 @@ class TilingEncoder:
         check(self._L.tm_load_settings_ini(c_void_p(self._h), str(path).encode()))
 
     # -- video
+    def SetDeviceMask(self, mask):
+        """One process, several devices (tm_set_device_mask): bit d = HIP device d; before SetVideo."""
+        check(self._L.tm_set_device_mask(c_void_p(self._h), ctypes.c_uint32(int(mask))))
+
+    def SetDevices(self, devices):
+        """The same with a list of devices, which may repeat (several shards on one device)."""
+        devs = [int(d) for d in devices]
+        arr = (c_int * max(1, len(devs)))(*devs)
+        check(self._L.tm_set_devices(c_void_p(self._h), arr, len(devs)))
+
     def SetVideo(self, width, height, fps, frame_count):
         check(self._L.tm_set_video(c_void_p(self._h), width, height, float(fps), frame_count))
 
