@@ -587,6 +587,13 @@ def test_y4m_and_png_export_show_what_the_player_shows(oracle, tmp_path, radius)
     got = y4m_frames(y4i)
     for f in range(6):
         assert np.array_equal(got[f], to_yuv(np.asarray(src[f], np.uint32)))
+    # after ReloadGTM the frame tiles are not this stream's source: the input export is refused, as RenderFrames(input=True) is, and no file is left
+    from tiler_amd._lib import TileMotionError
+    enc.ReloadGTM(out)
+    y4r = tmp_path / "reloaded_in.y4m"
+    with pytest.raises(TileMotionError) as ei:
+        enc.GenerateY4M(str(y4r), True)
+    assert ei.value.code == -1 and not y4r.exists()
     enc.close()
 
 

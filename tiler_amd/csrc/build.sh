@@ -6,12 +6,14 @@ OUT="$HERE/../lib"
 mkdir -p "$OUT" "$HERE/.obj"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fvisibility=hidden -Wall -Wno-unused-function ${TM_EXTRA_FLAGS:-}"
+JOBS="${MAX_JOBS:-16}"  # concurrent compiles
 pids=()
 objs=()
 for src in "$HERE"/*.hip; do
   obj="$HERE/.obj/$(basename "${src%.hip}").o"
   objs+=("$obj")
   if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ -n "$(find "$HERE" "$HERE/../../include" -name '*.h' -newer "$obj" 2>/dev/null | head -1)" ]; then
+    if [ "${#pids[@]}" -ge "$JOBS" ]; then wait "${pids[0]}"; pids=("${pids[@]:1}"); fi
     $HIPCC $FLAGS -c "$src" -o "$obj" &
     pids+=($!)
   fi

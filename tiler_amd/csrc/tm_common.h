@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -138,5 +139,8 @@ extern const double kDCTWeights[3][8][8];
 
 inline bool mode_special(int mode) { return mode == TM_PVS_SPE_DCT || mode == TM_PVS_WEIGHTED_SPE_DCT; }
 inline bool mode_weighted(int mode) { return mode == TM_PVS_WEIGHTED_DCT || mode == TM_PVS_WEIGHTED_SPE_DCT; }
+
+// workgroups of 256 for a grid-stride loop over n items: one per 256 items, at most 4096
+inline int gridn(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 16)); }
 
 }  // namespace tmx

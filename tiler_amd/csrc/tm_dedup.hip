@@ -427,8 +427,6 @@ __global__ void k_remap(const uint32_t *__restrict__ rep, const int32_t *__restr
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) remap[i] = pos[rep[i]];
 }
 
-static inline int gridn(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 16)); }
-
 // m keys (prefix, row) into content order; the rows of that order to out_rows
 static int sort_prefix_keys(DevBuf &pk, int64_t m, const RowLess &less, uint32_t *out_rows, DevBuf &tmp, hipStream_t stream) {
   if (m <= 0) return TM_OK;

@@ -1,0 +1,374 @@
+// tm_export.hip -- what leaves the encoder as files or pictures: Save (.gtm), ReloadGTM, GenerateY4M / GeneratePNGs, and the device
+// render entry points tm_render_frames / tm_get_frame_quality (kernels in tm_render.hip).
+#include <cmath>
+#include <fstream>
+
+#include "tm_encoder.h"
+
+int save_to(tm_encoder *e, const char *path) {  // Save, tilingencoder.pas:2040-2058 -> SaveStream, 5177
+  TM_TRY(need(e, TM_STEP_REINDEX, "Reindex"));
+  TM_CHECK(path && *path, TM_E_INVAL, "Save: no output file name");
+  TM_TRY(load_tail(e));
+  TM_HIP(hipSetDevice(e->device));
+  GtmInput in;
+  in.tm_w = e->tm_w; in.tm_h = e->tm_h; in.nframes = e->nframes; in.fps = e->fps;
+  in.kf_start = e->kf_start;
+  std::vector<uint8_t> pal_px((size_t)e->t * 64);
+  in.use.resize((size_t)e->t);
+  if (e->t) {
+    TM_HIP(hipMemcpy(pal_px.data(), e->gpal_px.p, pal_px.size(), hipMemcpyDeviceToHost));
+    TM_HIP(hipMemcpy(in.use.data(), e->guse.p, (size_t)e->t * 4, hipMemcpyDeviceToHost));
+  }
+  in.pal_px = pal_px.data();
+  in.palettes = e->palettes_host.data();
+  in.pal_count = e->s.PaletteCount; in.pal_size = e->s.PaletteSize;
+  std::vector<tm_tilemap_item> tmi((size_t)e->q);
+  TM_TRY(tm_get_tilemaps(e, 0, e->nframes, tmi.data()));
+  in.tilemap = tmi.data();
+  in.settings = settings_text(e->s);
+  return write_gtm(path, in);
+}
+
+// ---- the decoded frames on the device (tm_render.hip): what tm_render_frames, tm_get_frame_quality and the exports draw
+static int render_range_ok(tm_encoder *e, int first, int count) {
+  TM_CHECK(e->nframes > 0 && first >= 0 && count >= 0 && (int64_t)first + count <= e->nframes, TM_E_INVAL, "frame range [%d,+%d) outside 0..%d",
+           first, count, e->nframes);
+  return TM_OK;
+}
+static int render_output_map(tm_encoder *e, RenderMap *m) {
+  TM_CHECK(e->has_pal_px && (e->steps_done & (1 << TM_STEP_RECONSTRUCT)) && e->tm_tile.p && e->tm_pal.p && e->fflags.p && e->palettes_dev.p, TM_E_INVAL,
+           "output frames: Reconstruct (or ReloadGTM) has not been run");
+  const bool pm = e->has_pm && e->tm_pred.p && e->tm_px.p && e->tm_py.p;
+  // (the palettes as made: a PaletteCount set since then does not reach past them)
+  const int npal = (int)std::min<int64_t>(e->s.PaletteCount, (int64_t)e->palettes_host.size() / std::max(1, e->s.PaletteSize));
+  *m = RenderMap{e->tm_tile.as<int32_t>(), e->tm_pal.as<int32_t>(), e->fflags.as<uint8_t>(), pm ? e->tm_pred.as<uint8_t>() : nullptr, 0xff,
+                 pm ? e->tm_px.as<int8_t>() : nullptr, pm ? e->tm_py.as<int8_t>() : nullptr, e->gpal_px.as<uint8_t>(), e->t,
+                 e->palettes_dev.as<int32_t>(), npal, e->s.PaletteSize, e->tm_w, e->tm_h};
+  return TM_OK;
+}
+static int render_input_src(tm_encoder *e, int first, int count, RenderInput *in) {
+  TM_CHECK(e->src_tiles && (e->steps_done & (1 << TM_STEP_LOAD)) && e->ftiles.p && e->fflags.p, TM_E_INVAL,
+           "source frames: the frame tiles are not in memory (run Load; ReloadGTM does not bring them)");
+  TM_CHECK(!e->load_sharded || (first >= e->load_first && first + count <= e->load_first + e->load_count), TM_E_INVAL,
+           "source frames: this process's Load kept frames [%d,+%d) only, not [%d,+%d)", e->load_first, e->load_count, first, count);
+  *in = RenderInput{e->ftiles.as<uint32_t>(), e->fflags.as<uint8_t>(), e->tm_w, e->tm_h};
+  return TM_OK;
+}
+
+// ---- GenerateY4M / GeneratePNGs (tilingencoder.pas:2126-2199, 2075-2124): the frames as Render (3455-3640) draws them with the
+// constructor's defaults (FRenderPredicted, FRenderMirrored, FRenderOutputDithered on, no gamma: 5505-5507) -- the device render's
+// pictures, brought to the host a chunk of frames at a time.  An export refuses exactly what the device render of the whole clip refuses
+// (init, before any file is opened: a refused call leaves no file behind).  In a device group it reads shard 0, the front encoder.
+namespace {
+struct ExportFrames {
+  tm_encoder *e;
+  bool input;
+  RenderMap m{};
+  RenderInput in{};
+  int sw = 0, sh = 0, chunk = 0, first = 0, count = 0;
+  DevBuf dev;
+  std::vector<uint32_t> host;  // frames [first, first + count), 0x00RRGGBB
+  int init() {
+    TM_HIP(hipSetDevice(e->device));
+    if (input) TM_TRY(render_input_src(e, 0, e->nframes, &in));
+    else TM_TRY(render_output_map(e, &m));
+    sw = e->tm_w * 8; sh = e->tm_h * 8;
+    const size_t fbytes = (size_t)sw * sh * 4;
+    chunk = (int)std::max<size_t>(1, std::min<size_t>(32, ((size_t)256 << 20) / fbytes));  // 32 frames or 256 MB, whichever is less
+    TM_TRY(dev.alloc(fbytes * chunk));
+    host.resize((size_t)sw * sh * chunk);
+    return TM_OK;
+  }
+  int frame(int f, const uint32_t **px) {  // frames are asked for in order
+    if (f >= first + count) {
+      first = f;
+      count = std::min(chunk, e->nframes - f);
+      TM_TRY(input ? launch_render_input(in, first, count, dev.p, e->stream) : launch_render_output(m, first, count, dev.p, e->stream));
+      TM_HIP(hipMemcpyAsync(host.data(), dev.p, (size_t)count * sw * sh * 4, hipMemcpyDeviceToHost, e->stream));
+      TM_HIP(hipStreamSynchronize(e->stream));
+    }
+    *px = host.data() + (size_t)(f - first) * sw * sh;
+    return TM_OK;
+  }
+};
+
+uint32_t crc32_of(const uint8_t *p, size_t n, uint32_t crc) {
+  static uint32_t table[256];
+  static bool made = false;
+  if (!made) {
+    for (uint32_t i = 0; i < 256; i++) { uint32_t c = i; for (int k = 0; k < 8; k++) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1; table[i] = c; }
+    made = true;
+  }
+  crc = ~crc;
+  for (size_t i = 0; i < n; i++) crc = table[(crc ^ p[i]) & 0xff] ^ (crc >> 8);
+  return ~crc;
+}
+void png_chunk(std::vector<uint8_t> &out, const char *type, const std::vector<uint8_t> &data) {
+  auto be32 = [&](uint32_t v) { out.push_back(v >> 24); out.push_back(v >> 16); out.push_back(v >> 8); out.push_back(v); };
+  be32((uint32_t)data.size());
+  const size_t at = out.size();
+  out.insert(out.end(), type, type + 4);
+  out.insert(out.end(), data.begin(), data.end());
+  be32(crc32_of(out.data() + at, out.size() - at, 0));
+}
+// 24-bit RGB PNG (pf24bit, 2086) of 0x00RRGGBB pixels; the image data travels in stored deflate blocks: valid for every decoder, no codec dependency
+int write_png(const std::string &path, const uint32_t *img, int w, int h) {
+  std::vector<uint8_t> raw((size_t)h * (1 + (size_t)w * 3));
+  for (int y = 0; y < h; y++) {
+    uint8_t *row = &raw[(size_t)y * (1 + (size_t)w * 3)];
+    row[0] = 0;  // filter: none
+    for (int x = 0; x < w; x++) { const uint32_t c = img[(size_t)y * w + x]; row[1 + x * 3] = (c >> 16) & 0xff; row[2 + x * 3] = (c >> 8) & 0xff; row[3 + x * 3] = c & 0xff; }
+  }
+  std::vector<uint8_t> z = {0x78, 0x01};
+  uint32_t a = 1, b = 0;
+  for (uint8_t v : raw) { a = (a + v) % 65521u; b = (b + a) % 65521u; }
+  for (size_t off = 0; off < raw.size() || off == 0; off += 65535) {
+    const size_t n = std::min<size_t>(65535, raw.size() - off);
+    z.push_back(off + n >= raw.size() ? 1 : 0);
+    z.push_back(n & 0xff); z.push_back(n >> 8); z.push_back(~n & 0xff); z.push_back((~n >> 8) & 0xff);
+    z.insert(z.end(), raw.begin() + off, raw.begin() + off + n);
+    if (raw.empty()) break;
+  }
+  z.push_back(b >> 8); z.push_back(b); z.push_back(a >> 8); z.push_back(a);
+  std::vector<uint8_t> out = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+  std::vector<uint8_t> ihdr = {(uint8_t)(w >> 24), (uint8_t)(w >> 16), (uint8_t)(w >> 8), (uint8_t)w, (uint8_t)(h >> 24), (uint8_t)(h >> 16), (uint8_t)(h >> 8), (uint8_t)h, 8, 2, 0, 0, 0};
+  png_chunk(out, "IHDR", ihdr);
+  png_chunk(out, "IDAT", z);
+  png_chunk(out, "IEND", {});
+  std::ofstream f(path, std::ios::binary);
+  TM_CHECK(f.good(), TM_E_IO, "cannot write %s", path.c_str());
+  f.write((const char *)out.data(), (std::streamsize)out.size());
+  return TM_OK;
+}
+std::string strip_ext(const std::string &p) {  // ChangeFileExt(name, '')
+  const size_t dot = p.find_last_of('.'), sep = p.find_last_of("/\\");
+  return (dot != std::string::npos && (sep == std::string::npos || dot > sep)) ? p.substr(0, dot) : p;
+}
+}  // namespace
+
+static int generate_y4m(tm_encoder *e, const char *path, bool input) {  // GenerateY4M, tilingencoder.pas:2126-2199
+  TM_CHECK(path && *path, TM_E_INVAL, "GenerateY4M: no file name");
+  ExportFrames r{e, input};
+  TM_TRY(r.init());
+  std::ofstream f(path, std::ios::binary);
+  TM_CHECK(f.good(), TM_E_IO, "cannot write %s", path);
+  char hdr[128];
+  snprintf(hdr, sizeof(hdr), "YUV4MPEG2 W%d H%d F%lld:1000000 Ip C444\n", r.sw, r.sh, (long long)std::nearbyint(e->fps * 1000000.0));  // 2146
+  f << hdr;
+  const size_t plane = (size_t)r.sw * r.sh;
+  std::vector<uint8_t> yuv(plane * 3);
+  auto rnd = [](float v, float add) { const long long q = (long long)std::nearbyint((double)(v + add)); return (uint8_t)std::min<long long>(255, std::max<long long>(0, q)); };
+  for (int fr = 0; fr < e->nframes; fr++) {
+    const uint32_t *px = nullptr;
+    TM_TRY(r.frame(fr, &px));
+    f << "FRAME \n";  // (with the space, 2161)
+    for (size_t i = 0; i < plane; i++) {
+      const uint32_t c = px[i];
+      const int rr = (c >> 16) & 0xff, gg = (c >> 8) & 0xff, bb = c & 0xff;
+      // RGBToYUV, utils.pas:478-490: the decimal constants are doubles, every right-hand side narrows to Single once
+      const float yy = (float)(rr * (299.0 / 1000) + gg * (587.0 / 1000) + bb * (114.0 / 1000));
+      const float uu = (float)(((double)bb - (double)yy) * 0.492), vv = (float)(((double)rr - (double)yy) * 0.877);
+      yuv[i] = rnd(yy, 0.0f);
+      yuv[plane + i] = rnd(uu, 128.0f);      // uf - Low(ShortInt)
+      yuv[2 * plane + i] = rnd(vv, 128.0f);
+    }
+    f.write((const char *)yuv.data(), (std::streamsize)yuv.size());
+    if ((fr & 15) == 15) progress(e, TM_STEP_SAVE, fr, e->nframes);
+  }
+  TM_CHECK(f.good(), TM_E_IO, "write to %s failed", path);
+  return TM_OK;
+}
+
+static int generate_pngs(tm_encoder *e, bool input) {  // GeneratePNGs, tilingencoder.pas:2075-2124
+  TM_CHECK(!e->s.OutputFileName.empty(), TM_E_INVAL, "GeneratePNGs: OutputFileName is not set");
+  ExportFrames r{e, input};
+  TM_TRY(r.init());
+  const std::string base = strip_ext(e->s.OutputFileName);
+  {
+    std::ofstream pf(base + ".txt");  // the palettes, one colour per line: IntToHex($ff000000 or PaletteRGB, 8) (2101-2104)
+    TM_CHECK(pf.good(), TM_E_IO, "cannot write %s.txt", base.c_str());
+    char line[16];
+    for (int32_t c : e->palettes_host) { snprintf(line, sizeof(line), "%08X", 0xff000000u | (uint32_t)c); pf << line << "\n"; }
+  }
+  for (int fr = 0; fr < e->nframes; fr++) {
+    const uint32_t *px = nullptr;
+    TM_TRY(r.frame(fr, &px));
+    char name[32];
+    snprintf(name, sizeof(name), "_%04d.png", fr);
+    TM_TRY(write_png(base + name, px, r.sw, r.sh));
+  }
+  return TM_OK;
+}
+
+extern "C" {
+
+int tm_reload_gtm(tm_encoder *e, const char *path) {  // ReloadGTM, tilingencoder.pas:2059 -> LoadStream, 4880-5175
+  TM_CHECK(e && path, TM_E_INVAL, "null argument");
+  TM_CHECK(e->nframes > 0 && e->width > 0, TM_E_INVAL, "tm_set_video has not been called");
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_reload_gtm(s, path); });
+  GtmLoaded g;
+  TM_TRY(read_gtm(path, &g));
+  // "Mismatch between GTM and loaded video!" (5021-5032)
+  TM_CHECK(g.header_frames < 0 || (g.header_frames == e->nframes && g.header_w == e->tm_w * 8 && g.header_h == e->tm_h * 8), TM_E_INVAL,
+           "mismatch between GTM (%d frames, %dx%d) and loaded video (%d frames, %dx%d)", g.header_frames, g.header_w, g.header_h, e->nframes,
+           e->tm_w * 8, e->tm_h * 8);
+  TM_CHECK(g.nframes == e->nframes && g.tm_w == e->tm_w && g.tm_h == e->tm_h, TM_E_INVAL, "GTM stream does not match the loaded video");
+  TM_HIP(hipSetDevice(e->device));
+  const int64_t q = (int64_t)e->nframes * e->tm_size(), T = (int64_t)g.use.size();
+  e->q = q; e->t = T; e->fps = g.fps;
+  e->s.PaletteSize = g.pal_size; e->s.PaletteCount = std::max(1, g.pal_count);
+  TM_TRY(load_tail(e));  // (not after these lines: a pending tail would put Load's key frames over the stream's)
+  e->kf_start = g.kf_start;
+  e->correl.assign((size_t)e->nframes, 0.0f);
+  e->palettes_host.assign(g.palettes.begin(), g.palettes.end());
+  e->palettes_host.resize((size_t)e->s.PaletteCount * e->s.PaletteSize, 0);
+  TM_TRY(e->palettes_dev.alloc(e->palettes_host.size() * 4));
+  TM_HIP(hipMemcpy(e->palettes_dev.p, e->palettes_host.data(), e->palettes_host.size() * 4, hipMemcpyHostToDevice));
+  e->pair_keys_n = 0;
+  TM_TRY(e->gtiles.alloc((size_t)std::max<int64_t>(T, 1) * 256)); TM_TRY(e->gpal_px.alloc((size_t)std::max<int64_t>(T, 1) * 64));
+  TM_TRY(e->gflags.alloc((size_t)std::max<int64_t>(T, 1))); TM_TRY(e->guse.alloc((size_t)std::max<int64_t>(T, 1) * 4));
+  TM_TRY(e->gpal_idx.alloc((size_t)std::max<int64_t>(T, 1) * 4));
+  TM_HIP(hipMemset(e->gtiles.p, 0, (size_t)std::max<int64_t>(T, 1) * 256));  // the stream carries no RGB pixels (HasRGBPixels = False, 4937)
+  TM_HIP(hipMemset(e->gflags.p, 0, (size_t)std::max<int64_t>(T, 1)));
+  TM_HIP(hipMemset(e->gpal_idx.p, 0xff, (size_t)std::max<int64_t>(T, 1) * 4));
+  if (T) {
+    TM_HIP(hipMemcpy(e->gpal_px.p, g.pal_px.data(), (size_t)T * 64, hipMemcpyHostToDevice));
+    TM_HIP(hipMemcpy(e->guse.p, g.use.data(), (size_t)T * 4, hipMemcpyHostToDevice));
+  }
+  std::vector<int32_t> ti((size_t)q), pi((size_t)q);
+  std::vector<uint32_t> er((size_t)q, 0xffffffffu);
+  std::vector<int8_t> px((size_t)q), py((size_t)q);
+  std::vector<uint8_t> pr((size_t)q);
+  e->h_fflags.assign((size_t)q, 0);
+  for (int64_t i = 0; i < q; i++) {
+    const tm_tilemap_item &it = g.tilemap[(size_t)i];
+    ti[(size_t)i] = it.TileIdx; pi[(size_t)i] = it.PalIdx; px[(size_t)i] = it.PredictedX; py[(size_t)i] = it.PredictedY;
+    pr[(size_t)i] = (it.Flags & 4) ? 1 : 0;
+    e->h_fflags[(size_t)i] = (uint8_t)(it.Flags & 3);
+  }
+  TM_TRY(e->tm_tile.alloc((size_t)q * 4)); TM_TRY(e->tm_pal.alloc((size_t)q * 4)); TM_TRY(e->tm_err.alloc((size_t)q * 4));
+  TM_TRY(e->tm_px.alloc((size_t)q)); TM_TRY(e->tm_py.alloc((size_t)q)); TM_TRY(e->tm_pred.alloc((size_t)q)); TM_TRY(e->pm_err.alloc((size_t)q * 4));
+  TM_TRY(e->fflags.alloc((size_t)q));
+  TM_HIP(hipMemcpy(e->tm_tile.p, ti.data(), (size_t)q * 4, hipMemcpyHostToDevice));
+  TM_HIP(hipMemcpy(e->tm_pal.p, pi.data(), (size_t)q * 4, hipMemcpyHostToDevice));
+  TM_HIP(hipMemcpy(e->tm_err.p, er.data(), (size_t)q * 4, hipMemcpyHostToDevice));
+  TM_HIP(hipMemcpy(e->pm_err.p, er.data(), (size_t)q * 4, hipMemcpyHostToDevice));
+  TM_HIP(hipMemcpy(e->tm_px.p, px.data(), (size_t)q, hipMemcpyHostToDevice));
+  TM_HIP(hipMemcpy(e->tm_py.p, py.data(), (size_t)q, hipMemcpyHostToDevice));
+  TM_HIP(hipMemcpy(e->tm_pred.p, pr.data(), (size_t)q, hipMemcpyHostToDevice));
+  TM_HIP(hipMemcpy(e->fflags.p, e->h_fflags.data(), (size_t)q, hipMemcpyHostToDevice));
+  e->has_pm = true;
+  e->has_pal_px = true;
+  e->reconstructed = false;  // PSNR is not in the stream
+  e->src_tiles = false;      // (the mirror flags are the stream's now; the source frames need a Load)
+  e->gtiles_have_rgb = false;
+  e->drop_prefetch();
+  // every step's product the stream holds is in place: Save, Reindex and the read-back views work.  Steps that compute from the frame
+  // tiles or from RGB pixels check for them (need_frame_tiles / need_global_rgb) and ask for Load / Reduce when they are missing.
+  e->steps_done = 0xff;
+  return TM_OK;
+}
+
+int tm_generate_y4m(tm_encoder *e, const char *path, int input) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  return generate_y4m(e, path, input != 0);
+}
+
+int tm_generate_pngs(tm_encoder *e, int input) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  return generate_pngs(e, input != 0);
+}
+
+int tm_save_gtm(tm_encoder *e, const char *path) {
+  TM_CHECK(e && path, TM_E_INVAL, "null argument");
+  return save_to(e, path);
+}
+
+int tm_render_frames(tm_encoder *e, int first_frame, int frame_count, int input, void *out, int out_on_device) {
+  TM_CHECK(e && out, TM_E_INVAL, "null argument");
+  TM_TRY(render_range_ok(e, first_frame, frame_count));
+  if (e->grp && input && e->load_sharded && frame_count > 0) {
+    // the source frames of a sharded Load: every shard draws the piece of the range it loaded
+    const std::vector<Piece> pc = group_pieces(e, first_frame, frame_count);
+    const size_t fb = (size_t)e->tm_w * 8 * e->tm_h * 8 * 4;
+    const int home = e->device;
+    return group_each(e, [&](tm_encoder *s) -> int {
+      const Piece p = pc[(size_t)s->co.rank];
+      if (p.count == 0) return TM_OK;
+      uint8_t *dst = (uint8_t *)out + fb * (size_t)(p.first - first_frame);
+      if (!out_on_device || s->device == home) return tm_render_frames(s, p.first, p.count, 1, dst, out_on_device);
+      DevBuf tmp;  // another device: drawn here, then copied to the caller's device
+      TM_TRY(tmp.alloc(fb * p.count));
+      TM_TRY(tm_render_frames(s, p.first, p.count, 1, tmp.p, 1));
+      TM_HIP(hipMemcpyPeer(dst, home, tmp.p, s->device, fb * p.count));
+      return TM_OK;
+    });
+  }
+  TM_HIP(hipSetDevice(e->device));
+  RenderMap m{};
+  RenderInput in{};
+  if (input) TM_TRY(render_input_src(e, first_frame, frame_count, &in));
+  else TM_TRY(render_output_map(e, &m));
+  if (frame_count == 0) return TM_OK;
+  const size_t bytes = (size_t)frame_count * e->tm_w * 8 * e->tm_h * 8 * 4;
+  DevBuf tmp;
+  void *dst = out;
+  if (!out_on_device) {
+    TM_TRY(tmp.alloc(bytes));
+    dst = tmp.p;
+  }
+  TM_TRY(input ? launch_render_input(in, first_frame, frame_count, dst, e->stream) : launch_render_output(m, first_frame, frame_count, dst, e->stream));
+  if (!out_on_device) TM_HIP(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, e->stream));  // page-locked destination: one DMA
+  TM_HIP(hipStreamSynchronize(e->stream));
+  return TM_OK;
+}
+
+int tm_get_frame_quality(tm_encoder *e, int first_frame, int frame_count, uint64_t *sse, double *psnr, double *ssim_y, double *clip_psnr,
+                         double *clip_ssim_y) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_TRY(render_range_ok(e, first_frame, frame_count));
+  TM_CHECK(frame_count > 0, TM_E_INVAL, "frame quality: no frames");
+  std::vector<uint64_t> h_sse((size_t)frame_count * 3);
+  std::vector<double> h_ssim((size_t)frame_count);
+  if (e->grp && e->load_sharded) {
+    // a sharded Load: every shard measures the piece of the range it loaded, the frames' sums are combined below in frame order
+    const std::vector<Piece> pc = group_pieces(e, first_frame, frame_count);
+    TM_TRY(group_each(e, [&](tm_encoder *s) {
+      const Piece p = pc[(size_t)s->co.rank];
+      if (p.count == 0) return (int)TM_OK;
+      const size_t off = (size_t)(p.first - first_frame);
+      return tm_get_frame_quality(s, p.first, p.count, h_sse.data() + off * 3, nullptr, h_ssim.data() + off, nullptr, nullptr);
+    }));
+  } else {
+  TM_HIP(hipSetDevice(e->device));
+  RenderMap m{};
+  RenderInput in{};
+  TM_TRY(render_output_map(e, &m));
+  TM_TRY(render_input_src(e, first_frame, frame_count, &in));
+  DevBuf d_sse, d_ssim;
+  TM_TRY(d_sse.alloc((size_t)frame_count * 3 * 8));
+  TM_TRY(d_ssim.alloc((size_t)frame_count * 8));
+  TM_TRY(launch_quality_render(in, m, first_frame, frame_count, d_sse.p, d_ssim.p, e->stream));
+  TM_HIP(hipMemcpyAsync(h_sse.data(), d_sse.p, h_sse.size() * 8, hipMemcpyDeviceToHost, e->stream));
+  TM_HIP(hipMemcpyAsync(h_ssim.data(), d_ssim.p, h_ssim.size() * 8, hipMemcpyDeviceToHost, e->stream));
+  TM_HIP(hipStreamSynchronize(e->stream));
+  }
+  // PSNR = 10 log10(3 W H 255^2 / SSE) over the three channels; the clip's from the summed SSE, its SSIM the mean of the frames'
+  const double peak = 3.0 * (e->tm_w * 8) * (e->tm_h * 8) * 255.0 * 255.0;
+  auto to_psnr = [](double top, uint64_t err) { return err ? 10.0 * std::log10(top / (double)err) : HUGE_VAL; };
+  uint64_t total = 0;
+  double ssum = 0.0;
+  for (int f = 0; f < frame_count; f++) {
+    const uint64_t fe = h_sse[(size_t)f * 3] + h_sse[(size_t)f * 3 + 1] + h_sse[(size_t)f * 3 + 2];
+    total += fe;
+    ssum += h_ssim[(size_t)f];
+    if (psnr) psnr[f] = to_psnr(peak, fe);
+  }
+  if (sse) memcpy(sse, h_sse.data(), h_sse.size() * 8);
+  if (ssim_y) memcpy(ssim_y, h_ssim.data(), h_ssim.size() * 8);
+  if (clip_psnr) *clip_psnr = to_psnr(peak * frame_count, total);
+  if (clip_ssim_y) *clip_ssim_y = ssum / frame_count;
+  return TM_OK;
+}
+
+}  // extern "C"

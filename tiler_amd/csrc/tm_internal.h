@@ -119,8 +119,14 @@ int launch_quality_frames(const void *a, const void *b, int n, int w, int h, int
 // are made on the caller's thread with the encoder's stream idle, and return with the result in place.
 struct Collectives {
   int rank = 0, world = 1;
-  std::function<int(void *buf, int64_t count)> allreduce_sum_i32, allreduce_max_i32, allreduce_sum_i64;
-  std::function<int(const void *send, void *recv, int64_t bytes_per_rank)> allgather;  // recv: world x bytes_per_rank, rank order
+  // the transport (kind: TM_COLL_*): an all-reduce works in place on send (recv null), an all-gather puts world x count bytes into recv
+  std::function<int(int kind, const void *send, void *recv, int64_t count)> call;
+  int allreduce_sum_i32(void *buf, int64_t count) const { return call(TM_COLL_ALLREDUCE_SUM_I32, buf, nullptr, count); }
+  int allreduce_max_i32(void *buf, int64_t count) const { return call(TM_COLL_ALLREDUCE_MAX_I32, buf, nullptr, count); }
+  int allreduce_sum_i64(void *buf, int64_t count) const { return call(TM_COLL_ALLREDUCE_SUM_I64, buf, nullptr, count); }
+  int allgather(const void *send, void *recv, int64_t bytes_per_rank) const {  // recv: world x bytes_per_rank, rank order
+    return call(TM_COLL_ALLGATHER_BYTES, send, recv, bytes_per_rank);
+  }
 };
 
 // tm_group.hip: the in-process communicator of a device group (tm_set_devices).  Shard `rank` calls these from its own host thread with

@@ -2715,7 +2715,7 @@ int run_palettize_dist(const void *feat_local, const void *use_local, int64_t n,
                        const Collectives &co, hipStream_t stream) {
   TM_TRY(require_device());
   TM_CHECK(npal >= 1 && npal <= 65536, TM_E_INVAL, "PaletteCount %d outside 1..65536 (tilingencoder.pas:2959)", npal);
-  TM_CHECK(co.world >= 1 && co.allgather && co.allreduce_sum_i64, TM_E_INVAL, "palettize: collectives missing");
+  TM_CHECK(co.world >= 1 && co.call, TM_E_INVAL, "palettize: collectives missing");
   const int k = npal, d = 192;
   const int32_t *pts = (const int32_t *)feat_local;
   const uint32_t *w = (const uint32_t *)use_local;

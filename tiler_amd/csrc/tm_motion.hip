@@ -493,8 +493,6 @@ __global__ void k_mark_predicted(const uint32_t *__restrict__ pm_err, const uint
   }
 }
 
-static inline int gridn(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 16)); }
-
 }  // namespace
 
 int launch_motion_search(const void *cur, int tm_w, int tm_h, const void *win, int radius, void *best_err, void *px, void *py,

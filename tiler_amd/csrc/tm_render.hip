@@ -1,6 +1,6 @@
 // tm_render.hip -- the decoded frames on the device and their pixel-domain quality (PSNR, SSIM on luma) against the source.
 //
-// Render (tilingencoder.pas:3455-3640) with the constructor's defaults, as the host FrameRenderer of GenerateY4M / GeneratePNGs draws it:
+// Render (tilingencoder.pas:3455-3640) with the constructor's defaults, the pictures GenerateY4M / GeneratePNGs export (tm_export.hip):
 // a predicted item copies 8 x 8 pixels of the previous output frame at its (clamped) offset, any other item is its palette-index tile
 // (mirrored) looked up in its palette.  Pixels are 0x00RRGGBB, the format frames are pushed in.
 //
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void k_render_input(RenderInput in, int first,
 // tree, then frame_ssim_mean over the workgroups in order): the result does not depend on scheduling.  SSE goes through 64-bit integer atomics.
 constexpr int QB_R = 4, QB_C = 50;  // (QB_R + 1) * (QB_C + 1) = 255 blocks: one per thread
 
-// GenerateY4M's Y plane (tm_encoder.hip generate_y4m): RGBToYUV's y (utils.pas:478-490) in double narrowed to Single, rounded half to even
+// GenerateY4M's Y plane (tm_export.hip generate_y4m): RGBToYUV's y (utils.pas:478-490) in double narrowed to Single, rounded half to even
 __device__ __forceinline__ int luma_y4m(uint32_t c /* 0x00RRGGBB */) {
   const int r = (c >> 16) & 0xff, g = (c >> 8) & 0xff, b = c & 0xff;
   const float yy = (float)(r * (299.0 / 1000) + g * (587.0 / 1000) + b * (114.0 / 1000));
