@@ -318,7 +318,7 @@ __global__ void k_dd_mark(const uint32_t *__restrict__ tiles, const int32_t *__r
     if (!(*w & m)) atomicOr(w, m);  // (a stale read only repeats the atomic)
   }
 }
-// the same table from a list of distinct pixel keys (palette << 24 | G << 16 | R << 8 | B: QuantizeUsingYakmo's, tm_kmeans.hip)
+// the same table from a list of distinct pixel keys (palette << 24 | G << 16 | R << 8 | B: QuantizeUsingYakmo's, tm_palettize.hip)
 __global__ void k_dd_mark_keys(const unsigned long long *__restrict__ keys, int64_t nk, int npal, const uint8_t *__restrict__ cls, uint32_t *__restrict__ bits) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nk; i += (int64_t)gridDim.x * blockDim.x) {
     const unsigned long long k = keys[i];

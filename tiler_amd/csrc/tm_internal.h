@@ -143,7 +143,7 @@ int group_allgather(GroupComm *g, int rank, const void *send, void *recv, int64_
 // dst[i] = sum / max over the nsrc sources' element i (TM_COLL_ALLREDUCE_* kinds; int32 sums wrap around); dst may be one of the sources
 int launch_group_reduce(int kind, const void *const *srcs, int nsrc, int64_t n_elem, void *dst, hipStream_t stream);
 
-// tm_kmeans.hip
+// tm_palettize.hip (PreparePalettes) and tm_kmeans.hip (run_kmeans, run_kmeans_seeded, kmeans_run_stats)
 // DoPalettization over `world` processes: every process holds the points of its own tile range (global index of the first:
 // global_begin); the farthest-first picks are settled by an all-gather of one candidate per process, the Lloyd iterations by
 // an all-reduce of the exact integer sums, so every process ends with the same centroids and with the assignment of its own
