@@ -69,6 +69,8 @@
  *                           other processes or shards (120)
  *   TM_GROUP_FAIL_SHARD=<r> shard r of a device group fails with TM_E_INVAL ("forced") at the start of its next step, before it queues any work
  *                           (tests: the other shards must leave their collectives at once)
+ *   TM_INPUT_CHUNK_FRAMES=<n> Load reads a Y4M file n frames at a time instead of 16 MB worth (tests: 1, so that a small clip walks the two staging
+ *                           buffers many times)
  *   TM_POOL_GIB=<x>         cap of the device-memory pool a thread keeps (96); TM_HOST_THREADS=<n>: OptimizePalettes' helper threads
  *                           (both read once per process)
  */
@@ -171,6 +173,46 @@ TM_API int tm_set_frames_host(tm_encoder *, const uint32_t *host_frames);
  * Borrowed until the adopting Load has returned.  At most one clip can wait beside the one in flight (TM_E_INVAL otherwise);
  * with both buffers taken the clip of the LAST Load gives way, after which a Load without new frames fails ("no frames"). */
 TM_API int tm_prefetch_frames_host(tm_encoder *, const uint32_t *host_frames);
+/* The probe half of Load (:1764-1820): reads InputFileName, StartFrame, FrameCount and Scaling, does what tm_set_video(DstWidth, DstHeight,
+ * fps, frames) does and makes the file the encoder's frame source; tm_run(TM_STEP_LOAD) then decodes it into a device clip the encoder owns
+ * and goes on as if that clip had been set with tm_set_frames_device (a second Load without a new tm_open_input reads that clip again).
+ * With no video described yet and InputFileName set, Load calls it itself.  tm_set_video, tm_push_frame_rgb32 and tm_set_frames_* switch
+ * the source back to memory (and the key frames back to the automatic rule).
+ *   An existing file must be Y4M ('YUV4MPEG2 '): W, H, F num:den (fps = num / den), I and C tags, XCOLORRANGE=FULL|LIMITED; frames are
+ * found by walking their 'FRAME...' headers, a last frame cut short does not count.  8-bit C444, C422, C420jpeg (also no C tag), C420mpeg2,
+ * Cmono; Ip, I? or no I tag.  Anything else -- other layouts, deeper samples, interlaced video, a file that is not Y4M (FFmpeg stays out of
+ * scope: DESIGN.md sections 9, 17; convert with `ffmpeg -i ... -f yuv4mpegpipe`) -- is TM_E_UNSUPPORTED with the tag in the message.
+ * DstWidth = Round(W * Scaling), DstHeight = Round(H * Scaling), at least 1 (extern.pas:780-781); frames = the file's - StartFrame, or
+ * FrameCount when > 0 (:1778-1782); a range that runs past the file is TM_E_INVAL.  The planes are uploaded as they are; chroma
+ * upsampling, the Lanczos-3 resize (this build's integer rule, DESIGN.md section 17, in place of libswscale's: extern.pas:837-840) and
+ * YUV -> RGB run on the device (tm_stage_yuv_to_rgb32).
+ *   Otherwise the name is a Format pattern with one %d or %.Nd (%% = '%'): the PNG sequence Format(name, [i + StartFrame])
+ * (LoadInputVideo, :3340-3353), fps 24 (:1791), FrameCount <= 0 counts files up to the first gap (:1797-1806), the size is the first
+ * file's (:1813-1814; a later file of another size: TM_E_INVAL at Load), Scaling is ignored (:3347-3348).  Key frames are manual: frame 0
+ * and every frame i for which Format(ChangeFileExt(name, '.kf'), [i + StartFrame]) exists (FindKeyFrames(AManualMode), :3380-3384). */
+TM_API int tm_open_input(tm_encoder *);
+TM_API int tm_get_video(tm_encoder *, int *width, int *height, double *fps, int *frames); /* as tm_set_video / tm_open_input left them; any pointer may be NULL */
+/* How a Y4M clip's samples become RGB (not a settings key: the INI text is the reference's).  AUTO: BT601_FULL under XCOLORRANGE=FULL, else
+ * BT601_LIMITED (what FFmpeg assumes for an untagged file).  TILER: YUVToRGB(Y, U - 128, V - 128) (utils.pas:492-509), for files of
+ * tm_generate_y4m. */
+enum { TM_YUV_AUTO = 0, TM_YUV_BT601_LIMITED = 1, TM_YUV_BT601_FULL = 2, TM_YUV_TILER = 3 };
+TM_API int tm_set_input_yuv(tm_encoder *, int mode);
+enum { TM_INPUT_Y4M = 1, TM_INPUT_PNGS = 2 };
+/* chroma layouts: where the U / V samples sit among the luma samples (420jpeg: centred in both axes; 420mpeg2 and 422: on the even luma
+ * columns, 420mpeg2 centred vertically); odd luma sizes give planes of (n + 1) / 2 samples */
+enum { TM_CHROMA_444 = 0, TM_CHROMA_422 = 1, TM_CHROMA_420JPEG = 2, TM_CHROMA_420MPEG2 = 3, TM_CHROMA_MONO = 4 };
+/* Host-only seams of the above (no device needed).  tm_probe_input_host: what tm_open_input would find (kind: TM_INPUT_*; width, height:
+ * the file's; any pointer may be NULL).  tm_read_png_host: a non-interlaced 8-bit PNG (grey, grey + alpha, RGB, RGBA, palette; alpha
+ * dropped; CRCs and Adler-32 checked) as 0x00RRGGBB; out_rgb32 NULL gives the size only.  tm_inflate_host: one zlib stream (stored, fixed
+ * and dynamic blocks); TM_E_INVAL for a damaged or truncated stream or one longer than cap.  tm_resample_taps_host: the resampling table
+ * of one axis -- n luma samples in, m out, a plane of np samples at luma positions s k + o_halves / 2 (s 1 or 2) -- as the first tap,
+ * the number of taps and the coefficients in 1/16384 (64 per output sample, unused ones 0); TM_E_UNSUPPORTED when n / m / s > 8. */
+#define TM_RESAMPLE_MAX_TAPS 64
+TM_API int tm_probe_input_host(const char *name, int start_frame, int frame_count, double scaling, int *kind, int *width, int *height, int *dst_width,
+                               int *dst_height, double *fps, int *frames, int *chroma);
+TM_API int tm_read_png_host(const char *path, uint32_t *out_rgb32, int64_t cap_px, int *width, int *height);
+TM_API int tm_inflate_host(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *out_n);
+TM_API int tm_resample_taps_host(int n, int m, int np, int s, int o_halves, int32_t *first /* [m] */, int32_t *count /* [m] */, int32_t *coef /* [m][64] */);
 TM_API int tm_run(tm_encoder *, int step);          /* Run(AStep), :5529-5554; blocking */
 /* read-back views (copy-out) */
 TM_API int tm_get_counts(tm_encoder *, int64_t *tiles, int *frames, int *palettes, int *tm_w, int *tm_h, int *keyframes);
@@ -309,6 +351,18 @@ TM_API int tm_get_kmeans_iters(tm_encoder *, int *tile_iters, int64_t *tile_poin
  * lab_means f32 [ntiles][3]. */
 TM_API int tm_stage_load(const void *frames, int nframes, int img_w, int img_h, int tm_w, int tm_h,
                          void *tiles, void *flags, void *lab_means, void *stream);
+
+/* Planes of 8-bit Y, U, V -> RGB32 frames [nframes][dst_h][dst_w] 0x00RRGGBB, the format frames are pushed in: chroma upsampling, the
+ * Lanczos-3 resize to dst_w x dst_h and the colour conversion in one kernel (what tm_open_input's Load runs per chunk of frames).  strides
+ * (HOST array): row and frame stride in bytes of y, u, v -- {y_row, y_frame, u_row, u_frame, v_row, v_frame}; chroma: TM_CHROMA_* (MONO: u,
+ * v unused, U = V = 128); yuv_mode: TM_YUV_* (AUTO = BT601_LIMITED here: there is no header).  The rule, bit for bit (DESIGN.md section
+ * 17): separable, horizontal first; per axis r = n / m, f = max(1, r / s), u_j = ((j + 0.5) r - 0.5 - o) / s, taps ceil(u_j - 3f) ..
+ * floor(u_j + 3f) inside the plane, c_k = RoundHalfEven(16384 w_k / sum w) with w_k = sinc(t) sinc(t / 3), t = (k - u_j) / f, the
+ * remainder to the largest tap; h = (sum c p + 64) >> 7, v = clamp((sum c h + 2^20) >> 21, 0, 255).  BT601_LIMITED: C = Y - 16,
+ * R = (298C + 409E + 128) >> 8, G = (298C - 100D - 208E + 128) >> 8, B = (298C + 516D + 128) >> 8; BT601_FULL: libjpeg's 16-bit
+ * constants 91881, 22554, 46802, 116130.  Blocking (builds and frees the tap tables). */
+TM_API int tm_stage_yuv_to_rgb32(const void *y, const void *u, const void *v, const int64_t *host_strides /* [6] */, int nframes, int src_w, int src_h,
+                                 int chroma, int dst_w, int dst_h, int yuv_mode, void *out_rgb32, void *stream);
 
 /* RGBToLAB (utils.pas:374-410) of n colours 0x00RRGGBB -> float [n][3] (L, a, b): the colour conversion the load and feature kernels
  * share, as an operator of its own (the whole 24-bit domain is checked against the oracle through it). */

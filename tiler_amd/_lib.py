@@ -59,6 +59,11 @@ SIGNATURES = {
     "tm_stage_render": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_int,
                                 c_void_p, c_void_p]),
     "tm_stage_frame_quality": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "tm_stage_yuv_to_rgb32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "tm_probe_input_host": (c_int, [c_char_p, c_int, c_int, c_double] + [ctypes.POINTER(c_int)] * 5 + [ctypes.POINTER(c_double)] + [ctypes.POINTER(c_int)] * 2),
+    "tm_read_png_host": (c_int, [c_char_p, c_void_p, c_int64, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "tm_inflate_host": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "tm_resample_taps_host": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 

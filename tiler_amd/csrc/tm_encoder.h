@@ -48,6 +48,12 @@ struct tm_encoder {
   // device state
   DevBuf frames_owned;
   const void *frames = nullptr;  // [nframes][height][width] RGB32
+  // the frame source "file" (tm_open_input): Load decodes InputFileName into a clip the encoder owns (tm_input.hip)
+  InputInfo input;
+  int input_yuv = TM_YUV_AUTO;
+  InputTables input_tables;
+  PinnedBuf input_pinned[2];         // the two staging buffers of a Y4M file's chunks
+  std::vector<uint32_t> input_clip;  // a PNG sequence, decoded on the host, until Load has uploaded it
   const void *frames_host = nullptr;  // the same in HOST memory (tm_set_frames_host): Load copies it over in chunks beside its own kernel
   hipStream_t copy_stream = nullptr;
   // Clips that come from host memory land in one of two device buffers: the one the last Load read, and the one a prefetch
@@ -70,6 +76,8 @@ struct tm_encoder {
   DevBuf dcorrel;
   bool load_tail_pending = false;
   double kf_lo_thres = 0, kf_min_s = 0, kf_max_s = 0, kf_fps = 0;  // ShotTrans* and the frame rate at the time of that Load
+  bool kf_manual = false;               // that Load read a PNG sequence: the key frames are the .kf files' (FindKeyFrames(AManualMode), 3380-3384)
+  std::vector<int32_t> kf_manual_list;
   DevBuf ftiles, fflags, flab;   // frame tiles (canonical), mirror flags, Lab means
   DevBuf gtiles, gflags, guse, gpal_idx, gpal_px, palettes_dev;  // global tiles
   DevBuf tm_tile, tm_pal, tm_err;  // tile map, frame-major: TileIdx, PalIdx, error behind PSNR (KNN or motion)
@@ -172,6 +180,9 @@ std::string settings_text(const Settings &s);
 int run_step(tm_encoder *e, int step);
 int load_tail(tm_encoder *e);
 int queue_host_clip(tm_encoder *e, int slot, const void *host);
+
+// tm_input.hip
+int load_from_input(tm_encoder *e);
 
 // tm_shard.hip
 void share_of(int64_t n, int rank, int world, int64_t *lo, int64_t *hi);

@@ -249,6 +249,7 @@ int tm_set_video(tm_encoder *e, int width, int height, double fps, int frame_cou
   if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_set_video(s, width, height, fps, frame_count); });
   TM_HIP(hipSetDevice(e->device));
   e->frames_peer = nullptr;
+  e->input = InputInfo();  // the frames come from memory again, the key frames from the automatic rule
   e->width = width; e->height = height; e->fps = fps; e->nframes = frame_count;
   e->tm_w = (width - 1) / 8 + 1;   // ReframeUI((DstWidth - 1) div cTileWidth + 1, ...), tilingencoder.pas:1776
   e->tm_h = (height - 1) / 8 + 1;
@@ -273,6 +274,7 @@ int tm_push_frame_rgb32(tm_encoder *e, int index, const uint32_t *pixels, int st
   if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_push_frame_rgb32(s, index, pixels, stride_px); });
   TM_HIP(hipSetDevice(e->device));
   const size_t fbytes = (size_t)e->width * e->height * 4;
+  e->input = InputInfo();
   e->frames_host = nullptr;
   e->frames_peer = nullptr;
   e->hclip_cur = -1;
@@ -299,6 +301,7 @@ int tm_set_frames_device(tm_encoder *e, const void *dev_frames) {
     });
   }
   e->frames_owned.release();
+  e->input = InputInfo();
   e->frames = dev_frames;
   e->frames_host = nullptr;
   e->frames_peer = nullptr;
@@ -311,6 +314,7 @@ int tm_set_frames_host(tm_encoder *e, const uint32_t *host_frames) {
   TM_CHECK(e->nframes > 0, TM_E_INVAL, "tm_set_video has not been called");
   if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_set_frames_host(s, host_frames); });  // every shard loads the whole clip
   e->frames_peer = nullptr;
+  e->input = InputInfo();
   e->frames_host = host_frames;
   e->frames = nullptr;
   e->hclip_cur = -1;
@@ -340,6 +344,8 @@ int tm_prefetch_frames_host(tm_encoder *e, const uint32_t *host_frames) {
 int tm_run(tm_encoder *e, int step) {
   TM_CHECK(e, TM_E_INVAL, "null encoder");
   knobs_reload();  // the environment switches are sampled here, once per Run; the steps read the sampled set
+  // Load takes nothing but the settings (1764-1820): with no video described yet it opens InputFileName itself
+  if ((step == TM_STEP_LOAD || step == TM_STEP_ALL) && e->nframes == 0 && !e->s.InputFileName.empty()) TM_TRY(tm_open_input(e));
   if (e->grp) {  // every step on every shard at once; Save is shard 0's (every shard holds the merged state)
     if (step == TM_STEP_ALL) {
       for (int s = TM_STEP_LOAD; s <= TM_STEP_REINDEX; s++) TM_TRY(group_run_step(e, s));

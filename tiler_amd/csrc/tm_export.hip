@@ -92,24 +92,13 @@ struct ExportFrames {
   }
 };
 
-uint32_t crc32_of(const uint8_t *p, size_t n, uint32_t crc) {
-  static uint32_t table[256];
-  static bool made = false;
-  if (!made) {
-    for (uint32_t i = 0; i < 256; i++) { uint32_t c = i; for (int k = 0; k < 8; k++) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1; table[i] = c; }
-    made = true;
-  }
-  crc = ~crc;
-  for (size_t i = 0; i < n; i++) crc = table[(crc ^ p[i]) & 0xff] ^ (crc >> 8);
-  return ~crc;
-}
 void png_chunk(std::vector<uint8_t> &out, const char *type, const std::vector<uint8_t> &data) {
   auto be32 = [&](uint32_t v) { out.push_back(v >> 24); out.push_back(v >> 16); out.push_back(v >> 8); out.push_back(v); };
   be32((uint32_t)data.size());
   const size_t at = out.size();
   out.insert(out.end(), type, type + 4);
   out.insert(out.end(), data.begin(), data.end());
-  be32(crc32_of(out.data() + at, out.size() - at, 0));
+  be32(crc32_ieee(out.data() + at, out.size() - at));
 }
 // 24-bit RGB PNG (pf24bit, 2086) of 0x00RRGGBB pixels; the image data travels in stored deflate blocks: valid for every decoder, no codec dependency
 int write_png(const std::string &path, const uint32_t *img, int w, int h) {

@@ -1,0 +1,655 @@
+// tm_input.hip -- Load's input: the probe half of Load (tilingencoder.pas:1764-1820) for Y4M files and numbered PNG sequences, the
+// Lanczos-3 resampling tables, and the kernel that turns planes of Y, U, V into the RGB32 frames Load reads.
+//
+// The reference opens "any file" through FFmpeg and scales with libswscale's Lanczos (extern.pas:780-781, 837-840).  Neither exists here
+// (DESIGN.md sections 9 and 17): Y4M is the uncompressed container every FFmpeg build writes, and the resampler is a stated integer rule of
+// this build -- separable, horizontal pass first, coefficients in 1/16384 from tables made on the host in double:
+//   r = n / m;  f = max(1, r / s);  u_j = ((j + 0.5) r - 0.5 - o) / s;  taps ceil(u_j - 3f) .. floor(u_j + 3f) inside the plane
+//   c_k = RoundHalfEven(16384 w_k / sum w), the remainder to the tap of largest w;  h = (sum c p + 64) >> 7;  v = clamp((sum c h + 2^20) >> 21)
+// for a plane whose samples sit at luma positions s k + o (s = 2 for subsampled chroma, o = 0.5 where it is centred).
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <atomic>
+#include <cmath>
+#include <mutex>
+#include <thread>
+
+#include "tm_encoder.h"
+
+namespace tmx {
+
+// ---- resampling tables (host) ----------------------------------------------------------------------------------
+static double lanczos3(double t) {
+  t = std::fabs(t);
+  if (t >= 3.0) return 0.0;
+  if (t == 0.0) return 1.0;
+  const double x = M_PI * t;
+  return (std::sin(x) / x) * (std::sin(x / 3.0) / (x / 3.0));
+}
+
+// one axis: n luma samples in, m samples out, a plane of np samples at luma positions s k + o_halves / 2.  first / count [m], coef [m][64].
+int resample_taps(int n, int m, int np, int s, int o_halves, int32_t *first, int32_t *count, int32_t *coef, int64_t *sum_abs_max) {
+  TM_CHECK(n > 0 && m > 0 && np > 0 && (s == 1 || s == 2) && (o_halves == 0 || o_halves == 1), TM_E_INVAL, "resample: bad axis %d -> %d (plane %d, step %d)", n, m, np, s);
+  const double r = (double)n / (double)m;
+  TM_CHECK(r / s <= 8.0, TM_E_UNSUPPORTED, "resample: %d -> %d samples shrinks by more than 8 (more than %d taps)", n, m, TM_RESAMPLE_MAX_TAPS);
+  const double f = std::max(1.0, r / s), o = o_halves * 0.5;
+  int64_t amax = 0;
+  for (int j = 0; j < m; j++) {
+    const double x = (j + 0.5) * r - 0.5;
+    const double u = (x - o) / s;
+    const int k0 = (int)std::max(0.0, std::ceil(u - 3.0 * f)), k1 = (int)std::min((double)(np - 1), std::floor(u + 3.0 * f));
+    const int cnt = k1 - k0 + 1;
+    TM_CHECK(cnt >= 1 && cnt <= TM_RESAMPLE_MAX_TAPS, TM_E_UNSUPPORTED, "resample: %d taps for sample %d of %d -> %d", cnt, j, n, m);
+    double w[TM_RESAMPLE_MAX_TAPS], tot = 0.0;
+    for (int k = 0; k < cnt; k++) { w[k] = lanczos3(((double)(k0 + k) - u) / f); tot += w[k]; }
+    int32_t *c = coef + (size_t)j * TM_RESAMPLE_MAX_TAPS;
+    int64_t sum = 0, sa = 0;
+    int best = 0;
+    for (int k = 0; k < TM_RESAMPLE_MAX_TAPS; k++) c[k] = 0;
+    for (int k = 0; k < cnt; k++) {
+      c[k] = (int32_t)std::nearbyint(w[k] / tot * 16384.0);  // (round half to even: the default rounding mode)
+      sum += c[k];
+      if (w[k] > w[best]) best = k;  // the lowest k on a tie
+    }
+    c[best] += (int32_t)(16384 - sum);
+    for (int k = 0; k < cnt; k++) sa += std::abs(c[k]);
+    amax = std::max(amax, sa);
+    first[j] = k0;
+    count[j] = cnt;
+  }
+  if (sum_abs_max) *sum_abs_max = amax;
+  return TM_OK;
+}
+
+// where a layout's chroma samples sit: step and offset (in halves of a luma sample) per axis, plane size
+struct ChromaGeom { int sx, sy, ox, oy, cw, ch; };
+static int chroma_geom(int chroma, int w, int h, ChromaGeom *g) {
+  switch (chroma) {
+    case TM_CHROMA_444: *g = {1, 1, 0, 0, w, h}; break;
+    case TM_CHROMA_422: *g = {2, 1, 0, 0, (w + 1) / 2, h}; break;
+    case TM_CHROMA_420JPEG: *g = {2, 2, 1, 1, (w + 1) / 2, (h + 1) / 2}; break;
+    case TM_CHROMA_420MPEG2: *g = {2, 2, 0, 1, (w + 1) / 2, (h + 1) / 2}; break;
+    case TM_CHROMA_MONO: *g = {1, 1, 0, 0, 0, 0}; break;
+    default: set_error("bad chroma layout %d", chroma); return TM_E_INVAL;
+  }
+  return TM_OK;
+}
+
+// ---- the kernel ------------------------------------------------------------------------------------------------
+// A workgroup owns IN_TW x th output pixels of one frame.  Per plane: the horizontal pass of the source rows its vertical taps reach goes
+// into LDS as int32 (the rule keeps 7 extra bits between the passes), then every lane runs the vertical pass for four neighbouring pixels of
+// one row out of LDS; the three results stay in registers for the colour conversion and leave as one 16-byte store.  No plane goes to HBM
+// between the passes.  The host picks th so that the rows a tile reaches fit IN_HROWS (in_tile_rows).
+constexpr int IN_TW = 64, IN_HROWS = 96, IN_TH_MAX = 16;
+struct PlaneSrc { const uint8_t *p; int64_t row, frame; };
+
+__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+
+__device__ __forceinline__ uint32_t yuv_to_rgb32(int Y, int U, int V, int mode) {
+  const int D = U - 128, E = V - 128;
+  int R, G, B;
+  if (mode == TM_YUV_BT601_FULL) {  // libjpeg's constants, 16 fractional bits
+    R = (65536 * Y + 91881 * E + 32768) >> 16;
+    G = (65536 * Y - 22554 * D - 46802 * E + 32768) >> 16;
+    B = (65536 * Y + 116130 * D + 32768) >> 16;
+  } else if (mode == TM_YUV_TILER) {  // YUVToRGB, utils.pas:492-509: Single operands, every right-hand side in double, narrowed once
+    const double y = (double)(float)Y, u = (double)(float)D, v = (double)(float)E;
+    const float r = __double2float_rn(__dadd_rn(y, __dmul_rn(v, 1.13983)));
+    const float g = __double2float_rn(__dsub_rn(__dsub_rn(y, __dmul_rn(u, 0.39465)), __dmul_rn(v, 0.58060)));
+    const float b = __double2float_rn(__dadd_rn(y, __dmul_rn(u, 2.03211)));
+    R = __float2int_rn(r); G = __float2int_rn(g); B = __float2int_rn(b);  // Round: half to even
+  } else {  // BT.601, limited range
+    const int C = Y - 16;
+    R = (298 * C + 409 * E + 128) >> 8;
+    G = (298 * C - 100 * D - 208 * E + 128) >> 8;
+    B = (298 * C + 516 * D + 128) >> 8;
+  }
+  return (uint32_t)clamp255(R) << 16 | (uint32_t)clamp255(G) << 8 | (uint32_t)clamp255(B);
+}
+
+__global__ __launch_bounds__(256) void k_yuv_to_rgb32(PlaneSrc sy, PlaneSrc su, PlaneSrc sv, AxisTaps lh, AxisTaps lv, AxisTaps ch, AxisTaps cv, int dst_w,
+                                                      int dst_h, int th, int mode, int vec_ok, uint32_t *__restrict__ out) {
+  __shared__ __attribute__((aligned(16))) int32_t hbuf[IN_HROWS * IN_TW];
+  const int x0 = blockIdx.x * IN_TW, y0 = blockIdx.y * th, frame = blockIdx.z;
+  const int y_last = min(y0 + th, dst_h) - 1;
+  const int tx = (threadIdx.x & 15) * 4, ty = threadIdx.x >> 4;
+  const int hx = threadIdx.x & (IN_TW - 1), hr0 = threadIdx.x / IN_TW;  // the horizontal pass: one column, rows hr0, hr0 + 4, ...
+  const bool mine = ty < th && y0 + ty <= y_last;
+  // every table entry the three planes will need, asked for at once: the passes below then wait for one load, not for a chain of them
+  const int oxc = min(x0 + hx, dst_w - 1), oyc = min(y0 + ty, dst_h - 1);
+  const int hfirst[2] = {lh.first[oxc], ch.first[oxc]}, hcount[2] = {lh.count[oxc], ch.count[oxc]};
+  const int vfirst[2] = {lv.first[oyc], cv.first[oyc]}, vcount[2] = {lv.count[oyc], cv.count[oyc]};
+  const int2 span[2] = {lv.span[blockIdx.y], cv.span[blockIdx.y]};  // the source rows the tile's samples reach: first row, number of rows
+  int val[3][4];
+#pragma unroll
+  for (int p = 0; p < 3; p++) {
+    const PlaneSrc src = p == 0 ? sy : p == 1 ? su : sv;
+    if (src.p == nullptr) {  // Cmono: U = V = 128
+#pragma unroll
+      for (int j = 0; j < 4; j++) val[p][j] = 128;
+      continue;
+    }
+    const AxisTaps ah = p == 0 ? lh : ch, av = p == 0 ? lv : cv;
+    const int c01 = p == 0 ? 0 : 1, r0 = span[c01].x, rows = span[c01].y;
+    __syncthreads();  // the plane before has been read
+    if (x0 + hx < dst_w) {
+      const int ox = x0 + hx, k0 = hfirst[c01], cnt = hcount[c01];
+      const uint8_t *col = src.p + (int64_t)frame * src.frame + k0;
+      // four rows at a time, so that a coefficient is loaded once for four products
+      constexpr int RS = 256 / IN_TW;
+      for (int rb = hr0; rb < rows; rb += 4 * RS) {
+        const uint8_t *row = col + (int64_t)(r0 + rb) * src.row;
+        int acc[4] = {0, 0, 0, 0};
+        for (int k = 0; k < cnt; k++) {
+          const int c = ah.coef[(int64_t)k * dst_w + ox];
+#pragma unroll
+          for (int i = 0; i < 4; i++)
+            if (rb + i * RS < rows) acc[i] += c * (int)row[(int64_t)i * RS * src.row + k];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (rb + i * RS < rows) hbuf[(rb + i * RS) * IN_TW + hx] = (acc[i] + 64) >> 7;  // (arithmetic shift, no clamp)
+      }
+    }
+    __syncthreads();
+    if (mine) {
+      const int oy = y0 + ty, k0 = vfirst[c01] - r0, cnt = vcount[c01];
+      int acc[4] = {0, 0, 0, 0};
+      for (int k = 0; k < cnt; k++) {
+        const int c = av.coef[(int64_t)k * dst_h + oy];
+        const int4 h = *reinterpret_cast<const int4 *>(&hbuf[(k0 + k) * IN_TW + tx]);
+        acc[0] += c * h.x; acc[1] += c * h.y; acc[2] += c * h.z; acc[3] += c * h.w;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; j++) val[p][j] = clamp255((acc[j] + (1 << 20)) >> 21);
+    }
+  }
+  if (!mine || x0 + tx >= dst_w) return;
+  uint32_t px[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) px[j] = yuv_to_rgb32(val[0][j], val[1][j], val[2][j], mode);
+  uint32_t *o = out + ((int64_t)frame * dst_h + (y0 + ty)) * dst_w + x0 + tx;
+  if (vec_ok && x0 + tx + 3 < dst_w) *reinterpret_cast<uint4 *>(o) = make_uint4(px[0], px[1], px[2], px[3]);
+  else
+    for (int j = 0; j < 4 && x0 + tx + j < dst_w; j++) o[j] = px[j];
+}
+
+// ---- the tables of one conversion (InputTables, tm_internal.h), made once per (source size, layout, output size) and kept on the device
+// the source rows the samples of every tile of th output rows reach, as (first row, number of rows) per tile
+static std::vector<int32_t> tile_spans(const std::vector<int32_t> &first, const std::vector<int32_t> &count, int m, int th, int *widest) {
+  std::vector<int32_t> sp;
+  for (int y0 = 0; y0 < m; y0 += th) {
+    int r0 = INT32_MAX, r1 = 0;
+    for (int y = y0; y < std::min(y0 + th, m); y++) { r0 = std::min(r0, first[y]); r1 = std::max(r1, first[y] + count[y]); }
+    sp.push_back(r0); sp.push_back(r1 - r0);
+    *widest = std::max(*widest, r1 - r0);
+  }
+  return sp;
+}
+// the tile height: the largest of 16, 8, 4, 2, 1 for which no tile's vertical taps reach more than IN_HROWS source rows
+static int in_tile_rows(const std::vector<int32_t> *firsts, const std::vector<int32_t> *counts, int nplanes, int m) {
+  for (int th = IN_TH_MAX; th >= 1; th /= 2) {
+    int widest = 0;
+    for (int p = 0; p < nplanes; p++) tile_spans(firsts[p], counts[p], m, th, &widest);
+    if (widest <= IN_HROWS) return th;
+  }
+  return 0;
+}
+
+static int build_input_tables(int src_w, int src_h, int chroma, int dst_w, int dst_h, InputTables *t, hipStream_t stream) {
+  if (t->dev.p && t->src_w == src_w && t->src_h == src_h && t->chroma == chroma && t->dst_w == dst_w && t->dst_h == dst_h) return TM_OK;
+  ChromaGeom g;
+  TM_TRY(chroma_geom(chroma, src_w, src_h, &g));
+  const bool has_c = chroma != TM_CHROMA_MONO;
+  // axis tables: 0 luma horizontal, 1 luma vertical, 2 chroma horizontal, 3 chroma vertical
+  std::vector<int32_t> first[4], count[4], coef[4];
+  int64_t amax[4] = {0, 0, 0, 0};
+  const int m[4] = {dst_w, dst_h, dst_w, dst_h};
+  for (int a = 0; a < (has_c ? 4 : 2); a++) {
+    first[a].resize(m[a]); count[a].resize(m[a]); coef[a].resize((size_t)m[a] * TM_RESAMPLE_MAX_TAPS);
+    const bool horiz = (a & 1) == 0, c = a >= 2;
+    TM_TRY(resample_taps(horiz ? src_w : src_h, m[a], c ? (horiz ? g.cw : g.ch) : (horiz ? src_w : src_h), c ? (horiz ? g.sx : g.sy) : 1,
+                         c ? (horiz ? g.ox : g.oy) : 0, first[a].data(), count[a].data(), coef[a].data(), &amax[a]));
+  }
+  // the vertical sum fits int32: |h| <= 255 A_h / 128 + 1, |sum| <= that times A_v
+  for (int a = 0; a < (has_c ? 4 : 2); a += 2)
+    TM_CHECK((255 * amax[a] / 128 + 1) * amax[a + 1] < (1ll << 31), TM_E_UNSUPPORTED, "resample: the coefficients of %dx%d -> %dx%d overflow the 32-bit sums",
+             src_w, src_h, dst_w, dst_h);
+  // On the device a sample's taps start at its first and end at its last coefficient that is not 0 (the sums are the same): at equal size
+  // the window still spans the six neighbours at whole distances, whose weights sin(k pi) round to 0 -- one tap is left, the sample itself.
+  for (int a = 0; a < (has_c ? 4 : 2); a++)
+    for (int j = 0; j < m[a]; j++) {
+      int32_t *c = &coef[a][(size_t)j * TM_RESAMPLE_MAX_TAPS];
+      int lo = 0, hi = count[a][j];
+      while (hi - lo > 1 && c[hi - 1] == 0) hi--;
+      while (hi - lo > 1 && c[lo] == 0) lo++;
+      for (int k = 0; k < hi - lo; k++) c[k] = c[lo + k];
+      first[a][j] += lo;
+      count[a][j] = hi - lo;
+    }
+  // (trimmed windows need no longer be ordered along the axis: the rows a tile reaches are the span of all its samples' windows)
+  const std::vector<int32_t> vf[2] = {first[1], first[3]}, vc[2] = {count[1], count[3]};
+  const int th = in_tile_rows(vf, vc, has_c ? 2 : 1, dst_h);
+  TM_CHECK(th > 0, TM_E_UNSUPPORTED, "resample: %d -> %d rows reach too many source rows per tile", src_h, dst_h);
+  // device layout per axis: first [m], count [m], coef [maxcount][m], and for a vertical axis its tiles' spans
+  std::vector<int32_t> host;
+  size_t off[4][4];
+  for (int a = 0; a < (has_c ? 4 : 2); a++) {
+    int mc = 0;
+    for (int j = 0; j < m[a]; j++) mc = std::max(mc, count[a][j]);
+    off[a][0] = host.size(); host.insert(host.end(), first[a].begin(), first[a].end());
+    off[a][1] = host.size(); host.insert(host.end(), count[a].begin(), count[a].end());
+    off[a][2] = host.size(); host.resize(host.size() + (size_t)mc * m[a]);
+    for (int k = 0; k < mc; k++)
+      for (int j = 0; j < m[a]; j++) host[off[a][2] + (size_t)k * m[a] + j] = coef[a][(size_t)j * TM_RESAMPLE_MAX_TAPS + k];
+    host.resize((host.size() + 1) & ~(size_t)1);  // (the spans are read as pairs)
+    off[a][3] = host.size();
+    if (a & 1) {
+      int widest = 0;
+      const std::vector<int32_t> sp = tile_spans(first[a], count[a], m[a], th, &widest);
+      TM_CHECK(widest <= IN_HROWS, TM_E_UNSUPPORTED, "resample: a tile reaches %d source rows", widest);  // (what in_tile_rows chose th for)
+      host.insert(host.end(), sp.begin(), sp.end());
+    }
+  }
+  TM_HIP(hipStreamSynchronize(stream));  // a conversion in flight may still read the tables being replaced
+  TM_TRY(t->dev.alloc(host.size() * 4));
+  TM_HIP(hipMemcpyAsync(t->dev.p, host.data(), host.size() * 4, hipMemcpyHostToDevice, stream));
+  TM_HIP(hipStreamSynchronize(stream));  // (`host` goes out of scope)
+  AxisTaps *ax[4] = {&t->lh, &t->lv, &t->ch, &t->cv};
+  for (int a = 0; a < 4; a++) {
+    const int s = has_c ? a : (a & 1);  // Cmono: the chroma tables are never read
+    *ax[a] = AxisTaps{t->dev.as<int32_t>() + off[s][0], t->dev.as<int32_t>() + off[s][1], t->dev.as<int32_t>() + off[s][2],
+                      reinterpret_cast<const int2 *>(t->dev.as<int32_t>() + off[s][3])};
+  }
+  t->src_w = src_w; t->src_h = src_h; t->chroma = chroma; t->dst_w = dst_w; t->dst_h = dst_h; t->th = th;
+  return TM_OK;
+}
+
+static int launch_yuv_to_rgb32(const InputTables &t, const void *y, const void *u, const void *v, const int64_t strides[6], int nframes, int yuv_mode, void *out,
+                               hipStream_t stream) {
+  if (nframes == 0) return TM_OK;
+  const bool has_c = t.chroma != TM_CHROMA_MONO;
+  const PlaneSrc sy{(const uint8_t *)y, strides[0], strides[1]}, su{has_c ? (const uint8_t *)u : nullptr, strides[2], strides[3]},
+      sv{has_c ? (const uint8_t *)v : nullptr, strides[4], strides[5]};
+  const int vec_ok = (t.dst_w % 4 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
+  const dim3 grid((unsigned)((t.dst_w + IN_TW - 1) / IN_TW), (unsigned)((t.dst_h + t.th - 1) / t.th), (unsigned)nframes);
+  TM_CHECK(grid.y <= 65535 && grid.z <= 65535, TM_E_UNSUPPORTED, "yuv_to_rgb32: %d rows x %d frames in one launch", t.dst_h, nframes);
+  hipLaunchKernelGGL(k_yuv_to_rgb32, grid, dim3(256), 0, stream, sy, su, sv, t.lh, t.lv, t.ch, t.cv, t.dst_w, t.dst_h, t.th, yuv_mode, vec_ok, (uint32_t *)out);
+  TM_HIP(hipGetLastError());
+  return TM_OK;
+}
+
+// ---- probing (host) --------------------------------------------------------------------------------------------
+static bool file_exists(const std::string &p) {
+  struct stat st;
+  return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode);
+}
+
+static int pas_round_dim(double v) {  // Round(W * Scaling), at least 1 (extern.pas:780-781)
+  return (int)std::max<long long>(1, llrint(v));
+}
+
+// Pascal's Format(pattern, [i]) for a pattern with exactly one integer specifier, %d or %.Nd; %% is a literal
+int format_pattern(const std::string &pat, int64_t i, std::string *out) {
+  out->clear();
+  int specs = 0;
+  for (size_t p = 0; p < pat.size(); p++) {
+    if (pat[p] != '%') { *out += pat[p]; continue; }
+    if (p + 1 < pat.size() && pat[p + 1] == '%') { *out += '%'; p++; continue; }
+    size_t q = p + 1;
+    int prec = 0;
+    if (q < pat.size() && pat[q] == '.') {
+      q++;
+      TM_CHECK(q < pat.size() && isdigit((unsigned char)pat[q]), TM_E_INVAL, "input pattern '%s': digits expected after '%%.'", pat.c_str());
+      while (q < pat.size() && isdigit((unsigned char)pat[q])) prec = std::min(prec * 10 + (pat[q++] - '0'), 64);
+    }
+    TM_CHECK(q < pat.size() && (pat[q] == 'd' || pat[q] == 'D'), TM_E_INVAL, "input pattern '%s': only %%d and %%.Nd are understood", pat.c_str());
+    char buf[96];
+    snprintf(buf, sizeof(buf), "%.*lld", prec, (long long)i);
+    *out += buf;
+    specs++;
+    p = q;
+  }
+  TM_CHECK(specs == 1, TM_E_INVAL, "'%s' is neither an existing file nor a pattern with one %%d or %%.Nd", pat.c_str());
+  return TM_OK;
+}
+
+static std::string change_ext(const std::string &p, const char *ext) {  // ChangeFileExt
+  const size_t dot = p.find_last_of('.'), sep = p.find_last_of("/\\");
+  return ((dot != std::string::npos && (sep == std::string::npos || dot > sep)) ? p.substr(0, dot) : p) + ext;
+}
+
+static int parse_y4m(const std::string &name, InputInfo *in) {
+  FILE *f = fopen(name.c_str(), "rb");
+  TM_CHECK(f, TM_E_IO, "cannot open %s", name.c_str());
+  struct Closer { FILE *f; ~Closer() { fclose(f); } } closer{f};
+  char line[1024];
+  const size_t got = fread(line, 1, sizeof(line) - 1, f);
+  line[got] = 0;
+  TM_CHECK(got >= 10 && !memcmp(line, "YUV4MPEG2 ", 10), TM_E_UNSUPPORTED,
+           "%s is not a Y4M file and there is no decoder in this build; convert with `ffmpeg -i ... -f yuv4mpegpipe`", name.c_str());
+  const char *nl = (const char *)memchr(line, '\n', got);
+  TM_CHECK(nl, TM_E_INVAL, "%s: the Y4M header has no end", name.c_str());
+  int w = 0, h = 0, chroma = TM_CHROMA_420JPEG, full = 0;
+  long long num = 0, den = -1;
+  for (const char *p = line + 10; p < nl;) {
+    while (p < nl && *p == ' ') p++;
+    const char *q = p;
+    while (q < nl && *q != ' ') q++;
+    if (q == p) break;
+    const std::string tag(p, q);
+    const char *val = tag.c_str() + 1;
+    switch (tag[0]) {
+      case 'W': w = atoi(val); break;
+      case 'H': h = atoi(val); break;
+      case 'F': TM_CHECK(sscanf(val, "%lld:%lld", &num, &den) == 2, TM_E_INVAL, "%s: bad frame rate tag '%s'", name.c_str(), tag.c_str()); break;
+      case 'I': TM_CHECK(!strcmp(val, "p") || !strcmp(val, "?"), TM_E_UNSUPPORTED, "%s: interlaced video (tag '%s') is not read", name.c_str(), tag.c_str()); break;
+      case 'C':
+        if (!strcmp(val, "444")) chroma = TM_CHROMA_444;
+        else if (!strcmp(val, "422")) chroma = TM_CHROMA_422;
+        else if (!strcmp(val, "420jpeg")) chroma = TM_CHROMA_420JPEG;
+        else if (!strcmp(val, "420mpeg2")) chroma = TM_CHROMA_420MPEG2;
+        else if (!strcmp(val, "mono")) chroma = TM_CHROMA_MONO;
+        else { set_error("%s: pixel layout '%s' is not read (8-bit C444, C422, C420jpeg, C420mpeg2, Cmono only)", name.c_str(), tag.c_str()); return TM_E_UNSUPPORTED; }
+        break;
+      case 'X':
+        if (tag == "XCOLORRANGE=FULL") full = 1;
+        else if (tag == "XCOLORRANGE=LIMITED") full = 0;
+        break;
+      default: break;  // (A: the pixel aspect, and whatever else a writer adds)
+    }
+    p = q;
+  }
+  TM_CHECK(w > 0 && h > 0 && w <= 65536 && h <= 65536, TM_E_INVAL, "%s: bad size %dx%d", name.c_str(), w, h);
+  TM_CHECK(den != -1, TM_E_INVAL, "%s: no frame rate tag", name.c_str());
+  TM_CHECK(den > 0 && num > 0, TM_E_INVAL, "%s: frame rate %lld:%lld", name.c_str(), num, den);
+  ChromaGeom g;
+  TM_TRY(chroma_geom(chroma, w, h, &g));
+  in->kind = TM_INPUT_Y4M;
+  in->src_w = w; in->src_h = h; in->chroma = chroma; in->full_range = full;
+  in->fps = (double)num / (double)den;
+  in->frame_bytes = (int64_t)w * h + 2 * (int64_t)g.cw * g.ch;
+  // the frames: 'FRAME' + parameters + '\n' + the planes; a last frame that is cut short does not count
+  fseek(f, 0, SEEK_END);
+  const int64_t fsize = ftell(f);
+  int64_t pos = (nl - line) + 1;
+  in->frame_off.clear();
+  while (pos < fsize) {
+    char fh[256];
+    fseek(f, (long)pos, SEEK_SET);
+    const size_t n = fread(fh, 1, sizeof(fh), f);
+    if (n < 6) break;
+    TM_CHECK(!memcmp(fh, "FRAME", 5), TM_E_INVAL, "%s: no FRAME header at offset %lld", name.c_str(), (long long)pos);
+    const char *e = (const char *)memchr(fh, '\n', n);
+    TM_CHECK(e || n < sizeof(fh), TM_E_INVAL, "%s: the FRAME header at offset %lld has no end", name.c_str(), (long long)pos);
+    if (!e) break;
+    const int64_t data = pos + (e - fh) + 1;
+    if (data + in->frame_bytes > fsize) break;
+    in->frame_off.push_back(data);
+    pos = data + in->frame_bytes;
+  }
+  return TM_OK;
+}
+
+// what tm_open_input finds out, without a device: the kind of input, its sizes, rate, frame range
+int probe_input(const std::string &name, int start_frame, int frame_count, double scaling, InputInfo *in) {
+  *in = InputInfo();
+  TM_CHECK(!name.empty(), TM_E_INVAL, "InputFileName is empty");
+  TM_CHECK(start_frame >= 0, TM_E_INVAL, "StartFrame %d", start_frame);
+  in->name = name;
+  in->start = start_frame;
+  if (file_exists(name)) {
+    TM_TRY(parse_y4m(name, in));
+    const int64_t total = (int64_t)in->frame_off.size();
+    const int64_t cnt = frame_count > 0 ? frame_count : total - start_frame;  // 1778-1782
+    TM_CHECK(cnt > 0 && start_frame + cnt <= total, TM_E_INVAL, "%s holds %lld whole frames: frames [%d,+%lld) are not all there", name.c_str(), (long long)total,
+             start_frame, (long long)cnt);
+    in->frames = (int)cnt;
+    in->dst_w = pas_round_dim(in->src_w * scaling);
+    in->dst_h = pas_round_dim(in->src_h * scaling);
+    TM_CHECK((double)in->src_w / in->dst_w <= 8.0 && (double)in->src_h / in->dst_h <= 8.0, TM_E_UNSUPPORTED,
+             "Scaling %g shrinks %dx%d by more than 8 (more than %d taps)", scaling, in->src_w, in->src_h, TM_RESAMPLE_MAX_TAPS);
+    return TM_OK;
+  }
+  // a numbered PNG sequence (LoadInputVideo, 3340-3353): Format(name, [i + StartFrame])
+  std::string path;
+  TM_TRY(format_pattern(name, start_frame, &path));
+  in->kind = TM_INPUT_PNGS;
+  in->fps = 24.0;  // 1791
+  in->chroma = TM_CHROMA_444;
+  int cnt = frame_count;
+  if (cnt <= 0) {  // count the files up to the first gap (1797-1806)
+    cnt = 0;
+    for (;; cnt++) {
+      TM_TRY(format_pattern(name, (int64_t)start_frame + cnt, &path));
+      if (!file_exists(path)) break;
+    }
+  }
+  TM_TRY(format_pattern(name, start_frame, &path));
+  TM_CHECK(cnt > 0 && file_exists(path), TM_E_IO, "input: %s does not exist", path.c_str());
+  in->frames = cnt;
+  TM_TRY(read_png(path.c_str(), nullptr, 0, &in->src_w, &in->src_h));  // the size comes from the first file (1813-1814)
+  in->dst_w = in->src_w; in->dst_h = in->src_h;                         // Scaling plays no part on this path (3347-3348)
+  // manual key frames (FindKeyFrames(AManualMode), 3380-3384): frame i where Format(ChangeFileExt(name, '.kf'), [i + StartFrame]) exists
+  const std::string kf = change_ext(name, ".kf");
+  in->manual_kf.clear();
+  for (int i = 0; i < cnt; i++) {
+    TM_TRY(format_pattern(kf, (int64_t)start_frame + i, &path));
+    if (i == 0 || file_exists(path)) in->manual_kf.push_back(i);
+  }
+  return TM_OK;
+}
+
+}  // namespace tmx
+
+// ---- Load from the file ------------------------------------------------------------------------------------------
+namespace {
+struct Events {
+  std::vector<hipEvent_t> ev;
+  ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+  int make(int n) {
+    for (int i = 0; i < n; i++) { hipEvent_t e; TM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ev.push_back(e); }
+    return TM_OK;
+  }
+};
+}  // namespace
+
+// fn(i) for i in [0, n) on up to IN_READERS host threads (the calling one included); the first failure's code and message come back.
+// Reading a file that the page cache holds is a copy the memory system bounds, not one core: a single reader brought the 0.41 GB of the
+// 720p x 300 clip in at 8 GB/s (50 ms, against 20 ms for the whole Load of the same clip lent as RGB32).
+constexpr int IN_READERS = 8;
+static int parallel_for(int n, const std::function<int(int)> &fn) {
+  const int nt = std::min(IN_READERS, n);
+  if (nt <= 1) {
+    for (int i = 0; i < n; i++) TM_TRY(fn(i));
+    return TM_OK;
+  }
+  std::atomic<int> next{0}, rc{TM_OK};
+  std::string err;
+  std::mutex mu;
+  auto work = [&] {
+    for (int i = next++; i < n && rc.load() == TM_OK; i = next++) {
+      const int r = fn(i);
+      if (r != TM_OK) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (rc.load() == TM_OK) { rc = r; err = get_error(); }  // (the message is the failing thread's: it is handed to the caller's below)
+      }
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 1; t < nt; t++) th.emplace_back(work);
+  work();
+  for (std::thread &t : th) t.join();
+  if (rc != TM_OK) set_error("%s", err.c_str());
+  return rc;
+}
+
+static int resolve_yuv_mode(int mode, int full_range) { return mode == TM_YUV_AUTO ? (full_range ? TM_YUV_BT601_FULL : TM_YUV_BT601_LIMITED) : mode; }
+
+// frames [a, b) of the Y4M clip into the encoder's device clip: chunks of frames are read into two page-locked buffers, uploaded on the copy
+// stream and converted on the main stream, so that the read of a chunk runs beside the upload and the conversion of the one before
+static int decode_y4m(tm_encoder *e, int a, int b) {
+  InputInfo &in = e->input;
+  InputTables &tables = e->input_tables;
+  TM_TRY(build_input_tables(in.src_w, in.src_h, in.chroma, e->width, e->height, &tables, e->stream));
+  const int fd = open(in.name.c_str(), O_RDONLY);
+  TM_CHECK(fd >= 0, TM_E_IO, "cannot open %s", in.name.c_str());
+  struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
+  ChromaGeom g;
+  TM_TRY(chroma_geom(in.chroma, in.src_w, in.src_h, &g));
+  const size_t fb = (size_t)in.frame_bytes, out_fb = (size_t)e->width * e->height * 4;
+  const size_t per_chunk = knobs().input_chunk_frames > 0 ? (size_t)knobs().input_chunk_frames : ((size_t)16 << 20) / fb;
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)(b - a), per_chunk));
+  PinnedBuf *host = e->input_pinned;  // (kept between Loads: page-locking 32 MB costs more than reading them)
+  DevBuf dev[2];
+  Events up, done;
+  TM_TRY(up.make(2)); TM_TRY(done.make(2));
+  for (int i = 0; i < 2; i++) { TM_TRY(host[i].alloc(fb * chunk)); TM_TRY(dev[i].alloc(fb * chunk)); }
+  if (!e->copy_stream) TM_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
+  const int64_t y_plane = (int64_t)in.src_w * in.src_h, c_plane = (int64_t)g.cw * g.ch;
+  const int64_t strides[6] = {in.src_w, (int64_t)fb, g.cw, (int64_t)fb, g.cw, (int64_t)fb};
+  const int mode = resolve_yuv_mode(e->input_yuv, in.full_range);
+  int c = 0;
+  for (int f0 = a; f0 < b; f0 += chunk, c++) {
+    const int nf = std::min(chunk, b - f0), s = c & 1;
+    if (c >= 2) TM_HIP(hipEventSynchronize(up.ev[s]));  // the upload that last read this host buffer
+    TM_TRY(parallel_for(nf, [&](int i) -> int {
+      uint8_t *dst = (uint8_t *)host[s].p + fb * i;
+      const int64_t at = in.frame_off[(size_t)(in.start + f0 + i)];
+      for (size_t got = 0; got < fb;) {
+        const ssize_t n = pread(fd, dst + got, fb - got, (off_t)(at + (int64_t)got));
+        TM_CHECK(n > 0, TM_E_IO, "%s: cannot read frame %d", in.name.c_str(), in.start + f0 + i);
+        got += (size_t)n;
+      }
+      return (int)TM_OK;
+    }));
+    if (c >= 2) TM_HIP(hipStreamWaitEvent(e->copy_stream, done.ev[s], 0));  // the conversion that last read this device buffer
+    TM_HIP(hipMemcpyAsync(dev[s].p, host[s].p, fb * nf, hipMemcpyHostToDevice, e->copy_stream));
+    TM_HIP(hipEventRecord(up.ev[s], e->copy_stream));
+    TM_HIP(hipStreamWaitEvent(e->stream, up.ev[s], 0));
+    const uint8_t *base = dev[s].as<uint8_t>();
+    TM_TRY(launch_yuv_to_rgb32(tables, base, base + y_plane, base + y_plane + c_plane, strides, nf, mode, e->frames_owned.as<uint8_t>() + out_fb * f0, e->stream));
+    TM_HIP(hipEventRecord(done.ev[s], e->stream));
+  }
+  TM_HIP(hipStreamSynchronize(e->stream));  // the staging buffers go back to the pool and to the host
+  return TM_OK;
+}
+
+// the PNG sequence, decoded on the host into a clip the encoder keeps until Load's chunked host-clip upload has taken it
+static int decode_pngs(tm_encoder *e) {
+  InputInfo &in = e->input;
+  const size_t px = (size_t)e->width * e->height;
+  e->input_clip.resize(px * e->nframes);
+  return parallel_for(e->nframes, [&](int i) -> int {  // (frames are files of their own: inflate is the time, and it is one core's per file)
+    std::string path;
+    TM_TRY(format_pattern(in.name, (int64_t)in.start + i, &path));
+    int w = 0, h = 0;
+    TM_TRY(read_png(path.c_str(), nullptr, 0, &w, &h));
+    TM_CHECK(w == e->width && h == e->height, TM_E_INVAL, "%s is %dx%d, the sequence's first frame is %dx%d", path.c_str(), w, h, e->width, e->height);
+    return read_png(path.c_str(), e->input_clip.data() + px * i, (int64_t)px, &w, &h);
+  });
+}
+
+// Load's first lines when the frames come from a file: leaves the clip where tm_set_frames_device / tm_set_frames_host would have put it
+int load_from_input(tm_encoder *e) {
+  InputInfo &in = e->input;
+  if (in.kind == TM_INPUT_PNGS) {
+    if (in.decoded && e->frames != nullptr) return TM_OK;  // a second Run(esLoad): the device copy of the last one
+    TM_TRY(decode_pngs(e));
+    e->frames = nullptr;
+    e->frames_host = e->input_clip.data();
+    e->hclip_cur = -1;
+    in.decoded = true;
+    return TM_OK;
+  }
+  int64_t a = 0, b = e->nframes;
+  if (e->dist() && e->s.MotionPredictRadius <= 0) {  // a shard decodes what its Load reads: its frames and the one before them
+    share_of(e->nframes, e->co.rank, e->co.world, &a, &b);
+    a = std::max<int64_t>(a - 1, 0);
+  }
+  const int mode = resolve_yuv_mode(e->input_yuv, in.full_range);
+  if (in.decoded && e->frames == e->frames_owned.p && e->frames_owned.p && in.dec_first <= a && b <= in.dec_first + in.dec_count && in.dec_mode == mode) return TM_OK;
+  TM_HIP(hipStreamSynchronize(e->stream));  // the destination may have been handed out by the pool a moment ago
+  TM_TRY(e->frames_owned.alloc((size_t)e->width * e->height * 4 * e->nframes));
+  e->frames = e->frames_owned.p;
+  e->frames_host = nullptr;
+  e->hclip_cur = -1;
+  in.decoded = false;
+  if (b > a) TM_TRY(decode_y4m(e, (int)a, (int)b));
+  in.decoded = true; in.dec_first = (int)a; in.dec_count = (int)(b - a); in.dec_mode = mode;
+  return TM_OK;
+}
+
+extern "C" {
+
+int tm_open_input(tm_encoder *e) {  // the probe half of Load, tilingencoder.pas:1764-1820
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  if (e->grp) return group_each(e, [](tm_encoder *s) { return tm_open_input(s); });
+  InputInfo in;
+  TM_TRY(probe_input(e->s.InputFileName, e->s.StartFrame, e->s.FrameCount, e->s.Scaling, &in));
+  TM_TRY(tm_set_video(e, in.dst_w, in.dst_h, in.fps, in.frames));
+  e->input = std::move(in);
+  e->input_clip.clear();
+  return TM_OK;
+}
+
+int tm_get_video(tm_encoder *e, int *width, int *height, double *fps, int *frames) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  if (width) *width = e->width;
+  if (height) *height = e->height;
+  if (fps) *fps = e->fps;
+  if (frames) *frames = e->nframes;
+  return TM_OK;
+}
+
+int tm_set_input_yuv(tm_encoder *e, int mode) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_CHECK(mode >= TM_YUV_AUTO && mode <= TM_YUV_TILER, TM_E_INVAL, "bad YUV mode %d", mode);
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_set_input_yuv(s, mode); });
+  e->input_yuv = mode;
+  return TM_OK;
+}
+
+int tm_probe_input_host(const char *name, int start_frame, int frame_count, double scaling, int *kind, int *width, int *height, int *dst_width, int *dst_height,
+                        double *fps, int *frames, int *chroma) {
+  TM_CHECK(name, TM_E_INVAL, "null argument");
+  InputInfo in;
+  TM_TRY(probe_input(name, start_frame, frame_count, scaling, &in));
+  if (kind) *kind = in.kind;
+  if (width) *width = in.src_w;
+  if (height) *height = in.src_h;
+  if (dst_width) *dst_width = in.dst_w;
+  if (dst_height) *dst_height = in.dst_h;
+  if (fps) *fps = in.fps;
+  if (frames) *frames = in.frames;
+  if (chroma) *chroma = in.chroma;
+  return TM_OK;
+}
+
+int tm_resample_taps_host(int n, int m, int np, int s, int o_halves, int32_t *first, int32_t *count, int32_t *coef) {
+  TM_CHECK(first && count && coef, TM_E_INVAL, "null argument");
+  return resample_taps(n, m, np, s, o_halves, first, count, coef, nullptr);
+}
+
+int tm_stage_yuv_to_rgb32(const void *y, const void *u, const void *v, const int64_t strides[6], int nframes, int src_w, int src_h, int chroma, int dst_w, int dst_h,
+                          int yuv_mode, void *out_rgb32, void *stream) {
+  knobs_reload();
+  TM_TRY(require_device());
+  ChromaGeom g;
+  TM_TRY(chroma_geom(chroma, src_w, src_h, &g));
+  const bool has_c = chroma != TM_CHROMA_MONO;
+  TM_CHECK(y && out_rgb32 && strides && (!has_c || (u && v)) && nframes >= 0 && src_w > 0 && src_h > 0 && dst_w > 0 && dst_h > 0, TM_E_INVAL, "yuv_to_rgb32: bad arguments");
+  TM_CHECK(yuv_mode >= TM_YUV_AUTO && yuv_mode <= TM_YUV_TILER, TM_E_INVAL, "bad YUV mode %d", yuv_mode);
+  TM_CHECK(strides[0] >= src_w && strides[1] >= 0 && (!has_c || (strides[2] >= g.cw && strides[4] >= g.cw && strides[3] >= 0 && strides[5] >= 0)), TM_E_INVAL,
+           "yuv_to_rgb32: a row stride is shorter than its plane's rows");
+  InputTables tables;
+  TM_TRY(build_input_tables(src_w, src_h, chroma, dst_w, dst_h, &tables, (hipStream_t)stream));
+  // (without a header to say otherwise a clip is limited range, as FFmpeg assumes)
+  TM_TRY(launch_yuv_to_rgb32(tables, y, u, v, strides, nframes, resolve_yuv_mode(yuv_mode, 0), out_rgb32, (hipStream_t)stream));
+  TM_HIP(hipStreamSynchronize((hipStream_t)stream));  // the tables are freed on return
+  return TM_OK;
+}
+
+}  // extern "C"

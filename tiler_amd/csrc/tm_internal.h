@@ -115,6 +115,49 @@ int launch_quality_render(const RenderInput &in, const RenderMap &m, int first, 
 // the same for two stacks of 0x00RRGGBB frames [n][h][stride_px] (w, h: multiples of 4, at least 8)
 int launch_quality_frames(const void *a, const void *b, int n, int w, int h, int64_t stride_px, void *sse, void *ssim, hipStream_t stream);
 
+// tm_png.hip (host only): inflate of a zlib stream, the PNG reader (8-bit, non-interlaced; pixels 0x00RRGGBB; out null: the size only)
+uint32_t crc32_ieee(const uint8_t *p, size_t n);
+int inflate_zlib(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *out_n);
+int read_png(const char *path, uint32_t *out, int64_t cap_px, int *w, int *h);
+
+// tm_input.hip: Load's input.  What the probe half of Load (tilingencoder.pas:1764-1820) finds out about InputFileName.
+struct InputInfo {
+  int kind = 0;  // 0: the frames come from memory (pushed or lent); TM_INPUT_Y4M / TM_INPUT_PNGS: from the file
+  std::string name;
+  int start = 0, frames = 0, src_w = 0, src_h = 0, dst_w = 0, dst_h = 0, chroma = 0, full_range = 0;
+  double fps = 0;
+  int64_t frame_bytes = 0;
+  std::vector<int64_t> frame_off;   // Y4M: where every whole frame's planes start in the file
+  std::vector<int32_t> manual_kf;   // PNGs: frame 0 and the frames a .kf file marks (3380-3384)
+  bool decoded = false;             // the device clip holds frames [dec_first, +dec_count) converted with dec_mode
+  int dec_first = 0, dec_count = 0, dec_mode = 0;
+};
+struct PinnedBuf {  // page-locked host memory that only grows
+  void *p = nullptr;
+  size_t bytes = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf &) = delete;
+  PinnedBuf &operator=(const PinnedBuf &) = delete;
+  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+  int alloc(size_t n) {
+    if (p && n <= bytes) return TM_OK;
+    if (p) (void)hipHostFree(p);
+    p = nullptr; bytes = 0;
+    TM_HIP(hipHostMalloc(&p, n, hipHostMallocDefault));
+    bytes = n;
+    return TM_OK;
+  }
+};
+int probe_input(const std::string &name, int start_frame, int frame_count, double scaling, InputInfo *in);
+// the resampling tables of one conversion on the device: per axis first [m], count [m], coef [tap][m] (the lanes of a wave read neighbouring
+// words); a vertical axis also has, per tile of th output rows, the source rows its samples reach as (first row, number of rows)
+struct AxisTaps { const int32_t *first, *count, *coef; const int2 *span; };
+struct InputTables {
+  int src_w = 0, src_h = 0, chroma = -1, dst_w = 0, dst_h = 0, th = 0;  // th: output rows per workgroup
+  DevBuf dev;
+  AxisTaps lh{}, lv{}, ch{}, cv{};  // luma / chroma, horizontal / vertical
+};
+
 // One process per GPU: the collectives a step needs between its kernels, handed in by the host (tm_set_collective).  The calls
 // are made on the caller's thread with the encoder's stream idle, and return with the result in place.
 struct Collectives {

@@ -140,8 +140,12 @@ int load_tail(tm_encoder *e) {
     const float den = denx * deny;
     e->correl[f] = den != 0.0f ? sums[f * 3] / den : 1.0f;
   }
-  // FindKeyFrames, automatic mode (3373-3411)
   e->kf_start.clear();
+  if (e->kf_manual) {  // FindKeyFrames, manual mode (3380-3384): the thresholds and the spacing play no part
+    e->kf_start = e->kf_manual_list;
+    return TM_OK;
+  }
+  // FindKeyFrames, automatic mode (3373-3411)
   int64_t last = INT32_MIN;
   for (int f = 0; f < e->nframes; f++) {
     bool kf = f == 0;
@@ -179,12 +183,13 @@ int queue_host_clip(tm_encoder *e, int slot, const void *host) {
   return TM_OK;
 }
 
-static int step_load(tm_encoder *e) {  // Load, tilingencoder.pas:1741-1841 (decode excluded: frames are pushed in)
+static int step_load(tm_encoder *e) {  // Load, tilingencoder.pas:1741-1841 (frames are pushed in, or decoded from InputFileName: tm_input.hip)
   TM_TRY(load_tail(e));  // (a correlation still running reads the Lab means this Load is about to replace)
   e->drop_prefetch();  // features of the previous frame tiles
   e->q_groups = 0;
   e->load_sharded = false;
   TM_CHECK(e->nframes > 0 && e->width > 0, TM_E_INVAL, "tm_set_video has not been called");
+  if (e->input.kind) TM_TRY(load_from_input(e));  // the source "file": from here on as if the clip had been set with tm_set_frames_device / _host
   if (e->frames_peer) {
     // a device group's clip on another device (tm_set_frames_device): this shard pulls the frames its Load reads into its own memory
     const size_t fbytes = (size_t)e->width * e->height * 4;
@@ -269,6 +274,8 @@ static int step_load(tm_encoder *e) {  // Load, tilingencoder.pas:1741-1841 (dec
   TM_TRY(dcorrel.alloc((size_t)e->nframes * 12));
   e->h_fflags.clear();  // fetched lazily by tm_get_tilemap
   e->kf_lo_thres = e->s.ShotTransCorrelLoThres; e->kf_min_s = e->s.ShotTransMinSecondsPerKF; e->kf_max_s = e->s.ShotTransMaxSecondsPerKF; e->kf_fps = e->fps;
+  e->kf_manual = e->input.kind == TM_INPUT_PNGS;
+  e->kf_manual_list = e->kf_manual ? e->input.manual_kf : std::vector<int32_t>();
   if (e->load_sharded) {
     const int64_t f0 = e->load_first, f1 = f0 + e->load_count, lo = std::max<int64_t>(f0 - 1, 0);
     TM_HIP(hipMemsetAsync(dcorrel.p, 0, (size_t)e->nframes * 12, e->stream));
@@ -304,6 +311,7 @@ static int step_load(tm_encoder *e) {  // Load, tilingencoder.pas:1741-1841 (dec
   e->t = 0;
   e->has_pal_px = e->reconstructed = e->has_pm = false;
   TM_HIP(hipStreamSynchronize(e->stream));  // Run(esLoad) is blocking for everything but the correlation above (and the stage times stay the stages')
+  std::vector<uint32_t>().swap(e->input_clip);  // (a PNG sequence's host copy: the device holds it now)
   progress(e, TM_STEP_LOAD, 3, 3);
   return TM_OK;
 }

@@ -33,6 +33,13 @@ class TPsyVisMode(enum.IntEnum):  # tilingencoder.pas:21
     pvsWeightedSpeDCT = 4
 
 
+class TInputYUV(enum.IntEnum):  # tm_set_input_yuv: how a Y4M clip's samples become RGB
+    yuvAuto = 0
+    yuvBT601Limited = 1
+    yuvBT601Full = 2
+    yuvTiler = 3
+
+
 TILE_HDR = np.dtype([("UseCount", "<u4"), ("TmpIndex", "<i4"), ("MergeIndex", "<i4"), ("PalIdx_Initial", "<i4"), ("Flags", "<u4")])
 TILEMAP_ITEM = np.dtype([("TileIdx", "<i4"), ("PalIdx", "<i4"), ("PredictedX", "i1"), ("PredictedY", "i1"), ("PSNR", "<f4"),
                          ("Flags", "<u4")])  # packed, 18 bytes (tilingencoder.pas:178-184)
@@ -58,6 +65,9 @@ _ENC_SIGS = {
     "tm_set_frames_device": (c_int, [c_void_p, c_void_p]),
     "tm_set_frames_host": (c_int, [c_void_p, c_void_p]),
     "tm_prefetch_frames_host": (c_int, [c_void_p, c_void_p]),
+    "tm_open_input": (c_int, [c_void_p]),
+    "tm_get_video": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_double), ctypes.POINTER(c_int)]),
+    "tm_set_input_yuv": (c_int, [c_void_p, c_int]),
     "tm_run": (c_int, [c_void_p, c_int]),
     "tm_get_counts": (c_int, [c_void_p, ctypes.POINTER(c_int64)] + [ctypes.POINTER(c_int)] * 5),
     "tm_get_tile": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
@@ -150,6 +160,9 @@ class TilingEncoder:
             check(self._L.tm_set_float(c_void_p(self._h), name.encode(), float(value)))
         elif name in ("InputFileName", "OutputFileName"):
             check(self._L.tm_set_str(c_void_p(self._h), name.encode(), str(value).encode()))
+        elif name == "InputYUV":  # not a settings key (the INI text is the reference's): TInputYUV
+            check(self._L.tm_set_input_yuv(c_void_p(self._h), int(value)))
+            object.__setattr__(self, "_input_yuv", TInputYUV(int(value)))
         else:
             object.__setattr__(self, name, value)
 
@@ -172,6 +185,23 @@ class TilingEncoder:
 
     def SetVideo(self, width, height, fps, frame_count):
         check(self._L.tm_set_video(c_void_p(self._h), width, height, float(fps), frame_count))
+
+    def OpenInput(self):
+        """The probe half of Load (tilingencoder.pas:1764-1820): InputFileName -- a Y4M file, or a Format pattern naming a PNG sequence --
+        with StartFrame, FrameCount and Scaling becomes the video (as SetVideo) and the frame source of the next Run(esLoad).  Run calls
+        it by itself when no video has been described yet.  Returns VideoInfo()."""
+        check(self._L.tm_open_input(c_void_p(self._h)))
+        return self.VideoInfo()
+
+    def VideoInfo(self):
+        """width, height, fps, frames as SetVideo / OpenInput left them (tm_get_video)"""
+        w, h, n, fps = c_int(), c_int(), c_int(), c_double()
+        check(self._L.tm_get_video(c_void_p(self._h), ctypes.byref(w), ctypes.byref(h), ctypes.byref(fps), ctypes.byref(n)))
+        return dict(width=w.value, height=h.value, fps=fps.value, frames=n.value)
+
+    @property
+    def InputYUV(self):
+        return self.__dict__.get("_input_yuv", TInputYUV.yuvAuto)
 
     def PushFrame(self, index, pixels):
         """pixels: numpy uint32 [height][width] RGB32 (AV_PIX_FMT_RGB32), host memory, read during the call only"""

@@ -30,6 +30,21 @@ def load(frames, tm_w, tm_h):
     return tiles, flags, lab
 
 
+def yuv_to_rgb32(y, u, v, chroma, dst_w, dst_h, yuv_mode=0):
+    """Planes of a Y4M clip -> RGB32 frames (tm_stage_yuv_to_rgb32): chroma upsampling, the Lanczos-3 resize and the colour conversion in
+    one kernel.  y uint8 [F][H][W]; u, v uint8 [F][ch][cw] (None for chroma 4 = mono); chroma: TM_CHROMA_* (0 444, 1 422, 2 420jpeg,
+    3 420mpeg2, 4 mono); yuv_mode: TM_YUV_* -> int32 [F][dst_h][dst_w] 0x00RRGGBB"""
+    assert y.is_cuda and y.dtype == torch.uint8 and y.dim() == 3 and y.stride(2) == 1
+    f, h, w = y.shape
+    strides = [y.stride(1), y.stride(0)]
+    for c in (u, v):
+        assert c is None or (c.is_cuda and c.dtype == torch.uint8 and c.dim() == 3 and c.stride(2) == 1 and c.shape[0] == f)
+        strides += [c.stride(1), c.stride(0)] if c is not None else [0, 0]
+    out = torch.empty((f, dst_h, dst_w), dtype=torch.int32, device=y.device)
+    check(lib().tm_stage_yuv_to_rgb32(_p(y), _p(u), _p(v), (ctypes.c_int64 * 6)(*strides), f, w, h, int(chroma), dst_w, dst_h, int(yuv_mode), _p(out), _stream()))
+    return out
+
+
 def rgb_to_lab(rgb):
     """RGBToLAB (utils.pas:374-410) of colours 0x00RRGGBB (int32 [n]) -> float32 [n][3]"""
     assert rgb.is_cuda and rgb.dtype == torch.int32 and rgb.is_contiguous()

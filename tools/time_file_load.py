@@ -1,0 +1,99 @@
+"""Wall time of Load from a Y4M file against Load of the same clip as RGB32 in page-locked host memory.
+
+    python tools/time_file_load.py [--mode file|host|both] [--frames 300 --width 1280 --height 720] [--scaling 1.0] [--passes 7] [--dir /dev/shm]
+
+The clip is bench.py's (SURVEY.md 8d's generator).  `file`: it is written as a 4:2:0 Y4M into --dir (memory-backed by default, so that the
+figure is the pipeline's and not a disk's) and every pass is OpenInput + Run(esLoad).  `host`: the RGB32 clip sits in pinned memory and every
+pass is SetFramesHost + Run(esLoad) -- the path a caller had before Load could read a file; it uses no call newer than that, so the same
+script times an older build of the library.  One warm-up pass, then the median of --passes passes with their spread; one JSON line."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def rgb_to_yuv420(frames):
+    """BT.601 limited range, chroma as the mean of each 2x2 block (centred: C420jpeg)"""
+    r, g, b = ((frames >> s) & 255 for s in (16, 8, 0))
+    y = ((66 * r + 129 * g + 25 * b + 128) >> 8) + 16
+    u = ((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128
+    v = ((112 * r - 94 * g - 18 * b + 128) >> 8) + 128
+    h, w = frames.shape
+    sub = lambda c: (c.reshape(h // 2, 2, w // 2, 2).sum((1, 3)) + 2) >> 2
+    return y.astype(np.uint8), sub(u).astype(np.uint8), sub(v).astype(np.uint8)
+
+
+def stats(ms):
+    return dict(median_ms=statistics.median(ms), min_ms=min(ms), max_ms=max(ms), passes=len(ms))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=["file", "host", "both"], default="both")
+    ap.add_argument("--frames", type=int, default=300)
+    ap.add_argument("--width", type=int, default=1280)
+    ap.add_argument("--height", type=int, default=720)
+    ap.add_argument("--scaling", type=float, default=1.0)
+    ap.add_argument("--passes", type=int, default=7)
+    ap.add_argument("--dir", default="/dev/shm")
+    args = ap.parse_args()
+    import torch
+    from bench import synth_clip
+    from tiler_amd.encoder import TilingEncoder, TEncoderStep as S
+    F, H, W = args.frames, args.height, args.width
+    assert W % 2 == 0 and H % 2 == 0
+    host = torch.empty((F, H, W), dtype=torch.int32, pin_memory=True)
+    clip = synth_clip(host.numpy(), freeze=True)
+    out = dict(clip="%dx%dx%d" % (W, H, F), scaling=args.scaling, rgb32_bytes=F * H * W * 4, yuv420_bytes=F * H * W * 3 // 2)
+
+    if args.mode in ("host", "both"):
+        enc = TilingEncoder()
+        enc.LoadDefaultSettings()
+        enc.SetVideo(W, H, 24.0, F)
+        ms = []
+        for p in range(args.passes + 1):
+            enc.SetFramesHost(host)
+            t0 = time.perf_counter()
+            enc.Run(S.esLoad)
+            ms.append((time.perf_counter() - t0) * 1e3)
+        enc.close()
+        out["load_host_rgb32"] = stats(ms[1:])
+
+    if args.mode in ("file", "both"):
+        path = os.path.join(args.dir, "time_file_load_%d.y4m" % os.getpid())
+        try:
+            with open(path, "wb") as f:
+                f.write(b"YUV4MPEG2 W%d H%d F24:1 Ip A1:1 C420jpeg\n" % (W, H))
+                for i in range(F):
+                    y, u, v = rgb_to_yuv420(clip[i].astype(np.int64))
+                    f.write(b"FRAME\n" + y.tobytes() + u.tobytes() + v.tobytes())
+            enc = TilingEncoder()
+            enc.LoadDefaultSettings()
+            enc.InputFileName = path
+            enc.Scaling = args.scaling
+            ms, open_ms = [], []
+            for p in range(args.passes + 1):
+                t0 = time.perf_counter()
+                info = enc.OpenInput()  # (a new probe: the Load behind it decodes the file again)
+                t1 = time.perf_counter()
+                enc.Run(S.esLoad)
+                t2 = time.perf_counter()
+                ms.append((t2 - t0) * 1e3)
+                open_ms.append((t1 - t0) * 1e3)
+            enc.close()
+            out["load_file_y4m420"] = dict(stats(ms[1:]), open_input_median_ms=statistics.median(open_ms[1:]), video=info)
+        finally:
+            if os.path.exists(path):
+                os.remove(path)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
