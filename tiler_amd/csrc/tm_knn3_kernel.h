@@ -122,8 +122,8 @@ __device__ __forceinline__ unsigned k3_bound_of(unsigned mx) { return mx == ~0u 
 
 // One block's chain: X over the digit products on one accumulator shifted between the phases; the rows' own term `cin` rides in on the
 // second shift.  With TD (database digits of 2 (t - c)) cin = |t-c|^2 and the chain ends in 2 X + |t-c|^2 = d'' - qn; without, cin =
-// |t-c|^2 >> 1 and it ends in Y = X + (|t-c|^2 >> 1): d'' - qn = 2 Y + (|t-c|^2 & 1), which the epilogue makes only for the blocks that
-// can matter (the doubling of sixteen registers was a fifth of a block's vector instructions).  `q` = the sub-tile's B operands in LDS at
+// |t-c|^2 >> 1 and it ends in Y = X + (|t-c|^2 >> 1): d'' - qn = 2 Y + (|t-c|^2 & 1), which the nearest-neighbour epilogue never makes per row
+// (the minimum and its row follow from min(Y) and the parities: k3_epilogue; the collection mode makes them for the blocks that can matter).  `q` = the sub-tile's B operands in LDS at
 // this lane's 16 bytes (chunk stride 1024).
 // `tm` / `qm` (wave-uniform): bit kc set = high-digit chunk kc of the tile / of the sub-tile holds a non-zero digit.  A product with an
 // all-zero chunk adds nothing and is skipped, its LDS read with it: the columns are packed widest first (make_plan_scaled), so a tile of
@@ -312,10 +312,12 @@ __device__ __forceinline__ void k3_load_tile_masked(const uint8_t *tb, int lane,
   k3_load_rows<KT>(tb, half, cin, pwh);
 }
 
-// the minimum of the chain's sixteen values of a lane
+// the minimum of the chain's sixteen values of a lane: a tree of three-way minima (five, two, one: eight instructions; pairs first cost ten)
+__device__ __forceinline__ int k3_min3(int a, int b, int c) { return min(min(a, b), c); }
 __device__ __forceinline__ int k3_min16(const int (&t)[16]) {
-  return min(min(min(min(t[0], t[1]), min(t[2], t[3])), min(min(t[4], t[5]), min(t[6], t[7]))),
-             min(min(min(t[8], t[9]), min(t[10], t[11])), min(min(t[12], t[13]), min(t[14], t[15]))));
+  const int a = k3_min3(t[0], t[1], t[2]), b = k3_min3(t[3], t[4], t[5]), c = k3_min3(t[6], t[7], t[8]), d = k3_min3(t[9], t[10], t[11]),
+            e = k3_min3(t[12], t[13], t[14]);
+  return min(k3_min3(a, b, c), k3_min3(d, e, t[15]));
 }
 // what a block's sixteen values say about a lane's query before anything is made of them: a LOWER bound of the smallest d'' - qn.  With
 // TD the chain's values are d'' - qn themselves; without, d'' - qn = 2 Y + parity and 2 min(Y) is at most one below the smallest.
@@ -343,34 +345,86 @@ __device__ __forceinline__ void k3_values(const v16i &acc, unsigned pwh, int (&t
   for (int r = 0; r < 16; r++) t[r] = TD ? acc[r] : (int)(((unsigned)acc[r] << 1) | ((pwh >> k3_prow(r)) & 1u));
 }
 
+// Which of a lane's sixteen registers hold `ym`: bit k3_prow(r) for register r, the positions `pwh` keeps the rows' parities at.  A compare
+// and an add-with-carry (E + E + equal: a shift that takes the compare's bit in) per register, from register 15 down, and a shift by four
+// between the groups of four: 35 vector instructions.  Written out by hand because a vector compare's result may be read by a vector
+// instruction only two issue slots later: left to the compiler every compare is followed by a two-cycle s_nop; here three compares are in
+// flight in three scalar pairs in turn, so every add-with-carry stands two instructions behind its compare and none waits.
+__device__ __forceinline__ unsigned k3_equal_mask(const v16i &acc, int ym) {
+  unsigned e;
+  unsigned long long c0, c1, c2;
+  asm("v_cmp_eq_u32_e64 %1, %19, %20\n\t"
+      "v_cmp_eq_u32_e64 %2, %18, %20\n\t"
+      "v_cmp_eq_u32_e64 %3, %17, %20\n\t"
+      "v_addc_co_u32_e64 %0, %1, 0, 0, %1\n\t"
+      "v_cmp_eq_u32_e64 %1, %16, %20\n\t"
+      "v_addc_co_u32_e64 %0, %2, %0, %0, %2\n\t"
+      "v_cmp_eq_u32_e64 %2, %15, %20\n\t"
+      "v_addc_co_u32_e64 %0, %3, %0, %0, %3\n\t"
+      "v_cmp_eq_u32_e64 %3, %14, %20\n\t"
+      "v_addc_co_u32_e64 %0, %1, %0, %0, %1\n\t"
+      "v_cmp_eq_u32_e64 %1, %13, %20\n\t"
+      "v_lshlrev_b32_e32 %0, 4, %0\n\t"
+      "v_addc_co_u32_e64 %0, %2, %0, %0, %2\n\t"
+      "v_cmp_eq_u32_e64 %2, %12, %20\n\t"
+      "v_addc_co_u32_e64 %0, %3, %0, %0, %3\n\t"
+      "v_cmp_eq_u32_e64 %3, %11, %20\n\t"
+      "v_addc_co_u32_e64 %0, %1, %0, %0, %1\n\t"
+      "v_cmp_eq_u32_e64 %1, %10, %20\n\t"
+      "v_addc_co_u32_e64 %0, %2, %0, %0, %2\n\t"
+      "v_cmp_eq_u32_e64 %2, %9, %20\n\t"
+      "v_lshlrev_b32_e32 %0, 4, %0\n\t"
+      "v_addc_co_u32_e64 %0, %3, %0, %0, %3\n\t"
+      "v_cmp_eq_u32_e64 %3, %8, %20\n\t"
+      "v_addc_co_u32_e64 %0, %1, %0, %0, %1\n\t"
+      "v_cmp_eq_u32_e64 %1, %7, %20\n\t"
+      "v_addc_co_u32_e64 %0, %2, %0, %0, %2\n\t"
+      "v_cmp_eq_u32_e64 %2, %6, %20\n\t"
+      "v_addc_co_u32_e64 %0, %3, %0, %0, %3\n\t"
+      "v_cmp_eq_u32_e64 %3, %5, %20\n\t"
+      "v_lshlrev_b32_e32 %0, 4, %0\n\t"
+      "v_addc_co_u32_e64 %0, %1, %0, %0, %1\n\t"
+      "v_cmp_eq_u32_e64 %1, %4, %20\n\t"
+      "v_addc_co_u32_e64 %0, %2, %0, %0, %2\n\t"
+      "v_addc_co_u32_e64 %0, %3, %0, %0, %3\n\t"
+      "v_addc_co_u32_e64 %0, %1, %0, %0, %1"
+      : "=&v"(e), "=&s"(c0), "=&s"(c1), "=&s"(c2)
+      : "v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]), "v"(acc[4]), "v"(acc[5]), "v"(acc[6]), "v"(acc[7]), "v"(acc[8]), "v"(acc[9]), "v"(acc[10]),
+        "v"(acc[11]), "v"(acc[12]), "v"(acc[13]), "v"(acc[14]), "v"(acc[15]), "v"(ym));
+  return e;
+}
+
 // A block's epilogue: the row minimum of each query (lane & 31; the two half-waves hold 16 rows each) against its running best in LDS.
 // d'' = 2 X + |t-c|^2 + 2 (|q-c|^2 >> 1) = SSD - parity.  Returns true in lanes whose improvement may have lowered the sub-tile's largest
 // best (the caller refreshes the bound when any lane says so); `sm_now` = the sub-tile's published bound, or 0 to ask for a refresh on
 // every improvement.
+// The minimum and the rows reaching it come from the first look's own minimum ym = min Y_r.  A row's value is 2 Y_r + parity_r,
+// and a row with Y_r >= ym + 1 is worth at least 2 ym + 2: so the minimum is 2 ym + p, p the smallest parity among the rows with Y_r = ym,
+// and the rows reaching it are those with Y_r = ym and parity p.  With TD the values are the Y_r (p = 0).  Neither the sixteen values nor a
+// second minimum are made, and the row is named by a bit scan: k3_prow grows with r, so the lowest set bit is the first register's row.
 template <bool TD>
 __device__ __forceinline__ bool k3_epilogue(const v16i &acc, unsigned pwh, int tile, int half, unsigned qn, unsigned long long *best, unsigned *tie,
                                             unsigned sm_now, unsigned cur_hi /* the query's best as read BEFORE the chain: stale only on the safe side (a best only falls) */) {
   bool refresh = false;
-  if (k3_may_matter<TD>(acc, qn, cur_hi)) {  // (by the counters nearly half of the listed blocks improve or tie some query's best)
-    int t[16];
-    k3_values<TD>(acc, pwh, t);
-    const int tm = k3_min16(t);
-    const unsigned key_hi = (unsigned)tm + qn + 1u;  // d'' + 1 >= 0
-    if (key_hi <= cur_hi) {
-      // which row (the first one reaching the minimum), and is it alone: a compare, a select and an add-with-carry per register
-      int ridx = 0;
-      unsigned cnt = 0;
+  int y[16];
 #pragma unroll
-      for (int r = 15; r >= 0; r--) {
-        const bool e = t[r] == tm;
-        ridx = e ? r : ridx;
-        cnt += e ? 1u : 0u;
-      }
-      const int row = (ridx & 3) + ((ridx & 12) << 1) + 4 * half;
+  for (int r = 0; r < 16; r++) y[r] = acc[r];
+  const int ym = k3_min16(y);
+  const unsigned look = (unsigned)(TD ? ym : (int)((unsigned)ym << 1)) + qn + 1u;  // k3_may_matter's test, on a minimum that is kept
+  if (TD ? look <= cur_hi : (int)look <= (int)min(cur_hi, 0x7FFFFFFFu)) {  // (by the counters nearly half of the listed blocks improve or tie some query's best)
+    const unsigned eq = k3_equal_mask(acc, ym);
+    unsigned win = eq, key_hi = look;  // d'' + 1 >= 0
+    if (!TD) {
+      const unsigned even = eq & ~pwh;  // the rows at ym whose parity is 0
+      win = even ? even : eq;
+      key_hi = look + (even ? 0u : 1u);
+    }
+    if (key_hi <= cur_hi) {
+      const int row = __builtin_ctz(win) + 4 * half;  // the first row reaching the minimum
       const unsigned long long key = ((unsigned long long)key_hi << 32) | (unsigned)((tile << 5) | row);
       const unsigned long long pre = atomicMin(best, key);
       const unsigned pre_hi = (unsigned)(pre >> 32);
-      if (pre_hi == key_hi || cnt > 1) atomicMin(tie, key_hi);  // the value was reached a second time
+      if (pre_hi == key_hi || (win & (win - 1u)) != 0) atomicMin(tie, key_hi);  // the value was reached a second time
       // The sub-tile's largest best can only have moved if this query held it: its old best is then no smaller than what the published
       // bound was made from ((bound - 3)^2; a bound of 0xFFFE stands for "some query has no best yet").  A refresh skipped by a race only
       // leaves the bound loose (and is made good at the end of the segment).
@@ -819,6 +873,13 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
   const int nseg = dense ? (int)((n_ttiles + LCAP - 1) / LCAP) : a.nsegs[g];
   __syncthreads();  // (waits for the LDS-DMA pieces too)
   const unsigned qmask_v = s_qmask[lane & 15];  // lane s: sub-tile s's mask of non-zero high-digit chunks
+  // Where this lane's query sits in a sub-tile's operands, bests and norms (LDS byte offsets): a block adds the sub-tile's part, which is
+  // wave-uniform, with one instruction each (made from the sub-tile's index per block, the three addresses took six, a multiply among them)
+  // (made per group from a thread index taken afresh, like the other phases' addresses: see the prologue)
+  unsigned tb = threadIdx.x;
+  asm volatile("" : "+v"(tb));
+  unsigned a_q = (tb & 63u) * 16u, a_best = (unsigned)OFF_BEST + (tb & 31u) * 8u, a_qn = (unsigned)OFF_QN + (tb & 31u) * 4u;
+  asm volatile("" : "+v"(a_q), "+v"(a_best), "+v"(a_qn));
   K3_STAMP(0);  // prologue
 
   for (int seg = 0; seg < nseg; seg++) {
@@ -901,18 +962,19 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
         const int vt = (int)min((int64_t)32, a.nt_rows - (int64_t)tile * 32);
         // a block's epilogue and the refresh of its sub-tile's bound
         auto finish = [&](const v16i &acc, int s, unsigned sm_now, unsigned cur_hi, unsigned qn) {
-          const int qi = s * 32 + (lane & 31);
+          unsigned long long *const bp = reinterpret_cast<unsigned long long *>(lds + (a_best + (unsigned)s * 256u));  // &s_best[s * 32 + (lane & 31)]
           bool refresh;
           if constexpr (TOPK) {
+            const int qi = s * 32 + (lane & 31);
             const int64_t q = (st0 + s) * 32 + (lane & 31);
             // (the last database tile pads with copies of its last row: they are candidates like any row -- the select stage drops them --
             // but must not count towards a rung)
             refresh = k3_epilogue_topk<TD>(acc, pwh, tile, tile != (int)n_ttiles - 1, half, qn, &s_best[qi], &s_lad[qi * 4], &s_tie[qi], q < a.nq, q, a, sm_now);
           } else {
-            refresh = k3_epilogue<TD>(acc, pwh, tile, half, qn, &s_best[qi], &s_tie[qi], sm_now, cur_hi);
+            refresh = k3_epilogue<TD>(acc, pwh, tile, half, qn, bp, reinterpret_cast<unsigned *>(lds + (a_qn + (unsigned)(OFF_TIE - OFF_QN) + (unsigned)s * 128u)), sm_now, cur_hi);
           }
           if (__builtin_amdgcn_ballot_w64(refresh)) {  // refresh the sub-tile's largest best (bests only go down: a late writer is only loose)
-            const unsigned mx = k3_wave_umax(k3_peek(reinterpret_cast<unsigned *>(s_best) + qi * 2 + 1));  // = largest d'' + 1
+            const unsigned mx = k3_wave_umax(k3_peek(reinterpret_cast<unsigned *>(bp) + 1));  // = largest d'' + 1
             if (mx != ~0u && lane == 0) atomicMin(&s_smax[s], k3_bound_of(mx));
           }
           nblocks++;
@@ -942,13 +1004,13 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
           // the sub-tile's mask comes out of a register (lane s of qmask_v), the query's best and norm are asked for before the chain: every
           // LDS round trip a block can do without, or start early, is one the wave does not sit out between its matrix instructions
           const unsigned qm0 = (unsigned)__builtin_amdgcn_readlane((int)qmask_v, s0);
-          const int qi0 = s0 * 32 + (lane & 31);
 #ifndef TM_KNN3_PRE_QN
 #define TM_KNN3_PRE_QN 1
 #endif
-          const unsigned cur0 = TOPK ? 0u : k3_peek(reinterpret_cast<unsigned *>(&s_best[qi0]) + 1);
+          const unsigned cur0 = TOPK ? 0u : k3_peek(reinterpret_cast<unsigned *>(lds + (a_best + (unsigned)s0 * 256u)) + 1);
+          const int *const qn0_p = reinterpret_cast<const int *>(lds + (a_qn + (unsigned)s0 * 128u));  // &s_qn[s0 * 32 + (lane & 31)]
           unsigned qn0 = 0;
-          if (TM_KNN3_PRE_QN) qn0 = (unsigned)s_qn[qi0];
+          if (TM_KNN3_PRE_QN) qn0 = (unsigned)*qn0_p;
           const int s1 = (TM_KNN3_DUAL && !TOPK) ? pick(sm1) : -1;
           if (s1 >= 0) {  // two blocks at once
             const unsigned qm1 = (unsigned)__builtin_amdgcn_readlane((int)qmask_v, s1);
@@ -964,10 +1026,13 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
             // (measured in round 5 and dropped: every product's operand read one product ahead -- the reads issued whatever the predicates say, with
             // no lane enabled where the product will not run, so that the waits can name the read they need: 13.5 against 11.8 ms; the thirteen
             // reads that read nothing still pass through the CU's one LDS queue)
-            const v16i acc = k3_chain<HT, HQ, TD>(T, cin, lds + s0 * (KQ * 1024) + lane * 16, tm, qm0);
+            // (the sub-tile's operands begin at s0 * KQ KB: a product the compiler makes on the vector unit, a 24-bit multiply, unless told otherwise)
+            unsigned q_off;
+            asm("s_mul_i32 %0, %1, %2" : "=s"(q_off) : "s"(s0), "n"(KQ * 1024));
+            const v16i acc = k3_chain<HT, HQ, TD>(T, cin, lds + (a_q + q_off), tm, qm0);
             nmfma += k3_chain_products<HT, HQ>(tm, qm0);
             K3_STAMP(6);  // the chain, up to the issue of its last matrix instruction
-            if (!TM_KNN3_PRE_QN) qn0 = (unsigned)s_qn[qi0];
+            if (!TM_KNN3_PRE_QN) qn0 = (unsigned)*qn0_p;
             finish(acc, s0, sm0, cur0, qn0);
             K3_STAMP(7);  // the epilogue (behind the wait for the chain's result)
           }
