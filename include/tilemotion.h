@@ -69,8 +69,8 @@
  *                           other processes or shards (120)
  *   TM_GROUP_FAIL_SHARD=<r> shard r of a device group fails with TM_E_INVAL ("forced") at the start of its next step, before it queues any work
  *                           (tests: the other shards must leave their collectives at once)
- *   TM_INPUT_CHUNK_FRAMES=<n> Load reads a Y4M file n frames at a time instead of 16 MB worth (tests: 1, so that a small clip walks the two staging
- *                           buffers many times)
+ *   TM_INPUT_CHUNK_FRAMES=<n> Load reads a Y4M file, or stages a lent YUV clip, n frames at a time instead of 16 MB worth (tests: 1, so that a small
+ *                           clip walks the two staging buffers many times)
  *   TM_POOL_GIB=<x>         cap of the device-memory pool a thread keeps (96); TM_HOST_THREADS=<n>: OptimizePalettes' helper threads
  *                           (both read once per process)
  */
@@ -194,13 +194,53 @@ TM_API int tm_open_input(tm_encoder *);
 TM_API int tm_get_video(tm_encoder *, int *width, int *height, double *fps, int *frames); /* as tm_set_video / tm_open_input left them; any pointer may be NULL */
 /* How a Y4M clip's samples become RGB (not a settings key: the INI text is the reference's).  AUTO: BT601_FULL under XCOLORRANGE=FULL, else
  * BT601_LIMITED (what FFmpeg assumes for an untagged file).  TILER: YUVToRGB(Y, U - 128, V - 128) (utils.pas:492-509), for files of
- * tm_generate_y4m. */
-enum { TM_YUV_AUTO = 0, TM_YUV_BT601_LIMITED = 1, TM_YUV_BT601_FULL = 2, TM_YUV_TILER = 3 };
+ * tm_generate_y4m.  BT709_LIMITED / BT709_FULL: the matrix of HD sources (Kr = 0.2126, Kb = 0.0722), never chosen by AUTO -- name it.  With
+ * D = U - 128, E = V - 128 and every channel clamped to 0 .. 255:
+ *   BT709_LIMITED, C = Y - 16:  R = (298C + 459E + 128) >> 8,  G = (298C - 55D - 136E + 128) >> 8,  B = (298C + 541D + 128) >> 8
+ *   BT709_FULL:  R = (65536Y + 103206E + 32768) >> 16,  G = (65536Y - 12276D - 30679E + 32768) >> 16,  B = (65536Y + 121609D + 32768) >> 16
+ * (round(k 2^n) of the matrix; the limited rule scales luma by 255/219 and chroma by 255/224). */
+enum { TM_YUV_AUTO = 0, TM_YUV_BT601_LIMITED = 1, TM_YUV_BT601_FULL = 2, TM_YUV_TILER = 3, TM_YUV_BT709_LIMITED = 4, TM_YUV_BT709_FULL = 5 };
 TM_API int tm_set_input_yuv(tm_encoder *, int mode);
 enum { TM_INPUT_Y4M = 1, TM_INPUT_PNGS = 2 };
 /* chroma layouts: where the U / V samples sit among the luma samples (420jpeg: centred in both axes; 420mpeg2 and 422: on the even luma
  * columns, 420mpeg2 centred vertically); odd luma sizes give planes of (n + 1) / 2 samples */
 enum { TM_CHROMA_444 = 0, TM_CHROMA_422 = 1, TM_CHROMA_420JPEG = 2, TM_CHROMA_420MPEG2 = 3, TM_CHROMA_MONO = 4 };
+/* A YUV clip LENT in memory, as a decoder leaves it: planar (yuv420p and its kin), or with U and V interleaved (NV12, P010, P016), 8-bit or
+ * 9 .. 16-bit samples in little-endian words, in host memory or on a device.  U16_LOW holds the sample in the low `depth` bits of the word
+ * (yuv420p10le), U16_HIGH in the high bits (P010, P016).  A deep sample becomes a byte where it is fetched, and everything after that is the
+ * 8-bit rule bit for bit:
+ *   p_d = word & (2^d - 1) (U16_LOW: the bits above the depth are ignored),  p_d = word >> (16 - d) (U16_HIGH: the low bits are ignored)
+ *   p = min(255, (p_d + 2^(d-9)) >> (d - 8))                                 (10-bit limited range 64 .. 940 lands on 16 .. 235)
+ * With v == NULL the plane u has cw (U, V) pairs per row: U is sample 2k, V sample 2k + 1 of the row; nothing else differs from two planes.
+ * Strides are in bytes.  The struct is 120 bytes: y 0, u 8, v 16, the six strides 24 .. 64, width 72, height 76, frames 80, fps 88, chroma 96,
+ * samples 100, depth 104, full_range 108, memory 112. */
+enum { TM_SAMPLES_U8 = 0, TM_SAMPLES_U16_LOW = 1, TM_SAMPLES_U16_HIGH = 2 };
+enum { TM_MEM_HOST = 0, TM_MEM_DEVICE = 1 };
+typedef struct {
+  const void *y, *u, *v;          /* v == NULL: u holds interleaved (U, V) pairs, U first (NV12, P010, P016) */
+  int64_t y_row, y_frame, u_row, u_frame, v_row, v_frame;   /* bytes */
+  int width, height, frames; double fps;
+  int chroma;                     /* TM_CHROMA_*; MONO: u, v unused */
+  int samples, depth;             /* U8: depth 8.  U16_*: little-endian words, depth 9..16 */
+  int full_range;                 /* what XCOLORRANGE says for a file: feeds TM_YUV_AUTO */
+  int memory;                     /* TM_MEM_* */
+} tm_yuv_clip;
+/* What tm_open_input does for a file, for a clip in memory: reads Scaling, describes the video as Round(width Scaling) x Round(height Scaling)
+ * (each at least 1; shrinking by more than 8 is TM_E_UNSUPPORTED) with the struct's fps and frame count, and makes the clip the frame source
+ * of the next tm_run(TM_STEP_LOAD), which converts it on the device as it does a Y4M file's planes.  StartFrame and FrameCount do not apply;
+ * the key frames follow the automatic rule.  The planes are BORROWED until that Load has returned; from then on the encoder reads its own
+ * RGB32 clip: a second Load with the same tm_set_input_yuv mode reads that clip again, one with another mode (or a larger share of the frames)
+ * is TM_E_INVAL -- lend the clip again.  tm_set_video, tm_push_frame_rgb32, tm_set_frames_* and tm_open_input switch the source away.
+ *   Planes on the encoder's own device (TM_MEM_DEVICE; the owner is asked of the runtime) are converted where they are.  Planes in host
+ * memory or on another device of a group go through two staging buffers in chunks (TM_INPUT_CHUNK_FRAMES applies), straight from page-locked
+ * memory, through the encoder's own page-locked buffers from pageable memory.
+ *   TM_E_INVAL, before anything is stored and before any device call: a null struct or y; chroma missing for a layout that has it, or v
+ * without u; width or height outside 1 .. 65536; frames < 1; fps <= 0; an unknown chroma, samples or memory value; depth != 8 with U8 or
+ * outside 9 .. 16 with U16_*; a row stride shorter than the plane's row in bytes (interleaved rows are twice as long); an odd pointer or
+ * stride with 16-bit samples; a negative frame stride.  A refused call leaves the encoder as it was.
+ *   tm_probe_yuv_clip_host is the host-only seam: the same checks and the size tm_set_frames_yuv would describe (pointers may be NULL). */
+TM_API int tm_set_frames_yuv(tm_encoder *, const tm_yuv_clip *clip);
+TM_API int tm_probe_yuv_clip_host(const tm_yuv_clip *clip, double scaling, int *dst_width, int *dst_height);
 /* Host-only seams of the above (no device needed).  tm_probe_input_host: what tm_open_input would find (kind: TM_INPUT_*; width, height:
  * the file's; any pointer may be NULL).  tm_read_png_host: a non-interlaced 8-bit PNG (grey, grey + alpha, RGB, RGBA, palette; alpha
  * dropped; CRCs and Adler-32 checked) as 0x00RRGGBB; out_rgb32 NULL gives the size only.  tm_inflate_host: one zlib stream (stored, fixed
@@ -363,6 +403,12 @@ TM_API int tm_stage_load(const void *frames, int nframes, int img_w, int img_h, 
  * constants 91881, 22554, 46802, 116130.  Blocking (builds and frees the tap tables). */
 TM_API int tm_stage_yuv_to_rgb32(const void *y, const void *u, const void *v, const int64_t *host_strides /* [6] */, int nframes, int src_w, int src_h,
                                  int chroma, int dst_w, int dst_h, int yuv_mode, void *out_rgb32, void *stream);
+/* The same for every sample format of tm_yuv_clip (see there for the depth rule and the interleaved layout): v == NULL means (U, V) pairs in
+ * u; samples: TM_SAMPLES_*; depth: 8, or 9 .. 16 for words.  With TM_SAMPLES_U8, depth 8 and three planes it is tm_stage_yuv_to_rgb32.
+ * yuv_mode also takes TM_YUV_BT709_LIMITED / _FULL, as the call above does. */
+TM_API int tm_stage_yuv_to_rgb32_fmt(const void *y, const void *u, const void *v /* NULL: pairs in u */, const int64_t *host_strides /* [6], bytes */,
+                                     int nframes, int src_w, int src_h, int chroma, int samples, int depth,
+                                     int dst_w, int dst_h, int yuv_mode, void *out_rgb32, void *stream);
 
 /* RGBToLAB (utils.pas:374-410) of n colours 0x00RRGGBB -> float [n][3] (L, a, b): the colour conversion the load and feature kernels
  * share, as an operator of its own (the whole 24-bit domain is checked against the oracle through it). */

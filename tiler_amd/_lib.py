@@ -22,6 +22,14 @@ _lib = None
 
 c_void_p, c_int, c_int64, c_double, c_char_p = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_char_p
 
+
+class YuvClip(ctypes.Structure):  # tm_yuv_clip: a YUV clip lent in memory (tm_set_frames_yuv)
+    _fields_ = [("y", c_void_p), ("u", c_void_p), ("v", c_void_p),
+                ("y_row", c_int64), ("y_frame", c_int64), ("u_row", c_int64), ("u_frame", c_int64), ("v_row", c_int64), ("v_frame", c_int64),
+                ("width", c_int), ("height", c_int), ("frames", c_int), ("fps", c_double),
+                ("chroma", c_int), ("samples", c_int), ("depth", c_int), ("full_range", c_int), ("memory", c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/tilemotion.h one to one
 SIGNATURES = {
     "tm_last_error": (c_char_p, []),
@@ -60,6 +68,9 @@ SIGNATURES = {
                                 c_void_p, c_void_p]),
     "tm_stage_frame_quality": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
     "tm_stage_yuv_to_rgb32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "tm_stage_yuv_to_rgb32_fmt": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                          c_void_p]),
+    "tm_probe_yuv_clip_host": (c_int, [ctypes.POINTER(YuvClip), c_double, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "tm_probe_input_host": (c_int, [c_char_p, c_int, c_int, c_double] + [ctypes.POINTER(c_int)] * 5 + [ctypes.POINTER(c_double)] + [ctypes.POINTER(c_int)] * 2),
     "tm_read_png_host": (c_int, [c_char_p, c_void_p, c_int64, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "tm_inflate_host": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),

@@ -1,5 +1,5 @@
-// tm_input.hip -- Load's input: the probe half of Load (tilingencoder.pas:1764-1820) for Y4M files and numbered PNG sequences, the
-// Lanczos-3 resampling tables, and the kernel that turns planes of Y, U, V into the RGB32 frames Load reads.
+// tm_input.hip -- Load's input: the probe half of Load (tilingencoder.pas:1764-1820) for Y4M files and numbered PNG sequences, YUV clips lent
+// in memory (tm_set_frames_yuv), the Lanczos-3 resampling tables, and the kernel that turns planes of Y, U, V into the RGB32 frames Load reads.
 //
 // The reference opens "any file" through FFmpeg and scales with libswscale's Lanczos (extern.pas:780-781, 837-840).  Neither exists here
 // (DESIGN.md sections 9 and 17): Y4M is the uncompressed container every FFmpeg build writes, and the resampler is a stated integer rule of
@@ -82,8 +82,22 @@ static int chroma_geom(int chroma, int w, int h, ChromaGeom *g) {
 // into LDS as int32 (the rule keeps 7 extra bits between the passes), then every lane runs the vertical pass for four neighbouring pixels of
 // one row out of LDS; the three results stay in registers for the colour conversion and leave as one 16-byte store.  No plane goes to HBM
 // between the passes.  The host picks th so that the rows a tile reaches fit IN_HROWS (in_tile_rows).
+//
+// The samples are read in one place, the horizontal pass, and how is a compile-time property of the kernel: BYTES per sample (1, or 2 for
+// little-endian words) and CSTEP, the distance in samples between a chroma plane's neighbours (2 where U and V alternate in one plane: NV12,
+// P010; V's plane then starts one sample behind U's).  Words become bytes right there (DeepRule), so everything behind the fetch is the 8-bit rule.
 constexpr int IN_TW = 64, IN_HROWS = 96, IN_TH_MAX = 16;
-struct PlaneSrc { const uint8_t *p; int64_t row, frame; };
+struct PlaneSrc { const uint8_t *p; int64_t row, frame; };  // strides in bytes
+struct DeepRule { int rshift, mask, half, nshift; };  // p_d = (word >> rshift) & mask;  p = min(255, (p_d + half) >> nshift), half = 2^(nshift - 1)
+
+template <int BYTES>
+__device__ __forceinline__ int fetch_sample(const uint8_t *at, const DeepRule &d) {
+  if constexpr (BYTES == 1) return (int)*at;
+  else {
+    const int pd = ((int)*reinterpret_cast<const uint16_t *>(at) >> d.rshift) & d.mask;
+    return min(255, (pd + d.half) >> d.nshift);
+  }
+}
 
 __device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 
@@ -94,6 +108,15 @@ __device__ __forceinline__ uint32_t yuv_to_rgb32(int Y, int U, int V, int mode) 
     R = (65536 * Y + 91881 * E + 32768) >> 16;
     G = (65536 * Y - 22554 * D - 46802 * E + 32768) >> 16;
     B = (65536 * Y + 116130 * D + 32768) >> 16;
+  } else if (mode == TM_YUV_BT709_FULL) {  // round(k 2^16) of the matrix of Kr = 0.2126, Kb = 0.0722
+    R = (65536 * Y + 103206 * E + 32768) >> 16;
+    G = (65536 * Y - 12276 * D - 30679 * E + 32768) >> 16;
+    B = (65536 * Y + 121609 * D + 32768) >> 16;
+  } else if (mode == TM_YUV_BT709_LIMITED) {  // the same matrix, luma scaled by 255/219 and chroma by 255/224, 8 fractional bits
+    const int C = Y - 16;
+    R = (298 * C + 459 * E + 128) >> 8;
+    G = (298 * C - 55 * D - 136 * E + 128) >> 8;
+    B = (298 * C + 541 * D + 128) >> 8;
   } else if (mode == TM_YUV_TILER) {  // YUVToRGB, utils.pas:492-509: Single operands, every right-hand side in double, narrowed once
     const double y = (double)(float)Y, u = (double)(float)D, v = (double)(float)E;
     const float r = __double2float_rn(__dadd_rn(y, __dmul_rn(v, 1.13983)));
@@ -109,7 +132,8 @@ __device__ __forceinline__ uint32_t yuv_to_rgb32(int Y, int U, int V, int mode) 
   return (uint32_t)clamp255(R) << 16 | (uint32_t)clamp255(G) << 8 | (uint32_t)clamp255(B);
 }
 
-__global__ __launch_bounds__(256) void k_yuv_to_rgb32(PlaneSrc sy, PlaneSrc su, PlaneSrc sv, AxisTaps lh, AxisTaps lv, AxisTaps ch, AxisTaps cv, int dst_w,
+template <int BYTES, int CSTEP>
+__global__ __launch_bounds__(256) void k_yuv_to_rgb32(PlaneSrc sy, PlaneSrc su, PlaneSrc sv, DeepRule deep, AxisTaps lh, AxisTaps lv, AxisTaps ch, AxisTaps cv, int dst_w,
                                                       int dst_h, int th, int mode, int vec_ok, uint32_t *__restrict__ out) {
   __shared__ __attribute__((aligned(16))) int32_t hbuf[IN_HROWS * IN_TW];
   const int x0 = blockIdx.x * IN_TW, y0 = blockIdx.y * th, frame = blockIdx.z;
@@ -133,10 +157,11 @@ __global__ __launch_bounds__(256) void k_yuv_to_rgb32(PlaneSrc sy, PlaneSrc su, 
     }
     const AxisTaps ah = p == 0 ? lh : ch, av = p == 0 ? lv : cv;
     const int c01 = p == 0 ? 0 : 1, r0 = span[c01].x, rows = span[c01].y;
+    const int eb = (p == 0 ? 1 : CSTEP) * BYTES;  // bytes from one of the plane's samples to the next (the loop over p is unrolled: a constant)
     __syncthreads();  // the plane before has been read
     if (x0 + hx < dst_w) {
       const int ox = x0 + hx, k0 = hfirst[c01], cnt = hcount[c01];
-      const uint8_t *col = src.p + (int64_t)frame * src.frame + k0;
+      const uint8_t *col = src.p + (int64_t)frame * src.frame + (int64_t)k0 * eb;
       // four rows at a time, so that a coefficient is loaded once for four products
       constexpr int RS = 256 / IN_TW;
       for (int rb = hr0; rb < rows; rb += 4 * RS) {
@@ -146,7 +171,7 @@ __global__ __launch_bounds__(256) void k_yuv_to_rgb32(PlaneSrc sy, PlaneSrc su, 
           const int c = ah.coef[(int64_t)k * dst_w + ox];
 #pragma unroll
           for (int i = 0; i < 4; i++)
-            if (rb + i * RS < rows) acc[i] += c * (int)row[(int64_t)i * RS * src.row + k];
+            if (rb + i * RS < rows) acc[i] += c * fetch_sample<BYTES>(row + (int64_t)i * RS * src.row + k * eb, deep);
         }
 #pragma unroll
         for (int i = 0; i < 4; i++)
@@ -267,16 +292,29 @@ static int build_input_tables(int src_w, int src_h, int chroma, int dst_w, int d
   return TM_OK;
 }
 
-static int launch_yuv_to_rgb32(const InputTables &t, const void *y, const void *u, const void *v, const int64_t strides[6], int nframes, int yuv_mode, void *out,
-                               hipStream_t stream) {
+// how the samples of a clip's planes are stored (tm_yuv_clip): TM_SAMPLES_*, the depth, and whether U and V alternate in the plane `u`
+struct SampleFmt {
+  int samples = TM_SAMPLES_U8, depth = 8;
+  bool pairs = false;
+  int bytes() const { return samples == TM_SAMPLES_U8 ? 1 : 2; }
+};
+
+static int launch_yuv_to_rgb32(const InputTables &t, const void *y, const void *u, const void *v, const int64_t strides[6], const SampleFmt &fmt, int nframes,
+                               int yuv_mode, void *out, hipStream_t stream) {
   if (nframes == 0) return TM_OK;
-  const bool has_c = t.chroma != TM_CHROMA_MONO;
+  const bool has_c = t.chroma != TM_CHROMA_MONO, pairs = has_c && fmt.pairs;
   const PlaneSrc sy{(const uint8_t *)y, strides[0], strides[1]}, su{has_c ? (const uint8_t *)u : nullptr, strides[2], strides[3]},
-      sv{has_c ? (const uint8_t *)v : nullptr, strides[4], strides[5]};
+      sv{has_c ? (pairs ? (const uint8_t *)u + fmt.bytes() : (const uint8_t *)v) : nullptr, strides[pairs ? 2 : 4], strides[pairs ? 3 : 5]};
+  DeepRule deep{0, 0xff, 0, 0};
+  if (fmt.bytes() == 2) {
+    const int d = fmt.depth;
+    deep = fmt.samples == TM_SAMPLES_U16_HIGH ? DeepRule{16 - d, 0xffff, 1 << (d - 9), d - 8} : DeepRule{0, (1 << d) - 1, 1 << (d - 9), d - 8};
+  }
   const int vec_ok = (t.dst_w % 4 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
   const dim3 grid((unsigned)((t.dst_w + IN_TW - 1) / IN_TW), (unsigned)((t.dst_h + t.th - 1) / t.th), (unsigned)nframes);
   TM_CHECK(grid.y <= 65535 && grid.z <= 65535, TM_E_UNSUPPORTED, "yuv_to_rgb32: %d rows x %d frames in one launch", t.dst_h, nframes);
-  hipLaunchKernelGGL(k_yuv_to_rgb32, grid, dim3(256), 0, stream, sy, su, sv, t.lh, t.lv, t.ch, t.cv, t.dst_w, t.dst_h, t.th, yuv_mode, vec_ok, (uint32_t *)out);
+  auto kernel = fmt.bytes() == 1 ? (pairs ? k_yuv_to_rgb32<1, 2> : k_yuv_to_rgb32<1, 1>) : (pairs ? k_yuv_to_rgb32<2, 2> : k_yuv_to_rgb32<2, 1>);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, sy, su, sv, deep, t.lh, t.lv, t.ch, t.cv, t.dst_w, t.dst_h, t.th, yuv_mode, vec_ok, (uint32_t *)out);
   TM_HIP(hipGetLastError());
   return TM_OK;
 }
@@ -488,8 +526,49 @@ static int parallel_for(int n, const std::function<int(int)> &fn) {
 
 static int resolve_yuv_mode(int mode, int full_range) { return mode == TM_YUV_AUTO ? (full_range ? TM_YUV_BT601_FULL : TM_YUV_BT601_LIMITED) : mode; }
 
-// frames [a, b) of the Y4M clip into the encoder's device clip: chunks of frames are read into two page-locked buffers, uploaded on the copy
-// stream and converted on the main stream, so that the read of a chunk runs beside the upload and the conversion of the one before
+// Frames [a, b) through the encoder's two staging buffers, `fb` staged bytes per frame: a chunk of frames is brought into a device buffer on
+// the copy stream and converted on the main stream, so that a chunk's transfer runs beside the conversion of the one before.  fill_host(f0,
+// nf, dst) puts the chunk into page-locked memory, from where it is uploaded in one copy (a file, pageable memory); without it copy_in(f0,
+// nf, dst, stream) queues the copies into the device buffer itself (page-locked memory, another device).  convert(base, f0, nf) launches.
+struct StagedSource {
+  size_t fb = 0;
+  std::function<int(int, int, uint8_t *)> fill_host;
+  std::function<int(int, int, uint8_t *, hipStream_t)> copy_in;
+  std::function<int(const uint8_t *, int, int)> convert;
+};
+static int convert_staged(tm_encoder *e, int a, int b, const StagedSource &src) {
+  const size_t fb = src.fb;
+  const size_t per_chunk = knobs().input_chunk_frames > 0 ? (size_t)knobs().input_chunk_frames : ((size_t)16 << 20) / fb;
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)(b - a), per_chunk));
+  PinnedBuf *host = e->input_pinned;  // (kept between Loads: page-locking 32 MB costs more than reading them)
+  DevBuf dev[2];
+  Events up, done;
+  TM_TRY(up.make(2)); TM_TRY(done.make(2));
+  for (int i = 0; i < 2; i++) {
+    if (src.fill_host) TM_TRY(host[i].alloc(fb * chunk));
+    TM_TRY(dev[i].alloc(fb * chunk));
+  }
+  if (!e->copy_stream) TM_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
+  int c = 0;
+  for (int f0 = a; f0 < b; f0 += chunk, c++) {
+    const int nf = std::min(chunk, b - f0), s = c & 1;
+    if (src.fill_host) {
+      if (c >= 2) TM_HIP(hipEventSynchronize(up.ev[s]));  // the upload that last read this host buffer
+      TM_TRY(src.fill_host(f0, nf, (uint8_t *)host[s].p));
+    }
+    if (c >= 2) TM_HIP(hipStreamWaitEvent(e->copy_stream, done.ev[s], 0));  // the conversion that last read this device buffer
+    if (src.fill_host) TM_HIP(hipMemcpyAsync(dev[s].p, host[s].p, fb * nf, hipMemcpyHostToDevice, e->copy_stream));
+    else TM_TRY(src.copy_in(f0, nf, dev[s].as<uint8_t>(), e->copy_stream));
+    TM_HIP(hipEventRecord(up.ev[s], e->copy_stream));
+    TM_HIP(hipStreamWaitEvent(e->stream, up.ev[s], 0));
+    TM_TRY(src.convert(dev[s].as<uint8_t>(), f0, nf));
+    TM_HIP(hipEventRecord(done.ev[s], e->stream));
+  }
+  TM_HIP(hipStreamSynchronize(e->stream));  // the staging buffers go back to the pool and to the host
+  return TM_OK;
+}
+
+// frames [a, b) of the Y4M clip into the encoder's device clip: the chunks are read into the page-locked buffers by several threads
 static int decode_y4m(tm_encoder *e, int a, int b) {
   InputInfo &in = e->input;
   InputTables &tables = e->input_tables;
@@ -500,23 +579,14 @@ static int decode_y4m(tm_encoder *e, int a, int b) {
   ChromaGeom g;
   TM_TRY(chroma_geom(in.chroma, in.src_w, in.src_h, &g));
   const size_t fb = (size_t)in.frame_bytes, out_fb = (size_t)e->width * e->height * 4;
-  const size_t per_chunk = knobs().input_chunk_frames > 0 ? (size_t)knobs().input_chunk_frames : ((size_t)16 << 20) / fb;
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)(b - a), per_chunk));
-  PinnedBuf *host = e->input_pinned;  // (kept between Loads: page-locking 32 MB costs more than reading them)
-  DevBuf dev[2];
-  Events up, done;
-  TM_TRY(up.make(2)); TM_TRY(done.make(2));
-  for (int i = 0; i < 2; i++) { TM_TRY(host[i].alloc(fb * chunk)); TM_TRY(dev[i].alloc(fb * chunk)); }
-  if (!e->copy_stream) TM_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
   const int64_t y_plane = (int64_t)in.src_w * in.src_h, c_plane = (int64_t)g.cw * g.ch;
   const int64_t strides[6] = {in.src_w, (int64_t)fb, g.cw, (int64_t)fb, g.cw, (int64_t)fb};
   const int mode = resolve_yuv_mode(e->input_yuv, in.full_range);
-  int c = 0;
-  for (int f0 = a; f0 < b; f0 += chunk, c++) {
-    const int nf = std::min(chunk, b - f0), s = c & 1;
-    if (c >= 2) TM_HIP(hipEventSynchronize(up.ev[s]));  // the upload that last read this host buffer
-    TM_TRY(parallel_for(nf, [&](int i) -> int {
-      uint8_t *dst = (uint8_t *)host[s].p + fb * i;
+  StagedSource src;
+  src.fb = fb;
+  src.fill_host = [&](int f0, int nf, uint8_t *host) -> int {
+    return parallel_for(nf, [&](int i) -> int {
+      uint8_t *dst = host + fb * i;
       const int64_t at = in.frame_off[(size_t)(in.start + f0 + i)];
       for (size_t got = 0; got < fb;) {
         const ssize_t n = pread(fd, dst + got, fb - got, (off_t)(at + (int64_t)got));
@@ -524,17 +594,152 @@ static int decode_y4m(tm_encoder *e, int a, int b) {
         got += (size_t)n;
       }
       return (int)TM_OK;
-    }));
-    if (c >= 2) TM_HIP(hipStreamWaitEvent(e->copy_stream, done.ev[s], 0));  // the conversion that last read this device buffer
-    TM_HIP(hipMemcpyAsync(dev[s].p, host[s].p, fb * nf, hipMemcpyHostToDevice, e->copy_stream));
-    TM_HIP(hipEventRecord(up.ev[s], e->copy_stream));
-    TM_HIP(hipStreamWaitEvent(e->stream, up.ev[s], 0));
-    const uint8_t *base = dev[s].as<uint8_t>();
-    TM_TRY(launch_yuv_to_rgb32(tables, base, base + y_plane, base + y_plane + c_plane, strides, nf, mode, e->frames_owned.as<uint8_t>() + out_fb * f0, e->stream));
-    TM_HIP(hipEventRecord(done.ev[s], e->stream));
+    });
+  };
+  src.convert = [&](const uint8_t *base, int f0, int nf) -> int {
+    return launch_yuv_to_rgb32(tables, base, base + y_plane, base + y_plane + c_plane, strides, SampleFmt(), nf, mode, e->frames_owned.as<uint8_t>() + out_fb * f0, e->stream);
+  };
+  return convert_staged(e, a, b, src);
+}
+
+// ---- a YUV clip lent in memory (tm_set_frames_yuv) ---------------------------------------------------------------------------------------
+// the checks of tm_set_frames_yuv and of the stage seam, with no device call; what they find out about the planes
+struct ClipPlanes {
+  SampleFmt fmt;
+  ChromaGeom g{};
+  int nplanes = 1;                      // 1 mono, 2 Y + pairs, 3 planar
+  int64_t row_bytes[3] = {0, 0, 0};     // of Y, U (or the pairs), V
+  int rows[3] = {0, 0, 0};
+};
+static int check_yuv_clip(const tm_yuv_clip *c, ClipPlanes *out) {
+  TM_CHECK(c, TM_E_INVAL, "yuv clip: null descriptor");
+  TM_CHECK(c->chroma >= TM_CHROMA_444 && c->chroma <= TM_CHROMA_MONO, TM_E_INVAL, "yuv clip: unknown chroma layout %d", c->chroma);
+  TM_CHECK(c->samples >= TM_SAMPLES_U8 && c->samples <= TM_SAMPLES_U16_HIGH, TM_E_INVAL, "yuv clip: unknown sample format %d", c->samples);
+  TM_CHECK(c->memory == TM_MEM_HOST || c->memory == TM_MEM_DEVICE, TM_E_INVAL, "yuv clip: unknown memory kind %d", c->memory);
+  TM_CHECK(c->y, TM_E_INVAL, "yuv clip: null y plane");
+  const bool has_c = c->chroma != TM_CHROMA_MONO;
+  TM_CHECK(!(c->v && !c->u), TM_E_INVAL, "yuv clip: a v plane without a u plane");
+  TM_CHECK(!has_c || c->u, TM_E_INVAL, "yuv clip: layout %d has chroma, but u is null", c->chroma);
+  TM_CHECK(c->width >= 1 && c->width <= 65536 && c->height >= 1 && c->height <= 65536, TM_E_INVAL, "yuv clip: bad size %dx%d", c->width, c->height);
+  TM_CHECK(c->frames >= 1, TM_E_INVAL, "yuv clip: %d frames", c->frames);
+  TM_CHECK(c->fps > 0, TM_E_INVAL, "yuv clip: frame rate %g", c->fps);
+  if (c->samples == TM_SAMPLES_U8) TM_CHECK(c->depth == 8, TM_E_INVAL, "yuv clip: depth %d with 8-bit samples", c->depth);
+  else TM_CHECK(c->depth >= 9 && c->depth <= 16, TM_E_INVAL, "yuv clip: depth %d with 16-bit samples (9 .. 16)", c->depth);
+  ClipPlanes p;
+  p.fmt.samples = c->samples; p.fmt.depth = c->depth; p.fmt.pairs = has_c && !c->v;
+  TM_TRY(chroma_geom(c->chroma, c->width, c->height, &p.g));
+  const int B = p.fmt.bytes();
+  p.nplanes = !has_c ? 1 : p.fmt.pairs ? 2 : 3;
+  p.row_bytes[0] = (int64_t)c->width * B; p.rows[0] = c->height;
+  p.row_bytes[1] = (int64_t)p.g.cw * B * (p.fmt.pairs ? 2 : 1); p.rows[1] = p.g.ch;
+  p.row_bytes[2] = (int64_t)p.g.cw * B; p.rows[2] = p.g.ch;
+  const void *ptr[3] = {c->y, c->u, c->v};
+  const int64_t row[3] = {c->y_row, c->u_row, c->v_row}, frame[3] = {c->y_frame, c->u_frame, c->v_frame};
+  static const char *const names[3] = {"y", "u", "v"};
+  for (int i = 0; i < p.nplanes; i++) {
+    TM_CHECK(row[i] >= p.row_bytes[i], TM_E_INVAL, "yuv clip: the %s row stride %lld is shorter than a row of %lld bytes", names[i], (long long)row[i], (long long)p.row_bytes[i]);
+    TM_CHECK(frame[i] >= 0, TM_E_INVAL, "yuv clip: negative %s frame stride %lld", names[i], (long long)frame[i]);
+    TM_CHECK(B == 1 || (((uintptr_t)ptr[i] | (uint64_t)row[i] | (uint64_t)frame[i]) & 1) == 0, TM_E_INVAL, "yuv clip: an odd %s pointer or stride with 16-bit samples", names[i]);
   }
-  TM_HIP(hipStreamSynchronize(e->stream));  // the staging buffers go back to the pool and to the host
+  if (out) *out = p;
   return TM_OK;
+}
+static int yuv_clip_dst(const tm_yuv_clip *c, double scaling, int *dw, int *dh) {  // as probe_input describes a file
+  *dw = pas_round_dim(c->width * scaling);
+  *dh = pas_round_dim(c->height * scaling);
+  TM_CHECK((double)c->width / *dw <= 8.0 && (double)c->height / *dh <= 8.0, TM_E_UNSUPPORTED, "Scaling %g shrinks %dx%d by more than 8 (more than %d taps)", scaling,
+           c->width, c->height, TM_RESAMPLE_MAX_TAPS);
+  return TM_OK;
+}
+
+// rows x row_bytes of nf frames from a plane with strides into a packed one, as few copies as the strides allow
+static int copy_plane_async(uint8_t *dst, const uint8_t *src, int64_t row_stride, int64_t frame_stride, int64_t row_bytes, int rows, int nf, hipStream_t stream) {
+  if (row_stride == row_bytes && frame_stride == row_bytes * rows) {
+    TM_HIP(hipMemcpyAsync(dst, src, (size_t)(row_bytes * rows) * nf, hipMemcpyDefault, stream));
+  } else if (frame_stride == row_stride * rows) {
+    TM_HIP(hipMemcpy2DAsync(dst, (size_t)row_bytes, src, (size_t)row_stride, (size_t)row_bytes, (size_t)rows * nf, hipMemcpyDefault, stream));
+  } else {
+    for (int f = 0; f < nf; f++)
+      TM_HIP(hipMemcpy2DAsync(dst + row_bytes * rows * f, (size_t)row_bytes, src + frame_stride * f, (size_t)row_stride, (size_t)row_bytes, (size_t)rows, hipMemcpyDefault, stream));
+  }
+  return TM_OK;
+}
+
+static bool is_page_locked(const void *p) {
+  hipPointerAttribute_t at;
+  const bool yes = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeHost;
+  (void)hipGetLastError();  // (pageable memory is an error to some runtimes and "unregistered" to others)
+  return yes;
+}
+
+// frames [a, b) of the lent clip into the encoder's device clip
+static int convert_yuv_clip(tm_encoder *e, int a, int b) {
+  InputInfo &in = e->input;
+  const tm_yuv_clip &c = in.clip;
+  ClipPlanes pl;
+  TM_TRY(check_yuv_clip(&c, &pl));
+  InputTables &tables = e->input_tables;
+  TM_TRY(build_input_tables(c.width, c.height, c.chroma, e->width, e->height, &tables, e->stream));
+  const int mode = resolve_yuv_mode(e->input_yuv, c.full_range);
+  const size_t out_fb = (size_t)e->width * e->height * 4;
+  const uint8_t *ptr[3] = {(const uint8_t *)c.y, (const uint8_t *)c.u, (const uint8_t *)c.v};
+  const int64_t row[3] = {c.y_row, c.u_row, c.v_row}, frame[3] = {c.y_frame, c.u_frame, c.v_frame};
+  bool in_place = false;
+  if (c.memory == TM_MEM_DEVICE) {
+    hipPointerAttribute_t at;
+    TM_CHECK(hipPointerGetAttributes(&at, c.y) == hipSuccess && at.type == hipMemoryTypeDevice, TM_E_INVAL, "yuv clip: the y plane is not device memory");
+    in_place = at.device == e->device;
+  }
+  if (in_place) {  // the planes are converted where they are
+    constexpr int IN_LAUNCH_FRAMES = 4096;
+    const int64_t strides[6] = {row[0], frame[0], row[1], frame[1], row[2], frame[2]};
+    for (int f0 = a; f0 < b; f0 += IN_LAUNCH_FRAMES) {
+      const int nf = std::min(IN_LAUNCH_FRAMES, b - f0);
+      TM_TRY(launch_yuv_to_rgb32(tables, ptr[0] + frame[0] * f0, ptr[1] ? ptr[1] + frame[1] * f0 : nullptr, ptr[2] ? ptr[2] + frame[2] * f0 : nullptr, strides, pl.fmt, nf,
+                                 mode, e->frames_owned.as<uint8_t>() + out_fb * f0, e->stream));
+    }
+    TM_HIP(hipStreamSynchronize(e->stream));  // the planes are the caller's again when Load returns
+    return TM_OK;
+  }
+  // Staged: a chunk holds nf packed frames of Y, then of U (or of the pairs), then of V
+  int64_t plane_bytes[3], fb = 0;
+  for (int i = 0; i < pl.nplanes; i++) { plane_bytes[i] = pl.row_bytes[i] * pl.rows[i]; fb += plane_bytes[i]; }
+  bool pinned = c.memory == TM_MEM_DEVICE;  // (another device of the group: copied by the runtime as page-locked memory is)
+  if (!pinned) {
+    pinned = true;
+    for (int i = 0; i < pl.nplanes; i++) pinned = pinned && is_page_locked(ptr[i]);
+  }
+  StagedSource src;
+  src.fb = (size_t)fb;
+  if (pinned)
+    src.copy_in = [&](int f0, int nf, uint8_t *dst, hipStream_t stream) -> int {
+      for (int i = 0; i < pl.nplanes; i++) {
+        TM_TRY(copy_plane_async(dst, ptr[i] + frame[i] * f0, row[i], frame[i], pl.row_bytes[i], pl.rows[i], nf, stream));
+        dst += plane_bytes[i] * nf;
+      }
+      return (int)TM_OK;
+    };
+  else
+    src.fill_host = [&](int f0, int nf, uint8_t *host) -> int {
+      return parallel_for(nf, [&](int f) -> int {
+        uint8_t *base = host;
+        for (int i = 0; i < pl.nplanes; i++) {
+          uint8_t *dst = base + plane_bytes[i] * f;
+          const uint8_t *from = ptr[i] + frame[i] * (f0 + f);
+          if (row[i] == pl.row_bytes[i]) memcpy(dst, from, (size_t)plane_bytes[i]);
+          else
+            for (int r = 0; r < pl.rows[i]; r++) memcpy(dst + pl.row_bytes[i] * r, from + row[i] * r, (size_t)pl.row_bytes[i]);
+          base += plane_bytes[i] * nf;
+        }
+        return (int)TM_OK;
+      });
+    };
+  src.convert = [&](const uint8_t *base, int f0, int nf) -> int {
+    const uint8_t *u = base + plane_bytes[0] * nf, *v = pl.nplanes == 3 ? u + plane_bytes[1] * nf : nullptr;
+    const int64_t strides[6] = {pl.row_bytes[0], plane_bytes[0], pl.row_bytes[1], plane_bytes[1], pl.row_bytes[2], plane_bytes[2]};
+    return launch_yuv_to_rgb32(tables, base, u, v, strides, pl.fmt, nf, mode, e->frames_owned.as<uint8_t>() + out_fb * f0, e->stream);
+  };
+  return convert_staged(e, a, b, src);
 }
 
 // the PNG sequence, decoded on the host into a clip the encoder keeps until Load's chunked host-clip upload has taken it
@@ -552,7 +757,7 @@ static int decode_pngs(tm_encoder *e) {
   });
 }
 
-// Load's first lines when the frames come from a file: leaves the clip where tm_set_frames_device / tm_set_frames_host would have put it
+// Load's first lines when the frames come from a file or from lent YUV planes: leaves the clip where tm_set_frames_device / tm_set_frames_host would have put it
 int load_from_input(tm_encoder *e) {
   InputInfo &in = e->input;
   if (in.kind == TM_INPUT_PNGS) {
@@ -571,13 +776,17 @@ int load_from_input(tm_encoder *e) {
   }
   const int mode = resolve_yuv_mode(e->input_yuv, in.full_range);
   if (in.decoded && e->frames == e->frames_owned.p && e->frames_owned.p && in.dec_first <= a && b <= in.dec_first + in.dec_count && in.dec_mode == mode) return TM_OK;
+  const bool lent_clip = in.kind == INPUT_YUV_CLIP;
+  TM_CHECK(!lent_clip || in.lent, TM_E_INVAL,
+           "the YUV planes were given back when the last Load returned: lend the clip again (tm_set_frames_yuv) to convert it with another InputYUV or for more frames");
   TM_HIP(hipStreamSynchronize(e->stream));  // the destination may have been handed out by the pool a moment ago
   TM_TRY(e->frames_owned.alloc((size_t)e->width * e->height * 4 * e->nframes));
   e->frames = e->frames_owned.p;
   e->frames_host = nullptr;
   e->hclip_cur = -1;
   in.decoded = false;
-  if (b > a) TM_TRY(decode_y4m(e, (int)a, (int)b));
+  if (b > a) TM_TRY(lent_clip ? convert_yuv_clip(e, (int)a, (int)b) : decode_y4m(e, (int)a, (int)b));
+  in.lent = false;  // (a lent clip is borrowed until this Load has returned: from here on the encoder reads its own RGB32 clip)
   in.decoded = true; in.dec_first = (int)a; in.dec_count = (int)(b - a); in.dec_mode = mode;
   return TM_OK;
 }
@@ -595,6 +804,33 @@ int tm_open_input(tm_encoder *e) {  // the probe half of Load, tilingencoder.pas
   return TM_OK;
 }
 
+int tm_set_frames_yuv(tm_encoder *e, const tm_yuv_clip *clip) {  // what tm_open_input does for a file, for planes in memory
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_TRY(check_yuv_clip(clip, nullptr));
+  int dw = 0, dh = 0;
+  TM_TRY(yuv_clip_dst(clip, e->s.Scaling, &dw, &dh));
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_set_frames_yuv(s, clip); });  // every shard converts what its Load reads
+  TM_TRY(tm_set_video(e, dw, dh, clip->fps, clip->frames));
+  InputInfo in;
+  in.kind = INPUT_YUV_CLIP;
+  in.clip = *clip;
+  in.lent = true;
+  in.frames = clip->frames; in.src_w = clip->width; in.src_h = clip->height; in.dst_w = dw; in.dst_h = dh;
+  in.chroma = clip->chroma; in.full_range = clip->full_range ? 1 : 0; in.fps = clip->fps;
+  e->input = std::move(in);
+  e->input_clip.clear();
+  return TM_OK;
+}
+
+int tm_probe_yuv_clip_host(const tm_yuv_clip *clip, double scaling, int *dst_width, int *dst_height) {
+  TM_TRY(check_yuv_clip(clip, nullptr));
+  int dw = 0, dh = 0;
+  TM_TRY(yuv_clip_dst(clip, scaling, &dw, &dh));
+  if (dst_width) *dst_width = dw;
+  if (dst_height) *dst_height = dh;
+  return TM_OK;
+}
+
 int tm_get_video(tm_encoder *e, int *width, int *height, double *fps, int *frames) {
   TM_CHECK(e, TM_E_INVAL, "null encoder");
   if (width) *width = e->width;
@@ -606,7 +842,7 @@ int tm_get_video(tm_encoder *e, int *width, int *height, double *fps, int *frame
 
 int tm_set_input_yuv(tm_encoder *e, int mode) {
   TM_CHECK(e, TM_E_INVAL, "null encoder");
-  TM_CHECK(mode >= TM_YUV_AUTO && mode <= TM_YUV_TILER, TM_E_INVAL, "bad YUV mode %d", mode);
+  TM_CHECK(mode >= TM_YUV_AUTO && mode <= TM_YUV_BT709_FULL, TM_E_INVAL, "bad YUV mode %d", mode);
   if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_set_input_yuv(s, mode); });
   e->input_yuv = mode;
   return TM_OK;
@@ -641,13 +877,33 @@ int tm_stage_yuv_to_rgb32(const void *y, const void *u, const void *v, const int
   TM_TRY(chroma_geom(chroma, src_w, src_h, &g));
   const bool has_c = chroma != TM_CHROMA_MONO;
   TM_CHECK(y && out_rgb32 && strides && (!has_c || (u && v)) && nframes >= 0 && src_w > 0 && src_h > 0 && dst_w > 0 && dst_h > 0, TM_E_INVAL, "yuv_to_rgb32: bad arguments");
-  TM_CHECK(yuv_mode >= TM_YUV_AUTO && yuv_mode <= TM_YUV_TILER, TM_E_INVAL, "bad YUV mode %d", yuv_mode);
+  TM_CHECK(yuv_mode >= TM_YUV_AUTO && yuv_mode <= TM_YUV_BT709_FULL, TM_E_INVAL, "bad YUV mode %d", yuv_mode);
   TM_CHECK(strides[0] >= src_w && strides[1] >= 0 && (!has_c || (strides[2] >= g.cw && strides[4] >= g.cw && strides[3] >= 0 && strides[5] >= 0)), TM_E_INVAL,
            "yuv_to_rgb32: a row stride is shorter than its plane's rows");
   InputTables tables;
   TM_TRY(build_input_tables(src_w, src_h, chroma, dst_w, dst_h, &tables, (hipStream_t)stream));
   // (without a header to say otherwise a clip is limited range, as FFmpeg assumes)
-  TM_TRY(launch_yuv_to_rgb32(tables, y, u, v, strides, nframes, resolve_yuv_mode(yuv_mode, 0), out_rgb32, (hipStream_t)stream));
+  TM_TRY(launch_yuv_to_rgb32(tables, y, u, v, strides, SampleFmt(), nframes, resolve_yuv_mode(yuv_mode, 0), out_rgb32, (hipStream_t)stream));
+  TM_HIP(hipStreamSynchronize((hipStream_t)stream));  // the tables are freed on return
+  return TM_OK;
+}
+
+int tm_stage_yuv_to_rgb32_fmt(const void *y, const void *u, const void *v, const int64_t strides[6], int nframes, int src_w, int src_h, int chroma, int samples, int depth,
+                              int dst_w, int dst_h, int yuv_mode, void *out_rgb32, void *stream) {
+  knobs_reload();
+  TM_TRY(require_device());
+  TM_CHECK(out_rgb32 && strides && nframes >= 0 && dst_w > 0 && dst_h > 0, TM_E_INVAL, "yuv_to_rgb32: bad arguments");
+  TM_CHECK(yuv_mode >= TM_YUV_AUTO && yuv_mode <= TM_YUV_BT709_FULL, TM_E_INVAL, "bad YUV mode %d", yuv_mode);
+  tm_yuv_clip c{};  // the planes as a clip: the checks are tm_set_frames_yuv's
+  c.y = y; c.u = u; c.v = v;
+  c.y_row = strides[0]; c.y_frame = strides[1]; c.u_row = strides[2]; c.u_frame = strides[3]; c.v_row = strides[4]; c.v_frame = strides[5];
+  c.width = src_w; c.height = src_h; c.frames = std::max(nframes, 1); c.fps = 1.0;
+  c.chroma = chroma; c.samples = samples; c.depth = depth; c.memory = TM_MEM_DEVICE;
+  ClipPlanes pl;
+  TM_TRY(check_yuv_clip(&c, &pl));
+  InputTables tables;
+  TM_TRY(build_input_tables(src_w, src_h, chroma, dst_w, dst_h, &tables, (hipStream_t)stream));
+  TM_TRY(launch_yuv_to_rgb32(tables, y, u, v, strides, pl.fmt, nframes, resolve_yuv_mode(yuv_mode, 0), out_rgb32, (hipStream_t)stream));
   TM_HIP(hipStreamSynchronize((hipStream_t)stream));  // the tables are freed on return
   return TM_OK;
 }

@@ -121,9 +121,12 @@ int inflate_zlib(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t 
 int read_png(const char *path, uint32_t *out, int64_t cap_px, int *w, int *h);
 
 // tm_input.hip: Load's input.  What the probe half of Load (tilingencoder.pas:1764-1820) finds out about InputFileName.
+constexpr int INPUT_YUV_CLIP = 3;  // InputInfo::kind of a YUV clip lent in memory (tm_set_frames_yuv), beside TM_INPUT_Y4M / TM_INPUT_PNGS
 struct InputInfo {
-  int kind = 0;  // 0: the frames come from memory (pushed or lent); TM_INPUT_Y4M / TM_INPUT_PNGS: from the file
+  int kind = 0;  // 0: RGB32 frames from memory (pushed or lent); TM_INPUT_Y4M / TM_INPUT_PNGS: from the file; INPUT_YUV_CLIP: lent planes
   std::string name;
+  tm_yuv_clip clip{};               // INPUT_YUV_CLIP: the descriptor as it was lent
+  bool lent = false;                // its planes are still borrowed: no Load has read them yet
   int start = 0, frames = 0, src_w = 0, src_h = 0, dst_w = 0, dst_h = 0, chroma = 0, full_range = 0;
   double fps = 0;
   int64_t frame_bytes = 0;

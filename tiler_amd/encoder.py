@@ -10,7 +10,7 @@ import enum
 
 import numpy as np
 
-from ._lib import lib, check, TileMotionError, c_void_p, c_int, c_int64, c_double, c_char_p
+from ._lib import lib, check, TileMotionError, YuvClip, c_void_p, c_int, c_int64, c_double, c_char_p
 
 
 class TEncoderStep(enum.IntEnum):  # tilingencoder.pas:18
@@ -38,6 +38,22 @@ class TInputYUV(enum.IntEnum):  # tm_set_input_yuv: how a Y4M clip's samples bec
     yuvBT601Limited = 1
     yuvBT601Full = 2
     yuvTiler = 3
+    yuvBT709Limited = 4
+    yuvBT709Full = 5
+
+
+class TChroma(enum.IntEnum):  # TM_CHROMA_*: where the U / V samples sit among the luma samples
+    c444 = 0
+    c422 = 1
+    c420jpeg = 2
+    c420mpeg2 = 3
+    mono = 4
+
+
+class TSamples(enum.IntEnum):  # TM_SAMPLES_*: bytes, or little-endian words with the sample in the low (yuv420p10le) or the high bits (P010)
+    u8 = 0
+    u16Low = 1
+    u16High = 2
 
 
 TILE_HDR = np.dtype([("UseCount", "<u4"), ("TmpIndex", "<i4"), ("MergeIndex", "<i4"), ("PalIdx_Initial", "<i4"), ("Flags", "<u4")])
@@ -65,6 +81,7 @@ _ENC_SIGS = {
     "tm_set_frames_device": (c_int, [c_void_p, c_void_p]),
     "tm_set_frames_host": (c_int, [c_void_p, c_void_p]),
     "tm_prefetch_frames_host": (c_int, [c_void_p, c_void_p]),
+    "tm_set_frames_yuv": (c_int, [c_void_p, ctypes.POINTER(YuvClip)]),
     "tm_open_input": (c_int, [c_void_p]),
     "tm_get_video": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_double), ctypes.POINTER(c_int)]),
     "tm_set_input_yuv": (c_int, [c_void_p, c_int]),
@@ -220,6 +237,44 @@ class TilingEncoder:
         ptr = frames.data_ptr() if hasattr(frames, "data_ptr") else frames.ctypes.data
         check(self._L.tm_set_frames_host(c_void_p(self._h), c_void_p(ptr)))
 
+    def SetFramesYUV(self, y, u, v=None, *, chroma, fps, samples=None, depth=8, full_range=False):
+        """A YUV clip lent in memory as a decoder leaves it (tm_set_frames_yuv): what OpenInput does for a file.  y [F][H][W]; u, v [F][ch][cw]
+        planes, or v=None and u [F][ch][2 cw] (or [F][ch][cw][2]) holding (U, V) pairs as in NV12 / P010; u=None for TChroma.mono.  torch
+        tensors on the device or the CPU (ideally pinned), or numpy arrays, of 8- or 16-bit integers; the last axis must be dense, the row
+        and frame strides are taken from the arrays.  samples: TSamples (default: u8 for bytes, u16Low for words), depth: bits per sample;
+        full_range feeds TInputYUV.yuvAuto.  Scaling applies as for a file.  The arrays are borrowed (and kept alive here) until the
+        Run that loads them has returned.  Returns VideoInfo()."""
+        planes = [y, u, v]
+        given = [a for a in planes if a is not None]
+        on_device = bool(getattr(y, "is_cuda", False))
+        item = y.element_size() if hasattr(y, "element_size") else y.itemsize
+        if item not in (1, 2):
+            raise ValueError("SetFramesYUV: samples must be 8- or 16-bit integers")
+        if samples is None:
+            samples = TSamples.u8 if item == 1 else TSamples.u16Low
+        if (int(samples) == TSamples.u8) != (item == 1):
+            raise ValueError("SetFramesYUV: samples=%r does not fit %d-byte elements" % (samples, item))
+        clip = YuvClip()
+        for name, a in zip("yuv", planes):
+            if a is None:
+                continue
+            torch_like = hasattr(a, "data_ptr")
+            if bool(getattr(a, "is_cuda", False)) != on_device or (a.element_size() if torch_like else a.itemsize) != item:
+                raise ValueError("SetFramesYUV: the planes must share their memory kind and sample type")
+            st = [s * item for s in a.stride()] if torch_like else list(a.strides)
+            dense = len(st) >= 3 and st[-1] == item and (len(st) == 3 or (len(st) == 4 and name == "u" and v is None and a.shape[3] == 2 and st[2] == 2 * item))
+            if not dense:
+                raise ValueError("SetFramesYUV: plane %s must be [F][rows][samples] with a dense last axis" % name)
+            setattr(clip, name, a.data_ptr() if torch_like else a.ctypes.data)
+            setattr(clip, name + "_row", st[1])
+            setattr(clip, name + "_frame", st[0])
+        clip.frames, clip.height, clip.width = (int(n) for n in y.shape[:3])
+        clip.fps, clip.chroma, clip.samples, clip.depth = float(fps), int(chroma), int(samples), int(depth)
+        clip.full_range, clip.memory = int(bool(full_range)), 1 if on_device else 0
+        check(self._L.tm_set_frames_yuv(c_void_p(self._h), ctypes.byref(clip)))
+        self._yuv_ref = given
+        return self.VideoInfo()
+
     def SaveSettings(self, path):
         self._L.tm_save_settings_ini.restype = c_int
         self._L.tm_save_settings_ini.argtypes = [c_void_p, c_char_p]
@@ -234,6 +289,8 @@ class TilingEncoder:
 
     def Run(self, step=TEncoderStep.esAll):
         check(self._L.tm_run(c_void_p(self._h), int(step)))
+        if int(step) in (TEncoderStep.esAll, TEncoderStep.esLoad):
+            self._yuv_ref = None  # planes lent with SetFramesYUV are the caller's again once Load has returned
 
     # -- read-back
     def counts(self):

@@ -45,6 +45,23 @@ def yuv_to_rgb32(y, u, v, chroma, dst_w, dst_h, yuv_mode=0):
     return out
 
 
+def yuv_to_rgb32_fmt(y, u, v, chroma, dst_w, dst_h, yuv_mode=0, samples=0, depth=8):
+    """The same for every sample format of a lent clip (tm_stage_yuv_to_rgb32_fmt): uint8 planes, or int16 / uint16 planes holding little-endian
+    words of `depth` bits (samples: TM_SAMPLES_* -- 0 bytes, 1 the sample in the low bits, 2 in the high bits as P010 has it); v=None: u
+    [F][ch][2 cw] holds (U, V) pairs as NV12 / P010 do.  Strides are taken from the tensors -> int32 [F][dst_h][dst_w] 0x00RRGGBB"""
+    item = y.element_size()
+    assert y.is_cuda and item in (1, 2) and y.dim() == 3 and y.stride(2) == 1
+    f, h, w = y.shape
+    strides = [y.stride(1) * item, y.stride(0) * item]
+    for c in (u, v):
+        assert c is None or (c.is_cuda and c.element_size() == item and c.dim() == 3 and c.stride(2) == 1 and c.shape[0] == f)
+        strides += [c.stride(1) * item, c.stride(0) * item] if c is not None else [0, 0]
+    out = torch.empty((f, dst_h, dst_w), dtype=torch.int32, device=y.device)
+    check(lib().tm_stage_yuv_to_rgb32_fmt(_p(y), _p(u), _p(v), (ctypes.c_int64 * 6)(*strides), f, w, h, int(chroma), int(samples), int(depth), dst_w, dst_h,
+                                          int(yuv_mode), _p(out), _stream()))
+    return out
+
+
 def rgb_to_lab(rgb):
     """RGBToLAB (utils.pas:374-410) of colours 0x00RRGGBB (int32 [n]) -> float32 [n][3]"""
     assert rgb.is_cuda and rgb.dtype == torch.int32 and rgb.is_contiguous()

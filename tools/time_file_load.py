@@ -1,11 +1,13 @@
-"""Wall time of Load from a Y4M file against Load of the same clip as RGB32 in page-locked host memory.
+"""Wall time of Load from a Y4M file against Load of the same clip as RGB32 in page-locked host memory, and of the same clip lent as YUV planes.
 
-    python tools/time_file_load.py [--mode file|host|both] [--frames 300 --width 1280 --height 720] [--scaling 1.0] [--passes 7] [--dir /dev/shm]
+    python tools/time_file_load.py [--mode file|host|both|yuv|all] [--frames 300 --width 1280 --height 720] [--scaling 1.0] [--passes 7] [--dir /dev/shm]
 
 The clip is bench.py's (SURVEY.md 8d's generator).  `file`: it is written as a 4:2:0 Y4M into --dir (memory-backed by default, so that the
 figure is the pipeline's and not a disk's) and every pass is OpenInput + Run(esLoad).  `host`: the RGB32 clip sits in pinned memory and every
 pass is SetFramesHost + Run(esLoad) -- the path a caller had before Load could read a file; it uses no call newer than that, so the same
-script times an older build of the library.  One warm-up pass, then the median of --passes passes with their spread; one JSON line."""
+script times an older build of the library.  `yuv` (`all`: every leg): the planes are lent with SetFramesYUV and every pass is SetFramesYUV +
+Run(esLoad) -- (d) planar 4:2:0 in page-locked host memory, (e) NV12 in device memory, (f) P010 in device memory (the bytes in the high
+bits of 10-bit samples).  One warm-up pass, then the median of --passes passes with their spread; one JSON line."""
 import argparse
 import json
 import os
@@ -36,7 +38,7 @@ def stats(ms):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["file", "host", "both"], default="both")
+    ap.add_argument("--mode", choices=["file", "host", "both", "yuv", "all"], default="both")
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=720)
@@ -53,7 +55,7 @@ def main():
     clip = synth_clip(host.numpy(), freeze=True)
     out = dict(clip="%dx%dx%d" % (W, H, F), scaling=args.scaling, rgb32_bytes=F * H * W * 4, yuv420_bytes=F * H * W * 3 // 2)
 
-    if args.mode in ("host", "both"):
+    if args.mode in ("host", "both", "all"):
         enc = TilingEncoder()
         enc.LoadDefaultSettings()
         enc.SetVideo(W, H, 24.0, F)
@@ -66,7 +68,33 @@ def main():
         enc.close()
         out["load_host_rgb32"] = stats(ms[1:])
 
-    if args.mode in ("file", "both"):
+    if args.mode in ("yuv", "all"):
+        from tiler_amd.encoder import TChroma, TSamples
+        planes = [torch.empty(shape, dtype=torch.uint8, pin_memory=True) for shape in ((F, H, W), (F, H // 2, W // 2), (F, H // 2, W // 2))]
+        for i in range(F):
+            for dst, src in zip(planes, rgb_to_yuv420(clip[i].astype(np.int64))):
+                dst[i] = torch.from_numpy(src)
+        y_dev = planes[0].cuda()
+        uv_dev = torch.stack([planes[1], planes[2]], -1).reshape(F, H // 2, W).cuda()  # NV12: (U, V) pairs
+        y10, uv10 = (t.to(torch.int16) << 8 for t in (y_dev, uv_dev))                  # P010: the sample in the high 10 bits of the word
+        legs = (("load_yuv420_host_pinned", planes, dict(samples=TSamples.u8, depth=8)),
+                ("load_nv12_device", (y_dev, uv_dev), dict(samples=TSamples.u8, depth=8)),
+                ("load_p010_device", (y10, uv10), dict(samples=TSamples.u16High, depth=10)))
+        for name, lent, fmt in legs:
+            enc = TilingEncoder()
+            enc.LoadDefaultSettings()
+            enc.Scaling = args.scaling
+            ms = []
+            for p in range(args.passes + 1):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                info = enc.SetFramesYUV(*lent, chroma=TChroma.c420jpeg, fps=24.0, **fmt)
+                enc.Run(S.esLoad)
+                ms.append((time.perf_counter() - t0) * 1e3)
+            enc.close()
+            out[name] = dict(stats(ms[1:]), video=info)
+
+    if args.mode in ("file", "both", "all"):
         path = os.path.join(args.dir, "time_file_load_%d.y4m" % os.getpid())
         try:
             with open(path, "wb") as f:
