@@ -71,6 +71,9 @@
  *                           (tests: the other shards must leave their collectives at once)
  *   TM_INPUT_CHUNK_FRAMES=<n> Load reads a Y4M file, or stages a lent YUV clip, n frames at a time instead of 16 MB worth (tests: 1, so that a small
  *                           clip walks the two staging buffers many times)
+ *   TM_RECON_CHUNK_FRAMES=<n> Reconstruct computes and searches its query features n frames at a time instead of 8 GiB worth (2 GiB with the
+ *                           extended palette usage); the features computed ahead during PreparePalettes are then those of the first n frames
+ *                           (tests: a small clip takes several chunks)
  *   TM_POOL_GIB=<x>         cap of the device-memory pool a thread keeps (96); TM_HOST_THREADS=<n>: OptimizePalettes' helper threads
  *                           (both read once per process)
  */

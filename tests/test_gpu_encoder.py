@@ -223,6 +223,25 @@ def test_distinct_query_groups_equal_per_item_queries(monkeypatch, epu):
     assert 0 < outs[0][2] < outs[1][2]
 
 
+@pytest.mark.parametrize("epu", [False, True])
+def test_reconstruct_in_several_chunks_equals_one_chunk(monkeypatch, epu):
+    """Reconstruct walks its query frames in chunks (8 GiB of features, so every test clip is one chunk); TM_RECON_CHUNK_FRAMES=5 cuts the
+    12 frames into chunks of 5, 5 and 2 -- the first is the one PreparePalettes computed ahead, the last is short -- searched item by item
+    (TM_NO_QUERY_GROUPS): same tile maps and tiles as the default run"""
+    from tiler_amd import synth
+    frames = synth.video(12, 320, 176, cut=6)
+    outs = []
+    for chunked in (False, True):
+        if chunked:
+            monkeypatch.setenv("TM_NO_QUERY_GROUPS", "1")
+            monkeypatch.setenv("TM_RECON_CHUNK_FRAMES", "5")
+        enc = _run_encoder(frames, PaletteCount=8, ShotTransMinSecondsPerKF=0.1, MotionPredictRadius=0, FrameTilingExtendedPaletteUsage=epu)
+        outs.append((np.stack([enc.TileMap(f) for f in range(12)]), enc.Tiles()[1], enc.KnnStats()["queries"]))
+        enc.close()
+    assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
+    assert outs[1][2] == 12 * 40 * 22
+
+
 def test_dither_plans_distinct_pairs_from_the_quantisation_keys(monkeypatch):
     """a clip with enough global tiles for Dither's distinct-pair path: with PreparePalettes' sorted pixel keys handed over (the
     default), with Dither marking the pairs from the pixels itself (TM_DITHER_OWN_KEYS) and with a plan per pixel
@@ -368,13 +387,7 @@ class _FakeDist:
         self.bar.wait()
 
 
-@pytest.mark.parametrize("radius,epu,world,pp_sharded", [(0, False, 2, False), (0, True, 2, True), (8, False, 2, True), (8, True, 2, False), (8, True, 3, True),
-                                                         (8, False, 6, False), (0, False, 5, True), (0, False, 4, False)])
-def test_sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, pp_sharded):
-    """tiler_amd.distributed.run_all with REAL encoders: the ranks (threads, one GPU) shard Load / Reduce / PreparePalettes (data-parallel
-    Lloyd, palette-parallel quantisation) / Dither / Reconstruct -- with motion prediction on: PredictMotion and whole key-frame groups --
-    through the library's collective callback, and must end with exactly the single-process result.  With 6 ranks on 4 key frames some
-    ranks own no frame at all; with 5 ranks on 3 palettes some own no palette."""
+def _sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, pp_sharded, recon_chunk=0):
     import threading
     from tiler_amd import synth, distributed
     from tiler_amd.encoder import TilingEncoder
@@ -389,6 +402,8 @@ def test_sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, 
     ref = _run_encoder(frames, **kw)
     want = (np.stack([ref.TileMap(f) for f in range(12)]), ref.Tiles())
     ref.close()
+    if recon_chunk:  # (after the single run: that one stays a single chunk)
+        monkeypatch.setenv("TM_RECON_CHUNK_FRAMES", str(recon_chunk))
     fake = _FakeDist(world)
     monkeypatch.setattr(distributed, "dist", fake)
     out, errs = [None] * world, []
@@ -421,6 +436,23 @@ def test_sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, 
         assert np.array_equal(out[r][0], want[0])
         for a, b in zip(out[r][1], want[1]):
             assert np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("radius,epu,world,pp_sharded", [(0, False, 2, False), (0, True, 2, True), (8, False, 2, True), (8, True, 2, False), (8, True, 3, True),
+                                                         (8, False, 6, False), (0, False, 5, True), (0, False, 4, False)])
+def test_sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, pp_sharded):
+    """tiler_amd.distributed.run_all with REAL encoders: the ranks (threads, one GPU) shard Load / Reduce / PreparePalettes (data-parallel
+    Lloyd, palette-parallel quantisation) / Dither / Reconstruct -- with motion prediction on: PredictMotion and whole key-frame groups --
+    through the library's collective callback, and must end with exactly the single-process result.  With 6 ranks on 4 key frames some
+    ranks own no frame at all; with 5 ranks on 3 palettes some own no palette."""
+    _sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, pp_sharded)
+
+
+@pytest.mark.parametrize("radius,epu", [(0, False), (8, True)])
+def test_sharded_ranks_merge_to_the_single_run_with_reconstruct_in_chunks(monkeypatch, radius, epu):
+    """the same with two ranks and TM_RECON_CHUNK_FRAMES=2: every rank's six query frames take three chunks, and the second rank's start at
+    a frame > 0 (the chunk offsets into the tile-map arrays, the features computed ahead being the rank's first chunk)"""
+    _sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, 2, False, recon_chunk=2)
 
 
 @pytest.mark.parametrize("mode", ["keys", "keys-colliding-hashes"])

@@ -1,4 +1,4 @@
-// tm_encoder.h -- the encoder object behind tm_create / tm_run, shared by tm_encoder.hip, tm_steps.hip, tm_shard.hip and tm_export.hip.
+// tm_encoder.h -- the encoder object behind tm_create / tm_run, shared by tm_encoder.hip, the steps (tm_steps.h), tm_shard.hip and tm_export.hip.
 #pragma once
 #include <algorithm>
 #include <functional>
@@ -176,9 +176,9 @@ inline int need(tm_encoder *e, int step_bit, const char *what) {
 void recompute_auto_tile_count(tm_encoder *e);
 std::string settings_text(const Settings &s);
 
-// tm_steps.hip
+// tm_steps.hip (what the steps' three files share among themselves: tm_steps.h)
 int run_step(tm_encoder *e, int step);
-int load_tail(tm_encoder *e);
+int load_tail(tm_encoder *e, hipStream_t st = nullptr);
 int queue_host_clip(tm_encoder *e, int slot, const void *host);
 
 // tm_input.hip

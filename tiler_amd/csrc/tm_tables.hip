@@ -159,6 +159,7 @@ void knobs_reload() {
   if (const char *v = getenv("TM_KNN_ARENA_ENTRIES")) k.knn_arena_entries = std::max(0ll, atoll(v));
   if (const char *v = getenv("TM_GROUP_FAIL_SHARD")) k.group_fail_shard = atoi(v);
   if (const char *v = getenv("TM_INPUT_CHUNK_FRAMES")) k.input_chunk_frames = std::max(0, atoi(v));
+  if (const char *v = getenv("TM_RECON_CHUNK_FRAMES")) k.recon_chunk_frames = std::max(0, atoi(v));
   t_knobs = k;
 }
 void knobs_set(const Knobs &k) { t_knobs = k; }
