@@ -74,6 +74,10 @@
  *   TM_RECON_CHUNK_FRAMES=<n> Reconstruct computes and searches its query features n frames at a time instead of 8 GiB worth (2 GiB with the
  *                           extended palette usage); the features computed ahead during PreparePalettes are then those of the first n frames
  *                           (tests: a small clip takes several chunks)
+ *   TM_PLAYER_NO_WORKER     tm_player_*: the next key frame is decoded when the last one has been played, on the calling thread, instead of
+ *                           by a worker thread beside the playing (measurements: what the overlap buys)
+ *   TM_PLAYER_CHUNK_FRAMES=<n> tm_player_*: item records go to the device n frames at a time instead of 8 MB worth, at most 16 (tests: 1 or 2,
+ *                           so that a small clip walks the two staging buffers many times)
  *   TM_POOL_GIB=<x>         cap of the device-memory pool a thread keeps (96); TM_HOST_THREADS=<n>: OptimizePalettes' helper threads
  *                           (both read once per process)
  */
@@ -189,6 +193,9 @@ TM_API int tm_prefetch_frames_host(tm_encoder *, const uint32_t *host_frames);
  * FrameCount when > 0 (:1778-1782); a range that runs past the file is TM_E_INVAL.  The planes are uploaded as they are; chroma
  * upsampling, the Lanczos-3 resize (this build's integer rule, DESIGN.md section 17, in place of libswscale's: extern.pas:837-840) and
  * YUV -> RGB run on the device (tm_stage_yuv_to_rgb32).
+ *   An existing file that starts with 'GTMv' is a .gtm stream: Load plays frames [StartFrame, StartFrame + FrameCount) with the player
+ * (tm_player_*) into the device clip; the video is tm_w*8 x tm_h*8 at the stream's rate.  Key frames follow the automatic rule: the stream's
+ * own are not taken over.  Scaling != 1 is TM_E_UNSUPPORTED (the resampler takes YUV planes), refused here, before the stream is read.
  *   Otherwise the name is a Format pattern with one %d or %.Nd (%% = '%'): the PNG sequence Format(name, [i + StartFrame])
  * (LoadInputVideo, :3340-3353), fps 24 (:1791), FrameCount <= 0 counts files up to the first gap (:1797-1806), the size is the first
  * file's (:1813-1814; a later file of another size: TM_E_INVAL at Load), Scaling is ignored (:3347-3348).  Key frames are manual: frame 0
@@ -204,7 +211,7 @@ TM_API int tm_get_video(tm_encoder *, int *width, int *height, double *fps, int 
  * (round(k 2^n) of the matrix; the limited rule scales luma by 255/219 and chroma by 255/224). */
 enum { TM_YUV_AUTO = 0, TM_YUV_BT601_LIMITED = 1, TM_YUV_BT601_FULL = 2, TM_YUV_TILER = 3, TM_YUV_BT709_LIMITED = 4, TM_YUV_BT709_FULL = 5 };
 TM_API int tm_set_input_yuv(tm_encoder *, int mode);
-enum { TM_INPUT_Y4M = 1, TM_INPUT_PNGS = 2 };
+enum { TM_INPUT_Y4M = 1, TM_INPUT_PNGS = 2, TM_INPUT_GTM = 4 };
 /* chroma layouts: where the U / V samples sit among the luma samples (420jpeg: centred in both axes; 420mpeg2 and 422: on the even luma
  * columns, 420mpeg2 centred vertically); odd luma sizes give planes of (n + 1) / 2 samples */
 enum { TM_CHROMA_444 = 0, TM_CHROMA_422 = 1, TM_CHROMA_420JPEG = 2, TM_CHROMA_420MPEG2 = 3, TM_CHROMA_MONO = 4 };
@@ -311,6 +318,65 @@ TM_API int tm_get_frame_quality(tm_encoder *, int first_frame, int frame_count, 
  * frames with the file's; the video set with tm_set_video must match the file's header (:5021-5032) or TM_E_INVAL comes back.
  * Afterwards the read-back views and tm_save_gtm work on the loaded state. */
 TM_API int tm_reload_gtm(tm_encoder *, const char *path);
+/* ---- The .gtm player: an object of its own, no encoder behind it (tm_player.hip) --------------------------------
+ * tm_player_open reads the GTMv header and the GTMk index and decodes the FIRST key frame's stream only (it carries the settings text,
+ * SetDimensions, the TileSet and the palettes); frames then come out in order, key frame by key frame, each frame one kernel launch that
+ * reads the frame before it.  A frame is, bit for bit, what tm_render_frames(first, count, input = 0) gives after tm_reload_gtm of the same
+ * file: a drawn item is palette[PalIdx][tile[mirrored (ty, tx)]] with R and B swapped (0 for a colour index >= the palette size, for a
+ * tile or palette index out of range); a predicted item is the previous output frame at (clamp(y + PredictedY), clamp(x + PredictedX)),
+ * clamped per pixel; SkipBlock items are predicted with offset (0, 0); before frame 0 the picture is 0.  An intra tile travels with its
+ * item.  Two differences, neither reachable with a stream tm_save_gtm writes: a ShortShort / LongShort / LongLong item that names a tile at
+ * or beyond the end of the TileSet draws 0 (after tm_reload_gtm it draws whatever intra tile of the WHOLE file landed in that slot), and
+ * after tm_player_seek a predicted item in a key frame's first frame reads 0 instead of the key frame before.
+ *   Memory does not depend on the clip's length beyond the index (28 bytes per key frame).  Host: the records of two key frames (the one
+ * playing, the one a worker thread decodes ahead: 8 bytes per item + 64 per intra item) and two page-locked chunks.  Device: the TileSet,
+ * the palettes, two chunks of records, one kept frame, and -- for host destinations and seeks -- a ring of two chunks of frames.
+ *   Refusals, all before any device call: TM_E_UNSUPPORTED for a file without the GTMv header (tm_reload_gtm reads those; without the index
+ * there is no seek and no frame count); TM_E_IO for a truncated or damaged file, index or command stream, a key frame whose decoded size
+ * or frame count differs from its GTMk entry, a SetDimensions that is not the header's picture size (or more than 2^24 items a frame), an
+ * incomplete tile map at FrameEnd, a tile set beyond the declared tile count;
+ * TM_E_INVAL for a seek out of range. */
+typedef struct tm_player tm_player;
+typedef struct {
+  int32_t width, height, tm_w, tm_h, frames, keyframes;   /* pixels: tm_w * 8 x tm_h * 8 is what tm_player_read delivers */
+  int32_t tile_count, tileset_tiles, pal_size, pal_count, encoder_version;
+  uint32_t avg_bytes_per_s, kf_max_bytes_per_s;            /* the header's two byte rates */
+  double fps;                                              /* 1e9 / SetDimensions' nanoseconds per frame */
+  int64_t host_bytes, device_bytes;                        /* what the player holds now (high-water marks of its buffers) */
+} tm_gtm_info;
+TM_API int tm_player_open(const char *path, int device, tm_player **out);
+TM_API int tm_player_info(tm_player *, tm_gtm_info *info);
+TM_API int tm_player_keyframes(tm_player *, int32_t *start_frames /* keyframes */);
+TM_API int tm_player_settings_text(tm_player *, char *buf, size_t cap, size_t *n);  /* *n = the text's length; buf may be NULL */
+/* the next `count` frames as [count][tm_h*8][tm_w*8] uint32 0x00RRGGBB, into device memory of the player's device (16-byte aligned; frame i
+ * of a call reads frame i - 1 of the same buffer, the last frame is also kept by the player, so the buffer is the caller's again on return)
+ * or host memory (one copy per chunk; a single DMA each when page-locked).  *got < count only at the end of the stream.  Blocking.
+ *   The player writes on a non-blocking stream of its own, which waits for nobody else's work: whatever the caller has queued that reads or
+ * writes `out` must have completed before the call.  Every player call leaves the calling thread's current device as it found it.
+ *   A later key frame that cannot be read (TM_E_IO) ends the call at the frame before it: *got frames have been delivered and are right,
+ * the position stands at the damaged key frame, and a seek elsewhere goes on playing. */
+TM_API int tm_player_read(tm_player *, int count, void *out, int out_on_device, int *got);
+/* the next read starts at `frame` (0 .. frames; frames = the end): restarts at the key frame at or before it and plays forward without delivering */
+TM_API int tm_player_seek(tm_player *, int frame);
+TM_API int tm_player_tell(tm_player *);  /* the frame the next read starts at */
+/* wall ms since open, summed: LZMA decode, command parse (both on the worker thread when there is one), record staging + upload calls,
+ * waits for the worker, kernel launches (host side); and ms from open's entry to the first delivered frame's completion */
+TM_API int tm_player_timings(tm_player *, double ms[5], double *first_frame_ms);
+TM_API void tm_player_close(tm_player *);
+/* Host-only seams (no device).  tm_player_probe_host: header and index of a file as tm_player_open checks them (kf: [cap_kf][4] = first
+ * frame, raw size, compressed size, milliseconds; *nkf = the file's count).  tm_player_parse_host: one key frame's decoded command bytes
+ * into the player's records -- per frame tm_w * tm_h records of 8 bytes {uint32 a; uint16 pal; uint8 flags; uint8 0}: flags bit 0 / 1 H / V
+ * mirror, bit 2 predicted (a = (uint8) PredictedX | (uint8) PredictedY << 8), bit 3 intra (a = index of its 64 index bytes among the
+ * frame's intra tiles), else a = tile index -- and the frames' intra tiles (intra_first[f] = index of frame f's first one, [frames + 1]).
+ * tm_w / tm_h / tile_count are what SetDimensions of the first key frame said (a SetDimensions in the stream itself must agree or they
+ * must be 0).  Capacities count frames and tiles; *frames / *nintra are set even when a capacity is too small (TM_E_INVAL). */
+TM_API int tm_player_probe_host(const char *path, tm_gtm_info *info, int32_t *kf, int cap_kf, int *nkf);
+TM_API int tm_player_parse_host(const uint8_t *raw, size_t n, int tm_w, int tm_h, int64_t tile_count, uint64_t *records, int cap_frames,
+                                uint8_t *intra, int64_t cap_intra, int64_t *intra_first, int *frames, int64_t *nintra);
+/* One frame with the player's kernel on caller-held device arrays: records [tm_w*tm_h] (above), intra [nintra][64] (an index beyond: 0), tiles [ntiles][64],
+ * palettes i32 [npal][pal_size] 0x00BBGGRR, prev (NULL: black) and out u32 [tm_h*8][tm_w*8] 0x00RRGGBB, 16-byte aligned. */
+TM_API int tm_stage_play_frame(const void *records, const void *intra, int64_t nintra, const void *tiles, const void *palettes, const void *prev, void *out,
+                               int tm_w, int tm_h, int pal_size, int64_t ntiles, int npal, void *stream);
 /* Multi-GPU (one process per GPU): this process matches only frames [first, first+count) in Reconstruct (frames are
  * independent in the KNN branch, DoXY :1464); the host then merges the per-frame results of all processes with an
  * all-reduce(MAX) over the arrays below (other shards hold -1) and calls tm_sync_tilemap before Reindex.

@@ -8,8 +8,6 @@ using namespace tmx;
 
 extern "C" {
 
-const char *tm_last_error(void) { return tmx::get_error(); }
-
 int tm_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

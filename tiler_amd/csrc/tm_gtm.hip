@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "tm_common.h"
+#include "tm_gtm_walk.h"
 #include "tm_internal.h"
 
 namespace tmx {
@@ -141,9 +142,11 @@ class LzmaOptEncoder {
     for (int i = nbits - 1; i >= 0; i--) { const int b = (sym >> i) & 1; pr += price(probs[m], b); m = (m << 1) | b; }
     return pr;
   }
-  uint32_t rtree_price(const uint16_t *probs, int nbits, uint32_t sym) const {
+  // (reverse bit trees: node numbers start at 1 and `at` is where node 0 would lie -- -1 for the distance slot 4's tree in pos_special_ --
+  // so the table and the offset travel apart and only at + m >= 0 is ever formed)
+  uint32_t rtree_price(const uint16_t *probs, int at, int nbits, uint32_t sym) const {
     uint32_t m = 1, pr = 0;
-    for (int i = 0; i < nbits; i++) { const int b = sym & 1; pr += price(probs[m], b); m = (m << 1) | b; sym >>= 1; }
+    for (int i = 0; i < nbits; i++) { const int b = sym & 1; pr += price(probs[at + (int)m], b); m = (m << 1) | b; sym >>= 1; }
     return pr;
   }
   uint32_t literal_price(size_t pos, uint32_t state, uint32_t rep0) const {
@@ -186,7 +189,7 @@ class LzmaOptEncoder {
         if (slot >= 4) {
           const int footer = (int)(slot >> 1) - 1;
           const uint32_t base = (2u | (slot & 1)) << footer;
-          pr += rtree_price(pos_special_ + ((int)base - (int)slot - 1), footer, d - base);
+          pr += rtree_price(pos_special_, (int)base - (int)slot - 1, footer, d - base);
         }
         dist_prices_[ls][d] = pr;
       }
@@ -194,7 +197,7 @@ class LzmaOptEncoder {
     match_counter_ = 0;
   }
   void fill_align_prices() {
-    for (uint32_t i = 0; i < 16; i++) align_prices_[i] = rtree_price(pos_align_, 4, i);
+    for (uint32_t i = 0; i < 16; i++) align_prices_[i] = rtree_price(pos_align_, 0, 4, i);
     align_counter_ = 0;
   }
   uint32_t dist_len_price(uint32_t dist, uint32_t len, uint32_t pos_state) const {
@@ -441,9 +444,9 @@ class LzmaOptEncoder {
     uint32_t m = 1;
     for (int i = nbits - 1; i >= 0; i--) { const int b = (sym >> i) & 1; rc_.bit(probs[m], b); m = (m << 1) | b; }
   }
-  void rtree(uint16_t *probs, int nbits, uint32_t sym) {
+  void rtree(uint16_t *probs, int at, int nbits, uint32_t sym) {
     uint32_t m = 1;
-    for (int i = 0; i < nbits; i++) { const int b = sym & 1; rc_.bit(probs[m], b); m = (m << 1) | b; sym >>= 1; }
+    for (int i = 0; i < nbits; i++) { const int b = sym & 1; rc_.bit(probs[at + (int)m], b); m = (m << 1) | b; sym >>= 1; }
   }
   void emit_len(LenCoder &lc, uint32_t len, uint32_t pos_state, uint32_t (*tab)[272], int &counter) {
     len -= 2;
@@ -498,10 +501,10 @@ class LzmaOptEncoder {
     if (slot >= 4) {
       const int footer = (int)(slot >> 1) - 1;
       const uint32_t base = (2u | (slot & 1)) << footer, reduced = dist - base;
-      if (slot < 14) rtree(pos_special_ + ((int)base - (int)slot - 1), footer, reduced);
+      if (slot < 14) rtree(pos_special_, (int)base - (int)slot - 1, footer, reduced);
       else {
         rc_.direct(reduced >> 4, footer - 4);
-        rtree(pos_align_, 4, reduced & 15);
+        rtree(pos_align_, 0, 4, reduced & 15);
         if (++align_counter_ >= 16) fill_align_prices();
       }
     }
@@ -544,8 +547,6 @@ struct Stream {
   void u32(uint32_t v) { u16(v); u16(v >> 16); }
   void cmd(int c, uint32_t data) { u16((data << 4) | (uint32_t)c); }  // DoCmd, 5200-5206
 };
-enum { gtPredShort = 0, gtPredLong = 1, gtShortShort = 2, gtLongShort = 3, gtLongLong = 4, gtIntra = 5, gtSkip = 6, gtFrameEnd = 11,
-       gtLoadPalette = 12, gtTileSet = 13, gtSetDimensions = 14, gtExtended = 15 };  // TGTMCommand, 72-86
 
 void put_le32(std::vector<uint8_t> &f, size_t at, uint32_t v) { for (int i = 0; i < 4; i++) f[at + i] = (uint8_t)(v >> (8 * i)); }
 
@@ -586,7 +587,9 @@ int write_gtm(const char *path, const GtmInput &in) {
   z.u32((uint32_t)llrint(1000.0 * 1000 * 1000 / in.fps));
   z.u32((uint32_t)ntiles);
   // WriteTiles (5292-5316): tiles before the first UseCount = 1 (sorted by use, most used first) go into one TileSet
-  int64_t reused = 0;
+  // (5296 starts the count at 0, so a table WITHOUT a UseCount = 1 tile got no TileSet at all while all its items name one: a stream nobody
+  // can draw.  Such a table goes into the TileSet whole.)
+  int64_t reused = ntiles;
   for (int64_t t = 0; t < ntiles; t++)
     if (in.use[t] == 1) { reused = t; break; }
   if (reused > 0) {
@@ -638,7 +641,8 @@ int write_gtm(const char *path, const GtmInput &in) {
             z.cmd(gtPredShort, ((uint8_t)it.PredictedX & 63u) | (((uint8_t)it.PredictedY & 63u) << 6));
           }
         } else {
-          const uint32_t tile = (uint32_t)std::max(0, it.TileIdx), pal = (uint32_t)std::max(0, it.PalIdx) & 0xffff;
+          const int32_t tile_idx = it.TileIdx, pal_idx = it.PalIdx;  // (copies: the item is packed, std::max takes references)
+          const uint32_t tile = (uint32_t)std::max(0, tile_idx), pal = (uint32_t)std::max(0, pal_idx) & 0xffff;
           const bool intra = (int64_t)tile < ntiles && in.use[tile] <= 1;
           const uint32_t attrs = ((it.Flags & 2) ? 2u : 0u) | ((it.Flags & 1) ? 1u : 0u);
           if (intra) {
@@ -724,9 +728,9 @@ struct RangeDecoder {
     for (int i = 0; i < nbits; i++) m = (m << 1) | (uint32_t)bit(probs[m]);
     return m - (1u << nbits);
   }
-  uint32_t rtree(uint16_t *probs, int nbits) {
+  uint32_t rtree(uint16_t *probs, int at, int nbits) {  // (at: where node 0 would lie; nodes start at 1)
     uint32_t m = 1, sym = 0;
-    for (int i = 0; i < nbits; i++) { const int b = bit(probs[m]); m = (m << 1) | (uint32_t)b; sym |= (uint32_t)b << i; }
+    for (int i = 0; i < nbits; i++) { const int b = bit(probs[at + (int)m]); m = (m << 1) | (uint32_t)b; sym |= (uint32_t)b << i; }
     return sym;
   }
 };
@@ -741,7 +745,7 @@ struct LenDecoder {
 };
 }  // namespace
 
-int lz_decompress(const uint8_t *src, size_t n, std::vector<uint8_t> &dst, size_t *consumed) {
+int lz_decompress(const uint8_t *src, size_t n, std::vector<uint8_t> &dst, size_t *consumed, size_t max_out) {
   TM_CHECK(n >= 18, TM_E_IO, "LZMA stream too short");
   int props = src[0];
   const int lc = props % 9; props /= 9;
@@ -761,6 +765,7 @@ int lz_decompress(const uint8_t *src, size_t n, std::vector<uint8_t> &dst, size_
   bool ok = false;
   while (!rc.overrun) {
     const size_t pos = dst.size();
+    TM_CHECK(pos <= max_out, TM_E_IO, "LZMA stream decodes to more than the %zu bytes expected", max_out);  // (checked per symbol: a match adds at most 273)
     const uint32_t ps = (uint32_t)pos & ((1u << pb) - 1);
     if (!rc.bit(is_match[(state << 4) + ps])) {
       uint16_t *probs = &lit[(size_t)0x300 * ((((uint32_t)pos & ((1u << lp) - 1)) << lc) + (prev >> (8 - lc)))];
@@ -807,10 +812,10 @@ int lz_decompress(const uint8_t *src, size_t n, std::vector<uint8_t> &dst, size_
       if (slot >= 4) {
         const int nd = (int)(slot >> 1) - 1;
         rep0 = (2u | (slot & 1)) << nd;
-        if (slot < 14) rep0 += rc.rtree(pos_dec + ((int)rep0 - (int)slot - 1), nd);
+        if (slot < 14) rep0 += rc.rtree(pos_dec, (int)rep0 - (int)slot - 1, nd);
         else {
           rep0 += rc.direct(nd - 4) << 4;
-          rep0 += rc.rtree(pos_align, 4);
+          rep0 += rc.rtree(pos_align, 0, 4);
           if (rep0 == 0xFFFFFFFFu) { ok = true; break; }  // end marker
         }
       } else rep0 = slot;
@@ -824,7 +829,97 @@ int lz_decompress(const uint8_t *src, size_t n, std::vector<uint8_t> &dst, size_
   return TM_OK;
 }
 
-// LoadStream (tilingencoder.pas:4880-5175): the command streams of all key frames back into tables
+// LoadStream (tilingencoder.pas:4880-5175): the command streams of all key frames back into tables.  The grammar is walk_gtm_keyframe's
+// (tm_gtm_walk.h); this sink is what LoadStream makes of the commands: frames open at their first item, an intra item becomes the next tile
+// after the tile sets, SetTMI counts the uses.
+namespace {
+struct ReloadSink {
+  GtmLoaded *out;
+  int frm = -1, tm_pos = 0, last_tile = -1, loaded = 0;
+  bool frame_open = false;
+
+  int per() const { return out->tm_w * out->tm_h; }
+  tm_tilemap_item *item() {  // "next frame if needed" (5091-5093 ...)
+    if (!frame_open) { frm++; out->tilemap.resize((size_t)(frm + 1) * per()); frame_open = true; }
+    tm_tilemap_item *it = &out->tilemap[(size_t)frm * per() + tm_pos];
+    memset(it, 0, sizeof(*it));
+    it->TileIdx = -1; it->PalIdx = -1;
+    return it;
+  }
+  bool room() const { return out->tm_w > 0 && tm_pos < per(); }
+
+  int settings(uint32_t kind, const uint8_t *text, size_t n) {
+    if (kind != 0) return TM_OK;
+    out->settings.assign((const char *)text, n);
+    if (out->pal_size == 0) out->pal_size = settings_palette_size(text, n);  // (until a TileSet says it: a stream of intra and predicted items has none)
+    return TM_OK;
+  }
+  int dimensions(int tm_w, int tm_h, uint32_t ns, uint32_t tc) {
+    out->tm_w = tm_w; out->tm_h = tm_h;
+    out->fps = 1000.0 * 1000 * 1000 / ns;
+    out->pal_px.assign((size_t)tc * 64, 0);
+    out->use.assign(tc, 0);
+    return TM_OK;
+  }
+  int pal_size() const { return out->pal_size; }
+  int tile_set(int pal_size, uint32_t a, uint32_t b, const uint8_t *px) {
+    TM_CHECK((size_t)b < out->use.size(), TM_E_IO, "bad tile set");
+    memcpy(&out->pal_px[(size_t)a * 64], px, (size_t)(b - a + 1) * 64);
+    last_tile = std::max(last_tile, (int)b);
+    out->pal_size = pal_size;
+    return TM_OK;
+  }
+  int load_palette(uint32_t pi, const uint8_t *c) {
+    if (out->palettes.size() < (size_t)(pi + 1) * out->pal_size) out->palettes.resize((size_t)(pi + 1) * out->pal_size, 0);
+    for (int k = 0; k < out->pal_size; k++, c += 4)
+      out->palettes[(size_t)pi * out->pal_size + k] = (int32_t)(((uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16)));  // alpha stripped (4951)
+    return TM_OK;
+  }
+  int frame_end(bool) {
+    TM_CHECK(tm_pos == per(), TM_E_IO, "incomplete tile map");
+    tm_pos = 0;
+    frame_open = false;
+    loaded++;
+    return TM_OK;
+  }
+  int skip(uint32_t count) {
+    for (uint32_t k = 0; k < count; k++) {
+      TM_CHECK(room(), TM_E_IO, "skip past the tile map");
+      item()->Flags = 4;
+      tm_pos++;
+    }
+    return TM_OK;
+  }
+  int drawn(uint32_t tile, uint32_t pal, uint32_t mirror) {
+    TM_CHECK(room(), TM_E_IO, "bad tile-map item");
+    tm_tilemap_item *it = item();
+    it->TileIdx = (int32_t)tile; it->PalIdx = (int32_t)pal; it->Flags = mirror;
+    if ((size_t)tile < out->use.size()) out->use[tile]++;
+    tm_pos++;
+    return TM_OK;
+  }
+  int predicted(int ox, int oy) {
+    TM_CHECK(room(), TM_E_IO, "bad tile-map item");
+    tm_tilemap_item *it = item();
+    it->PredictedX = (int8_t)ox; it->PredictedY = (int8_t)oy;
+    it->Flags = 4;
+    tm_pos++;
+    return TM_OK;
+  }
+  int intra(uint32_t pal, uint32_t mirror, const uint8_t *px) {
+    TM_CHECK(room(), TM_E_IO, "bad intra tile");
+    last_tile++;
+    TM_CHECK((size_t)last_tile < out->use.size(), TM_E_IO, "more intra tiles than the tile count allows");
+    memcpy(&out->pal_px[(size_t)last_tile * 64], px, 64);
+    tm_tilemap_item *it = item();
+    it->TileIdx = last_tile; it->PalIdx = (int32_t)pal; it->Flags = mirror;
+    out->use[(size_t)last_tile]++;
+    tm_pos++;
+    return TM_OK;
+  }
+};
+}  // namespace
+
 int read_gtm(const char *path, GtmLoaded *out) {
   FILE *fp = fopen(path, "rb");
   TM_CHECK(fp != nullptr, TM_E_IO, "cannot open %s", path);
@@ -842,122 +937,18 @@ int read_gtm(const char *path, GtmLoaded *out) {
     out->header_w = (int)le32(16); out->header_h = (int)le32(20); out->header_frames = (int)le32(28);
     pos = le32(8);
   }
-  int frm = -1, tm_pos = 0, last_tile = -1, loaded = 0;
-  bool frame_open = false;
+  ReloadSink sink{out};
   std::vector<uint8_t> kf;
   while (pos < file.size()) {
     size_t used = 0;
     TM_TRY(lz_decompress(file.data() + pos, file.size() - pos, kf, &used));
     pos += used;
-    out->kf_start.push_back(loaded);
-    size_t p = 0;
-    auto need = [&](size_t k) { return p + k <= kf.size(); };
-    auto u8 = [&]() { return (uint32_t)kf[p++]; };
-    auto u16 = [&]() { const uint32_t v = kf[p] | (kf[p + 1] << 8); p += 2; return v; };
-    auto u32 = [&]() { const uint32_t v = (uint32_t)kf[p] | ((uint32_t)kf[p + 1] << 8) | ((uint32_t)kf[p + 2] << 16) | ((uint32_t)kf[p + 3] << 24); p += 4; return v; };
-    auto item = [&]() -> tm_tilemap_item * {  // "next frame if needed" (5091-5093 ...)
-      if (!frame_open) { frm++; out->tilemap.resize((size_t)(frm + 1) * out->tm_w * out->tm_h); frame_open = true; }
-      tm_tilemap_item *it = &out->tilemap[(size_t)frm * out->tm_w * out->tm_h + tm_pos];
-      memset(it, 0, sizeof(*it));
-      it->TileIdx = -1; it->PalIdx = -1;
-      return it;
-    };
-    bool kf_end = false;
-    while (!kf_end) {
-      TM_CHECK(need(2), TM_E_IO, "%s: truncated command stream", path);
-      const uint32_t w = u16(), cmd = w & 15, data = w >> 4;
-      switch (cmd) {
-        case gtExtended: { TM_CHECK(need(4), TM_E_IO, "truncated"); const uint32_t k = u32(); TM_CHECK(need(k), TM_E_IO, "truncated"); if (data == 0) out->settings.assign((const char *)&kf[p], k); p += k; break; }
-        case gtSetDimensions: {
-          TM_CHECK(need(12), TM_E_IO, "truncated");
-          out->tm_w = (int)u16(); out->tm_h = (int)u16();
-          const uint32_t ns = u32();
-          out->fps = 1000.0 * 1000 * 1000 / ns;
-          const uint32_t tc = u32();
-          TM_CHECK(out->tm_w > 0 && out->tm_h > 0 && ns > 0, TM_E_IO, "bad dimensions");
-          out->pal_px.assign((size_t)tc * 64, 0);
-          out->use.assign(tc, 0);
-          break;
-        }
-        case gtTileSet: {
-          TM_CHECK(need(8), TM_E_IO, "truncated");
-          const uint32_t a = u32(), b = u32();
-          TM_CHECK(b >= a && (size_t)b < out->use.size() && need((size_t)(b - a + 1) * 64), TM_E_IO, "bad tile set");
-          memcpy(&out->pal_px[(size_t)a * 64], &kf[p], (size_t)(b - a + 1) * 64);
-          p += (size_t)(b - a + 1) * 64;
-          last_tile = std::max(last_tile, (int)b);
-          out->pal_size = (int)data;
-          break;
-        }
-        case gtLoadPalette: {
-          TM_CHECK(need(2 + (size_t)out->pal_size * 4), TM_E_IO, "truncated");
-          const uint32_t pi = u16();
-          if (out->palettes.size() < (size_t)(pi + 1) * out->pal_size) out->palettes.resize((size_t)(pi + 1) * out->pal_size, 0);
-          for (int c = 0; c < out->pal_size; c++) out->palettes[(size_t)pi * out->pal_size + c] = (int32_t)(u32() & 0xffffff);
-          break;
-        }
-        case gtFrameEnd:
-          TM_CHECK(tm_pos == out->tm_w * out->tm_h, TM_E_IO, "incomplete tile map");
-          tm_pos = 0;
-          frame_open = false;
-          loaded++;
-          kf_end = (data & 1) != 0;
-          break;
-        case gtSkip:
-          for (uint32_t k = 0; k <= data; k++) {
-            TM_CHECK(out->tm_w > 0 && tm_pos < out->tm_w * out->tm_h, TM_E_IO, "skip past the tile map");
-            tm_tilemap_item *it = item();
-            it->Flags = 4;
-            tm_pos++;
-          }
-          break;
-        case gtShortShort: case gtLongShort: case gtLongLong: {
-          TM_CHECK(out->tm_w > 0 && tm_pos < out->tm_w * out->tm_h && need(cmd == gtShortShort ? 2 : (cmd == gtLongShort ? 4 : 6)), TM_E_IO, "bad tile-map item");
-          uint32_t pal = cmd == gtLongLong ? u16() : (data >> 2) & 1023;
-          const uint32_t tile = cmd == gtShortShort ? u16() : u32();
-          tm_tilemap_item *it = item();
-          it->TileIdx = (int32_t)tile; it->PalIdx = (int32_t)pal; it->Flags = data & 3;
-          if ((size_t)tile < out->use.size()) out->use[tile]++;
-          tm_pos++;
-          break;
-        }
-        case gtPredShort: {
-          TM_CHECK(out->tm_w > 0 && tm_pos < out->tm_w * out->tm_h, TM_E_IO, "bad tile-map item");
-          tm_tilemap_item *it = item();
-          it->PredictedX = (int8_t)((int)(data & 31) - (int)(data & 32));
-          it->PredictedY = (int8_t)((int)((data >> 6) & 31) - (int)((data >> 6) & 32));
-          it->Flags = 4;
-          tm_pos++;
-          break;
-        }
-        case gtPredLong: {
-          TM_CHECK(out->tm_w > 0 && tm_pos < out->tm_w * out->tm_h && need(2), TM_E_IO, "bad tile-map item");
-          tm_tilemap_item *it = item();
-          it->PredictedX = (int8_t)u8(); it->PredictedY = (int8_t)u8();
-          it->Flags = 4;
-          tm_pos++;
-          break;
-        }
-        case gtIntra: {
-          TM_CHECK(out->tm_w > 0 && tm_pos < out->tm_w * out->tm_h && need(66), TM_E_IO, "bad intra tile");
-          const uint32_t pal = u16();
-          last_tile++;
-          TM_CHECK((size_t)last_tile < out->use.size(), TM_E_IO, "more intra tiles than the tile count allows");
-          memcpy(&out->pal_px[(size_t)last_tile * 64], &kf[p], 64);
-          p += 64;
-          tm_tilemap_item *it = item();
-          it->TileIdx = last_tile; it->PalIdx = (int32_t)pal; it->Flags = data & 3;
-          out->use[(size_t)last_tile]++;
-          tm_pos++;
-          break;
-        }
-        default: set_error("%s: unknown command %u", path, cmd); return TM_E_IO;
-      }
-    }
+    out->kf_start.push_back(sink.loaded);
+    TM_TRY(walk_gtm_keyframe(kf.data(), kf.size(), path, sink));
   }
-  out->nframes = loaded;
+  out->nframes = sink.loaded;
   out->pal_count = out->pal_size > 0 ? (int)(out->palettes.size() / out->pal_size) : 0;
-  TM_CHECK(out->tilemap.size() == (size_t)loaded * out->tm_w * out->tm_h, TM_E_IO, "%s: frame count mismatch", path);
+  TM_CHECK(out->tilemap.size() == (size_t)sink.loaded * out->tm_w * out->tm_h, TM_E_IO, "%s: frame count mismatch", path);
   return TM_OK;
 }
 }  // namespace tmx

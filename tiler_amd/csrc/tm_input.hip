@@ -431,6 +431,15 @@ static int parse_y4m(const std::string &name, InputInfo *in) {
   return TM_OK;
 }
 
+static bool has_gtm_magic(const std::string &name) {
+  FILE *f = fopen(name.c_str(), "rb");
+  if (!f) return false;
+  char m[4] = {0, 0, 0, 0};
+  const size_t n = fread(m, 1, 4, f);
+  fclose(f);
+  return n == 4 && memcmp(m, "GTMv", 4) == 0;
+}
+
 // what tm_open_input finds out, without a device: the kind of input, its sizes, rate, frame range
 int probe_input(const std::string &name, int start_frame, int frame_count, double scaling, InputInfo *in) {
   *in = InputInfo();
@@ -438,6 +447,18 @@ int probe_input(const std::string &name, int start_frame, int frame_count, doubl
   TM_CHECK(start_frame >= 0, TM_E_INVAL, "StartFrame %d", start_frame);
   in->name = name;
   in->start = start_frame;
+  if (file_exists(name) && has_gtm_magic(name)) {  // a .gtm stream: its frames are played into the clip (tm_player.hip)
+    TM_CHECK(scaling == 1.0, TM_E_UNSUPPORTED, "%s: Scaling %g with a .gtm input (the resampler takes YUV planes; only Scaling = 1 is read)", name.c_str(), scaling);
+    int total = 0;
+    TM_TRY(probe_gtm(name.c_str(), &in->src_w, &in->src_h, &in->fps, &total));
+    in->kind = INPUT_GTM;
+    in->chroma = TM_CHROMA_444;
+    const int64_t cnt = frame_count > 0 ? frame_count : (int64_t)total - start_frame;  // 1778-1782
+    TM_CHECK(cnt > 0 && start_frame + cnt <= total, TM_E_INVAL, "%s holds %d frames: frames [%d,+%lld) are not all there", name.c_str(), total, start_frame, (long long)cnt);
+    in->frames = (int)cnt;
+    in->dst_w = in->src_w; in->dst_h = in->src_h;
+    return TM_OK;
+  }
   if (file_exists(name)) {
     TM_TRY(parse_y4m(name, in));
     const int64_t total = (int64_t)in->frame_off.size();
@@ -757,6 +778,19 @@ static int decode_pngs(tm_encoder *e) {
   });
 }
 
+// frames [a, b) of the .gtm stream, played straight into the encoder's device clip (the player writes frame i where frame i + 1 reads it)
+static int play_gtm(tm_encoder *e, int a, int b) {
+  const InputInfo &in = e->input;
+  tm_player *p = nullptr;
+  TM_TRY(tm_player_open(in.name.c_str(), e->device, &p));
+  struct Closer { tm_player *p; ~Closer() { tm_player_close(p); } } closer{p};
+  TM_TRY(tm_player_seek(p, in.start + a));
+  int got = 0;
+  TM_TRY(tm_player_read(p, b - a, e->frames_owned.as<uint8_t>() + (size_t)e->width * e->height * 4 * a, 1, &got));
+  TM_CHECK(got == b - a, TM_E_IO, "%s: %d of %d frames played", in.name.c_str(), got, b - a);
+  return TM_OK;
+}
+
 // Load's first lines when the frames come from a file or from lent YUV planes: leaves the clip where tm_set_frames_device / tm_set_frames_host would have put it
 int load_from_input(tm_encoder *e) {
   InputInfo &in = e->input;
@@ -785,7 +819,7 @@ int load_from_input(tm_encoder *e) {
   e->frames_host = nullptr;
   e->hclip_cur = -1;
   in.decoded = false;
-  if (b > a) TM_TRY(lent_clip ? convert_yuv_clip(e, (int)a, (int)b) : decode_y4m(e, (int)a, (int)b));
+  if (b > a) TM_TRY(lent_clip ? convert_yuv_clip(e, (int)a, (int)b) : in.kind == INPUT_GTM ? play_gtm(e, (int)a, (int)b) : decode_y4m(e, (int)a, (int)b));
   in.lent = false;  // (a lent clip is borrowed until this Load has returned: from here on the encoder reads its own RGB32 clip)
   in.decoded = true; in.dec_first = (int)a; in.dec_count = (int)(b - a); in.dec_mode = mode;
   return TM_OK;

@@ -122,6 +122,9 @@ int read_png(const char *path, uint32_t *out, int64_t cap_px, int *w, int *h);
 
 // tm_input.hip: Load's input.  What the probe half of Load (tilingencoder.pas:1764-1820) finds out about InputFileName.
 constexpr int INPUT_YUV_CLIP = 3;  // InputInfo::kind of a YUV clip lent in memory (tm_set_frames_yuv), beside TM_INPUT_Y4M / TM_INPUT_PNGS
+constexpr int INPUT_GTM = TM_INPUT_GTM;  // a .gtm stream ('GTMv'): Load plays its frames into the device clip (tm_player.hip)
+// tm_player.hip (host only): a .gtm file's picture size (tm_w * 8 x tm_h * 8), rate and frame count, from its header and first key frame
+int probe_gtm(const char *path, int *width, int *height, double *fps, int *frames);
 struct InputInfo {
   int kind = 0;  // 0: RGB32 frames from memory (pushed or lent); TM_INPUT_Y4M / TM_INPUT_PNGS: from the file; INPUT_YUV_CLIP: lent planes
   std::string name;
@@ -243,7 +246,7 @@ struct GtmInput {
 };
 int write_gtm(const char *path, const GtmInput &in);
 void lz_compress(const std::vector<uint8_t> &raw, std::vector<uint8_t> &dst);
-int lz_decompress(const uint8_t *src, size_t n, std::vector<uint8_t> &dst, size_t *consumed);
+int lz_decompress(const uint8_t *src, size_t n, std::vector<uint8_t> &dst, size_t *consumed, size_t max_out = (size_t)-1);  // max_out: TM_E_IO once the output passes it
 // LoadStream (tilingencoder.pas:4880-5175)
 struct GtmLoaded {
   int header_w = 0, header_h = 0, header_frames = -1;  // from the GTMv header (-1: headerless stream)

@@ -18,6 +18,9 @@ void set_error(const char *fmt, ...) {
   va_end(ap);
 }
 const char *get_error() { return g_err; }
+}  // namespace tmx
+extern "C" const char *tm_last_error(void) { return tmx::get_error(); }  // (here, beside the message: host-only programs link this file alone)
+namespace tmx {
 
 // ---- small read-backs through page-locked memory (HostRead, tm_common.h) ---------------------------------------------
 namespace {
@@ -160,6 +163,8 @@ void knobs_reload() {
   if (const char *v = getenv("TM_GROUP_FAIL_SHARD")) k.group_fail_shard = atoi(v);
   if (const char *v = getenv("TM_INPUT_CHUNK_FRAMES")) k.input_chunk_frames = std::max(0, atoi(v));
   if (const char *v = getenv("TM_RECON_CHUNK_FRAMES")) k.recon_chunk_frames = std::max(0, atoi(v));
+  k.player_no_worker = on("TM_PLAYER_NO_WORKER");
+  if (const char *v = getenv("TM_PLAYER_CHUNK_FRAMES")) k.player_chunk_frames = std::max(0, atoi(v));
   t_knobs = k;
 }
 void knobs_set(const Knobs &k) { t_knobs = k; }

@@ -204,7 +204,7 @@ class TilingEncoder:
         check(self._L.tm_set_video(c_void_p(self._h), width, height, float(fps), frame_count))
 
     def OpenInput(self):
-        """The probe half of Load (tilingencoder.pas:1764-1820): InputFileName -- a Y4M file, or a Format pattern naming a PNG sequence --
+        """The probe half of Load (tilingencoder.pas:1764-1820): InputFileName -- a Y4M file, a .gtm stream (played on the device), or a Format pattern naming a PNG sequence --
         with StartFrame, FrameCount and Scaling becomes the video (as SetVideo) and the frame source of the next Run(esLoad).  Run calls
         it by itself when no video has been described yet.  Returns VideoInfo()."""
         check(self._L.tm_open_input(c_void_p(self._h)))

@@ -1,7 +1,7 @@
 """A video file to a .gtm: python tools/encode_file.py IN OUT.gtm [--scaling S --start N --frames N --yuv auto|bt601|bt601-full|tiler|bt709|bt709-full]
 
-IN is a Y4M file (`ffmpeg -i clip.mp4 -f yuv4mpegpipe clip.y4m`) or a Format pattern naming a PNG sequence (frame_%.4d.png; key frames
-where a frame_NNNN.kf file exists).  Prints the video as Load found it and the FrameQuality of the encode."""
+IN is a Y4M file (`ffmpeg -i clip.mp4 -f yuv4mpegpipe clip.y4m`), a .gtm stream (its frames are played on the device and encoded again;
+--scaling must stay 1) or a Format pattern naming a PNG sequence (frame_%.4d.png; key frames where a frame_NNNN.kf file exists).  Prints the video as Load found it and the FrameQuality of the encode."""
 import argparse
 import json
 import os
