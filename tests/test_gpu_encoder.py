@@ -629,30 +629,64 @@ def test_y4m_and_png_export_show_what_the_player_shows(oracle, tmp_path, radius)
     enc.close()
 
 
-@pytest.mark.parametrize("tc,full", [(40, False), (151, False), (400, False), (151, True)])
-def test_tile_budget_without_motion_prediction_keeps_the_first_tiles_of_the_order(oracle, monkeypatch, tc, full):
-    """MotionPredictRadius = 0 with a GlobalTilingTileCount below the number of distinct tiles: Reduce keeps the first `tc` tiles of
-    ReindexTiles' order (use count descending, content ascending).  The library orders only the rows that can be among them (a histogram
-    of the use counts, one of the leading dword among the rows at the cut-off's count, a sort of those candidates: VERDICT r02 item 8);
-    the oracle sorts everything.  Budgets that cut inside the single-use tiles, inside the multiply used ones, and the full sort forced
-    (TM_DEDUP_FULL_ORDER) all give the oracle's tiles, palettes and tile maps."""
-    from tiler_amd import synth
-    from tests import oracle_pipeline
-    if full:
-        monkeypatch.setenv("TM_DEDUP_FULL_ORDER", "1")
-    frames = synth.video(9, 104, 56, cut=4)
-    exp = oracle_pipeline.run(oracle, frames, palette_count=2, min_s=0.1, motion_radius=0, tile_count=tc)
+_BUDGET_ORACLE = {}
+
+
+def _budget_oracle(oracle, key, frames, tc):
+    """the oracle's run of a tile-budget clip, made once per clip and budget and read by every case that needs it"""
+    if key not in _BUDGET_ORACLE:
+        from tests import oracle_pipeline
+        _BUDGET_ORACLE[key] = oracle_pipeline.run(oracle, frames, palette_count=2, min_s=0.1, motion_radius=0, tile_count=tc)
+    return _BUDGET_ORACLE[key]
+
+
+def _budget_run_equals_oracle(exp, frames, tc):
     enc = _run_encoder(frames, PaletteCount=2, ShotTransMinSecondsPerKF=0.1, MotionPredictRadius=0, FrameTilingExtendedPaletteUsage=False, GlobalTilingTileCount=tc)
     assert enc.counts()["tiles"] == exp["final_T"]
     hdr, pal, rgb = enc.Tiles()
     assert np.array_equal(pal, exp["final_pal_px"]) and np.array_equal(hdr["UseCount"], exp["final_use"]) and np.array_equal(rgb, exp["final_rgb"])
     assert np.array_equal(enc.Palettes(), exp["palettes"])
     per = exp["per"]
-    for f in range(9):
+    for f in range(frames.shape[0]):
         tm = enc.TileMap(f)
         sl = slice(f * per, (f + 1) * per)
         assert np.array_equal(tm["TileIdx"], exp["final_tm_tile"][sl]) and np.array_equal(tm["PalIdx"], exp["tm_pal"][sl])
     enc.close()
+
+
+@pytest.mark.parametrize("tc,full,front", [pytest.param(40, False, None, id="40-False"), pytest.param(151, False, None, id="151-False"),
+                                           pytest.param(400, False, None, id="400-False"), pytest.param(151, True, None, id="151-True")] +
+                         [pytest.param(151, False, k, id="151-False-" + k) for k in ("TM_DEDUP_SORT", "TM_DEDUP_RADIX_MIN", "TM_DEDUP_DEGRADE_HASH", "TM_DEDUP_PLAIN")])
+def test_tile_budget_without_motion_prediction_keeps_the_first_tiles_of_the_order(oracle, monkeypatch, tc, full, front):
+    """MotionPredictRadius = 0 with a GlobalTilingTileCount below the number of distinct tiles: Reduce keeps the first `tc` tiles of
+    ReindexTiles' order (use count descending, content ascending).  The library orders only the rows that can be among them (a histogram
+    of the use counts, one of the leading dword among the rows at the cut-off's count, a sort of those candidates: VERDICT r02 item 8);
+    the oracle sorts everything.  Budgets that cut inside the single-use tiles, inside the multiply used ones, and the full sort forced
+    (TM_DEDUP_FULL_ORDER) all give the oracle's tiles, palettes and tile maps.
+    `front`: the same with another grouping front end under the dedup -- the hash sort (the partial order then gathers use counts and leading
+    dwords per row), the radix leg of the content sort from one key on, hashes that collide (plain grouping, no partial order) and the plain
+    merge sort asked for outright; Reduce's call and Reconstruct's by-index call of the database rows both run under it."""
+    from tiler_amd import synth
+    if full:
+        monkeypatch.setenv("TM_DEDUP_FULL_ORDER", "1")
+    if front:
+        monkeypatch.setenv(front, "1")
+    frames = synth.video(9, 104, 56, cut=4)
+    _budget_run_equals_oracle(_budget_oracle(oracle, ("synth", tc), frames, tc), frames, tc)
+
+
+def test_tile_budget_that_cuts_inside_the_clamped_use_count_bin(oracle):
+    """The partial order's histogram of use counts clamps at 1023: a budget whose last position falls among the tiles used 1023 times or
+    more cannot be placed by it, and the dedup takes the full sort.  30 frames of 13 x 7 tiles: six tile columns of one flat colour (1260
+    uses), five of another (1050), two of noise (420 tiles used once); the budget of 2 keeps the two flat tiles, most used first."""
+    rng = np.random.Generator(np.random.PCG64(1023))
+    frames = np.empty((30, 56, 104), np.uint32)
+    frames[:, :, :48] = 0xFF2060A0
+    frames[:, :, 48:88] = 0xFFC08030
+    frames[:, :, 88:] = 0xFF000000 | rng.integers(0, 1 << 24, size=(30, 56, 16), dtype=np.uint32)
+    exp = _budget_oracle(oracle, ("clamped", 2), frames, 2)
+    assert exp["T"] == 2 and list(exp["guse"]) == [1260, 1050]
+    _budget_run_equals_oracle(exp, frames, 2)
 
 
 def _state(enc, nframes):

@@ -102,6 +102,23 @@ struct DevBuf {
   template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// rocPRIM's device primitives are called twice with one argument list: with a null temporary they only report its size, with the temporary
+// they run.  `call` is (void *tmp, size_t &bytes) -> hipError_t and holds that argument list once; `tmp` grows to the size asked for and stays
+// the caller's (later users are ordered behind the primitive on the same stream); `what` names the primitive in the error text.
+template <class Call>
+inline int with_temp(DevBuf &tmp, const char *what, Call &&call) {
+  size_t bytes = 0;
+  hipError_t e = call(nullptr, bytes);
+  if (e == hipSuccess) {
+    const int rc = tmp.alloc(bytes);
+    if (rc != TM_OK) return rc;
+    e = call(tmp.p, bytes);
+  }
+  if (e == hipSuccess) return TM_OK;
+  set_error("%s failed: %s", what, hipGetErrorString(e));
+  return (e == hipErrorOutOfMemory) ? TM_E_NOMEM : TM_E_HIP;
+}
+
 // Small read-backs (counts, flags, a handful of sums) through page-locked memory: a device-to-host copy into pageable memory -- a stack
 // variable -- takes the runtime's staging path and costs 27 us behind a small kernel where the same copy into pinned memory costs 15
 // (tools/micro/readback.hip; a step holds 50-100 of them).  Scoped: the destinations must outlive the object; copies queued and not

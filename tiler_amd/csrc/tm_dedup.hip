@@ -6,14 +6,20 @@
 // 584-599).  Content order is CompareDWord on the 64 RGB dwords (unsigned) or CompareByte on the 64 palette
 // indices (940-948).
 //
-// GPU form: rows are first GROUPED by a 64-bit content hash (stable radix sort of (hash, index): equal rows become
-// neighbours, lowest index first); every non-head row is compared in full with its predecessor, so a hash collision
-// cannot merge different rows -- it only sends the call down the plain path, a stable merge sort of all row indices
-// with a comparator that reads the rows.  Only the distinct rows are then merge-sorted by content (the order ReindexTiles
-// needs), run bookkeeping uses integer atomics for the merged use counts (order free), and a stable radix sort on
-// ~UseCount finishes.  rocPRIM supplies the sort and scan primitives; the hash, comparator, run detection, merge
-// bookkeeping and ranking kernels are ours.  Representative of a run = its lowest original index (the reference's
-// choice among byte-identical tiles is implementation defined).
+// GPU form, in the order run_dedup_ex states it:
+//   1. GROUP equal rows: every row's representative (the lowest index among the rows equal to it; the reference's choice among
+//      byte-identical tiles is implementation defined), the group's summed use count, the list of the distinct rows.
+//      The front end is a hash TABLE of 64-bit content hashes (k_dd_*: no sort).  TM_DEDUP_SORT=1 takes the hash SORT instead, a
+//      stable radix sort of (hash, index) that makes equal rows neighbours, lowest index first.  Either way a row is compared IN FULL
+//      with the row it would be merged with, so a hash that two different rows share cannot merge them: it raises a flag, and the
+//      call groups once more the PLAIN way -- a stable merge sort of all row indices with a comparator that reads the rows (exact
+//      and slow; TM_DEDUP_PLAIN=1 asks for it outright).  Use counts add up with integer atomics (order free).
+//   2. ORDER the distinct rows: by content (a radix sort of 8-byte prefixes, whole rows only where prefixes tie; the comparator merge
+//      sort where they tie in long runs or the rows are few), then a stable radix sort on ~UseCount.  A caller that keeps only the
+//      first rows of the order (exact_first) has only the rows that can be among them sorted (k_po_*).
+//   3. NUMBER the rows: every row's position is its representative's.
+// rocPRIM supplies the sort and scan primitives; the hash, table, comparator, run detection, merge bookkeeping and ranking kernels
+// are ours.
 #include <cstring>
 
 #include <rocprim/device/device_merge_sort.hpp>
@@ -78,7 +84,7 @@ __global__ __launch_bounds__(256) void k_row_hash(const uint32_t *__restrict__ r
     const int64_t row = r0 + (threadIdx.x >> 4);
     uint32_t lead = 0;
     const unsigned long long h = row_hash16(rows, row, n, dwords, sub, lead);
-    if (row < n && sub == 0) hash[row] = degrade ? (h & 3) : (h >> shift);  // degrade: test hook that forces collisions; shift: only the top bits are kept (run_dedup_ex)
+    if (row < n && sub == 0) hash[row] = degrade ? (h & 3) : (h >> shift);  // degrade: test hook that forces collisions; shift: only the top bits are kept (group_by_hash_sort)
   }
 }
 
@@ -427,38 +433,256 @@ __global__ void k_remap(const uint32_t *__restrict__ rep, const int32_t *__restr
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) remap[i] = pos[rep[i]];
 }
 
+// ---- the host side: run_dedup_ex at the end of the file states the order of the phases below -------------------------------------------
+namespace {
+
+// one call: its arguments, its n x 4 byte scratch arrays, and what the grouping found
+struct Dedup {
+  const uint32_t *rows;
+  int64_t n;
+  int row_bytes;
+  const uint32_t *use_in;
+  int by_index;
+  hipStream_t stream;
+  RowLess less;
+  DevBuf idx, sorted, head, headpos, hps, head_excl;  // the sorting front ends: 0..n-1, the sorted indices, run heads and their two scans
+  DevBuf rep, use_rep, uniq;                          // what every front end leaves: row -> representative, use count at a representative, the distinct rows
+  DevBuf cuse, clead;                                 // the table's extra: use count and leading dword of the distinct rows, in uniq's order
+  DevBuf key, key2, ord2, pos;                        // the ranking sort's keys, the final order, row -> position
+  DevBuf tmp, cnt, hflag;                             // rocPRIM's temporary, the live count, "two different rows shared a hash"
+  int64_t nu = 0;                                     // distinct rows
+  int alloc(bool table) {
+    for (DevBuf *b : {&idx, &sorted, &head, &headpos, &head_excl, &hps, &rep, &use_rep, &uniq, &key, &key2, &ord2, &pos}) TM_TRY(b->alloc(n * 4));
+    if (table) { TM_TRY(cuse.alloc(n * 4)); TM_TRY(clead.alloc(n * 4)); }
+    TM_TRY(cnt.alloc(16));
+    return hflag.alloc(4);
+  }
+};
+enum Front { FRONT_TABLE, FRONT_HASH_SORT, FRONT_PLAIN };
+
+// the one read-back of a grouping: the number of distinct rows (= head_excl[n-1] + head[n-1]) and the collision flag, one round trip for all
+int read_groups(Dedup &d, bool *collision) {
+  uint32_t last_excl = 0, last_head = 0;
+  int flag = 0;
+  HostRead hr(d.stream);
+  TM_TRY(hr.get(&last_excl, d.head_excl.as<uint32_t>() + (d.n - 1), 4));
+  TM_TRY(hr.get(&last_head, d.head.as<uint32_t>() + (d.n - 1), 4));
+  TM_TRY(hr.get(&flag, d.hflag.p, 4));
+  TM_TRY(hr.wait());
+  d.nu = (int64_t)last_excl + last_head;
+  *collision = flag != 0;
+  return TM_OK;
+}
+
+// The three grouping front ends share one contract: rep, use_rep, uniq and nu are filled (uniq in index order after the table, in hash order
+// after the hash sort, in content order after the plain sort); *collision says that two different rows shared a hash: what was filled is then not to be used.
+
+// the table (see k_dd_insert): no sort; cuse and clead come with it
+int group_by_table(Dedup &d, bool *collision) {
+  const int64_t n = d.n;
+  int64_t slots = 1024;
+  while (slots * 2 < n * 3) slots *= 2;
+  DevBuf tkey, tslot, slot_of, lead_of;
+  TM_TRY(tkey.alloc((size_t)slots * 8)); TM_TRY(tslot.alloc((size_t)slots * sizeof(DdSlot))); TM_TRY(slot_of.alloc(n * 4)); TM_TRY(lead_of.alloc(n * 4));
+  TM_HIP(hipMemsetAsync(tkey.p, 0, (size_t)slots * 8, d.stream));
+  TM_HIP(hipMemsetAsync(tslot.p, 0xff, (size_t)slots * sizeof(DdSlot), d.stream));
+  TM_HIP(hipMemsetAsync(d.use_rep.p, 0, n * 4, d.stream));
+  hipLaunchKernelGGL(k_dd_insert, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 256 * 8)), dim3(256), 0, d.stream, d.rows, n, d.row_bytes / 4,
+                     knobs().dedup_degrade_hash ? 1 : 0, d.less.bytewise, tkey.as<unsigned long long>(), tslot.as<DdSlot>(), (uint32_t)(slots - 1), slot_of.as<uint32_t>(),
+                     lead_of.as<uint32_t>());
+  hipLaunchKernelGGL(k_dd_resolve, dim3(gridn(n)), dim3(256), 0, d.stream, n, tslot.as<DdSlot>(), slot_of.as<uint32_t>(), d.use_in, d.rep.as<uint32_t>(),
+                     d.head.as<uint32_t>(), d.use_rep.as<uint32_t>());
+  hipLaunchKernelGGL(k_dd_verify, dim3(gridn(n)), dim3(256), 0, d.stream, d.rows, n, d.row_bytes / 4, d.rep.as<uint32_t>(), d.hflag.as<int>());
+  TM_TRY(with_temp(d.tmp, "dedup: scan of the table's head marks", [&](void *t, size_t &b) {
+    return rocprim::exclusive_scan(t, b, d.head.as<uint32_t>(), d.head_excl.as<uint32_t>(), 0u, (size_t)n, rocprim::plus<uint32_t>(), d.stream);
+  }));
+  hipLaunchKernelGGL(k_dd_compact, dim3(gridn(n)), dim3(256), 0, d.stream, n, d.head.as<uint32_t>(), d.head_excl.as<uint32_t>(), d.use_in,
+                     lead_of.as<uint32_t>(), d.use_rep.as<uint32_t>(), d.uniq.as<uint32_t>(), d.cuse.as<uint32_t>(), d.clead.as<uint32_t>());
+  TM_HIP(hipGetLastError());
+  return read_groups(d, collision);  // (a collision: about once in 2^20 calls of the bench clip's size)
+}
+
+// what the two sorting front ends share: `sorted` holds runs of equal rows, lowest index first, head / headpos mark where they begin
+int merge_runs(Dedup &d, bool *collision) {
+  const int64_t n = d.n;
+  TM_TRY(with_temp(d.tmp, "dedup: scan of the run heads' positions", [&](void *t, size_t &b) {
+    return rocprim::inclusive_scan(t, b, d.headpos.as<uint32_t>(), d.hps.as<uint32_t>(), (size_t)n, rocprim::maximum<uint32_t>(), d.stream);
+  }));
+  TM_TRY(with_temp(d.tmp, "dedup: scan of the run heads", [&](void *t, size_t &b) {
+    return rocprim::exclusive_scan(t, b, d.head.as<uint32_t>(), d.head_excl.as<uint32_t>(), 0u, (size_t)n, rocprim::plus<uint32_t>(), d.stream);
+  }));
+  TM_HIP(hipMemsetAsync(d.use_rep.p, 0, n * 4, d.stream));
+  hipLaunchKernelGGL(k_merge_runs, dim3(gridn(n)), dim3(256), 0, d.stream, d.sorted.as<uint32_t>(), d.hps.as<uint32_t>(), d.head_excl.as<uint32_t>(),
+                     d.head.as<uint32_t>(), n, d.use_in, d.rep.as<uint32_t>(), d.use_rep.as<uint32_t>(), d.uniq.as<uint32_t>());
+  TM_HIP(hipGetLastError());
+  return read_groups(d, collision);
+}
+
+// the hash sort (TM_DEDUP_SORT): equal rows become neighbours by a stable radix sort of (hash, index)
+int group_by_hash_sort(Dedup &d, bool *collision) {
+  const int64_t n = d.n;
+  DevBuf hkey, hkey2;
+  TM_TRY(hkey.alloc(n * 8)); TM_TRY(hkey2.alloc(n * 8));
+  // The sort only has to bring equal rows together, so the hash keeps only as many of its top bits (whole 8-bit passes of the sort) as hold
+  // the chance of two different rows among n sharing them below 2^-12 -- 48 for Reindex's 321 k rows, 56 for the bench clip's 4.32 M frame tiles
+  // (seven passes instead of eight).  Rows that share them and differ are caught by the full compare like any collision.
+  // The kept bits are moved DOWN and sorted as bits [0, hbits): a range that ends at bit 64 without starting at 0 sends rocPRIM's
+  // merge-sort path (up to ~1 M keys) through a mask built with a shift by 64 -- it then orders by the wrong bits and its merge reads out
+  // of bounds (found the hard way: a memory access fault on the GPU box).
+  const int degrade = knobs().dedup_degrade_hash ? 1 : 0;
+  const int hbits = degrade ? 64 : std::min(64, ((int)std::ceil(2.0 * std::log2((double)std::max<int64_t>(n, 2)) + 11.0) + 7) / 8 * 8);  // n^2 / 2^(bits + 1) <= 2^-12
+  const dim3 grid16((unsigned)std::min<int64_t>((n + 15) / 16, 256 * 32));  // 16 rows per workgroup and pass
+  hipLaunchKernelGGL(k_row_hash, grid16, dim3(256), 0, d.stream, d.rows, n, d.row_bytes / 4, degrade, 64 - hbits, hkey.as<unsigned long long>());
+  TM_TRY(with_temp(d.tmp, "dedup: radix sort of the row hashes", [&](void *t, size_t &b) {
+    return rocprim::radix_sort_pairs(t, b, hkey.as<unsigned long long>(), hkey2.as<unsigned long long>(), d.idx.as<uint32_t>(), d.sorted.as<uint32_t>(), (size_t)n, 0, hbits, d.stream);
+  }));
+  hipLaunchKernelGGL(k_mark_heads_hash, grid16, dim3(256), 0, d.stream, d.sorted.as<uint32_t>(), hkey2.as<unsigned long long>(), n, d.less, d.head.as<uint32_t>(),
+                     d.headpos.as<uint32_t>(), d.hflag.as<int>());
+  return merge_runs(d, collision);  // (a collision: about once in 2^12 calls by the choice of bits above)
+}
+
+// the plain way: a stable merge sort of all row indices with a comparator that reads the rows.  No hash, nothing to collide.
+int group_plain(Dedup &d, bool *collision) {
+  TM_TRY(with_temp(d.tmp, "dedup: merge sort of the rows", [&](void *t, size_t &b) {
+    return rocprim::merge_sort(t, b, d.idx.as<uint32_t>(), d.sorted.as<uint32_t>(), (size_t)d.n, d.less, d.stream);
+  }));
+  hipLaunchKernelGGL(k_mark_heads, dim3(gridn(d.n)), dim3(256), 0, d.stream, d.sorted.as<uint32_t>(), d.n, d.less, d.head.as<uint32_t>(), d.headpos.as<uint32_t>());
+  bool stale;  // (the flag that comes back with the count is the front end's that sent the call here)
+  TM_TRY(merge_runs(d, &stale));
+  *collision = false;
+  return TM_OK;
+}
+
 // m keys (prefix, row) into content order; the rows of that order to out_rows
-static int sort_prefix_keys(DevBuf &pk, int64_t m, const RowLess &less, uint32_t *out_rows, DevBuf &tmp, hipStream_t stream) {
+int sort_prefix_keys(DevBuf &pk, int64_t m, const RowLess &less, uint32_t *out_rows, DevBuf &tmp, hipStream_t stream) {
   if (m <= 0) return TM_OK;
   if (m >= knobs().dedup_radix_min) {
     DevBuf k1, k2, r1, r2, flag;
     TM_TRY(k1.alloc((size_t)m * 8)); TM_TRY(k2.alloc((size_t)m * 8)); TM_TRY(r1.alloc((size_t)m * 4)); TM_TRY(r2.alloc((size_t)m * 4)); TM_TRY(flag.alloc(4));
     TM_HIP(hipMemsetAsync(flag.p, 0, 4, stream));
     hipLaunchKernelGGL(k_pk_split, dim3(gridn(m)), dim3(256), 0, stream, pk.as<PrefixKey>(), m, k1.as<unsigned long long>(), r1.as<uint32_t>());
-    size_t tb = 0;
-    TM_HIP(rocprim::radix_sort_pairs(nullptr, tb, k1.as<unsigned long long>(), k2.as<unsigned long long>(), r1.as<uint32_t>(), r2.as<uint32_t>(), (size_t)m, 0, 64, stream));
-    TM_TRY(tmp.alloc(tb));
-    TM_HIP(rocprim::radix_sort_pairs(tmp.p, tb, k1.as<unsigned long long>(), k2.as<unsigned long long>(), r1.as<uint32_t>(), r2.as<uint32_t>(), (size_t)m, 0, 64, stream));
+    TM_TRY(with_temp(tmp, "dedup: radix sort of the row prefixes", [&](void *t, size_t &b) {
+      return rocprim::radix_sort_pairs(t, b, k1.as<unsigned long long>(), k2.as<unsigned long long>(), r1.as<uint32_t>(), r2.as<uint32_t>(), (size_t)m, 0, 64, stream);
+    }));
     hipLaunchKernelGGL(k_pk_ties, dim3(gridn(m)), dim3(256), 0, stream, k2.as<unsigned long long>(), r2.as<uint32_t>(), m, less, flag.as<int>());
     TM_HIP(hipMemcpyAsync(out_rows, r2.p, (size_t)m * 4, hipMemcpyDeviceToDevice, stream));
+    TM_HIP(hipGetLastError());
     int too_long = 0;
     {
-      HostRead hr_(stream);
-      TM_TRY(hr_.get(&too_long, flag.p, 4));
-      TM_TRY(hr_.wait());
+      HostRead hr(stream);
+      TM_TRY(hr.get(&too_long, flag.p, 4));
+      TM_TRY(hr.wait());
     }
-    if (!too_long) return TM_OK;
+    if (!too_long) return TM_OK;  // else a run of equal prefixes longer than k_pk_ties sorts: the comparator merge sort, the same order by construction
   }
   DevBuf pk2;
   TM_TRY(pk2.alloc((size_t)m * sizeof(PrefixKey)));
   const PrefixLess pless{less};
-  size_t tbu = 0;
-  TM_HIP(rocprim::merge_sort(nullptr, tbu, pk.as<PrefixKey>(), pk2.as<PrefixKey>(), (size_t)m, pless, stream));
-  TM_TRY(tmp.alloc(tbu));
-  TM_HIP(rocprim::merge_sort(tmp.p, tbu, pk.as<PrefixKey>(), pk2.as<PrefixKey>(), (size_t)m, pless, stream));
+  TM_TRY(with_temp(tmp, "dedup: merge sort of the row prefixes", [&](void *t, size_t &b) {
+    return rocprim::merge_sort(t, b, pk.as<PrefixKey>(), pk2.as<PrefixKey>(), (size_t)m, pless, stream);
+  }));
   hipLaunchKernelGGL(k_prefix_rows, dim3(gridn(m)), dim3(256), 0, stream, pk2.as<PrefixKey>(), m, out_rows);
+  TM_HIP(hipGetLastError());
+  return TM_OK;  // pk2 goes back to the pool here; later users are ordered behind these kernels on the same stream (as with `tmp`)
+}
+
+// Only the first exact_first positions have to be right.  The order is use count descending, content ascending: a histogram of the use
+// counts finds the count u* of position exact_first, a histogram of the leading dword's top bits among the rows used u* times finds
+// the bucket that position falls into; rows used more often, or u* times with a leading dword up to that bucket, are the only ones
+// that can come before it.  They alone are sorted (the comparator reads the rows where the keys tie); the others follow as they come.
+// 3.24 M distinct rows for a budget of 321 k on the bench clip: a merge sort of a tenth of them instead of all.
+// *done: ord2 holds the final order of all nu distinct rows.  Not done -- nothing written -- when the cut falls inside the clamped bin
+// (1023 uses and more: the histogram cannot tell those rows apart) or no row is used at all: the caller takes the full sort.
+int order_candidates(Dedup &d, bool from_table, int64_t exact_first, bool *done) {
+  const int64_t nu = d.nu;
+  *done = false;
+  DevBuf h1, h2, h8, flag, fpos, pk;
+  TM_TRY(h1.alloc(1024 * 4)); TM_TRY(h2.alloc(4096 * 4)); TM_TRY(h8.alloc(8 * 4096 * 4));
+  const int po_grid = std::min(gridn(nu), 1024);  // (every workgroup flushes its bins: fewer workgroups, fewer atomics on the popular ones)
+  const uint32_t *uniq = d.uniq.as<uint32_t>(), *use_rep = d.use_rep.as<uint32_t>();
+  const uint32_t *cu = from_table ? d.cuse.as<uint32_t>() : nullptr, *cl = from_table ? d.clead.as<uint32_t>() : nullptr;  // (null: the kernels gather both per row)
+  TM_HIP(hipMemsetAsync(h8.p, 0, 8 * 1024 * 4, d.stream));
+  hipLaunchKernelGGL(k_po_use_hist, dim3(po_grid), dim3(256), 0, d.stream, uniq, nu, use_rep, cu, h8.as<uint32_t>());
+  hipLaunchKernelGGL(k_po_fold, dim3(4), dim3(256), 0, d.stream, h8.as<uint32_t>(), 1024, h1.as<uint32_t>());
+  TM_HIP(hipGetLastError());
+  std::vector<uint32_t> hh1(1024), hh2(4096);
+  {
+    HostRead hr(d.stream);
+    TM_TRY(hr.get(hh1.data(), h1.p, 1024 * 4));
+    TM_TRY(hr.wait());
+  }
+  int64_t above = 0;  // rows used more often than u*
+  int ustar = -1;
+  for (int u = 1023; u >= 1; u--) {
+    if (above + hh1[(size_t)u] >= exact_first) { ustar = u; break; }
+    above += hh1[(size_t)u];
+  }
+  if (ustar < 1 || ustar >= 1023) return TM_OK;
+  TM_HIP(hipMemsetAsync(h8.p, 0, 8 * 4096 * 4, d.stream));
+  hipLaunchKernelGGL(k_po_lead_hist, dim3(po_grid), dim3(256), 0, d.stream, uniq, nu, use_rep, (uint32_t)ustar, d.less, cu, cl, h8.as<uint32_t>());
+  hipLaunchKernelGGL(k_po_fold, dim3(16), dim3(256), 0, d.stream, h8.as<uint32_t>(), 4096, h2.as<uint32_t>());
+  TM_HIP(hipGetLastError());
+  {
+    HostRead hr(d.stream);
+    TM_TRY(hr.get(hh2.data(), h2.p, 4096 * 4));
+    TM_TRY(hr.wait());
+  }
+  int64_t ncand = above;  // ... and those used u* times up to the bucket b*
+  int bstar = 4095;
+  for (int b = 0; b < 4096; b++) {
+    ncand += hh2[(size_t)b];
+    if (ncand >= exact_first) { bstar = b; break; }
+  }
+  TM_TRY(flag.alloc((size_t)nu * 4)); TM_TRY(fpos.alloc((size_t)nu * 4));
+  hipLaunchKernelGGL(k_po_flags, dim3(gridn(nu)), dim3(256), 0, d.stream, uniq, nu, use_rep, (uint32_t)ustar, (uint32_t)bstar, d.less, cu, cl, flag.as<uint32_t>());
+  TM_TRY(with_temp(d.tmp, "dedup: scan of the candidate flags", [&](void *t, size_t &b) {
+    return rocprim::exclusive_scan(t, b, flag.as<uint32_t>(), fpos.as<uint32_t>(), 0u, (size_t)nu, rocprim::plus<uint32_t>(), d.stream);
+  }));
+  TM_TRY(pk.alloc((size_t)ncand * sizeof(PrefixKey)));
+  hipLaunchKernelGGL(k_po_split, dim3(gridn(nu)), dim3(256), 0, d.stream, uniq, nu, flag.as<uint32_t>(), fpos.as<uint32_t>(), ncand, use_rep, d.less, cu, cl,
+                     pk.as<PrefixKey>(), d.ord2.as<uint32_t>());
+  TM_HIP(hipGetLastError());
+  TM_TRY(sort_prefix_keys(pk, ncand, d.less, d.ord2.as<uint32_t>(), d.tmp, d.stream));
+  *done = true;
   return TM_OK;
 }
+
+// the distinct rows, in hash or index order -> content order (what the stable ranking sort relies on)
+int content_order(Dedup &d) {
+  DevBuf pk;
+  TM_TRY(pk.alloc((size_t)d.nu * sizeof(PrefixKey)));
+  hipLaunchKernelGGL(k_prefix_keys, dim3(gridn(d.nu)), dim3(256), 0, d.stream, d.uniq.as<uint32_t>(), d.nu, d.less, pk.as<PrefixKey>());
+  TM_HIP(hipGetLastError());
+  return sort_prefix_keys(pk, d.nu, d.less, d.uniq.as<uint32_t>(), d.tmp, d.stream);
+}
+
+// uniq -> ord2 by a stable radix sort: on ~UseCount (content order stays within a count; *live = the rows in use, they come first), or on the
+// row number (by_index: every distinct row is live)
+int rank(Dedup &d, unsigned long long *live) {
+  TM_HIP(hipMemsetAsync(d.cnt.p, 0, 16, d.stream));
+  hipLaunchKernelGGL(k_rank_keys, dim3(gridn(d.nu)), dim3(256), 0, d.stream, d.uniq.as<uint32_t>(), d.nu, d.use_rep.as<uint32_t>(), d.by_index, d.key.as<uint32_t>(),
+                     d.cnt.as<unsigned long long>());
+  TM_TRY(with_temp(d.tmp, "dedup: radix sort of the ranking keys", [&](void *t, size_t &b) {
+    return rocprim::radix_sort_pairs(t, b, d.key.as<uint32_t>(), d.key2.as<uint32_t>(), d.uniq.as<uint32_t>(), d.ord2.as<uint32_t>(), (size_t)d.nu, 0, 32, d.stream);
+  }));
+  TM_HIP(hipGetLastError());
+  HostRead hr(d.stream);
+  TM_TRY(hr.get(live, d.cnt.p, 8));
+  return hr.wait();
+}
+
+// ord2 -> the caller's arrays: a live row's position, its use count, and every row's position through its representative
+int finish(Dedup &d, int64_t live, void *remap, void *order, void *use_out) {
+  TM_HIP(hipMemsetAsync(d.pos.p, 0xff, d.n * 4, d.stream));
+  hipLaunchKernelGGL(k_scatter_pos, dim3(gridn(live)), dim3(256), 0, d.stream, d.ord2.as<uint32_t>(), live, d.use_rep.as<uint32_t>(), d.pos.as<int32_t>(), (uint32_t *)use_out);
+  hipLaunchKernelGGL(k_remap, dim3(gridn(d.n)), dim3(256), 0, d.stream, d.rep.as<uint32_t>(), d.pos.as<int32_t>(), d.n, (int32_t *)remap);
+  TM_HIP(hipMemcpyAsync(order, d.ord2.p, (size_t)live * 4, hipMemcpyDeviceToDevice, d.stream));
+  TM_HIP(hipGetLastError());
+  TM_HIP(hipStreamSynchronize(d.stream));  // the scratch DevBufs die with the caller's frame
+  return TM_OK;
+}
+
+}  // namespace
 
 // by_index = 0: the reference's ReindexTiles order (use desc, content asc), zero-use rows dropped.
 // by_index = 1: representatives in ascending original index (used to search only distinct database rows; any
@@ -473,400 +697,34 @@ int run_dedup_ex(const void *rows, int64_t n, int row_bytes, const void *use_in,
   TM_CHECK(n >= 0 && n < (int64_t)1 << 31, TM_E_INVAL, "dedup: row count out of range");
   if (host_n_unique) *host_n_unique = 0;
   if (n == 0) return TM_OK;
-  RowLess less{(const uint32_t *)rows, row_bytes / 4, (!by_index && row_bytes == 64) ? 1 : 0};
-  DevBuf idx, sorted, head, headpos, hps, head_excl, rep, use_rep, uniq, key, key2, ord2, pos, tmp, cnt;
-  TM_TRY(idx.alloc(n * 4)); TM_TRY(sorted.alloc(n * 4)); TM_TRY(head.alloc(n * 4)); TM_TRY(headpos.alloc(n * 4));
-  TM_TRY(head_excl.alloc(n * 4)); TM_TRY(hps.alloc(n * 4)); TM_TRY(rep.alloc(n * 4)); TM_TRY(use_rep.alloc(n * 4)); TM_TRY(uniq.alloc(n * 4));
-  TM_TRY(key.alloc(n * 4)); TM_TRY(key2.alloc(n * 4)); TM_TRY(ord2.alloc(n * 4)); TM_TRY(pos.alloc(n * 4)); TM_TRY(cnt.alloc(16));
-  hipLaunchKernelGGL(k_iota, dim3(gridn(n)), dim3(256), 0, stream, idx.as<uint32_t>(), n);
-  bool grouped = false;  // true: `sorted` is in hash order (runs of equal rows, lowest index first), not yet in content order
-  DevBuf hflag;  // set by the full compares of the hash groups: two different rows shared a hash
-  TM_TRY(hflag.alloc(4));
-  TM_HIP(hipMemsetAsync(hflag.p, 0, 4, stream));
-  auto plain_heads = [&]() -> int {  // the plain path: a stable merge sort of all row indices with a comparator that reads the rows
-    size_t tb = 0;
-    TM_HIP(rocprim::merge_sort(nullptr, tb, idx.as<uint32_t>(), sorted.as<uint32_t>(), (size_t)n, less, stream));
-    TM_TRY(tmp.alloc(tb));
-    TM_HIP(rocprim::merge_sort(tmp.p, tb, idx.as<uint32_t>(), sorted.as<uint32_t>(), (size_t)n, less, stream));
-    hipLaunchKernelGGL(k_mark_heads, dim3(gridn(n)), dim3(256), 0, stream, sorted.as<uint32_t>(), n, less, head.as<uint32_t>(),
-                       headpos.as<uint32_t>());
-    return TM_OK;
-  };
-  // the table front end (see k_dd_insert): rep, use_rep, uniq (in index order) and the distinct count without a sort
-  DevBuf cuse, clead;
-  bool table_ok = false;
-  uint32_t last_excl = 0, last_head = 0;
-  if (!knobs().dedup_plain && !knobs().dedup_sort) {
-    int64_t slots = 1024;
-    while (slots * 2 < n * 3) slots *= 2;
-    DevBuf tkey, tslot, slot_of, lead_of;
-    TM_TRY(tkey.alloc((size_t)slots * 8)); TM_TRY(tslot.alloc((size_t)slots * sizeof(DdSlot))); TM_TRY(slot_of.alloc(n * 4)); TM_TRY(lead_of.alloc(n * 4));
-    TM_TRY(cuse.alloc(n * 4)); TM_TRY(clead.alloc(n * 4));
-    TM_HIP(hipMemsetAsync(tkey.p, 0, (size_t)slots * 8, stream));
-    TM_HIP(hipMemsetAsync(tslot.p, 0xff, (size_t)slots * sizeof(DdSlot), stream));
-    TM_HIP(hipMemsetAsync(use_rep.p, 0, n * 4, stream));
-    hipLaunchKernelGGL(k_dd_insert, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 256 * 8)), dim3(256), 0, stream, (const uint32_t *)rows, n, row_bytes / 4,
-                       knobs().dedup_degrade_hash ? 1 : 0, less.bytewise, tkey.as<unsigned long long>(), tslot.as<DdSlot>(), (uint32_t)(slots - 1), slot_of.as<uint32_t>(),
-                       lead_of.as<uint32_t>());
-    hipLaunchKernelGGL(k_dd_resolve, dim3(gridn(n)), dim3(256), 0, stream, n, tslot.as<DdSlot>(), slot_of.as<uint32_t>(), (const uint32_t *)use_in, rep.as<uint32_t>(),
-                       head.as<uint32_t>(), use_rep.as<uint32_t>());
-    hipLaunchKernelGGL(k_dd_verify, dim3(gridn(n)), dim3(256), 0, stream, (const uint32_t *)rows, n, row_bytes / 4, rep.as<uint32_t>(), hflag.as<int>());
-    size_t tb3 = 0;
-    TM_HIP(rocprim::exclusive_scan(nullptr, tb3, head.as<uint32_t>(), head_excl.as<uint32_t>(), 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    TM_TRY(tmp.alloc(tb3));
-    TM_HIP(rocprim::exclusive_scan(tmp.p, tb3, head.as<uint32_t>(), head_excl.as<uint32_t>(), 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    hipLaunchKernelGGL(k_dd_compact, dim3(gridn(n)), dim3(256), 0, stream, n, head.as<uint32_t>(), head_excl.as<uint32_t>(), (const uint32_t *)use_in,
-                       lead_of.as<uint32_t>(), use_rep.as<uint32_t>(), uniq.as<uint32_t>(), cuse.as<uint32_t>(), clead.as<uint32_t>());
-    int collision = 0;
-    {
-      HostRead hr_(stream);
-      TM_TRY(hr_.get(&last_excl, head_excl.as<uint32_t>() + (n - 1), 4));
-      TM_TRY(hr_.get(&last_head, head.as<uint32_t>() + (n - 1), 4));
-      TM_TRY(hr_.get(&collision, hflag.p, 4));
-      TM_TRY(hr_.wait());
-    }
-    if (!collision) grouped = table_ok = true;  // (two different rows under one hash, about once in 2^20 calls of the clip's size: the plain path below, exact and slow)
+  Dedup d{(const uint32_t *)rows, n, row_bytes, (const uint32_t *)use_in, by_index, stream,
+          RowLess{(const uint32_t *)rows, row_bytes / 4, (!by_index && row_bytes == 64) ? 1 : 0}};
+  // 1. group: the front end the knobs name; two different rows under one hash send the call to the plain one
+  Front front = knobs().dedup_plain ? FRONT_PLAIN : knobs().dedup_sort ? FRONT_HASH_SORT : FRONT_TABLE;
+  TM_TRY(d.alloc(front == FRONT_TABLE));
+  hipLaunchKernelGGL(k_iota, dim3(gridn(n)), dim3(256), 0, stream, d.idx.as<uint32_t>(), n);
+  TM_HIP(hipMemsetAsync(d.hflag.p, 0, 4, stream));
+  bool collision = false;
+  TM_TRY(front == FRONT_TABLE ? group_by_table(d, &collision) : front == FRONT_HASH_SORT ? group_by_hash_sort(d, &collision) : group_plain(d, &collision));
+  if (collision) {
+    front = FRONT_PLAIN;
+    TM_TRY(group_plain(d, &collision));
   }
-  if (!knobs().dedup_plain && knobs().dedup_sort) {
-    DevBuf hkey, hkey2;
-    TM_TRY(hkey.alloc(n * 8)); TM_TRY(hkey2.alloc(n * 8));
-    // The sort only has to bring equal rows together, so the hash keeps only as many of its top bits (whole 8-bit passes of the sort) as hold
-    // the chance of two different rows among n sharing them below 2^-12 -- 48 for Reindex's 321 k rows, 56 for the bench clip's 4.32 M frame tiles
-    // (seven passes instead of eight).  Rows that share them and differ are caught by the full compare like any collision (the plain path then: exact, slow).
-    // The kept bits are moved DOWN and sorted as bits [0, hbits): a range that ends at bit 64 without starting at 0 sends rocPRIM's
-    // merge-sort path (up to ~1 M keys) through a mask built with a shift by 64 -- it then orders by the wrong bits and its merge reads out
-    // of bounds (found the hard way: a memory access fault on the GPU box).
-    int hbits = 64;
-    const int degrade = knobs().dedup_degrade_hash ? 1 : 0;
-    if (!degrade) {
-      hbits = std::min(64, ((int)std::ceil(2.0 * std::log2((double)std::max<int64_t>(n, 2)) + 11.0) + 7) / 8 * 8);  // n^2 / 2^(bits + 1) <= 2^-12
-    }
-    hipLaunchKernelGGL(k_row_hash, dim3((unsigned)std::min<int64_t>((n + 15) / 16, 256 * 32)), dim3(256), 0, stream, (const uint32_t *)rows, n,
-                       row_bytes / 4, degrade, 64 - hbits, hkey.as<unsigned long long>());
-    size_t tbh = 0;
-    TM_HIP(rocprim::radix_sort_pairs(nullptr, tbh, hkey.as<unsigned long long>(), hkey2.as<unsigned long long>(), idx.as<uint32_t>(),
-                                     sorted.as<uint32_t>(), (size_t)n, 0, hbits, stream));
-    TM_TRY(tmp.alloc(tbh));
-    TM_HIP(rocprim::radix_sort_pairs(tmp.p, tbh, hkey.as<unsigned long long>(), hkey2.as<unsigned long long>(), idx.as<uint32_t>(),
-                                     sorted.as<uint32_t>(), (size_t)n, 0, hbits, stream));
-    hipLaunchKernelGGL(k_mark_heads_hash, dim3((unsigned)std::min<int64_t>((n + 15) / 16, 256 * 32)), dim3(256), 0, stream, sorted.as<uint32_t>(),
-                       hkey2.as<unsigned long long>(), n, less, head.as<uint32_t>(), headpos.as<uint32_t>(), hflag.as<int>());
-    grouped = true;  // until the flag says otherwise: it is read with the distinct count below, one round trip for both
-  }
-  if (!grouped) TM_TRY(plain_heads());
-  while (!table_ok) {
-    size_t tb2 = 0;
-    TM_HIP(rocprim::inclusive_scan(nullptr, tb2, headpos.as<uint32_t>(), hps.as<uint32_t>(), (size_t)n, rocprim::maximum<uint32_t>(), stream));
-    size_t tb3 = 0;
-    TM_HIP(rocprim::exclusive_scan(nullptr, tb3, head.as<uint32_t>(), head_excl.as<uint32_t>(), 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    TM_TRY(tmp.alloc(std::max(tb2, tb3)));
-    TM_HIP(rocprim::inclusive_scan(tmp.p, tb2, headpos.as<uint32_t>(), hps.as<uint32_t>(), (size_t)n, rocprim::maximum<uint32_t>(), stream));
-    TM_HIP(rocprim::exclusive_scan(tmp.p, tb3, head.as<uint32_t>(), head_excl.as<uint32_t>(), 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    TM_HIP(hipMemsetAsync(use_rep.p, 0, n * 4, stream));
-    hipLaunchKernelGGL(k_merge_runs, dim3(gridn(n)), dim3(256), 0, stream, sorted.as<uint32_t>(), hps.as<uint32_t>(),
-                       head_excl.as<uint32_t>(), head.as<uint32_t>(), n, (const uint32_t *)use_in, rep.as<uint32_t>(),
-                       use_rep.as<uint32_t>(), uniq.as<uint32_t>());
-    // number of runs = head_excl[n-1] + head[n-1]
-    int collision = 0;
-    {
-      HostRead hr_(stream);
-      TM_TRY(hr_.get(&last_excl, head_excl.as<uint32_t>() + (n - 1), 4));
-      TM_TRY(hr_.get(&last_head, head.as<uint32_t>() + (n - 1), 4));
-      TM_TRY(hr_.get(&collision, hflag.p, 4));
-      TM_TRY(hr_.wait());
-    }
-    if (!(grouped && collision)) break;
-    grouped = false;  // a collision among the hashes (about once in 2^12 calls by the choice of bits above): the same again over the plain order
-    TM_TRY(plain_heads());
-  }
-  const int64_t nu = (int64_t)last_excl + last_head;
-  bool ranked = false;  // ord2 already holds the final order
+  // 2. order.  The partial order wants groups that are not in content order yet, plain use counts and a cut inside the distinct rows.  Else
+  //    the content order (the plain grouping left it; the by-index form ranks by row number alone: any order of the distinct rows will do),
+  //    then the ranking sort.
+  bool ordered = false;
   unsigned long long live = 0;
-  if (grouped && !by_index && !use_in && exact_first > 0 && exact_first < nu && !knobs().dedup_full_order) {
-    // Only the first exact_first positions have to be right.  The order is use count descending, content ascending: a histogram of the use
-    // counts finds the count u* of position exact_first, a histogram of the leading dword's top bits among the rows used u* times finds
-    // the bucket that position falls into; rows used more often, or u* times with a leading dword up to that bucket, are the only ones
-    // that can come before it.  They alone are sorted (the comparator reads the rows where the keys tie); the others follow as they come.
-    // 3.24 M distinct rows for a budget of 321 k on the bench clip: a merge sort of a tenth of them instead of all.
-    DevBuf h1, h2, h8, flag, fpos;
-    TM_TRY(h1.alloc(1024 * 4)); TM_TRY(h2.alloc(4096 * 4)); TM_TRY(h8.alloc(8 * 4096 * 4));
-    const int po_grid = std::min(gridn(nu), 1024);  // (every workgroup flushes its bins: fewer workgroups, fewer atomics on the popular ones)
-    TM_HIP(hipMemsetAsync(h8.p, 0, 8 * 1024 * 4, stream));
-    const uint32_t *cu = table_ok ? cuse.as<uint32_t>() : nullptr, *cl = table_ok ? clead.as<uint32_t>() : nullptr;
-    hipLaunchKernelGGL(k_po_use_hist, dim3(po_grid), dim3(256), 0, stream, uniq.as<uint32_t>(), nu, use_rep.as<uint32_t>(), cu, h8.as<uint32_t>());
-    hipLaunchKernelGGL(k_po_fold, dim3(4), dim3(256), 0, stream, h8.as<uint32_t>(), 1024, h1.as<uint32_t>());
-    std::vector<uint32_t> hh1(1024), hh2(4096);
-    {
-      HostRead hr_(stream);
-      TM_TRY(hr_.get(hh1.data(), h1.p, 1024 * 4));
-      TM_TRY(hr_.wait());
-    }
-    int64_t above = 0;
-    int ustar = -1;
-    for (int u = 1023; u >= 1; u--) {
-      if (above + hh1[(size_t)u] >= exact_first) { ustar = u; break; }
-      above += hh1[(size_t)u];
-    }
-    if (ustar >= 1 && ustar < 1023) {  // (a cut inside the clamped bin -- 1023 uses and more -- takes the full sort below)
-      TM_HIP(hipMemsetAsync(h8.p, 0, 8 * 4096 * 4, stream));
-      hipLaunchKernelGGL(k_po_lead_hist, dim3(po_grid), dim3(256), 0, stream, uniq.as<uint32_t>(), nu, use_rep.as<uint32_t>(), (uint32_t)ustar, less, cu, cl, h8.as<uint32_t>());
-      hipLaunchKernelGGL(k_po_fold, dim3(16), dim3(256), 0, stream, h8.as<uint32_t>(), 4096, h2.as<uint32_t>());
-      {
-        HostRead hr_(stream);
-        TM_TRY(hr_.get(hh2.data(), h2.p, 4096 * 4));
-        TM_TRY(hr_.wait());
-      }
-      int64_t ncand = above;
-      int bstar = 4095;
-      for (int b = 0; b < 4096; b++) {
-        ncand += hh2[(size_t)b];
-        if (ncand >= exact_first) { bstar = b; break; }
-      }
-      TM_TRY(flag.alloc((size_t)nu * 4)); TM_TRY(fpos.alloc((size_t)nu * 4));
-      hipLaunchKernelGGL(k_po_flags, dim3(gridn(nu)), dim3(256), 0, stream, uniq.as<uint32_t>(), nu, use_rep.as<uint32_t>(), (uint32_t)ustar, (uint32_t)bstar, less, cu, cl, flag.as<uint32_t>());
-      size_t tbs = 0;
-      TM_HIP(rocprim::exclusive_scan(nullptr, tbs, flag.as<uint32_t>(), fpos.as<uint32_t>(), 0u, (size_t)nu, rocprim::plus<uint32_t>(), stream));
-      TM_TRY(tmp.alloc(tbs));
-      TM_HIP(rocprim::exclusive_scan(tmp.p, tbs, flag.as<uint32_t>(), fpos.as<uint32_t>(), 0u, (size_t)nu, rocprim::plus<uint32_t>(), stream));
-      DevBuf pk;
-      TM_TRY(pk.alloc((size_t)ncand * sizeof(PrefixKey)));
-      hipLaunchKernelGGL(k_po_split, dim3(gridn(nu)), dim3(256), 0, stream, uniq.as<uint32_t>(), nu, flag.as<uint32_t>(), fpos.as<uint32_t>(), ncand, use_rep.as<uint32_t>(), less, cu, cl,
-                         pk.as<PrefixKey>(), ord2.as<uint32_t>());
-      TM_TRY(sort_prefix_keys(pk, ncand, less, ord2.as<uint32_t>(), tmp, stream));
-      TM_HIP(hipGetLastError());
-      ranked = true;
-      live = (unsigned long long)nu;
-    }
+  if (front != FRONT_PLAIN && !by_index && !use_in && exact_first > 0 && exact_first < d.nu && !knobs().dedup_full_order)
+    TM_TRY(order_candidates(d, front == FRONT_TABLE, exact_first, &ordered));
+  if (ordered) live = (unsigned long long)d.nu;
+  else {
+    if (front != FRONT_PLAIN && !by_index) TM_TRY(content_order(d));
+    TM_TRY(rank(d, &live));
   }
-  if (!ranked && grouped && !by_index) {  // the distinct rows, now in hash order -> content order (what the stable ranking sort below relies on; the
-                               // by-index form ranks by row number alone: any order of the distinct rows will do)
-    DevBuf pk;
-    TM_TRY(pk.alloc((size_t)nu * sizeof(PrefixKey)));
-    hipLaunchKernelGGL(k_prefix_keys, dim3(gridn(nu)), dim3(256), 0, stream, uniq.as<uint32_t>(), nu, less, pk.as<PrefixKey>());
-    TM_TRY(sort_prefix_keys(pk, nu, less, uniq.as<uint32_t>(), tmp, stream));
-    // pk / pk2 go back to the pool here; later users are ordered behind these kernels on the same stream (as with `tmp`)
-  }
-  if (!ranked) {
-  TM_HIP(hipMemsetAsync(cnt.p, 0, 16, stream));
-  hipLaunchKernelGGL(k_rank_keys, dim3(gridn(nu)), dim3(256), 0, stream, uniq.as<uint32_t>(), nu, use_rep.as<uint32_t>(), by_index,
-                     key.as<uint32_t>(), cnt.as<unsigned long long>());
-  size_t tb4 = 0;
-  TM_HIP(rocprim::radix_sort_pairs(nullptr, tb4, key.as<uint32_t>(), key2.as<uint32_t>(), uniq.as<uint32_t>(), ord2.as<uint32_t>(),
-                                   (size_t)nu, 0, 32, stream));
-  TM_TRY(tmp.alloc(tb4));
-  TM_HIP(rocprim::radix_sort_pairs(tmp.p, tb4, key.as<uint32_t>(), key2.as<uint32_t>(), uniq.as<uint32_t>(), ord2.as<uint32_t>(),
-                                   (size_t)nu, 0, 32, stream));
-  {
-    HostRead hr_(stream);
-    TM_TRY(hr_.get(&live, cnt.p, 8));
-    TM_TRY(hr_.wait());
-  }
-  }
-  TM_HIP(hipMemsetAsync(pos.p, 0xff, n * 4, stream));
-  hipLaunchKernelGGL(k_scatter_pos, dim3(gridn((int64_t)live)), dim3(256), 0, stream, ord2.as<uint32_t>(), (int64_t)live,
-                     use_rep.as<uint32_t>(), pos.as<int32_t>(), (uint32_t *)use_out);
-  hipLaunchKernelGGL(k_remap, dim3(gridn(n)), dim3(256), 0, stream, rep.as<uint32_t>(), pos.as<int32_t>(), n, (int32_t *)remap);
-  TM_HIP(hipMemcpyAsync(order, ord2.p, (size_t)live * 4, hipMemcpyDeviceToDevice, stream));
-  TM_HIP(hipGetLastError());
-  TM_HIP(hipStreamSynchronize(stream));  // the scratch DevBufs die with this frame
+  // 3. number
+  TM_TRY(finish(d, (int64_t)live, remap, order, use_out));
   if (host_n_unique) *host_n_unique = (int64_t)live;
-  return TM_OK;
-}
-
-namespace {
-__global__ void k_scatter_kept(const int32_t *__restrict__ keep, const uint32_t *__restrict__ pos, int64_t n, int32_t *__restrict__ out_idx) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    if (keep[i]) out_idx[pos[i]] = (int32_t)i;
-}
-}  // namespace
-
-// indices of the flagged items in ascending order (TransferTiles' gather, tilingencoder.pas:4048-4103, made deterministic);
-// pos[i] = rank of item i among the kept ones (valid where keep[i] != 0)
-int compact_kept(const void *keep, int64_t n, void *out_idx, void *pos, int64_t *host_count, hipStream_t stream) {
-  TM_CHECK(n >= 0 && n < (int64_t)1 << 31, TM_E_INVAL, "compact: count out of range");
-  *host_count = 0;
-  if (n == 0) return TM_OK;
-  size_t tb = 0;
-  DevBuf tmp;
-  TM_HIP(rocprim::exclusive_scan(nullptr, tb, (const uint32_t *)keep, (uint32_t *)pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-  TM_TRY(tmp.alloc(tb));
-  TM_HIP(rocprim::exclusive_scan(tmp.p, tb, (const uint32_t *)keep, (uint32_t *)pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-  hipLaunchKernelGGL(k_scatter_kept, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, stream, (const int32_t *)keep,
-                     (const uint32_t *)pos, n, (int32_t *)out_idx);
-  TM_HIP(hipGetLastError());
-  uint32_t last_pos = 0;
-  int32_t last_keep = 0;
-  {
-    HostRead hr_(stream);
-    TM_TRY(hr_.get(&last_pos, (const uint32_t *)pos + (n - 1), 4));
-    TM_TRY(hr_.get(&last_keep, (const int32_t *)keep + (n - 1), 4));
-    TM_TRY(hr_.wait());
-  }
-  *host_count = (int64_t)last_pos + (last_keep ? 1 : 0);
-  return TM_OK;
-}
-
-namespace {
-__global__ void k_iota_u32(uint32_t *__restrict__ v, int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = (uint32_t)i;
-}
-}  // namespace
-
-// member lists of a dedup: off[g] .. off[g+1] index `members`, which holds the rows of group g in ascending row order
-// (remap = row -> group, counts = rows per group, as run_dedup_ex(by_index = 1) returns them)
-int build_groups(const void *remap, int64_t n, const void *counts, int64_t ngroups, void *off, void *members, hipStream_t stream) {
-  TM_CHECK(n >= 0 && n < (int64_t)1 << 31 && ngroups >= 0, TM_E_INVAL, "groups: count out of range");
-  if (n == 0) return TM_OK;
-  DevBuf tmp, keys_out, iota;
-  size_t tb = 0;
-  TM_HIP(rocprim::exclusive_scan(nullptr, tb, (const uint32_t *)counts, (uint32_t *)off, 0u, (size_t)ngroups + 1, rocprim::plus<uint32_t>(), stream));
-  TM_TRY(tmp.alloc(tb));
-  // counts has ngroups entries; the scan's extra input element is read but its value never reaches an output we use
-  TM_HIP(rocprim::exclusive_scan(tmp.p, tb, (const uint32_t *)counts, (uint32_t *)off, 0u, (size_t)ngroups, rocprim::plus<uint32_t>(), stream));
-  const uint32_t total = (uint32_t)n;
-  TM_HIP(hipMemcpyAsync((uint32_t *)off + ngroups, &total, 4, hipMemcpyHostToDevice, stream));
-  TM_TRY(keys_out.alloc((size_t)n * 4)); TM_TRY(iota.alloc((size_t)n * 4));
-  hipLaunchKernelGGL(k_iota_u32, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, stream, iota.as<uint32_t>(), n);
-  size_t tb2 = 0;
-  TM_HIP(rocprim::radix_sort_pairs(nullptr, tb2, (const uint32_t *)remap, keys_out.as<uint32_t>(), iota.as<uint32_t>(), (uint32_t *)members, (size_t)n, 0,
-                                   32, stream));
-  TM_TRY(tmp.alloc(tb2));
-  TM_HIP(rocprim::radix_sort_pairs(tmp.p, tb2, (const uint32_t *)remap, keys_out.as<uint32_t>(), iota.as<uint32_t>(), (uint32_t *)members, (size_t)n, 0, 32,
-                                   stream));
-  TM_HIP(hipGetLastError());
-  TM_HIP(hipStreamSynchronize(stream));  // `total` is on the stack; temporaries are released on return
-  return TM_OK;
-}
-
-// ---- Reduce over several processes: which distinct tiles have to travel ---------------------------------------------------------------
-// Every process has deduplicated its own frame tiles; the merged order (use count descending, content ascending) keeps the first `target`
-// tiles.  Instead of all-gathering every process's distinct tiles (857 MB on the 720p bench clip for 321 k survivors) the processes
-// exchange a 16-byte KEY per distinct tile -- a 64-bit content hash, the first dword of the content (its leading bytes in comparison
-// order) and the local use count -- and every process runs this selection on the gathered keys (identical input, identical result):
-//   * keys whose hash no other key shares are SINGLES: no other process holds that content, the local use count is the true one;
-//   * keys that share their hash form a group: duplicates of one tile across processes (or a hash collision -- the groups are never
-//     trusted to be equal content, they only decide what travels); the group's summed use bounds every member's true use from above;
-//   * the singles ordered by (use descending, leading dword ascending): the key at position `target` is the cut-off -- every single
-//     beyond it (strictly) has `target` tiles before it in the true order whatever the groups turn out to be, and so has every member
-//     of a group whose SUM stays below the cut-off's use count.  Everything else is a candidate.
-// The candidates' tiles (a superset of the true first `target`, whole groups always) are then all-gathered and deduplicated exactly,
-// full compares and all, as the union was before.
-struct ReduceKey { unsigned long long hash; uint32_t prefix, use; };
-
-namespace {
-__global__ __launch_bounds__(256) void k_reduce_keys(const uint32_t *__restrict__ rows, const int32_t *__restrict__ idx, const uint32_t *__restrict__ use, int64_t n,
-                                                     int dwords, int degrade /* test hook: force hash collisions */, ReduceKey *__restrict__ out) {
-  const int sub = threadIdx.x & 15;
-  const int64_t stride = (int64_t)gridDim.x * 16;
-  for (int64_t r0 = blockIdx.x * (int64_t)16; r0 < n; r0 += stride) {  // k_row_hash's terms, through an index
-    const int64_t r = r0 + (threadIdx.x >> 4);
-    const int64_t row = r < n ? (int64_t)idx[r] : 0;
-    unsigned long long h = 0;
-    if (r < n)
-      for (int v = sub; v < dwords / 4; v += 16) {
-        const uint4 x = *reinterpret_cast<const uint4 *>(rows + row * dwords + v * 4);
-        unsigned long long a = ((unsigned long long)x.y << 32 | x.x) + 0x9E3779B97F4A7C15ull * (unsigned long long)(2 * v + 1);
-        unsigned long long b = ((unsigned long long)x.w << 32 | x.z) + 0xC2B2AE3D27D4EB4Full * (unsigned long long)(2 * v + 2);
-        a ^= a >> 32; a *= 0xD6E8FEB86659FD93ull; a ^= a >> 32;
-        b ^= b >> 29; b *= 0xBF58476D1CE4E5B9ull; b ^= b >> 32;
-        h += a * 0x94D049BB133111EBull + b;
-      }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) h += __shfl_xor(h, o);
-    if (r < n && sub == 0) out[r] = ReduceKey{degrade ? (h & 3) : h, rows[row * dwords], use[r]};
-  }
-}
-}  // namespace
-
-namespace {
-__global__ void k_rk_split(const ReduceKey *__restrict__ keys, int64_t n, unsigned long long *__restrict__ hash, uint32_t *__restrict__ idx) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) { hash[i] = keys[i].hash; idx[i] = (uint32_t)i; }
-}
-__global__ void k_rk_heads(const unsigned long long *__restrict__ hs, int64_t n, uint32_t *__restrict__ head) {
-  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) head[j] = (j == 0 || hs[j] != hs[j - 1]) ? 1u : 0u;
-}
-// gid = inclusive scan of the heads - 1; every key adds itself to its group
-__global__ void k_rk_groups(const uint32_t *__restrict__ sorted_idx, const uint32_t *__restrict__ head_incl, const ReduceKey *__restrict__ keys, int64_t n,
-                            uint32_t *__restrict__ gid_of, unsigned long long *__restrict__ gsum, uint32_t *__restrict__ gsize) {
-  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
-    const uint32_t g = head_incl[j] - 1u, i = sorted_idx[j];
-    gid_of[i] = g;
-    atomicAdd(&gsum[g], (unsigned long long)keys[i].use);
-    atomicAdd(&gsize[g], 1u);
-  }
-}
-__global__ void k_rk_single_keys(const ReduceKey *__restrict__ keys, const uint32_t *__restrict__ gid_of, const uint32_t *__restrict__ gsize, int64_t n,
-                                 unsigned long long *__restrict__ skey, unsigned long long *__restrict__ nsingles) {
-  unsigned long long local = 0;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const bool single = gsize[gid_of[i]] == 1;
-    skey[i] = single ? ((unsigned long long)(~keys[i].use) << 32) | keys[i].prefix : ~0ull;
-    local += single ? 1 : 0;
-  }
-  for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
-  if ((threadIdx.x & 63) == 0 && local) atomicAdd(nsingles, local);
-}
-__global__ void k_rk_select(const unsigned long long *__restrict__ skey, const uint32_t *__restrict__ gid_of, const unsigned long long *__restrict__ gsum, int64_t n,
-                            unsigned long long cutoff, unsigned long long min_use, uint32_t *__restrict__ in_s) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    in_s[i] = skey[i] != ~0ull ? (skey[i] <= cutoff ? 1u : 0u) : (gsum[gid_of[i]] >= min_use ? 1u : 0u);
-}
-}  // namespace
-
-int reduce_make_keys(const void *rows, const void *idx, const void *use, int64_t n, int row_bytes, void *keys_out, hipStream_t stream) {
-  if (n <= 0) return TM_OK;
-  hipLaunchKernelGGL(k_reduce_keys, dim3((unsigned)std::min<int64_t>((n + 15) / 16, 256 * 32)), dim3(256), 0, stream, (const uint32_t *)rows, (const int32_t *)idx,
-                     (const uint32_t *)use, n, row_bytes / 4, knobs().dedup_degrade_hash ? 1 : 0, (ReduceKey *)keys_out);
-  TM_HIP(hipGetLastError());
-  return TM_OK;
-}
-
-int reduce_select_candidates(const void *keys_v, int64_t n, int64_t target, void *in_s, hipStream_t stream) {
-  TM_CHECK(n > 0 && n < (int64_t)1 << 31, TM_E_INVAL, "reduce: key count out of range");
-  const ReduceKey *keys = (const ReduceKey *)keys_v;
-  DevBuf hash, hash2, idx, idx2, head, head_incl, gid_of, gsum, gsize, skey, skey2, tmp, cnt;
-  TM_TRY(hash.alloc(n * 8)); TM_TRY(hash2.alloc(n * 8)); TM_TRY(idx.alloc(n * 4)); TM_TRY(idx2.alloc(n * 4)); TM_TRY(head.alloc(n * 4)); TM_TRY(head_incl.alloc(n * 4));
-  TM_TRY(gid_of.alloc(n * 4)); TM_TRY(gsum.alloc(n * 8)); TM_TRY(gsize.alloc(n * 4)); TM_TRY(skey.alloc(n * 8)); TM_TRY(skey2.alloc(n * 8)); TM_TRY(cnt.alloc(8));
-  hipLaunchKernelGGL(k_rk_split, dim3(gridn(n)), dim3(256), 0, stream, keys, n, hash.as<unsigned long long>(), idx.as<uint32_t>());
-  size_t tb = 0;
-  TM_HIP(rocprim::radix_sort_pairs(nullptr, tb, hash.as<unsigned long long>(), hash2.as<unsigned long long>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), (size_t)n, 0, 64, stream));
-  TM_TRY(tmp.alloc(tb));
-  TM_HIP(rocprim::radix_sort_pairs(tmp.p, tb, hash.as<unsigned long long>(), hash2.as<unsigned long long>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), (size_t)n, 0, 64, stream));
-  hipLaunchKernelGGL(k_rk_heads, dim3(gridn(n)), dim3(256), 0, stream, hash2.as<unsigned long long>(), n, head.as<uint32_t>());
-  size_t tb2 = 0;
-  TM_HIP(rocprim::inclusive_scan(nullptr, tb2, head.as<uint32_t>(), head_incl.as<uint32_t>(), (size_t)n, rocprim::plus<uint32_t>(), stream));
-  TM_TRY(tmp.alloc(tb2));
-  TM_HIP(rocprim::inclusive_scan(tmp.p, tb2, head.as<uint32_t>(), head_incl.as<uint32_t>(), (size_t)n, rocprim::plus<uint32_t>(), stream));
-  TM_HIP(hipMemsetAsync(gsum.p, 0, n * 8, stream));
-  TM_HIP(hipMemsetAsync(gsize.p, 0, n * 4, stream));
-  TM_HIP(hipMemsetAsync(cnt.p, 0, 8, stream));
-  hipLaunchKernelGGL(k_rk_groups, dim3(gridn(n)), dim3(256), 0, stream, idx2.as<uint32_t>(), head_incl.as<uint32_t>(), keys, n, gid_of.as<uint32_t>(),
-                     gsum.as<unsigned long long>(), gsize.as<uint32_t>());
-  hipLaunchKernelGGL(k_rk_single_keys, dim3(gridn(n)), dim3(256), 0, stream, keys, gid_of.as<uint32_t>(), gsize.as<uint32_t>(), n, skey.as<unsigned long long>(),
-                     cnt.as<unsigned long long>());
-  unsigned long long nsingles = 0;
-  {
-    HostRead hr_(stream);
-    TM_TRY(hr_.get(&nsingles, cnt.p, 8));
-    TM_TRY(hr_.wait());
-  }
-  unsigned long long cutoff = ~0ull - 1ull, min_use = 0;  // fewer singles than the budget: everything travels
-  if (target > 0 && (unsigned long long)target <= nsingles) {
-    size_t tb3 = 0;
-    TM_HIP(rocprim::radix_sort_keys(nullptr, tb3, skey.as<unsigned long long>(), skey2.as<unsigned long long>(), (size_t)n, 0, 64, stream));
-    TM_TRY(tmp.alloc(tb3));
-    TM_HIP(rocprim::radix_sort_keys(tmp.p, tb3, skey.as<unsigned long long>(), skey2.as<unsigned long long>(), (size_t)n, 0, 64, stream));
-    {
-      HostRead hr_(stream);
-      TM_TRY(hr_.get(&cutoff, skey2.as<unsigned long long>() + (target - 1), 8));
-      TM_TRY(hr_.wait());
-    }
-    min_use = (unsigned long long)(uint32_t)(~(uint32_t)(cutoff >> 32));
-  }
-  hipLaunchKernelGGL(k_rk_select, dim3(gridn(n)), dim3(256), 0, stream, skey.as<unsigned long long>(), gid_of.as<uint32_t>(), gsum.as<unsigned long long>(), n, cutoff, min_use,
-                     (uint32_t *)in_s);
-  TM_HIP(hipGetLastError());
-  TM_HIP(hipStreamSynchronize(stream));  // the scratch DevBufs die with this frame
   return TM_OK;
 }
 

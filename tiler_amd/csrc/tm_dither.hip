@@ -499,10 +499,9 @@ int launch_dither(const void *tiles, const void *flags, const void *pal_idx, int
           hipLaunchKernelGGL(k_dd_mark, dim3((unsigned)std::min<int64_t>((n * 64 + 255) / 256, 256 * 32)), dim3(256), 0, stream, (const uint32_t *)tiles, (const int32_t *)pal_idx, n, npal,
                              cls.as<uint8_t>(), bits.as<uint32_t>());
         hipLaunchKernelGGL(k_dd_count, dim3((unsigned)std::min<int64_t>((nent + 256) / 256, 256 * 16)), dim3(256), 0, stream, bits.as<uint32_t>(), nent, cnt.as<uint32_t>());
-        size_t tb = 0;
-        TM_HIP(rocprim::exclusive_scan(nullptr, tb, cnt.as<uint32_t>(), off.as<uint32_t>(), 0u, (size_t)(nent + 1), rocprim::plus<uint32_t>(), stream));
-        TM_TRY(scan_tmp.alloc(tb));
-        TM_HIP(rocprim::exclusive_scan(scan_tmp.p, tb, cnt.as<uint32_t>(), off.as<uint32_t>(), 0u, (size_t)(nent + 1), rocprim::plus<uint32_t>(), stream));
+        TM_TRY(with_temp(scan_tmp, "dither: scan of the pair counts", [&](void *t, size_t &b) {
+          return rocprim::exclusive_scan(t, b, cnt.as<uint32_t>(), off.as<uint32_t>(), 0u, (size_t)(nent + 1), rocprim::plus<uint32_t>(), stream);
+        }));
         hipLaunchKernelGGL(k_dd_seg, dim3((npal + 1 + 63) / 64), dim3(64), 0, stream, off.as<uint32_t>(), npal, seg.as<uint32_t>());
         {
           HostRead hr_(stream);

@@ -251,10 +251,9 @@ int run_dl3quant(const void *dev_rgb, int64_t npixels, int quant_to, int lookup_
                      cell.as<uint32_t>(), lookup_size);
   const unsigned g = (unsigned)std::min<int64_t>((lookup_size + 255) / 256, 4096);
   hipLaunchKernelGGL(k_dl3_flags, dim3(g), dim3(256), 0, stream, cell.as<uint32_t>(), lookup_size, flag.as<uint32_t>());
-  size_t tb = 0;
-  TM_HIP(rocprim::exclusive_scan(nullptr, tb, flag.as<uint32_t>(), pos.as<uint32_t>(), 0u, (size_t)lookup_size, rocprim::plus<uint32_t>(), stream));
-  TM_TRY(tmp.alloc(tb));
-  TM_HIP(rocprim::exclusive_scan(tmp.p, tb, flag.as<uint32_t>(), pos.as<uint32_t>(), 0u, (size_t)lookup_size, rocprim::plus<uint32_t>(), stream));
+  TM_TRY(with_temp(tmp, "dl3: scan of the cell flags", [&](void *t, size_t &b) {
+    return rocprim::exclusive_scan(t, b, flag.as<uint32_t>(), pos.as<uint32_t>(), 0u, (size_t)lookup_size, rocprim::plus<uint32_t>(), stream);
+  }));
   uint32_t last[2] = {0, 0};
   TM_HIP(hipMemcpyAsync(&last[0], pos.as<uint32_t>() + lookup_size - 1, 4, hipMemcpyDeviceToHost, stream));
   TM_HIP(hipMemcpyAsync(&last[1], flag.as<uint32_t>() + lookup_size - 1, 4, hipMemcpyDeviceToHost, stream));

@@ -278,10 +278,9 @@ int launch_epu_rerank_ondemand(const void *queries, int64_t nq, const void *knn_
     TM_TRY(cnt.alloc((size_t)(n + 1) * 8)); TM_TRY(off.alloc((size_t)(n + 1) * 8));
     TM_HIP(hipMemsetAsync(cnt.p, 0, (size_t)(n + 1) * 8, stream));
     hipLaunchKernelGGL(k_epu_count, dim3((unsigned)n), dim3(64), 0, stream, n, idx, k, (const int32_t *)tile_pal, ntiles, cnt.as<unsigned long long>());
-    size_t tb = 0;
-    TM_HIP(rocprim::exclusive_scan(nullptr, tb, cnt.as<unsigned long long>(), off.as<unsigned long long>(), 0ull, (size_t)(n + 1), rocprim::plus<unsigned long long>(), stream));
-    TM_TRY(tmp.alloc(tb));
-    TM_HIP(rocprim::exclusive_scan(tmp.p, tb, cnt.as<unsigned long long>(), off.as<unsigned long long>(), 0ull, (size_t)(n + 1), rocprim::plus<unsigned long long>(), stream));
+    TM_TRY(with_temp(tmp, "epu: scan of the pair counts", [&](void *t, size_t &b) {
+      return rocprim::exclusive_scan(t, b, cnt.as<unsigned long long>(), off.as<unsigned long long>(), 0ull, (size_t)(n + 1), rocprim::plus<unsigned long long>(), stream);
+    }));
     unsigned long long m = 0;
     {
       HostRead hr_(stream);
@@ -294,14 +293,14 @@ int launch_epu_rerank_ondemand(const void *queries, int64_t nq, const void *knn_
       TM_TRY(head.alloc((size_t)m * 4)); TM_TRY(rank.alloc((size_t)m * 4)); TM_TRY(row_of.alloc((size_t)m * 4));
       hipLaunchKernelGGL(k_epu_emit, dim3((unsigned)n), dim3(64), 0, stream, n, idx, k, (const int32_t *)tile_pal, ntiles, off.as<unsigned long long>(),
                          keys.as<unsigned long long>(), pos.as<uint32_t>());
-      TM_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys.as<unsigned long long>(), keys2.as<unsigned long long>(), pos.as<uint32_t>(), pos2.as<uint32_t>(), (size_t)m, 0, 64, stream));
-      TM_TRY(tmp.alloc(tb));
-      TM_HIP(rocprim::radix_sort_pairs(tmp.p, tb, keys.as<unsigned long long>(), keys2.as<unsigned long long>(), pos.as<uint32_t>(), pos2.as<uint32_t>(), (size_t)m, 0, 64, stream));
+      TM_TRY(with_temp(tmp, "epu: radix sort of the pair keys", [&](void *t, size_t &b) {
+        return rocprim::radix_sort_pairs(t, b, keys.as<unsigned long long>(), keys2.as<unsigned long long>(), pos.as<uint32_t>(), pos2.as<uint32_t>(), (size_t)m, 0, 64, stream);
+      }));
       const int g = (int)std::min<unsigned long long>((m + 255) / 256, 8192);
       hipLaunchKernelGGL(k_epu_heads, dim3(g), dim3(256), 0, stream, keys2.as<unsigned long long>(), (int64_t)m, head.as<uint32_t>());
-      TM_HIP(rocprim::inclusive_scan(nullptr, tb, head.as<uint32_t>(), rank.as<uint32_t>(), (size_t)m, rocprim::plus<uint32_t>(), stream));
-      TM_TRY(tmp.alloc(tb));
-      TM_HIP(rocprim::inclusive_scan(tmp.p, tb, head.as<uint32_t>(), rank.as<uint32_t>(), (size_t)m, rocprim::plus<uint32_t>(), stream));
+      TM_TRY(with_temp(tmp, "epu: scan of the pair heads", [&](void *t, size_t &b) {
+        return rocprim::inclusive_scan(t, b, head.as<uint32_t>(), rank.as<uint32_t>(), (size_t)m, rocprim::plus<uint32_t>(), stream);
+      }));
       uint32_t nu = 0;
       {
         HostRead hr_(stream);

@@ -69,6 +69,7 @@ int run_dedup(const void *rows, int64_t n, int row_bytes, const void *use_in, vo
 int run_dedup_ex(const void *rows, int64_t n, int row_bytes, const void *use_in, void *remap, void *order, void *use_out,
                  int64_t *host_n_unique, int by_index, hipStream_t stream, int64_t exact_first = 0);
 
+// tm_lists.hip
 int build_groups(const void *remap, int64_t n, const void *counts, int64_t ngroups, void *off, void *members, hipStream_t stream);
 int compact_kept(const void *keep, int64_t n, void *out_idx, void *pos, int64_t *host_count, hipStream_t stream);
 
@@ -214,7 +215,7 @@ int run_quantize_palettes_part(const void *tiles, const void *pal_idx, int64_t n
                                int pal_rank, int pal_world, hipStream_t stream, DevBuf *keep_keys = nullptr, int64_t *keep_n = nullptr);
 int run_palettize(const void *feat, const void *use, int64_t n, int npal, int max_iter, void *out_pal_idx, hipStream_t stream);
 bool palettize_resident(int64_t n, int npal);  // the clustering above would take the resident launch (then several processes each run it whole)
-// tm_dedup.hip, Reduce over several processes (see there): a 16-byte key per distinct tile (rows[idx[r]], use[r]) and, on the gathered keys of
+// tm_reduce_keys.hip, Reduce over several processes (see there): a 16-byte key per distinct tile (rows[idx[r]], use[r]) and, on the gathered keys of
 // all processes, the tiles that can be among the first `target` of the merged order (in_s: uint32 flags)
 int reduce_make_keys(const void *rows, const void *idx, const void *use, int64_t n, int row_bytes, void *keys_out /* n x 16 bytes */, hipStream_t stream);
 int reduce_select_candidates(const void *keys, int64_t n, int64_t target, void *in_s, hipStream_t stream);

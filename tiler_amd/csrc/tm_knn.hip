@@ -671,12 +671,9 @@ static int sort_by_curve(tm_knn_index_impl *ix, const DevBuf &ccol, int64_t n, c
   const int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
   hipLaunchKernelGGL(k_curve_keys, dim3(grid), dim3(256), 0, stream, ccol.as<uint2>(), n, ix->curve, radial.as<float>(),
                      ix->skey.as<uint32_t>(), ix->sidx.as<uint32_t>());
-  size_t tb = 0;
-  TM_HIP(rocprim::radix_sort_pairs(nullptr, tb, ix->skey.as<uint32_t>(), keys_sorted.as<uint32_t>(), ix->sidx.as<uint32_t>(),
-                                   perm.as<uint32_t>(), (size_t)n, 0, 32, stream));
-  TM_TRY(ix->sort_tmp.alloc(tb));
-  TM_HIP(rocprim::radix_sort_pairs(ix->sort_tmp.p, tb, ix->skey.as<uint32_t>(), keys_sorted.as<uint32_t>(), ix->sidx.as<uint32_t>(),
-                                   perm.as<uint32_t>(), (size_t)n, 0, 32, stream));
+  TM_TRY(with_temp(ix->sort_tmp, "knn: radix sort of the curve keys", [&](void *t, size_t &b) {
+    return rocprim::radix_sort_pairs(t, b, ix->skey.as<uint32_t>(), keys_sorted.as<uint32_t>(), ix->sidx.as<uint32_t>(), perm.as<uint32_t>(), (size_t)n, 0, 32, stream);
+  }));
   TM_HIP(hipGetLastError());
   return TM_OK;
 }

@@ -550,18 +550,14 @@ int run_quantize_palettes_part(const void *tiles, const void *pal_idx, int64_t n
     TM_TRY(nruns.alloc(8));
     hipLaunchKernelGGL(k_pixel_keys, dim3((int)std::min<int64_t>((npx + 255) / 256, 4096)), dim3(256), 0, stream, (const uint32_t *)tiles,
                        (const int32_t *)pal_idx, n, keys.as<u64>());
-    size_t tb = 0;
     int key_bits = 25;  // 24 bits of colour + the palette number's: every 8 bits less is a pass over all pixels less
     while (key_bits < 41 && (1ll << (key_bits - 24)) < npal) key_bits++;
-    TM_HIP(rocprim::radix_sort_keys(nullptr, tb, keys.as<u64>(), keys2.as<u64>(), (size_t)npx, 0, key_bits, stream));
-    TM_TRY(tmp.alloc(tb));
-    TM_HIP(rocprim::radix_sort_keys(tmp.p, tb, keys.as<u64>(), keys2.as<u64>(), (size_t)npx, 0, key_bits, stream));
-    size_t tb2 = 0;
-    TM_HIP(rocprim::run_length_encode(nullptr, tb2, keys2.as<u64>(), (unsigned int)npx, ukeys.as<u64>(), ucnt.as<uint32_t>(),
-                                      nruns.as<unsigned int>(), stream));
-    TM_TRY(tmp.alloc(tb2));
-    TM_HIP(rocprim::run_length_encode(tmp.p, tb2, keys2.as<u64>(), (unsigned int)npx, ukeys.as<u64>(), ucnt.as<uint32_t>(),
-                                      nruns.as<unsigned int>(), stream));
+    TM_TRY(with_temp(tmp, "palettes: radix sort of the pixel keys", [&](void *t, size_t &b) {
+      return rocprim::radix_sort_keys(t, b, keys.as<u64>(), keys2.as<u64>(), (size_t)npx, 0, key_bits, stream);
+    }));
+    TM_TRY(with_temp(tmp, "palettes: run lengths of the pixel keys", [&](void *t, size_t &b) {
+      return rocprim::run_length_encode(t, b, keys2.as<u64>(), (unsigned int)npx, ukeys.as<u64>(), ucnt.as<uint32_t>(), nruns.as<unsigned int>(), stream);
+    }));
     unsigned int nu = 0;
     {
       HostRead hr_(stream);

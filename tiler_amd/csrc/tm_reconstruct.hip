@@ -77,9 +77,9 @@ static int database_rows(tm_encoder *e, DevBuf &rows) {
   return TM_OK;
 }
 
-static int build_database(tm_encoder *e, int use_spare, ReconDb *db) {  // use_spare: one more item behind the counts (build_groups' scan)
+static int build_database(tm_encoder *e, ReconDb *db) {
   TM_TRY(database_rows(e, db->rows));
-  TM_TRY(db->remap.alloc((size_t)e->t * 4)); TM_TRY(db->order.alloc((size_t)e->t * 4)); TM_TRY(db->use.alloc((size_t)(e->t + use_spare) * 4));
+  TM_TRY(db->remap.alloc((size_t)e->t * 4)); TM_TRY(db->order.alloc((size_t)e->t * 4)); TM_TRY(db->use.alloc((size_t)e->t * 4));
   TM_TRY(run_dedup_ex(db->rows.p, e->t, 384, nullptr, db->remap.p, db->order.p, db->use.p, &db->n, 1, e->stream));
   TM_TRY(db->distinct.alloc((size_t)db->n * 384));
   TM_TRY(gather_rows(e, db->rows.p, db->order.p, db->n, 384, db->distinct.p));
@@ -247,7 +247,7 @@ int step_reconstruct(tm_encoder *e) {
   e->knn_split_pairs[0] = e->knn_split_pairs[1] = e->knn_split_pairs[2] = 0;
   {
     ReconDb db;
-    TM_TRY(build_database(e, epu ? 1 : 0, &db));
+    TM_TRY(build_database(e, &db));
     progress(e, TM_STEP_RECONSTRUCT, 1, 2);
     if (shard) TM_TRY(clear_items(e, TMA_TILE | TMA_ERR | TMA_PAL));  // frames of other shards
     TM_TRY(epu ? search_extended(e, db, sf, sn) : search_nearest(e, db, sf, sn));

@@ -128,7 +128,7 @@ static int64_t rank_offset(const std::vector<int64_t> &counts, int rank, int64_t
 }
 
 // What travels in sharded Reduce: only the tiles that can be among the first GlobalTilingTileCount of the merged order, chosen on 16-byte
-// keys every process exchanges first (tm_dedup.hip, "Reduce over several processes"; gathering every distinct tile of every process, as
+// keys every process exchanges first (tm_reduce_keys.hip; gathering every distinct tile of every process, as
 // the first two rounds did, moved 857 MB on the bench clip).
 struct Selection {
   DevBuf in_s, spos;  // a flag per key of every process (this process's start at key_off); a local distinct tile's number among the selected
