@@ -251,6 +251,43 @@ typedef struct {
  *   tm_probe_yuv_clip_host is the host-only seam: the same checks and the size tm_set_frames_yuv would describe (pointers may be NULL). */
 TM_API int tm_set_frames_yuv(tm_encoder *, const tm_yuv_clip *clip);
 TM_API int tm_probe_yuv_clip_host(const tm_yuv_clip *clip, double scaling, int *dst_width, int *dst_height);
+/* ---- Frames delivered as YUV (tm_yuv_out.hip): the mirror image of the above ----------------------------------------
+ * A destination has tm_yuv_clip's field layout (same offsets, 120 bytes); its plane pointers are WRITTEN.  `frames` is its capacity, fps is
+ * not read, v == NULL means u takes interleaved (U, V) pairs, memory is TM_MEM_HOST or TM_MEM_DEVICE (the device of the player / encoder).
+ * width and height must equal the frames being delivered (tm_w*8 x tm_h*8); odd sizes give chroma planes of (n + 1) / 2 samples.
+ *   The rule.  For BT601_LIMITED / _FULL and BT709_LIMITED / _FULL the forward matrix follows from Kr, Kb (0.299 / 0.114, 0.2126 / 0.0722):
+ * Y = (Kr, Kg, Kb) ys, U = (-Kr, -Kg, 1 - Kb) / (2 (1 - Kb)) cs, V = (1 - Kr, -Kg, -Kb) / (2 (1 - Kr)) cs; limited: ys = 219/255, cs = 224/255.
+ * The constants are round(k 65536), the G coefficient of a row absorbing the rounding so that the Y row sums to round(ys 65536) and the U and
+ * V rows to 0 (grey stays grey); tm_yuv_out_matrix_host gives them (rows Y, U, V; columns R, G, B).  A sample at depth d is
+ *   ((c . S + half) >> s) + off, clamped to 0 .. 2^d - 1;   s = 16 - (d - 8) + lw, half = 1 << (s - 1)
+ * with S the weighted sum of R, G, B over the sample's footprint (weights totalling 2^lw) and off = 16 << (d - 8) for limited luma, 0 for
+ * full luma, 128 << (d - 8) for chroma.  Footprints: the pixel itself for luma and 4:4:4 chroma; the 2 x 2 block for 420JPEG; columns 2k - 1,
+ * 2k, 2k + 1 with weights 1, 2, 1 for 422; those columns on rows 2j and 2j + 1 for 420MPEG2.  Coordinates outside the picture repeat the edge
+ * pixel.  MONO writes luma only.  U16_LOW stores the d-bit value in the low bits, U16_HIGH shifted left by 16 - d (d = 9 .. 16).
+ *   Only the limited rules take deep samples (scale 2^(d-8): 64 .. 940 at 10 bits).  A full-range rule with deep samples is
+ * TM_E_UNSUPPORTED: its standard scale, (2^d - 1) / 255, is not a shift, and nothing here consumes it.  TM_YUV_TILER is tm_generate_y4m's
+ * arithmetic bit for bit (RGBToYUV, utils.pas:478-490: double products narrowed once to Single, + 128 in Single, round half to even, clamp),
+ * defined for 8-bit 4:4:4 and MONO only: anything else with it is TM_E_INVAL.  TM_YUV_AUTO: BT601_FULL when full_range is set, else
+ * BT601_LIMITED.
+ *   TM_E_INVAL, before any device call and with nothing written: a null struct or y; chroma pointers missing for a layout that has them (or v
+ * without u); a size that differs from the frames'; frames < 1 or fewer than the call delivers; unknown chroma, samples, memory or mode
+ * values; depth != 8 with U8 or outside 9 .. 16 with words; a row stride shorter than the row (pairs: twice as long); an odd pointer or
+ * stride with words; a negative frame stride.  U8 planes may sit at any byte address; 16-byte aligned rows get the widest stores.
+ * tm_probe_yuv_out_host makes these checks and nothing else. */
+typedef struct {
+  void *y, *u, *v;                /* v == NULL: u takes interleaved (U, V) pairs, U first (NV12, P010, P016) */
+  int64_t y_row, y_frame, u_row, u_frame, v_row, v_frame;   /* bytes */
+  int width, height, frames; double fps;
+  int chroma;                     /* TM_CHROMA_*; MONO: u, v unused */
+  int samples, depth;             /* U8: depth 8.  U16_*: little-endian words, depth 9..16 */
+  int full_range;                 /* feeds TM_YUV_AUTO */
+  int memory;                     /* TM_MEM_* */
+} tm_yuv_out;
+TM_API int tm_probe_yuv_out_host(const tm_yuv_out *dst, int width, int height, int mode);
+/* Host seams of the pixel rule (no device): the integer matrix of a mode (TM_E_INVAL for AUTO and TILER), and n pixels 0x00RRGGBB through the
+ * one-pixel footprint at `depth` (8 .. 16; the d-bit values, unshifted; AUTO = BT601_LIMITED; any of y, u, v may be NULL). */
+TM_API int tm_yuv_out_matrix_host(int mode, int32_t m[9]);
+TM_API int tm_rgb32_to_yuv_host(const uint32_t *rgb, int64_t n, int mode, int depth, uint16_t *y, uint16_t *u, uint16_t *v);
 /* Host-only seams of the above (no device needed).  tm_probe_input_host: what tm_open_input would find (kind: TM_INPUT_*; width, height:
  * the file's; any pointer may be NULL).  tm_read_png_host: a non-interlaced 8-bit PNG (grey, grey + alpha, RGB, RGBA, palette; alpha
  * dropped; CRCs and Adler-32 checked) as 0x00RRGGBB; out_rgb32 NULL gives the size only.  tm_inflate_host: one zlib stream (stored, fixed
@@ -296,7 +333,7 @@ TM_API int tm_lz_decompress_host(const uint8_t *src, size_t n, uint8_t *dst, siz
  * (predicted items copied from the previous output frame, tiles through the item's palette and mirrors; :3573-3640, :5505-5507), or the
  * source frames (input != 0).  Y4M: 'YUV4MPEG2 W.. H.. F..:1000000 Ip C444', full-resolution Y, U + 128, V + 128 planes from RGBToYUV
  * (utils.pas:478-490), rounded and clamped.  PNGs: <OutputFileName without extension>_NNNN.png (24-bit RGB) + <...>.txt with the
- * palettes, one 'FFBBGGRR' line per colour.  Host code (export tooling). */
+ * palettes, one 'FFBBGGRR' line per colour.  Host code (export tooling); the Y4M planes are made on the device (TM_YUV_TILER) and cross as 3 bytes a pixel. */
 TM_API int tm_generate_y4m(tm_encoder *, const char *path, int input);
 TM_API int tm_generate_pngs(tm_encoder *, int input);
 /* The same pictures rendered on the device (Render :3455-3640, Output tab with the constructor's defaults; or the Input tab: input != 0):
@@ -307,6 +344,12 @@ TM_API int tm_generate_pngs(tm_encoder *, int input);
  * reconstructed or reloaded, when the source frames are not in memory (input: after ReloadGTM without Load, or frames a sharded Load
  * did not keep), or when the range is out of bounds. */
 TM_API int tm_render_frames(tm_encoder *, int first_frame, int frame_count, int input, void *out, int out_on_device);
+/* The same frames as YUV (tm_yuv_out above): frame first_frame + i goes to frame i of dst, converted on the device behind the render; a
+ * device destination is written in place, a host destination receives 1 to 6 bytes a pixel instead of 4.  Refuses what tm_render_frames
+ * refuses, and what tm_probe_yuv_out_host refuses (frame_count > dst->frames included), before any device call.  In a device group it
+ * reads shard 0, like the exports -- one refusal more than tm_render_frames: with input != 0 after a sharded Load, a range outside the
+ * frames shard 0 loaded is TM_E_INVAL (tm_render_frames gathers such a range from every shard's piece).  Blocking. */
+TM_API int tm_render_frames_yuv(tm_encoder *, int first_frame, int frame_count, int input, const tm_yuv_out *dst, int mode);
 /* Pixel-domain quality of the decoded output against the source, frames [first_frame, first_frame+frame_count), over tm_w*8 x tm_h*8:
  * sse [count][3] exact squared errors of R, G, B; psnr [count] = 10 log10(3 W H 255^2 / (SSE_R+SSE_G+SSE_B)), +inf for SSE 0;
  * ssim_y [count] = mean SSIM of the 8x8 windows on a 4-pixel grid of GenerateY4M's Y plane (c1 = (64*0.01*255)^2, c2 = (64*0.03*255)^2 on
@@ -356,6 +399,12 @@ TM_API int tm_player_settings_text(tm_player *, char *buf, size_t cap, size_t *n
  *   A later key frame that cannot be read (TM_E_IO) ends the call at the frame before it: *got frames have been delivered and are right,
  * the position stands at the damaged key frame, and a seek elsewhere goes on playing. */
 TM_API int tm_player_read(tm_player *, int count, void *out, int out_on_device, int *got);
+/* tm_player_read with a YUV destination (tm_yuv_out, see tm_probe_yuv_out_host): position, *got, errors and seeks behave as above; frame i
+ * of the call goes to frame i of dst.  The player plays into its own RGB ring (a predicted item needs the previous RGB frame) and converts
+ * each frame behind its k_play_frame on the same stream: device planes are written in place, host planes through a packed device ring, one
+ * copy per plane and chunk (a 2-D copy where rows have padding).  A refused descriptor (TM_E_INVAL / TM_E_UNSUPPORTED; also when the call
+ * would deliver more than dst->frames frames: min(count, frames left)) leaves position and destination untouched. */
+TM_API int tm_player_read_yuv(tm_player *, int count, const tm_yuv_out *dst, int mode, int *got);
 /* the next read starts at `frame` (0 .. frames; frames = the end): restarts at the key frame at or before it and plays forward without delivering */
 TM_API int tm_player_seek(tm_player *, int frame);
 TM_API int tm_player_tell(tm_player *);  /* the frame the next read starts at */
@@ -478,6 +527,11 @@ TM_API int tm_stage_yuv_to_rgb32(const void *y, const void *u, const void *v, co
 TM_API int tm_stage_yuv_to_rgb32_fmt(const void *y, const void *u, const void *v /* NULL: pairs in u */, const int64_t *host_strides /* [6], bytes */,
                                      int nframes, int src_w, int src_h, int chroma, int samples, int depth,
                                      int dst_w, int dst_h, int yuv_mode, void *out_rgb32, void *stream);
+/* The way back (k_rgb32_to_yuv, tm_yuv_out.hip): frames [nframes][h][stride_px] 0x00RRGGBB -> planes as tm_yuv_out describes them (rule,
+ * footprints and refusals: see tm_probe_yuv_out_host; AUTO = BT601_LIMITED).  v == NULL: pairs in u.  Any w, h >= 1; U8 planes at any byte
+ * address.  Bytes outside the rows are not touched.  Queued on `stream`, not blocking. */
+TM_API int tm_stage_rgb32_to_yuv_fmt(const void *rgb32, int64_t stride_px, int nframes, int w, int h, void *y, void *u, void *v /* NULL: pairs in u */,
+                                     const int64_t *host_strides /* [6], bytes */, int chroma, int samples, int depth, int mode, void *stream);
 
 /* RGBToLAB (utils.pas:374-410) of n colours 0x00RRGGBB -> float [n][3] (L, a, b): the colour conversion the load and feature kernels
  * share, as an operator of its own (the whole 24-bit domain is checked against the oracle through it). */

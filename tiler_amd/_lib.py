@@ -23,7 +23,7 @@ _lib = None
 c_void_p, c_int, c_int64, c_double, c_char_p = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_char_p
 
 
-class YuvClip(ctypes.Structure):  # tm_yuv_clip: a YUV clip lent in memory (tm_set_frames_yuv)
+class YuvClip(ctypes.Structure):  # tm_yuv_clip: a YUV clip lent in memory (tm_set_frames_yuv); tm_yuv_out has the same fields (yuv_out.py)
     _fields_ = [("y", c_void_p), ("u", c_void_p), ("v", c_void_p),
                 ("y_row", c_int64), ("y_frame", c_int64), ("u_row", c_int64), ("u_frame", c_int64), ("v_row", c_int64), ("v_frame", c_int64),
                 ("width", c_int), ("height", c_int), ("frames", c_int), ("fps", c_double),
@@ -70,6 +70,11 @@ SIGNATURES = {
     "tm_stage_yuv_to_rgb32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "tm_stage_yuv_to_rgb32_fmt": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                           c_void_p]),
+    "tm_stage_rgb32_to_yuv_fmt": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_int, c_int, c_int,
+                                          c_void_p]),
+    "tm_probe_yuv_out_host": (c_int, [ctypes.POINTER(YuvClip), c_int, c_int, c_int]),
+    "tm_yuv_out_matrix_host": (c_int, [c_int, ctypes.POINTER(ctypes.c_int32)]),
+    "tm_rgb32_to_yuv_host": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tm_probe_yuv_clip_host": (c_int, [ctypes.POINTER(YuvClip), c_double, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "tm_probe_input_host": (c_int, [c_char_p, c_int, c_int, c_double] + [ctypes.POINTER(c_int)] * 5 + [ctypes.POINTER(c_double)] + [ctypes.POINTER(c_int)] * 2),
     "tm_read_png_host": (c_int, [c_char_p, c_void_p, c_int64, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),

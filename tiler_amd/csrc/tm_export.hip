@@ -63,11 +63,16 @@ namespace {
 struct ExportFrames {
   tm_encoder *e;
   bool input;
+  bool y4m = false;  // the frames come to the host as GenerateY4M's planes (Y, U, V of a frame in a row: 3 bytes a pixel), not as RGB32
   RenderMap m{};
   RenderInput in{};
   int sw = 0, sh = 0, chunk = 0, first = 0, count = 0;
   DevBuf dev;
   std::vector<uint32_t> host;  // frames [first, first + count), 0x00RRGGBB
+  DevBuf dev_yuv;
+  std::vector<uint8_t> host_yuv;
+  tm_yuv_out planes{};
+  YuvOutPlan plan;
   int init() {
     TM_HIP(hipSetDevice(e->device));
     if (input) TM_TRY(render_input_src(e, 0, e->nframes, &in));
@@ -76,18 +81,36 @@ struct ExportFrames {
     const size_t fbytes = (size_t)sw * sh * 4;
     chunk = (int)std::max<size_t>(1, std::min<size_t>(32, ((size_t)256 << 20) / fbytes));  // 32 frames or 256 MB, whichever is less
     TM_TRY(dev.alloc(fbytes * chunk));
-    host.resize((size_t)sw * sh * chunk);
-    return TM_OK;
+    if (!y4m) { host.resize((size_t)sw * sh * chunk); return TM_OK; }
+    const int64_t plane = (int64_t)sw * sh;
+    TM_TRY(dev_yuv.alloc((size_t)plane * 3 * chunk));
+    host_yuv.resize((size_t)plane * 3 * chunk);
+    planes.y = dev_yuv.p; planes.u = dev_yuv.as<uint8_t>() + plane; planes.v = dev_yuv.as<uint8_t>() + 2 * plane;
+    planes.y_row = planes.u_row = planes.v_row = sw;
+    planes.y_frame = planes.u_frame = planes.v_frame = 3 * plane;
+    planes.width = sw; planes.height = sh; planes.frames = chunk; planes.fps = 1.0;
+    planes.chroma = TM_CHROMA_444; planes.samples = TM_SAMPLES_U8; planes.depth = 8; planes.memory = TM_MEM_DEVICE;
+    return check_yuv_out(&planes, sw, sh, TM_YUV_TILER, &plan);
   }
   int frame(int f, const uint32_t **px) {  // frames are asked for in order
     if (f >= first + count) {
       first = f;
       count = std::min(chunk, e->nframes - f);
       TM_TRY(input ? launch_render_input(in, first, count, dev.p, e->stream) : launch_render_output(m, first, count, dev.p, e->stream));
-      TM_HIP(hipMemcpyAsync(host.data(), dev.p, (size_t)count * sw * sh * 4, hipMemcpyDeviceToHost, e->stream));
+      if (y4m) {
+        TM_TRY(launch_rgb32_to_yuv(plan, dev.p, sw, count, yuv_dst_of(planes, 0), e->stream));
+        TM_HIP(hipMemcpyAsync(host_yuv.data(), dev_yuv.p, (size_t)count * sw * sh * 3, hipMemcpyDeviceToHost, e->stream));
+      } else {
+        TM_HIP(hipMemcpyAsync(host.data(), dev.p, (size_t)count * sw * sh * 4, hipMemcpyDeviceToHost, e->stream));
+      }
       TM_HIP(hipStreamSynchronize(e->stream));
     }
-    *px = host.data() + (size_t)(f - first) * sw * sh;
+    if (px) *px = host.data() + (size_t)(f - first) * sw * sh;
+    return TM_OK;
+  }
+  int frame_y4m(int f, const uint8_t **yuv) {
+    TM_TRY(frame(f, nullptr));
+    *yuv = host_yuv.data() + (size_t)(f - first) * sw * sh * 3;
     return TM_OK;
   }
 };
@@ -137,31 +160,20 @@ std::string strip_ext(const std::string &p) {  // ChangeFileExt(name, '')
 
 static int generate_y4m(tm_encoder *e, const char *path, bool input) {  // GenerateY4M, tilingencoder.pas:2126-2199
   TM_CHECK(path && *path, TM_E_INVAL, "GenerateY4M: no file name");
-  ExportFrames r{e, input};
+  ExportFrames r{e, input, true};
   TM_TRY(r.init());
   std::ofstream f(path, std::ios::binary);
   TM_CHECK(f.good(), TM_E_IO, "cannot write %s", path);
   char hdr[128];
   snprintf(hdr, sizeof(hdr), "YUV4MPEG2 W%d H%d F%lld:1000000 Ip C444\n", r.sw, r.sh, (long long)std::nearbyint(e->fps * 1000000.0));  // 2146
   f << hdr;
+  // RGBToYUV (utils.pas:478-490), rounded and clamped, runs on the device (TM_YUV_TILER, tm_yuv_out.hip): the planes arrive as the file holds them
   const size_t plane = (size_t)r.sw * r.sh;
-  std::vector<uint8_t> yuv(plane * 3);
-  auto rnd = [](float v, float add) { const long long q = (long long)std::nearbyint((double)(v + add)); return (uint8_t)std::min<long long>(255, std::max<long long>(0, q)); };
   for (int fr = 0; fr < e->nframes; fr++) {
-    const uint32_t *px = nullptr;
-    TM_TRY(r.frame(fr, &px));
+    const uint8_t *yuv = nullptr;
+    TM_TRY(r.frame_y4m(fr, &yuv));
     f << "FRAME \n";  // (with the space, 2161)
-    for (size_t i = 0; i < plane; i++) {
-      const uint32_t c = px[i];
-      const int rr = (c >> 16) & 0xff, gg = (c >> 8) & 0xff, bb = c & 0xff;
-      // RGBToYUV, utils.pas:478-490: the decimal constants are doubles, every right-hand side narrows to Single once
-      const float yy = (float)(rr * (299.0 / 1000) + gg * (587.0 / 1000) + bb * (114.0 / 1000));
-      const float uu = (float)(((double)bb - (double)yy) * 0.492), vv = (float)(((double)rr - (double)yy) * 0.877);
-      yuv[i] = rnd(yy, 0.0f);
-      yuv[plane + i] = rnd(uu, 128.0f);      // uf - Low(ShortInt)
-      yuv[2 * plane + i] = rnd(vv, 128.0f);
-    }
-    f.write((const char *)yuv.data(), (std::streamsize)yuv.size());
+    f.write((const char *)yuv, (std::streamsize)(plane * 3));
     if ((fr & 15) == 15) progress(e, TM_STEP_SAVE, fr, e->nframes);
   }
   TM_CHECK(f.good(), TM_E_IO, "write to %s failed", path);
@@ -308,6 +320,37 @@ int tm_render_frames(tm_encoder *e, int first_frame, int frame_count, int input,
   }
   TM_TRY(input ? launch_render_input(in, first_frame, frame_count, dst, e->stream) : launch_render_output(m, first_frame, frame_count, dst, e->stream));
   if (!out_on_device) TM_HIP(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, e->stream));  // page-locked destination: one DMA
+  TM_HIP(hipStreamSynchronize(e->stream));
+  return TM_OK;
+}
+
+int tm_render_frames_yuv(tm_encoder *e, int first_frame, int frame_count, int input, const tm_yuv_out *dst, int mode) {
+  TM_CHECK(e, TM_E_INVAL, "null argument");
+  TM_TRY(render_range_ok(e, first_frame, frame_count));
+  YuvOutPlan plan;
+  TM_TRY(check_yuv_out(dst, e->tm_w * 8, e->tm_h * 8, mode, &plan));
+  TM_CHECK(frame_count <= dst->frames, TM_E_INVAL, "yuv out: %d frames asked for, room for %d", frame_count, dst->frames);
+  TM_HIP(hipSetDevice(e->device));
+  RenderMap m{};
+  RenderInput in{};
+  if (input) TM_TRY(render_input_src(e, first_frame, frame_count, &in));
+  else TM_TRY(render_output_map(e, &m));
+  const bool to_device = dst->memory == TM_MEM_DEVICE;
+  if (to_device) TM_TRY(yuv_out_is_device(*dst, e->device));
+  if (frame_count == 0) return TM_OK;
+  // a chunk of frames is drawn as RGB32 and converted behind the render; host planes go through a packed chunk, one copy per plane
+  const int sw = e->tm_w * 8, sh = e->tm_h * 8;
+  const size_t fbytes = (size_t)sw * sh * 4;
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(frame_count, 32), ((size_t)256 << 20) / fbytes));
+  DevBuf rgb, packed;
+  TM_TRY(rgb.alloc(fbytes * chunk));
+  if (!to_device) TM_TRY(packed.alloc((size_t)plan.frame_bytes() * chunk));
+  for (int f0 = 0; f0 < frame_count; f0 += chunk) {
+    const int nf = std::min(chunk, frame_count - f0);
+    TM_TRY(input ? launch_render_input(in, first_frame + f0, nf, rgb.p, e->stream) : launch_render_output(m, first_frame + f0, nf, rgb.p, e->stream));
+    TM_TRY(launch_rgb32_to_yuv(plan, rgb.p, sw, nf, to_device ? yuv_dst_of(*dst, f0) : yuv_dst_packed(plan, packed.as<uint8_t>(), chunk, 0), e->stream));
+    if (!to_device) TM_TRY(yuv_copy_out(plan, packed.as<uint8_t>(), chunk, *dst, f0, nf, e->stream));
+  }
   TM_HIP(hipStreamSynchronize(e->stream));
   return TM_OK;
 }

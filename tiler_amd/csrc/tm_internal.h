@@ -116,6 +116,26 @@ int launch_quality_render(const RenderInput &in, const RenderMap &m, int first, 
 // the same for two stacks of 0x00RRGGBB frames [n][h][stride_px] (w, h: multiples of 4, at least 8)
 int launch_quality_frames(const void *a, const void *b, int n, int w, int h, int64_t stride_px, void *sse, void *ssim, hipStream_t stream);
 
+// tm_yuv_out.hip: decoded frames delivered as YUV.  check_yuv_out makes every check of a destination without a device
+// call and says what its planes look like; the resolved colour rule travels with the plan.
+struct YuvOutPlan {
+  int w = 0, h = 0, cw = 0, ch = 0, chroma = 0, samples = 0, depth = 8, mode = 0, bytes = 1, nplanes = 1;  // nplanes: 1 mono, 2 Y + pairs, 3 planar
+  bool pairs = false;
+  int64_t row_bytes[3] = {0, 0, 0};  // of Y, U (or the pairs), V
+  int rows[3] = {0, 0, 0};
+  int64_t plane_bytes(int i) const { return row_bytes[i] * rows[i]; }
+  int64_t frame_bytes() const { int64_t n = 0; for (int i = 0; i < nplanes; i++) n += plane_bytes(i); return n; }
+};
+struct YuvDst { uint8_t *p[3]; int64_t row[3], frame[3]; };  // device planes, strides in bytes
+int check_yuv_out(const tm_yuv_out *d, int width, int height, int mode, YuvOutPlan *out);
+int yuv_out_is_device(const tm_yuv_out &d, int device);  // TM_E_INVAL unless every plane is memory of that device
+YuvDst yuv_dst_of(const tm_yuv_out &d, int64_t frame0);  // the caller's planes from frame0 on
+// a packed chunk of `cap` frames at base -- [cap frames of Y][of U or the pairs][of V], frame_bytes() * cap bytes -- from frame0 on
+YuvDst yuv_dst_packed(const YuvOutPlan &p, uint8_t *base, int cap, int frame0);
+// rgb: [nframes][h][stride_px] 0x00RRGGBB on the device
+int launch_rgb32_to_yuv(const YuvOutPlan &p, const void *rgb, int64_t stride_px, int nframes, const YuvDst &d, hipStream_t stream);
+int yuv_copy_out(const YuvOutPlan &p, const uint8_t *packed, int cap, const tm_yuv_out &d, int64_t frame0, int nf, hipStream_t stream);
+
 // tm_png.hip (host only): inflate of a zlib stream, the PNG reader (8-bit, non-interlaced; pixels 0x00RRGGBB; out null: the size only)
 uint32_t crc32_ieee(const uint8_t *p, size_t n);
 int inflate_zlib(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *out_n);

@@ -277,6 +277,9 @@ struct DeviceScope {
   ~DeviceScope() { if (before >= 0) (void)hipSetDevice(before); }
 };
 
+// a YUV destination of one read (tm_player_read_yuv): the plan check_yuv_out made of it
+struct YuvSink { const tm_yuv_out *dst; YuvOutPlan plan; };
+
 struct Events2 {
   hipEvent_t ev[2] = {nullptr, nullptr};
   ~Events2() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
@@ -308,6 +311,7 @@ struct tm_player {
   bool dev_ready = false;
   hipStream_t play = nullptr, copy = nullptr;
   DevBuf d_tiles, d_pal, d_chunk[2], d_kept, d_ring;
+  DevBuf d_yuv;               // host YUV destinations: a ring of two packed chunks of planes
   PinnedBuf h_chunk[2];
   Events2 up, done;
   bool used[2] = {false, false};
@@ -323,7 +327,7 @@ struct tm_player {
       (void)hipSetDevice(device);
       if (play) { (void)hipStreamSynchronize(play); (void)hipStreamDestroy(play); }
       if (copy) { (void)hipStreamSynchronize(copy); (void)hipStreamDestroy(copy); }
-      for (DevBuf *b : {&d_tiles, &d_pal, &d_chunk[0], &d_chunk[1], &d_kept, &d_ring}) b->release();  // (here: the pool files a block under the current device)
+      for (DevBuf *b : {&d_tiles, &d_pal, &d_chunk[0], &d_chunk[1], &d_kept, &d_ring, &d_yuv}) b->release();  // (here: the pool files a block under the current device)
     }
     if (fd >= 0) close(fd);
   }
@@ -409,16 +413,17 @@ struct tm_player {
     return TM_OK;
   }
 
-  // the next `count` frames into dev_out, or through the ring into host_out, or (both null) nowhere: a seek's catching up
+  // the next `count` frames into dev_out, or through the ring into host_out, or (both null) nowhere: a seek's catching up; with `yuv` the
+  // frames are played into the ring and each is converted behind its launch, into the caller's device planes or a packed ring of planes
   // A key frame that cannot be read ends the call at the frame before it: those frames are delivered and counted in *got, the last of them
   // is kept, and the next call stands at the damaged key frame again.  After a device error nothing is known about the frames in flight:
   // the player forgets its place in the key frame and its previous frame, so that no later launch reads a pointer left over from this call.
-  int play_frames(int count, uint32_t *dev_out, uint32_t *host_out, int *got) {
+  int play_frames(int count, uint32_t *dev_out, uint32_t *host_out, int *got, const YuvSink *yuv = nullptr) {
     DeviceScope scope;
     TM_HIP(hipSetDevice(device));
     int n_done = 0;
     bool between_chunks = true;  // false: queue_chunks stopped inside a chunk (a device call failed)
-    const int rc = queue_chunks(count, dev_out, host_out, &n_done, &between_chunks);
+    const int rc = queue_chunks(count, dev_out, host_out, &n_done, &between_chunks, yuv);
     hipError_t e = hipSuccess;
     if (n_done > 0 && between_chunks) {  // the last frame stays with the player: the caller's buffer, or the ring, may be overwritten before the next call
       e = hipMemcpyAsync(d_kept.p, prev, (size_t)fpx * 4, hipMemcpyDeviceToDevice, play);
@@ -432,9 +437,12 @@ struct tm_player {
     TM_HIP(e);
     return TM_OK;
   }
-  int queue_chunks(int count, uint32_t *dev_out, uint32_t *host_out, int *n_done_out, bool *between_chunks) {
+  int queue_chunks(int count, uint32_t *dev_out, uint32_t *host_out, int *n_done_out, bool *between_chunks, const YuvSink *yuv) {
     const bool ring = dev_out == nullptr;
     if (ring && count > 0) TM_TRY(d_ring.alloc((size_t)2 * chunk * fpx * 4));
+    const bool yuv_host = yuv && yuv->dst->memory == TM_MEM_HOST;
+    const size_t yuv_chunk = yuv_host ? (size_t)yuv->plan.frame_bytes() * chunk : 0;
+    if (yuv_host && count > 0) TM_TRY(d_yuv.alloc(2 * yuv_chunk));
     int &n_done = *n_done_out;
     while (n_done < count && pos < ix.frames) {
       if (cur.index < 0 || pos < cur.first || pos >= cur.first + cur.nframes) {
@@ -464,11 +472,16 @@ struct tm_player {
         TM_TRY(launch_play_frame(d_chunk[b].as<uint8_t>() + (size_t)i * per * sizeof(PlayRec), d_chunk[b].as<uint8_t>() + rb + (size_t)(f0 - i0) * 64, f1 - f0, d_tiles.p,
                                  tileset_tiles, d_pal.p, pal_count, head.pal_size, prev, dst, head.tm_w, head.tm_h, play));
         prev = dst;
+        if (yuv) {
+          const YuvDst to = yuv_host ? yuv_dst_packed(yuv->plan, d_yuv.as<uint8_t>() + yuv_chunk * b, chunk, i) : yuv_dst_of(*yuv->dst, n_done + i);
+          TM_TRY(launch_rgb32_to_yuv(yuv->plan, dst, head.tm_w * 8, 1, to, play));
+        }
       }
       TM_HIP(hipEventRecord(done.ev[b], play));
+      if (yuv_host) TM_TRY(yuv_copy_out(yuv->plan, d_yuv.as<uint8_t>() + yuv_chunk * b, chunk, *yuv->dst, n_done, n, play));
       if (host_out) TM_HIP(hipMemcpyAsync(host_out + (int64_t)n_done * fpx, d_ring.as<uint32_t>() + (int64_t)b * chunk * fpx, (size_t)n * fpx * 4, hipMemcpyDeviceToHost, play));
       ms_launch += now_ms() - t0;
-      if (first_frame_ms < 0 && (dev_out || host_out)) {  // (once in a player's life: the wait is part of what is measured)
+      if (first_frame_ms < 0 && (dev_out || host_out || yuv)) {  // (once in a player's life: the wait is part of what is measured)
         TM_HIP(hipStreamSynchronize(play));
         first_frame_ms = now_ms() - t_open;
       }
@@ -559,7 +572,7 @@ int tm_player_info(tm_player *p, tm_gtm_info *info) {
   TM_CHECK(p && info, TM_E_INVAL, "null argument");
   fill_info(p->ix, p->head, p->tileset_tiles, p->pal_count, info);
   info->host_bytes = (int64_t)(p->h_chunk[0].bytes + p->h_chunk[1].bytes + p->peak_records + p->ix.kf.size() * sizeof(KfEntry));
-  info->device_bytes = (int64_t)(p->d_tiles.bytes + p->d_pal.bytes + p->d_chunk[0].bytes + p->d_chunk[1].bytes + p->d_kept.bytes + p->d_ring.bytes);
+  info->device_bytes = (int64_t)(p->d_tiles.bytes + p->d_pal.bytes + p->d_chunk[0].bytes + p->d_chunk[1].bytes + p->d_kept.bytes + p->d_ring.bytes + p->d_yuv.bytes);
   return TM_OK;
 }
 
@@ -585,6 +598,22 @@ int tm_player_read(tm_player *p, int count, void *out, int out_on_device, int *g
   TM_CHECK(((uintptr_t)out & 15) == 0 || !out_on_device, TM_E_INVAL, "the device destination must be 16-byte aligned");
   if (count == 0) return TM_OK;
   return out_on_device ? p->play_frames(count, (uint32_t *)out, nullptr, got) : p->play_frames(count, nullptr, (uint32_t *)out, got);
+}
+
+int tm_player_read_yuv(tm_player *p, int count, const tm_yuv_out *dst, int mode, int *got) {
+  TM_CHECK(p && got, TM_E_INVAL, "null argument");
+  *got = 0;
+  TM_CHECK(count >= 0, TM_E_INVAL, "read of %d frames", count);
+  YuvSink sink{dst, YuvOutPlan()};
+  TM_TRY(check_yuv_out(dst, p->head.tm_w * 8, p->head.tm_h * 8, mode, &sink.plan));
+  const int deliver = std::min(count, p->ix.frames - p->pos);  // (as tm_player_read: what is left of the stream is what a call delivers)
+  TM_CHECK(deliver <= dst->frames, TM_E_INVAL, "yuv out: %d frames to deliver, room for %d", deliver, dst->frames);
+  if (dst->memory == TM_MEM_DEVICE) {
+    DeviceScope scope;
+    TM_TRY(yuv_out_is_device(*dst, p->device));
+  }
+  if (count == 0) return TM_OK;
+  return p->play_frames(count, nullptr, nullptr, got, &sink);
 }
 
 int tm_player_seek(tm_player *p, int frame) {

@@ -101,6 +101,7 @@ _ENC_SIGS = {
     "tm_generate_y4m": (c_int, [c_void_p, c_char_p, c_int]),
     "tm_generate_pngs": (c_int, [c_void_p, c_int]),
     "tm_render_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int]),
+    "tm_render_frames_yuv": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(YuvClip), c_int]),
     "tm_get_frame_quality": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
     "tm_set_query_shard": (c_int, [c_void_p, c_int, c_int]),
     "tm_set_dither_shard": (c_int, [c_void_p, c_int, c_int]),
@@ -457,6 +458,16 @@ class TilingEncoder:
         out = np.empty(shape, np.uint32)
         check(self._L.tm_render_frames(c_void_p(self._h), first, count, int(bool(input)), out.ctypes.data_as(c_void_p), 0))
         return out
+
+    def RenderFramesYUV(self, first=0, count=None, input=False, layout="nv12", yuv="auto", device=True, out=None, full_range=False):
+        """RenderFrames' frames as YUV planes (tm_render_frames_yuv), converted on the device behind the render: (y, u, v) as
+        GtmPlayer.ReadYUV returns them (layout, yuv, out and full_range as there)"""
+        from . import yuv_out
+        c = self.counts()
+        count = c["frames"] - first if count is None else count
+        planes, d = yuv_out.destination(layout, count, c["tm_h"] * 8, c["tm_w"] * 8, "cuda" if device else None, out, full_range)
+        check(self._L.tm_render_frames_yuv(c_void_p(self._h), first, count, int(bool(input)), ctypes.byref(d), yuv_out.mode_of(yuv)))
+        return yuv_out.first(planes, max(count, 0))
 
     def FrameQuality(self, first=0, count=None):
         """Pixel-domain quality of the decoded frames [first, first+count) against the source (tm_get_frame_quality): sse uint64 [count][3]

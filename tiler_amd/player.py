@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 
 from ._lib import lib, check, c_void_p, c_int, c_int64, c_double, c_char_p
+from . import yuv_out
 
 
 class GtmInfo(ctypes.Structure):  # tm_gtm_info
@@ -29,6 +30,7 @@ _SIGS = {
     "tm_player_keyframes": (c_int, [c_void_p, c_void_p]),
     "tm_player_settings_text": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "tm_player_read": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "tm_player_read_yuv": (c_int, [c_void_p, c_int, ctypes.POINTER(yuv_out.YuvOut), c_int, ctypes.POINTER(c_int)]),
     "tm_player_seek": (c_int, [c_void_p, c_int]),
     "tm_player_tell": (c_int, [c_void_p]),
     "tm_player_timings": (c_int, [c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
@@ -160,6 +162,19 @@ class GtmPlayer:
                 out = np.empty(shape, np.uint32)
             check(self._L.tm_player_read(c_void_p(self._h), count, out.ctypes.data_as(c_void_p), 0, ctypes.byref(got)))
         return out[:got.value]
+
+    def ReadYUV(self, count=None, layout="nv12", yuv="auto", device=True, out=None, full_range=False):
+        """the next `count` frames (None: to the end) as YUV planes (tm_player_read_yuv), converted on the device: (y, u, v) of [got][rows]
+        [samples], torch tensors on the player's device (uint8, or int16 holding the words) or numpy arrays (uint8 / uint16); u is None for
+        "mono", v is None where u holds (U, V) pairs ([got][ch][2 cw]).  layout: 444 422 420 420mpeg2 mono nv12 p010, or (chroma, samples,
+        depth, pairs); yuv: auto bt601-limited bt601-full tiler bt709-limited bt709-full (auto: bt601-full when full_range, else
+        bt601-limited).  out: (y, u, v) of at least that size to fill instead (strides are taken from the arrays)"""
+        i = self.info()
+        count = i["frames"] - self.Tell() if count is None else int(count)
+        planes, d = yuv_out.destination(layout, count, i["tm_h"] * 8, i["tm_w"] * 8, "cuda:%d" % self._device if device else None, out, full_range)
+        got = c_int()
+        check(self._L.tm_player_read_yuv(c_void_p(self._h), count, ctypes.byref(d), yuv_out.mode_of(yuv), ctypes.byref(got)))
+        return yuv_out.first(planes, got.value)
 
     def Timings(self):
         ms = (c_double * 5)()

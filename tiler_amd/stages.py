@@ -62,6 +62,23 @@ def yuv_to_rgb32_fmt(y, u, v, chroma, dst_w, dst_h, yuv_mode=0, samples=0, depth
     return out
 
 
+def rgb32_to_yuv(rgb, layout="nv12", yuv="auto", out=None, width=None):
+    """RGB32 frames -> YUV planes (tm_stage_rgb32_to_yuv_fmt, the kernel behind GtmPlayer.ReadYUV): rgb int32 [F][H][W'] 0x00RRGGBB with a
+    dense last axis, of which `width` columns (default: all) are converted; layout and yuv as ReadYUV takes them (auto = bt601-limited).
+    out: (y, u, v) CUDA tensors to fill (strides are taken from them) -> (y, u, v), u None for mono, v None where u holds pairs"""
+    from . import yuv_out
+    assert rgb.is_cuda and rgb.dtype == torch.int32 and rgb.dim() == 3 and rgb.stride(2) == 1 and rgb.stride(0) == rgb.stride(1) * rgb.shape[1]
+    f, h = rgb.shape[0], rgb.shape[1]
+    w = rgb.shape[2] if width is None else int(width)
+    planes, d = yuv_out.destination(layout, f, h, w, rgb.device, out)
+    if (d.width, d.height) != (w, h) or d.frames < f or not d.memory:
+        raise ValueError("rgb32_to_yuv: out must be CUDA planes of %d frames of %d x %d" % (f, w, h))
+    strides = (ctypes.c_int64 * 6)(d.y_row, d.y_frame, d.u_row, d.u_frame, d.v_row, d.v_frame)
+    check(lib().tm_stage_rgb32_to_yuv_fmt(_p(rgb), rgb.stride(1), f, w, h, ctypes.c_void_p(d.y), ctypes.c_void_p(d.u), ctypes.c_void_p(d.v), strides, d.chroma,
+                                          d.samples, d.depth, yuv_out.mode_of(yuv), _stream()))
+    return yuv_out.first(planes, f)
+
+
 def rgb_to_lab(rgb):
     """RGBToLAB (utils.pas:374-410) of colours 0x00RRGGBB (int32 [n]) -> float32 [n][3]"""
     assert rgb.is_cuda and rgb.dtype == torch.int32 and rgb.is_contiguous()

@@ -1,8 +1,12 @@
-"""Frames of a .gtm stream, played on the device: python tools/play_gtm.py IN.gtm [--start N --frames N] (--info | --raw OUT.rgb)
+"""Frames of a .gtm stream, played on the device:
+python tools/play_gtm.py IN.gtm [--start N --frames N] (--info | --raw OUT.rgb | --y4m OUT.y4m [--chroma 444|422|420jpeg|420mpeg2|mono] [--yuv MODE])
 
 --info prints what the stream says about itself (size, frames, key frames, rate, tiles, palettes, the embedded settings) as JSON;
 --raw writes frames [start, start + frames) as packed RGB24, one frame after the other (view with
-`ffplay -f rawvideo -pixel_format rgb24 -video_size WxH OUT.rgb`)."""
+`ffplay -f rawvideo -pixel_format rgb24 -video_size WxH OUT.rgb`);
+--y4m writes them as a Y4M file any player, FFmpeg and this library's OpenInput read: the frames are converted to YUV on the device
+(GtmPlayer.ReadYUV) and come to the host as 1 to 3 bytes a pixel.  --yuv: auto (= bt601-limited) bt601-limited bt601-full bt709-limited
+bt709-full tiler (444 and mono only); the header says XCOLORRANGE=FULL for the full-range rules and tiler."""
 import argparse
 import json
 import os
@@ -21,6 +25,9 @@ ap.add_argument("--frames", type=int, default=0, help="0: to the end")
 g = ap.add_mutually_exclusive_group(required=True)
 g.add_argument("--info", action="store_true")
 g.add_argument("--raw")
+g.add_argument("--y4m")
+ap.add_argument("--chroma", default="420jpeg", choices=["444", "422", "420jpeg", "420mpeg2", "mono"])
+ap.add_argument("--yuv", default="auto", choices=["auto", "bt601-limited", "bt601-full", "bt709-limited", "bt709-full", "tiler"])
 args = ap.parse_args()
 with GtmPlayer(args.input) as p:
     info = p.info()
@@ -28,6 +35,23 @@ with GtmPlayer(args.input) as p:
         info["keyframe_starts"] = p.KeyFrames().tolist()
         info["settings"] = p.SettingsText()
         print(json.dumps(info))
+    elif args.y4m:
+        p.Seek(args.start)
+        left = (args.frames if args.frames > 0 else info["frames"] - args.start)
+        w, h = info["tm_w"] * 8, info["tm_h"] * 8
+        full = args.yuv in ("bt601-full", "bt709-full", "tiler")
+        with open(args.y4m, "wb") as f:
+            f.write(("YUV4MPEG2 W%d H%d F%d:1000000 Ip C%s XCOLORRANGE=%s\n" % (w, h, round(info["fps"] * 1000000), args.chroma, "FULL" if full else "LIMITED")).encode())
+            while left > 0:
+                planes = p.ReadYUV(min(left, 16), layout=args.chroma, yuv=args.yuv, device=False)
+                if planes[0].shape[0] == 0:
+                    break
+                for i in range(planes[0].shape[0]):
+                    f.write(b"FRAME\n")
+                    for a in planes:
+                        if a is not None:
+                            f.write(a[i].tobytes())
+                left -= planes[0].shape[0]
     else:
         p.Seek(args.start)
         left = (args.frames if args.frames > 0 else info["frames"] - args.start)

@@ -3,6 +3,11 @@
                                                                           unless they are there, and times both ways on both
   python tools/time_player.py --dir DIR --only old|player --motion 0|1    one untimed pass of one way on one stream: the program to put behind
                                                                           `rocprofv3 --kernel-trace --stats --` for the kernels' own times
+  python tools/time_player.py --dir DIR --yuv rgb32|nv12|p010|... --to host|device [--motion 0|1] [--reps 7] [--json OUT.json]
+                                                                          the read leg: all frames of one stream as RGB32
+                                                                          (tm_player_read) or as YUV planes (tm_player_read_yuv) into device memory
+                                                                          or page-locked host memory; wall times and the bytes that cross PCIe.
+                                                                          With --only player: one untimed pass, for rocprofv3
 (a) the old way: tm_reload_gtm + tm_render_frames of all frames into device memory;  (b) tm_player_open + tm_player_read of all frames into
 device memory, with the worker thread and (TM_PLAYER_NO_WORKER=1) without.  Wall times are medians of --reps runs after one warm-up, with
 min and max; the player's own split (decode, parse, upload, wait for the worker, launches) and its time to the first frame are its Timings()."""
@@ -74,6 +79,43 @@ def player_way(path, out):
     return r
 
 
+def yuv_leg(path, layout, to, reps):
+    """all frames of the stream read `reps` times after one warm-up, each time by a fresh player: wall ms of open + read, of the read alone,
+    and the bytes the read sends over PCIe (0 for a device destination)"""
+    from tiler_amd import yuv_out
+    if layout == "rgb32":
+        out = torch.empty((F, H, W), dtype=torch.int32, device="cuda") if to == "device" else torch.empty((F, H, W), dtype=torch.int32, pin_memory=True)
+        nbytes = out.numel() * 4
+    else:
+        words = yuv_out.layout_of(layout)[1] != yuv_out.U8
+        shapes = yuv_out.plane_shapes(layout, F, H, W)
+        make = (lambda s: torch.empty(s, dtype=torch.int16 if words else torch.uint8, device="cuda")) if to == "device" else \
+               (lambda s: torch.empty(s, dtype=torch.int16 if words else torch.uint8, pin_memory=True))
+        out = tuple(None if s is None else make(s) for s in shapes)
+        nbytes = sum(a.numel() * a.element_size() for a in out if a is not None)
+
+    def once():
+        t0 = time.perf_counter()
+        with GtmPlayer(path) as p:
+            t1 = time.perf_counter()
+            if layout == "rgb32":
+                got = p.Read(F, device=True, out=out) if to == "device" else p.Read(F, device=False, out=out.numpy().view(np.uint32))
+                n = got.shape[0]
+            else:
+                n = p.ReadYUV(F, layout=layout, device=to == "device", out=out)[0].shape[0]
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+        assert n == F
+        return dict(wall_ms=(t2 - t0) * 1e3, read_ms=(t2 - t1) * 1e3)
+
+    once()
+    if reps <= 0:
+        return None
+    r = summarise([once() for _ in range(reps)])
+    r.update(layout=layout, to=to, reps=reps, bytes_written=nbytes, pcie_bytes=0 if to == "device" else nbytes, lib=os.environ.get("TM_LIB_VARIANT", ""))
+    return r
+
+
 def summarise(runs):
     out = {}
     for k in runs[0]:
@@ -89,9 +131,21 @@ def main():
     ap.add_argument("--json")
     ap.add_argument("--only", choices=["old", "player"])
     ap.add_argument("--motion", type=int, default=1)
+    ap.add_argument("--yuv", help="the read leg: rgb32, or a layout of GtmPlayer.ReadYUV (nv12, p010, 420, ...)")
+    ap.add_argument("--to", choices=["host", "device"], default="device")
     args = ap.parse_args()
     os.makedirs(args.dir, exist_ok=True)
     paths = {1: os.path.join(args.dir, "bench_motion32.gtm"), 0: os.path.join(args.dir, "bench_motion0.gtm")}
+    if args.yuv:
+        if not os.path.exists(paths[args.motion]):
+            make_stream(paths[args.motion], 32 if args.motion else 0)
+        r = yuv_leg(paths[args.motion], args.yuv, args.to, 0 if args.only else args.reps)
+        if r is not None:
+            print(json.dumps(r))
+            if args.json:
+                with open(args.json, "w") as f:
+                    f.write(json.dumps(r) + "\n")
+        return
     out = torch.empty((F, H, W), dtype=torch.int32, device="cuda")
     if args.only:
         (old_way if args.only == "old" else player_way)(paths[args.motion], out)
