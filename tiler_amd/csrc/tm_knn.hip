@@ -629,7 +629,7 @@ struct tm_knn_index_impl {
   uint64_t arena_cap = 0, arena_want = 0;           // list entries the arena holds / the largest cursor a search has reported
   hipEvent_t ev_seed = nullptr, ev_lists = nullptr;
   double last_seed_ms = 0, last_lists_ms = 0, last_consume_ms = 0;
-  int64_t last_blocks = 0, last_loads = 0, last_listed = 0;
+  int64_t last_blocks = 0, last_loads = 0, last_listed = 0, last_popped = 0;
   int64_t last_visited = 0, last_ties = 0;
   double last_ms = 0;
   int last_kbytes = 0;
@@ -1056,6 +1056,7 @@ static int launch_scan3(tm_knn_index_impl *ix, int64_t nq, int64_t nqt, int64_t 
   a.thmask = ix->thmask.as<uint8_t>();
   TM_CHECK(ntt < (1 << 24), TM_E_UNSUPPORTED, "knn: %lld database tiles exceed the list entries' 24-bit tile index", (long long)ntt);
   a.ns = ns; a.mode = prune ? K3_MODE_LISTS : K3_MODE_DENSE; a.tdouble = ix->plan.tscale == 2;
+  a.list_order = knobs().knn_list_order ? 1 : 0;
   a.n_groups = (nqt + ns - 1) / ns;
   a.max_segs = (int)(ntt / (K3_LCAP - K3_LIST_NT) + 2);  // every segment but a list's last holds more than K3_LCAP - K3_LIST_NT entries
   if (prune) {
@@ -1233,7 +1234,7 @@ int knn_index_search(tm_knn_index_impl *ix, const void *queries, int64_t nq, voi
   TM_TRY(ix->best_key.alloc((size_t)nqt * 32 * 4));
   TM_TRY(ix->best_tile.alloc((size_t)nqt * 32 * 4));
   TM_TRY(ix->tie_list.alloc((size_t)nq * 4));
-  TM_TRY(ix->counters.alloc(256 + 2048));  // [4..15]: phase stamps of a diagnostic build; bytes 128..159: the group tickets; bytes 256..: the seed kernel's striped counters
+  TM_TRY(ix->counters.alloc(256 + 2048));  // [4..15]: phase stamps of a diagnostic build; bytes 128..159: the group tickets; bytes 240..247 (stats[28]): list entries popped; bytes 256..: the seed kernel's striped counters
   const int prune = knobs().knn_noprune ? 0 : 1;  // diagnostic: full scan with the same kernel (bench.py roofline_dense)
   int *bt = ix->best_tile.as<int>();
   KnnBoxes bx;
@@ -1309,16 +1310,16 @@ int knn_index_search(tm_knn_index_impl *ix, const void *queries, int64_t nq, voi
   ix->last_pairs = (int64_t)(cnt[4] + cnt[14]);
   ix->last_seed_pairs = (int64_t)cnt[14];
   ix->last_mfma = (int64_t)cnt[21];
-  ix->last_blocks = (int64_t)(cnt[2] + cnt[12]); ix->last_loads = (int64_t)(cnt[3] + cnt[13]); ix->last_listed = (int64_t)cnt[5];
+  ix->last_blocks = (int64_t)(cnt[2] + cnt[12]); ix->last_loads = (int64_t)(cnt[3] + cnt[13]); ix->last_listed = (int64_t)cnt[5]; ix->last_popped = (int64_t)cnt[30];
   if (knobs().knn_debug) {
     const int nsg = knn3_sub_tiles(ix->plan.hq);
     const int64_t groups = (nqt + nsg - 1) / nsg;
     fprintf(stderr, "[tm_knn] seeds %.3f ms, lists %.3f ms (%.1f entries per group, arena %.0f %% full), consume %.3f ms, %.2f of %d matrix instructions per block\n", ix->last_seed_ms, ix->last_lists_ms,
             (double)cnt[20] / (double)groups, 100.0 * (double)cnt[20] / (double)std::max<uint64_t>(1, ix->arena_cap), ix->last_consume_ms,
             (double)cnt[21] / (double)std::max<unsigned long long>(1, cnt[2]), 6 + ix->plan.ht + ix->plan.hq + std::min(ix->plan.ht, ix->plan.hq));
-    fprintf(stderr, "[tm_knn] scan %.3f ms, evaluated %.3f%% of %lld x %lld pairs (%lld blocks; workgroups read %.3f%% of tiles, %.1f per group; %.1f list entries per group), %lld tie settlements\n",
+    fprintf(stderr, "[tm_knn] scan %.3f ms, evaluated %.3f%% of %lld x %lld pairs (%lld blocks; workgroups read %.3f%% of tiles, %.1f per group; %.1f list entries per group, %.1f popped), %lld tie settlements\n",
             ms, 100.0 * (double)ix->last_pairs / ((double)nq * (double)ix->nt), (long long)nq, (long long)ix->nt, (long long)ix->last_blocks,
-            100.0 * (double)ix->last_loads / ((double)groups * (double)ntt), (double)ix->last_loads / (double)groups, (double)ix->last_listed / (double)groups, (long long)ix->last_ties);
+            100.0 * (double)ix->last_loads / ((double)groups * (double)ntt), (double)ix->last_loads / (double)groups, (double)ix->last_listed / (double)groups, (double)ix->last_popped / (double)groups, (long long)ix->last_ties);
   }
 #if TM_KNN3_STAMPS
   {
@@ -1459,6 +1460,7 @@ static int topk_pass(tm_knn_index_impl *ix, const int16_t *feats, int64_t n, con
     a.n_groups = (nqt + ns - 1) / ns;
     a.max_segs = (int)(ntt / (K3_LCAP - K3_LIST_NT) + 2);
     a.no_seeds = 1;
+    a.list_order = knobs().knn_list_order ? 1 : 0;
     a.tau = tau.as<int>(); a.step = step.as<int>(); a.cand = cand.as<uint2>(); a.cand_cnt = cand_cnt.as<int>(); a.cand_cap = cap; a.cand_k = k;
     // few queries left: their few workgroups would each walk most of the database one after the other -- share the tile lists
     a.split = a.n_groups >= 512 ? 1 : (int)std::max<int64_t>(1, std::min<int64_t>(64, 1024 / std::max<int64_t>(a.n_groups, 1)));
@@ -1600,6 +1602,11 @@ void knn_index_stats(tm_knn_index_impl *ix, double *ms, int *kbytes, int64_t *pa
   if (ms) *ms = ix->last_ms;
   if (kbytes) *kbytes = ix->last_kbytes;
   if (pairs) *pairs = ix->last_pairs;
+}
+
+void knn_index_list_counts(tm_knn_index_impl *ix, int64_t *listed, int64_t *popped) {
+  if (listed) *listed = ix->last_listed;
+  if (popped) *popped = ix->last_popped;
 }
 
 int knn3_sub_tiles(int hq) { return k3_ns(6 + std::min(std::max(hq, 0), 6)); }

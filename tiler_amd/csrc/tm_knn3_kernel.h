@@ -10,15 +10,17 @@
 //   2. k_knn_lists   the tile list of every query group, judged against the seeds' bounds: runs of KNN_GROUP tiles first, then the tiles of
 //                    surviving runs; per entry the box lower bound of each (tile, sub-tile) pair as a 16-bit square root.  No MFMA, no query
 //                    operands: small workgroups, many per CU, whose global loads hide behind each other.  Lists go to an arena in HBM in
-//                    segments of <= K3_LCAP entries.
+//                    segments of <= K3_LCAP entries, each sorted by its entries' smallest bound.
 //   3. k_knn_consume persistent workgroups (one per CU, 16 waves): a group's query operands and its seeds' bests into LDS, then one list
 //                    segment after the other: copied into LDS, consumed by the waves on their own exactly as in the second shape (pop an
 //                    entry, re-judge it against the sub-tiles' bounds AS THEY ARE NOW, tile into registers, one MFMA chain per sub-tile
-//                    that wants it).  An entry judged with the seeds' bound instead of a later, tighter one costs one pop, not a block.
+//                    that wants it).  An entry judged with the seeds' bound instead of a later, tighter one costs one pop, not a block; a
+//                    sorted segment ends at the first entry whose smallest bound lies above every sub-tile's bound.
 // Arithmetic, operands, boxes, curve and the exactness argument are those of the earlier shapes: a pair is skipped only when its lower
 // bound exceeds the sub-tile's largest best + 1 (both sides of the 16-bit compare rounded the safe way), the minimum VALUE is exact, a
 // second row reaching it raises the tie flag that k_knn_ties settles by original index.
 #pragma once
+#include <type_traits>
 #include "tm_knn_kernel.h"
 
 namespace tmx {
@@ -90,7 +92,8 @@ struct Knn3Args {
   int cand_cap, cand_k;
   int split;                    // workgroups that share one group's tile list (entry j goes to part j mod split)
   int no_seeds;                 // lists: no seed kernel ran (collection mode), so no tile is left out of the lists
-  unsigned long long *stats;    // consume: [0] blocks evaluated, [1] tiles read, [2] exact (query, row) pairs, [3] list entries consumed
+  int list_order;               // lists: a segment leaves sorted by its entries' smallest bound; consume: a segment ends at the first entry nobody can want (0: run order, no stop)
+  unsigned long long *stats;    // consume: [0] blocks evaluated, [1] tiles read, [2] exact (query, row) pairs, [3] list entries consumed, [28] entries popped
   unsigned long long *seed_stats;  // [64][4] striped by workgroup: blocks, tiles read, pairs of the seed kernel
   int64_t n_groups;
   int grid_blocks;              // consume: persistent workgroups
@@ -612,7 +615,8 @@ __global__ __launch_bounds__(K3_SEEDS * 64, 4) void k_knn_seed(const Knn3Args a)
 // One workgroup (256 threads) per query group.  Runs of KNN_GROUP tiles are judged first, 16 of them at a time in outward order from the
 // home run (one thread per (run, sub-tile) pair); then only the tiles of surviving runs are tested, 128 threads per run, against the
 // sub-tiles that survived the run's box.  Entries collect in LDS in that order; a segment that is full (or the list's end) takes its place
-// in the arena with one atomic add and is copied out.  Past the arena's capacity nothing is written and the segment's count is 0: the
+// in the arena with one atomic add and is copied out, sorted by its entries' smallest bound (sort_segment; a.list_order = 0: as collected).
+// The segments of a list keep the outward order among themselves.  Past the arena's capacity nothing is written and the segment's count is 0: the
 // cursor keeps counting, the host sees the overflow with the scan's other counters and repeats the search with a larger arena.
 #ifdef TM_KNN3_WITH_LISTS  // (not a template: defined in one translation unit, tm_knn.hip)
 __global__ __launch_bounds__(K3_LIST_NT) void k_knn_lists(const Knn3Args a) {
@@ -625,6 +629,7 @@ __global__ __launch_bounds__(K3_LIST_NT) void k_knn_lists(const Knn3Args a) {
   __shared__ int s_ctl[4];  // [0] entries in the buffer, [1] surviving runs of the batch, [2] arena offset of the segment being flushed
   __shared__ unsigned s_ltile[LCAP];
   __shared__ unsigned s_llbw[LCAP * 8];  // [LCAP][nsp / 2] words
+  __shared__ __attribute__((aligned(4))) uint16_t s_key[LCAP];  // flush: the order the entries leave in (sort_segment)
   const int tid = threadIdx.x, lane = tid & 63;
   const int NS = a.ns, NSP = (NS + 1) & ~1, NSW = NSP / 2;
   const int64_t g = blockIdx.x, st0 = g * NS, n_ttiles = a.n_ttiles;
@@ -638,6 +643,63 @@ __global__ __launch_bounds__(K3_LIST_NT) void k_knn_lists(const Knn3Args a) {
   const int r0b = a.no_seeds ? 0 : (int)min((int64_t)r0a + K3_SEEDS, n_ttiles);
   const int n_grp = (int)((n_ttiles + KNN_GROUP - 1) / KNN_GROUP), home_run = home / KNN_GROUP;
   const int total_run_slots = 2 * max(home_run, n_grp - 1 - home_run) + 1, n_run_batches = (total_run_slots + RB - 1) / RB;
+  // A segment leaves in ascending order of its entries' smallest bound, equal keys in the order they came (run order): the consumer meets
+  // the tiles most likely to tighten its bounds first, and may end the segment at the first entry no sub-tile wants (next_entry).  An
+  // unwanted slot holds 0xFFFF, above every bound, and every entry has a wanted one: the key is the plain minimum of the row's sixteen
+  // halves.  The words key << 10 | position (distinct, so the order is stable and a function of the list alone) go through a bitonic
+  // network, EPT of them per thread: a step whose partner sits in the thread's own registers or in its wave costs no barrier (19 and 33 of
+  // the 55 steps at 1 024 words); the three steps that cross waves go through s_ltile, whose words wait in registers meanwhile.  What is
+  // left in LDS is s_key[rank] = position, 2 KB: the kernel stays at four workgroups per CU.  (Every entry counting the entries before it,
+  // n^2 / 2 compares on broadcast reads, was measured first: 1.22 against 0.66 ms for the kernel at the bench clip's 700 entries a group.)
+  auto sort_segment = [&](int n, auto ept_c) {  // (every thread calls it; n is uniform)
+    constexpr int EPT = decltype(ept_c)::value, P = NT * EPT;
+    static_assert(P <= LCAP && (EPT & (EPT - 1)) == 0, "the exchange buffer is s_ltile");
+    unsigned v[EPT], lt[EPT];
+#pragma unroll
+    for (int m = 0; m < EPT; m++) {
+      const int e = tid * EPT + m;
+      v[m] = ~0u;  // padding: behind every entry
+      lt[m] = 0;
+      if (e < n) {
+        unsigned k = 0xFFFFu;
+#pragma unroll
+        for (int p = 0; p < 8; p++) { const unsigned w = s_llbw[e * 8 + p]; k = min(k, min(w & 0xFFFFu, w >> 16)); }
+        v[m] = (k << 10) | (unsigned)e;
+        lt[m] = s_ltile[e];
+      }
+    }
+    __syncthreads();  // s_ltile's words are in registers
+#pragma unroll
+    for (int k = 2; k <= P; k <<= 1) {
+#pragma unroll
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        // word i meets word i ^ j and keeps the smaller one where (i & k) == 0 and (i & j) == 0 agree, the larger one where not
+        unsigned w[EPT];
+        if (j >= 64 * EPT) {
+#pragma unroll
+          for (int m = 0; m < EPT; m++) s_ltile[tid * EPT + m] = v[m];
+          __syncthreads();
+#pragma unroll
+          for (int m = 0; m < EPT; m++) w[m] = s_ltile[(tid * EPT + m) ^ j];
+          __syncthreads();
+        } else {
+#pragma unroll
+          for (int m = 0; m < EPT; m++) w[m] = j < EPT ? v[m ^ (j < EPT ? j : 0)] : (unsigned)__shfl_xor((int)v[m], j / EPT);
+        }
+#pragma unroll
+        for (int m = 0; m < EPT; m++) {
+          const int i = tid * EPT + m;
+          v[m] = (((i & k) == 0) == ((i & j) == 0)) ? min(v[m], w[m]) : max(v[m], w[m]);
+        }
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < EPT; m++) {
+      const int e = tid * EPT + m;
+      if (e < n) { s_ltile[e] = lt[m]; s_key[e] = (uint16_t)(v[m] & 1023u); }  // (the padding sorts behind the n entries)
+    }
+    __syncthreads();
+  };
   int nseg = 0;
   auto flush = [&]() {  // the buffer's entries become a segment (every thread calls it; n is uniform)
     const int n = s_ctl[0];
@@ -651,10 +713,18 @@ __global__ __launch_bounds__(K3_LIST_NT) void k_knn_lists(const Knn3Args a) {
       }
       __syncthreads();
       if (s_ctl[2]) {
+        const bool sorted = a.list_order != 0;
+        if (sorted) {
+          if (n <= 2 * NT) sort_segment(n, std::integral_constant<int, 2>());
+          else sort_segment(n, std::integral_constant<int, LCAP / NT>());
+        }
         const unsigned off = (unsigned)s_ctl[3];
-        for (int i = tid; i < n; i += NT) a.ltile[off + i] = s_ltile[i];
+        for (int i = tid; i < n; i += NT) a.ltile[off + i] = s_ltile[sorted ? (int)s_key[i] : i];
         unsigned *dst = reinterpret_cast<unsigned *>(a.llb) + (size_t)off * NSW;
-        for (int i = tid; i < n * NSW; i += NT) dst[i] = s_llbw[(i / NSW) * 8 + (i % NSW)];
+        for (int i = tid; i < n * NSW; i += NT) {
+          const int e = i / NSW;
+          dst[i] = s_llbw[(sorted ? (int)s_key[e] : e) * 8 + (i - e * NSW)];
+        }
       }
       nseg++;
       __syncthreads();
@@ -806,8 +876,8 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
   // helps the next one.
   unsigned xcc;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
-  long long nblocks = 0, nloads = 0, npairs = 0, nlisted = 0, nmfma = 0;
-  const bool dense = a.mode == K3_MODE_DENSE;
+  long long nblocks = 0, nloads = 0, npairs = 0, nlisted = 0, npopped = 0, nmfma = 0;
+  const bool dense = a.mode == K3_MODE_DENSE, ordered = a.list_order != 0 && !dense;
   const int split = TOPK ? max(1, a.split) : 1;
   const int64_t n_units = a.n_groups * split;  // what the tickets deal: (group, part of its list)
   for (;;) {
@@ -910,7 +980,7 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
     K3_STAMP(1);  // segment load
     // ---------------------------------------------------------------- consume: every wave on its own
     {
-      nlisted += (wave == 0) ? list_n : 0;
+      nlisted += (wave == 0) ? (TOPK ? (list_n - part + split - 1) / split : list_n) : 0;  // (a split list: this part's entries)
       auto next_entry = [&](int &tile_o, unsigned &tm_o, int &lb_o, unsigned &mask_o, int &sm_o) -> bool {
         for (;;) {
           int j = 0;
@@ -918,6 +988,7 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
           j = __builtin_amdgcn_readfirstlane(j);
           if (TOPK) j = j * split + part;  // a split group: this workgroup takes every split-th entry
           if (j >= list_n) return false;
+          npopped++;
 #if TM_KNN3_REFRESH_EVERY
           if ((j & (TM_KNN3_REFRESH_EVERY - 1)) == TM_KNN3_REFRESH_EVERY - 1)
             for (int s = 0; s < nvalid; s++) {  // every so many entries the popping wave makes every sub-tile's bound anew from its bests: what the
@@ -934,6 +1005,19 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
           // met a compiler combine that treats the 64-bit multiply by the tile size as a 24-bit multiply, drops the AND as redundant for one,
           // and then selects a full 32-bit v_mad_u64_u32: the loads went to word * 12 KB -- a memory aperture violation on the GPU box.)
           if (m) { tile_o = __builtin_amdgcn_readfirstlane((int)((unsigned)t >> 8)); tm_o = (unsigned)__builtin_amdgcn_readfirstlane(t) & 0xFFu; lb_o = lb; mask_o = m; sm_o = sm; return true; }
+          // Nobody wants the entry.  In a sorted segment (k_knn_lists' flush) its smallest listed bound is the smallest of every entry behind
+          // it as well, and a sub-tile's bound only falls: once that key lies above the largest bound of the group, no later entry can be
+          // wanted by anyone, now or later -- today's skip rule applied to the segment's tail at once.  The pop counter goes to the end so that
+          // the other waves stop too.  (A tile holding a row at some query's current minimum has a bound within its sub-tile's: what raises a tie
+          // flag is never behind the stop.  Collection mode: the same rule on thresholds that only fall; a part of a split list sees its own
+          // entries in ascending order.)
+          if (ordered) {
+            const unsigned smx = k3_wave_umax(lane < nvalid ? (unsigned)sm : 0u);
+            if (__builtin_amdgcn_ballot_w64(lb <= (int)smx) == 0) {
+              if (lane == 0) atomicMax(&s_ctl[1], list_n);
+              return false;
+            }
+          }
         }
       };
       int tile = 0, lbv = 0, smv = 0;
@@ -1080,6 +1164,7 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
     atomicAdd(a.stats + 1, (unsigned long long)nloads);
     atomicAdd(a.stats + 2, (unsigned long long)npairs);
     if (wave == 0) atomicAdd(a.stats + 3, (unsigned long long)nlisted);
+    atomicAdd(a.stats + 28, (unsigned long long)npopped);  // entries the waves took off their lists: short of [3] by what the stops left behind
     atomicAdd(a.stats + 19, (unsigned long long)nmfma);  // matrix instructions issued (a full chain has 6 + HT + HQ + min(HT, HQ))
   }
 }

@@ -188,6 +188,12 @@ class KnnIndex:
         check(lib().tm_knn_index_last_stats(ctypes.c_void_p(self.h), ctypes.byref(ms), ctypes.byref(kb), ctypes.byref(pairs)))
         return ms.value, kb.value, pairs.value
 
+    def last_list_counts(self):
+        """(entries listed, entries popped) of the last search's tile lists"""
+        listed, popped = ctypes.c_int64(), ctypes.c_int64()
+        check(lib().tm_knn_index_last_list_counts(ctypes.c_void_p(self.h), ctypes.byref(listed), ctypes.byref(popped)))
+        return listed.value, popped.value
+
     def close(self):
         if self.h:
             lib().tm_knn_index_destroy(ctypes.c_void_p(self.h))
