@@ -352,6 +352,35 @@ TM_API int tm_render_frames(tm_encoder *, int first_frame, int frame_count, int 
  * reads shard 0, like the exports -- one refusal more than tm_render_frames: with input != 0 after a sharded Load, a range outside the
  * frames shard 0 loaded is TM_E_INVAL (tm_render_frames gathers such a range from every shard's piece).  Blocking. */
 TM_API int tm_render_frames_yuv(tm_encoder *, int first_frame, int frame_count, int input, const tm_yuv_out *dst, int mode);
+/* ---- Decoded frames at a caller's size: RGB32 frames resampled on the device (tm_scale.hip) -----------------------
+ * A frame is uint32 0x00RRGGBB; R, G and B are three planes at luma positions (s = 1, o = 0 in tm_resample_taps_host's terms).
+ *   TM_SCALE_LANCZOS3  each channel through the rule of tm_stage_yuv_to_rgb32, unchanged: tables of tm_resample_taps_host(n, m, n, 1, 0),
+ *                      horizontal pass first, h = (sum c p + 64) >> 7, then v = clamp((sum c h + 2^20) >> 21, 0, 255).  At equal size one tap
+ *                      of 16384 is left: the output is the input.  Shrinking an axis by more than 8 is TM_E_UNSUPPORTED (the tables' limit).
+ *   TM_SCALE_NEAREST   output sample j of m takes source sample ((2 j + 1) n) / (2 m), in integer division, per axis.  No shrink limit.
+ * The output's top byte is 0, whatever the source's top byte holds.  Refusals, all before any device call and with nothing written:
+ * TM_E_INVAL for a size below 1, an unknown filter, a null (or not 4-byte aligned) pointer, a row stride shorter than the row (a frame
+ * stride shorter than the frame, with more than one), source and destination ranges that overlap; TM_E_UNSUPPORTED for a Lanczos shrink
+ * beyond 8 on either axis and for any of the four sizes above TM_SCALE_MAX_SIZE.
+ *   tm_probe_scale_host makes the size and filter checks and nothing else.  tm_scale_rgb32_host is the rule in plain loops, one frame, no
+ * device.  tm_stage_scale_rgb32 (k_scale_rgb32_lanczos3 / k_scale_rgb32_nearest): nframes frames, strides in pixels, both on the current
+ * device; 16-byte stores where dst is 16-byte aligned and dst_w and the destination strides are multiples of 4, 4-byte stores otherwise.
+ * Bytes outside the rows are not touched.  Queued on `stream`; the Lanczos filter waits for it (the tables are the call's). */
+#define TM_SCALE_LANCZOS3 0
+#define TM_SCALE_NEAREST  1
+#define TM_SCALE_MAX_SIZE 32768
+TM_API int tm_probe_scale_host(int src_w, int src_h, int dst_w, int dst_h, int filter);
+TM_API int tm_scale_rgb32_host(const uint32_t *src, int64_t src_stride_px, int src_w, int src_h,
+                               uint32_t *dst, int64_t dst_stride_px, int dst_w, int dst_h, int filter);
+TM_API int tm_stage_scale_rgb32(const void *src, int64_t src_stride_px, int64_t src_frame_px, int nframes, int src_w, int src_h,
+                                void *dst, int64_t dst_stride_px, int64_t dst_frame_px, int dst_w, int dst_h, int filter, void *stream);
+/* tm_render_frames / tm_render_frames_yuv at another size: the same frames, resampled (out: [frame_count][out_h][out_w]; for the YUV call
+ * dst->width and dst->height give the size).  The frames are drawn at tm_w*8 x tm_h*8 in chunks of at most 32 frames or 256 MB, scaled
+ * behind the render, then delivered or converted.  The refusals of the unscaled calls and of tm_probe_scale_host apply, before any device
+ * call; a device group reads what the unscaled twin reads.  Blocking. */
+TM_API int tm_render_frames_scaled(tm_encoder *, int first_frame, int frame_count, int input, int out_w, int out_h, int filter,
+                                   void *out, int out_on_device);
+TM_API int tm_render_frames_yuv_scaled(tm_encoder *, int first_frame, int frame_count, int input, const tm_yuv_out *dst, int mode, int filter);
 /* Pixel-domain quality of the decoded output against the source, frames [first_frame, first_frame+frame_count), over tm_w*8 x tm_h*8:
  * sse [count][3] exact squared errors of R, G, B; psnr [count] = 10 log10(3 W H 255^2 / (SSE_R+SSE_G+SSE_B)), +inf for SSE 0;
  * ssim_y [count] = mean SSIM of the 8x8 windows on a 4-pixel grid of GenerateY4M's Y plane (c1 = (64*0.01*255)^2, c2 = (64*0.03*255)^2 on
@@ -408,6 +437,15 @@ TM_API int tm_player_read(tm_player *, int count, void *out, int out_on_device, 
  * would deliver more than dst->frames frames: min(count, frames left)) leaves position and destination untouched. */
 TM_API int tm_player_read_yuv(tm_player *, int count, const tm_yuv_out *dst, int mode, int *got);
 /* the next read starts at `frame` (0 .. frames; frames = the end): restarts at the key frame at or before it and plays forward without delivering */
+/* The size frames are delivered at (0, 0: the stream's own, the default; filter: TM_SCALE_*).  May be called between any two reads; the
+ * position does not move.  Refuses what tm_probe_scale_host refuses (and a size of which only one part is 0: TM_E_INVAL) and then leaves
+ * the setting as it was.  With a size set, tm_player_read delivers [count][height][width] and tm_player_read_yuv wants a tm_yuv_out of
+ * that width and height.  The player goes on playing at the stream's size into a ring of its own (a predicted item reads the previous
+ * native frame; the kept last frame stays native) and scales a chunk behind its frames on the same stream, in one launch: straight into a
+ * device destination, through a ring of two scaled chunks (one copy per chunk) into a host destination, through the scaled ring into the
+ * YUV conversion.  A seek's catching up scales nothing.  tm_player_info keeps reporting the stream's size. */
+TM_API int tm_player_set_output(tm_player *, int width, int height, int filter);
+TM_API int tm_player_get_output(tm_player *, int *width, int *height, int *filter);  /* 0, 0: none set */
 TM_API int tm_player_seek(tm_player *, int frame);
 TM_API int tm_player_tell(tm_player *);  /* the frame the next read starts at */
 /* wall ms since open, summed: LZMA decode, command parse (both on the worker thread when there is one), record staging + upload calls,

@@ -81,7 +81,21 @@ SIGNATURES = {
     "tm_read_png_host": (c_int, [c_char_p, c_void_p, c_int64, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "tm_inflate_host": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "tm_resample_taps_host": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "tm_probe_scale_host": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "tm_scale_rgb32_host": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int]),
+    "tm_stage_scale_rgb32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p]),
 }
+
+
+SCALE_FILTERS = {"lanczos": 0, "nearest": 1}  # TM_SCALE_*
+
+
+def scale_filter_of(filter):
+    if isinstance(filter, str):
+        if filter not in SCALE_FILTERS:
+            raise ValueError("unknown scaling filter %r (one of %s)" % (filter, " ".join(SCALE_FILTERS)))
+        return SCALE_FILTERS[filter]
+    return int(filter)
 
 
 def lib():

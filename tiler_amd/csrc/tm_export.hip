@@ -355,6 +355,77 @@ int tm_render_frames_yuv(tm_encoder *e, int first_frame, int frame_count, int in
   return TM_OK;
 }
 
+// ---- the same frames at a caller's size (tm_scale.hip): drawn natively a chunk at a time -- at most 32 frames or
+// 256 MB, of either size -- scaled behind the render on the encoder's stream, then delivered or converted
+static int scaled_chunk_frames(int frame_count, size_t native_bytes, size_t scaled_bytes) {
+  return (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(frame_count, 32), ((size_t)256 << 20) / std::max(native_bytes, scaled_bytes)));
+}
+
+int tm_render_frames_scaled(tm_encoder *e, int first_frame, int frame_count, int input, int out_w, int out_h, int filter, void *out, int out_on_device) {
+  TM_CHECK(e && (out || frame_count == 0), TM_E_INVAL, "null argument");
+  TM_TRY(render_range_ok(e, first_frame, frame_count));
+  const int sw = e->tm_w * 8, sh = e->tm_h * 8;
+  ScaleTables tables;
+  TM_TRY(tables.prepare(sw, sh, out_w, out_h, filter));
+  const bool gathered = e->grp && input && e->load_sharded;  // tm_render_frames asks every shard for its piece (and makes the checks there)
+  RenderMap m{};
+  RenderInput in{};
+  if (!gathered) TM_TRY(input ? render_input_src(e, first_frame, frame_count, &in) : render_output_map(e, &m));
+  if (frame_count == 0) return TM_OK;
+  TM_HIP(hipSetDevice(e->device));
+  const int64_t spx = (int64_t)sw * sh, opx = (int64_t)out_w * out_h;
+  const int chunk = scaled_chunk_frames(frame_count, (size_t)spx * 4, (size_t)opx * 4);
+  DevBuf native, scaled;
+  TM_TRY(native.alloc((size_t)spx * 4 * chunk));
+  if (!out_on_device) TM_TRY(scaled.alloc((size_t)opx * 4 * chunk));
+  TM_TRY(tables.upload(e->stream));
+  for (int f0 = 0; f0 < frame_count; f0 += chunk) {
+    const int nf = std::min(chunk, frame_count - f0);
+    TM_TRY(tm_render_frames(e, first_frame + f0, nf, input, native.p, 1));  // (blocking: the chunk before has left `native` and `scaled`)
+    TM_HIP(hipSetDevice(e->device));
+    uint32_t *to = out_on_device ? (uint32_t *)out + opx * f0 : scaled.as<uint32_t>();
+    TM_TRY(launch_scale_rgb32(tables, native.p, sw, spx, nf, to, out_w, opx, e->stream));
+    if (!out_on_device) TM_HIP(hipMemcpyAsync((uint32_t *)out + opx * f0, to, (size_t)opx * 4 * nf, hipMemcpyDeviceToHost, e->stream));
+    TM_HIP(hipStreamSynchronize(e->stream));
+  }
+  return TM_OK;
+}
+
+int tm_render_frames_yuv_scaled(tm_encoder *e, int first_frame, int frame_count, int input, const tm_yuv_out *dst, int mode, int filter) {
+  TM_CHECK(e, TM_E_INVAL, "null argument");
+  TM_CHECK(dst, TM_E_INVAL, "yuv out: null descriptor");
+  TM_TRY(render_range_ok(e, first_frame, frame_count));
+  const int sw = e->tm_w * 8, sh = e->tm_h * 8, ow = dst->width, oh = dst->height;
+  ScaleTables tables;
+  TM_TRY(tables.prepare(sw, sh, ow, oh, filter));
+  YuvOutPlan plan;
+  TM_TRY(check_yuv_out(dst, ow, oh, mode, &plan));
+  TM_CHECK(frame_count <= dst->frames, TM_E_INVAL, "yuv out: %d frames asked for, room for %d", frame_count, dst->frames);
+  RenderMap m{};
+  RenderInput in{};
+  TM_TRY(input ? render_input_src(e, first_frame, frame_count, &in) : render_output_map(e, &m));  // (shard 0 of a group, as tm_render_frames_yuv reads)
+  TM_HIP(hipSetDevice(e->device));
+  const bool to_device = dst->memory == TM_MEM_DEVICE;
+  if (to_device) TM_TRY(yuv_out_is_device(*dst, e->device));
+  if (frame_count == 0) return TM_OK;
+  const int64_t spx = (int64_t)sw * sh, opx = (int64_t)ow * oh;
+  const int chunk = scaled_chunk_frames(frame_count, (size_t)spx * 4, (size_t)opx * 4);
+  DevBuf native, scaled, packed;
+  TM_TRY(native.alloc((size_t)spx * 4 * chunk));
+  TM_TRY(scaled.alloc((size_t)opx * 4 * chunk));
+  if (!to_device) TM_TRY(packed.alloc((size_t)plan.frame_bytes() * chunk));
+  TM_TRY(tables.upload(e->stream));
+  for (int f0 = 0; f0 < frame_count; f0 += chunk) {
+    const int nf = std::min(chunk, frame_count - f0);
+    TM_TRY(input ? launch_render_input(in, first_frame + f0, nf, native.p, e->stream) : launch_render_output(m, first_frame + f0, nf, native.p, e->stream));
+    TM_TRY(launch_scale_rgb32(tables, native.p, sw, spx, nf, scaled.p, ow, opx, e->stream));
+    TM_TRY(launch_rgb32_to_yuv(plan, scaled.p, ow, nf, to_device ? yuv_dst_of(*dst, f0) : yuv_dst_packed(plan, packed.as<uint8_t>(), chunk, 0), e->stream));
+    if (!to_device) TM_TRY(yuv_copy_out(plan, packed.as<uint8_t>(), chunk, *dst, f0, nf, e->stream));
+  }
+  TM_HIP(hipStreamSynchronize(e->stream));
+  return TM_OK;
+}
+
 int tm_get_frame_quality(tm_encoder *e, int first_frame, int frame_count, uint64_t *sse, double *psnr, double *ssim_y, double *clip_psnr,
                          double *clip_ssim_y) {
   TM_CHECK(e, TM_E_INVAL, "null encoder");

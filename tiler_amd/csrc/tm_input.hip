@@ -1,5 +1,5 @@
 // tm_input.hip -- Load's input: the probe half of Load (tilingencoder.pas:1764-1820) for Y4M files and numbered PNG sequences, YUV clips lent
-// in memory (tm_set_frames_yuv), the Lanczos-3 resampling tables, and the kernel that turns planes of Y, U, V into the RGB32 frames Load reads.
+// in memory (tm_set_frames_yuv), and the kernel that turns planes of Y, U, V into the RGB32 frames Load reads (its Lanczos-3 tables: tm_resample.hip).
 //
 // The reference opens "any file" through FFmpeg and scales with libswscale's Lanczos (extern.pas:780-781, 837-840).  Neither exists here
 // (DESIGN.md sections 9 and 17): Y4M is the uncompressed container every FFmpeg build writes, and the resampler is a stated integer rule of
@@ -19,49 +19,6 @@
 #include "tm_encoder.h"
 
 namespace tmx {
-
-// ---- resampling tables (host) ----------------------------------------------------------------------------------
-static double lanczos3(double t) {
-  t = std::fabs(t);
-  if (t >= 3.0) return 0.0;
-  if (t == 0.0) return 1.0;
-  const double x = M_PI * t;
-  return (std::sin(x) / x) * (std::sin(x / 3.0) / (x / 3.0));
-}
-
-// one axis: n luma samples in, m samples out, a plane of np samples at luma positions s k + o_halves / 2.  first / count [m], coef [m][64].
-int resample_taps(int n, int m, int np, int s, int o_halves, int32_t *first, int32_t *count, int32_t *coef, int64_t *sum_abs_max) {
-  TM_CHECK(n > 0 && m > 0 && np > 0 && (s == 1 || s == 2) && (o_halves == 0 || o_halves == 1), TM_E_INVAL, "resample: bad axis %d -> %d (plane %d, step %d)", n, m, np, s);
-  const double r = (double)n / (double)m;
-  TM_CHECK(r / s <= 8.0, TM_E_UNSUPPORTED, "resample: %d -> %d samples shrinks by more than 8 (more than %d taps)", n, m, TM_RESAMPLE_MAX_TAPS);
-  const double f = std::max(1.0, r / s), o = o_halves * 0.5;
-  int64_t amax = 0;
-  for (int j = 0; j < m; j++) {
-    const double x = (j + 0.5) * r - 0.5;
-    const double u = (x - o) / s;
-    const int k0 = (int)std::max(0.0, std::ceil(u - 3.0 * f)), k1 = (int)std::min((double)(np - 1), std::floor(u + 3.0 * f));
-    const int cnt = k1 - k0 + 1;
-    TM_CHECK(cnt >= 1 && cnt <= TM_RESAMPLE_MAX_TAPS, TM_E_UNSUPPORTED, "resample: %d taps for sample %d of %d -> %d", cnt, j, n, m);
-    double w[TM_RESAMPLE_MAX_TAPS], tot = 0.0;
-    for (int k = 0; k < cnt; k++) { w[k] = lanczos3(((double)(k0 + k) - u) / f); tot += w[k]; }
-    int32_t *c = coef + (size_t)j * TM_RESAMPLE_MAX_TAPS;
-    int64_t sum = 0, sa = 0;
-    int best = 0;
-    for (int k = 0; k < TM_RESAMPLE_MAX_TAPS; k++) c[k] = 0;
-    for (int k = 0; k < cnt; k++) {
-      c[k] = (int32_t)std::nearbyint(w[k] / tot * 16384.0);  // (round half to even: the default rounding mode)
-      sum += c[k];
-      if (w[k] > w[best]) best = k;  // the lowest k on a tie
-    }
-    c[best] += (int32_t)(16384 - sum);
-    for (int k = 0; k < cnt; k++) sa += std::abs(c[k]);
-    amax = std::max(amax, sa);
-    first[j] = k0;
-    count[j] = cnt;
-  }
-  if (sum_abs_max) *sum_abs_max = amax;
-  return TM_OK;
-}
 
 // where a layout's chroma samples sit: step and offset (in halves of a luma sample) per axis, plane size
 struct ChromaGeom { int sx, sy, ox, oy, cw, ch; };
@@ -86,7 +43,8 @@ static int chroma_geom(int chroma, int w, int h, ChromaGeom *g) {
 // The samples are read in one place, the horizontal pass, and how is a compile-time property of the kernel: BYTES per sample (1, or 2 for
 // little-endian words) and CSTEP, the distance in samples between a chroma plane's neighbours (2 where U and V alternate in one plane: NV12,
 // P010; V's plane then starts one sample behind U's).  Words become bytes right there (DeepRule), so everything behind the fetch is the 8-bit rule.
-constexpr int IN_TW = 64, IN_HROWS = 96, IN_TH_MAX = 16;
+constexpr int IN_TW = 64, IN_HROWS = 96;
+static_assert(RESAMPLE_TH_MAX * 16 == 256, "a workgroup's 256 lanes: 16 per output row of the tile");
 struct PlaneSrc { const uint8_t *p; int64_t row, frame; };  // strides in bytes
 struct DeepRule { int rshift, mask, half, nshift; };  // p_d = (word >> rshift) & mask;  p = min(255, (p_d + half) >> nshift), half = 2^(nshift - 1)
 
@@ -201,93 +159,31 @@ __global__ __launch_bounds__(256) void k_yuv_to_rgb32(PlaneSrc sy, PlaneSrc su, 
     for (int j = 0; j < 4 && x0 + tx + j < dst_w; j++) o[j] = px[j];
 }
 
-// ---- the tables of one conversion (InputTables, tm_internal.h), made once per (source size, layout, output size) and kept on the device
-// the source rows the samples of every tile of th output rows reach, as (first row, number of rows) per tile
-static std::vector<int32_t> tile_spans(const std::vector<int32_t> &first, const std::vector<int32_t> &count, int m, int th, int *widest) {
-  std::vector<int32_t> sp;
-  for (int y0 = 0; y0 < m; y0 += th) {
-    int r0 = INT32_MAX, r1 = 0;
-    for (int y = y0; y < std::min(y0 + th, m); y++) { r0 = std::min(r0, first[y]); r1 = std::max(r1, first[y] + count[y]); }
-    sp.push_back(r0); sp.push_back(r1 - r0);
-    *widest = std::max(*widest, r1 - r0);
-  }
-  return sp;
-}
-// the tile height: the largest of 16, 8, 4, 2, 1 for which no tile's vertical taps reach more than IN_HROWS source rows
-static int in_tile_rows(const std::vector<int32_t> *firsts, const std::vector<int32_t> *counts, int nplanes, int m) {
-  for (int th = IN_TH_MAX; th >= 1; th /= 2) {
-    int widest = 0;
-    for (int p = 0; p < nplanes; p++) tile_spans(firsts[p], counts[p], m, th, &widest);
-    if (widest <= IN_HROWS) return th;
-  }
-  return 0;
-}
-
+// ---- the tables of one conversion (InputTables, tm_internal.h), made once per (source size, layout, output size) and kept on the device.
+// The rule's tables, their trimming, the tile spans and the device layout are tm_resample.hip's; here: which axes a layout has.
 static int build_input_tables(int src_w, int src_h, int chroma, int dst_w, int dst_h, InputTables *t, hipStream_t stream) {
   if (t->dev.p && t->src_w == src_w && t->src_h == src_h && t->chroma == chroma && t->dst_w == dst_w && t->dst_h == dst_h) return TM_OK;
   ChromaGeom g;
   TM_TRY(chroma_geom(chroma, src_w, src_h, &g));
   const bool has_c = chroma != TM_CHROMA_MONO;
+  const int na = has_c ? 4 : 2;
   // axis tables: 0 luma horizontal, 1 luma vertical, 2 chroma horizontal, 3 chroma vertical
-  std::vector<int32_t> first[4], count[4], coef[4];
-  int64_t amax[4] = {0, 0, 0, 0};
-  const int m[4] = {dst_w, dst_h, dst_w, dst_h};
-  for (int a = 0; a < (has_c ? 4 : 2); a++) {
-    first[a].resize(m[a]); count[a].resize(m[a]); coef[a].resize((size_t)m[a] * TM_RESAMPLE_MAX_TAPS);
+  AxisTable ax[4];
+  for (int a = 0; a < na; a++) {
     const bool horiz = (a & 1) == 0, c = a >= 2;
-    TM_TRY(resample_taps(horiz ? src_w : src_h, m[a], c ? (horiz ? g.cw : g.ch) : (horiz ? src_w : src_h), c ? (horiz ? g.sx : g.sy) : 1,
-                         c ? (horiz ? g.ox : g.oy) : 0, first[a].data(), count[a].data(), coef[a].data(), &amax[a]));
+    TM_TRY(ax[a].make(horiz ? src_w : src_h, horiz ? dst_w : dst_h, c ? (horiz ? g.cw : g.ch) : (horiz ? src_w : src_h), c ? (horiz ? g.sx : g.sy) : 1,
+                      c ? (horiz ? g.ox : g.oy) : 0));
   }
-  // the vertical sum fits int32: |h| <= 255 A_h / 128 + 1, |sum| <= that times A_v
-  for (int a = 0; a < (has_c ? 4 : 2); a += 2)
-    TM_CHECK((255 * amax[a] / 128 + 1) * amax[a + 1] < (1ll << 31), TM_E_UNSUPPORTED, "resample: the coefficients of %dx%d -> %dx%d overflow the 32-bit sums",
-             src_w, src_h, dst_w, dst_h);
-  // On the device a sample's taps start at its first and end at its last coefficient that is not 0 (the sums are the same): at equal size
-  // the window still spans the six neighbours at whole distances, whose weights sin(k pi) round to 0 -- one tap is left, the sample itself.
-  for (int a = 0; a < (has_c ? 4 : 2); a++)
-    for (int j = 0; j < m[a]; j++) {
-      int32_t *c = &coef[a][(size_t)j * TM_RESAMPLE_MAX_TAPS];
-      int lo = 0, hi = count[a][j];
-      while (hi - lo > 1 && c[hi - 1] == 0) hi--;
-      while (hi - lo > 1 && c[lo] == 0) lo++;
-      for (int k = 0; k < hi - lo; k++) c[k] = c[lo + k];
-      first[a][j] += lo;
-      count[a][j] = hi - lo;
-    }
-  // (trimmed windows need no longer be ordered along the axis: the rows a tile reaches are the span of all its samples' windows)
-  const std::vector<int32_t> vf[2] = {first[1], first[3]}, vc[2] = {count[1], count[3]};
-  const int th = in_tile_rows(vf, vc, has_c ? 2 : 1, dst_h);
+  for (int a = 0; a < na; a += 2) TM_TRY(check_resample_sums(ax[a], ax[a + 1], src_w, src_h, dst_w, dst_h));
+  for (int a = 0; a < na; a++) ax[a].trim();
+  const AxisTable *const vert[2] = {&ax[1], &ax[3]};
+  const int th = resample_tile_rows(vert, has_c ? 2 : 1, IN_HROWS);
   TM_CHECK(th > 0, TM_E_UNSUPPORTED, "resample: %d -> %d rows reach too many source rows per tile", src_h, dst_h);
-  // device layout per axis: first [m], count [m], coef [maxcount][m], and for a vertical axis its tiles' spans
-  std::vector<int32_t> host;
-  size_t off[4][4];
-  for (int a = 0; a < (has_c ? 4 : 2); a++) {
-    int mc = 0;
-    for (int j = 0; j < m[a]; j++) mc = std::max(mc, count[a][j]);
-    off[a][0] = host.size(); host.insert(host.end(), first[a].begin(), first[a].end());
-    off[a][1] = host.size(); host.insert(host.end(), count[a].begin(), count[a].end());
-    off[a][2] = host.size(); host.resize(host.size() + (size_t)mc * m[a]);
-    for (int k = 0; k < mc; k++)
-      for (int j = 0; j < m[a]; j++) host[off[a][2] + (size_t)k * m[a] + j] = coef[a][(size_t)j * TM_RESAMPLE_MAX_TAPS + k];
-    host.resize((host.size() + 1) & ~(size_t)1);  // (the spans are read as pairs)
-    off[a][3] = host.size();
-    if (a & 1) {
-      int widest = 0;
-      const std::vector<int32_t> sp = tile_spans(first[a], count[a], m[a], th, &widest);
-      TM_CHECK(widest <= IN_HROWS, TM_E_UNSUPPORTED, "resample: a tile reaches %d source rows", widest);  // (what in_tile_rows chose th for)
-      host.insert(host.end(), sp.begin(), sp.end());
-    }
-  }
-  TM_HIP(hipStreamSynchronize(stream));  // a conversion in flight may still read the tables being replaced
-  TM_TRY(t->dev.alloc(host.size() * 4));
-  TM_HIP(hipMemcpyAsync(t->dev.p, host.data(), host.size() * 4, hipMemcpyHostToDevice, stream));
-  TM_HIP(hipStreamSynchronize(stream));  // (`host` goes out of scope)
-  AxisTaps *ax[4] = {&t->lh, &t->lv, &t->ch, &t->cv};
-  for (int a = 0; a < 4; a++) {
-    const int s = has_c ? a : (a & 1);  // Cmono: the chroma tables are never read
-    *ax[a] = AxisTaps{t->dev.as<int32_t>() + off[s][0], t->dev.as<int32_t>() + off[s][1], t->dev.as<int32_t>() + off[s][2],
-                      reinterpret_cast<const int2 *>(t->dev.as<int32_t>() + off[s][3])};
-  }
+  const AxisTable *const all[4] = {&ax[0], &ax[1], &ax[2], &ax[3]};
+  AxisTaps dev[4];
+  TM_TRY(upload_axis_tables(all, na, th, IN_HROWS, &t->dev, dev, stream));
+  t->lh = dev[0]; t->lv = dev[1];
+  t->ch = dev[has_c ? 2 : 0]; t->cv = dev[has_c ? 3 : 1];  // Cmono: the chroma tables are never read
   t->src_w = src_w; t->src_h = src_h; t->chroma = chroma; t->dst_w = dst_w; t->dst_h = dst_h; t->th = th;
   return TM_OK;
 }

@@ -180,11 +180,43 @@ int probe_input(const std::string &name, int start_frame, int frame_count, doubl
 // the resampling tables of one conversion on the device: per axis first [m], count [m], coef [tap][m] (the lanes of a wave read neighbouring
 // words); a vertical axis also has, per tile of th output rows, the source rows its samples reach as (first row, number of rows)
 struct AxisTaps { const int32_t *first, *count, *coef; const int2 *span; };
+// tm_resample.hip (host only): the rule's tables, shared by tm_input.hip (YUV planes in) and tm_scale.hip (RGB32 frames out)
+int resample_taps(int n, int m, int np, int s, int o_halves, int32_t *first, int32_t *count, int32_t *coef, int64_t *sum_abs_max);
+constexpr int RESAMPLE_TH_MAX = 16;  // output rows per workgroup, at most
+struct AxisTable {  // one axis on the host: first / count [m], coef [m][TM_RESAMPLE_MAX_TAPS], the largest sum of |coefficients| of a sample
+  int m = 0;
+  int64_t amax = 0;
+  std::vector<int32_t> first, count, coef;
+  int make(int n, int m_out, int np, int s, int o_halves);      // resample_taps
+  void trim();                                                  // a sample's window shrinks to its coefficients that are not 0
+  std::vector<int32_t> tile_spans(int th, int *widest) const;   // per tile of th samples: (first source sample, number of them)
+};
+int check_resample_sums(const AxisTable &h, const AxisTable &v, int src_w, int src_h, int dst_w, int dst_h);  // the vertical sum fits 32 bits
+int resample_tile_rows(const AxisTable *const *vertical, int nplanes, int max_rows);  // th (0: not even one row's taps fit)
+// the axes in the device layout above; odd ones are vertical and get the spans of tiles of th rows (none may reach more than max_rows)
+int upload_axis_tables(const AxisTable *const *axes, int naxes, int th, int max_rows, DevBuf *dev, AxisTaps *out, hipStream_t stream);
 struct InputTables {
   int src_w = 0, src_h = 0, chroma = -1, dst_w = 0, dst_h = 0, th = 0;  // th: output rows per workgroup
   DevBuf dev;
   AxisTaps lh{}, lv{}, ch{}, cv{};  // luma / chroma, horizontal / vertical
 };
+
+// tm_scale.hip: RGB32 frames [n][h][stride] 0x00RRGGBB at another size.  probe_scale: the sizes and the filter;
+// check_scale_args: those, the pointers, the strides in pixels and the overlap -- neither makes a device call.
+int probe_scale(int src_w, int src_h, int dst_w, int dst_h, int filter);
+int check_scale_args(const void *src, int64_t src_stride_px, int64_t src_frame_px, int nframes, int src_w, int src_h, const void *dst, int64_t dst_stride_px,
+                     int64_t dst_frame_px, int dst_w, int dst_h, int filter);
+struct ScaleTables {  // the tables of one (source size, output size, filter), kept until another is asked for
+  int src_w = 0, src_h = 0, dst_w = 0, dst_h = 0, filter = 0, th = 0;  // th: output rows per workgroup
+  bool ready = false, on_device = false;
+  AxisTable h, v;  // TM_SCALE_LANCZOS3 only
+  DevBuf dev;
+  AxisTaps taps_h{}, taps_v{};
+  int prepare(int src_w, int src_h, int dst_w, int dst_h, int filter);  // host: every refusal of the size pair, no device call
+  int upload(hipStream_t stream);                                       // drains the stream when there is something to upload
+};
+int launch_scale_rgb32(const ScaleTables &t, const void *src, int64_t src_stride_px, int64_t src_frame_px, int nframes, void *dst, int64_t dst_stride_px,
+                       int64_t dst_frame_px, hipStream_t stream);
 
 // One process per GPU: the collectives a step needs between its kernels, handed in by the host (tm_set_collective).  The calls
 // are made on the caller's thread with the encoder's stream idle, and return with the result in place.

@@ -15,7 +15,8 @@
 //   host    the records of two key frames (playing + decoded ahead): frames_in_kf * tm_w * tm_h * 8 bytes + 64 per intra item;
 //           two page-locked chunks of chunk_frames * tm_w * tm_h * 72 bytes (every item intra: the worst case)
 //   device  the TileSet (64 bytes per tile), the palettes, two chunks as above, one kept frame (the last one delivered: the next call's
-//           "previous frame"), and -- only for host destinations and seeks -- a ring of 2 * chunk_frames frames
+//           "previous frame"), and -- only for host destinations and seeks -- a ring of 2 * chunk_frames frames; with an output size
+//           (tm_player_set_output) that ring always, the tables, and for host and YUV destinations a ring of 2 * chunk_frames scaled frames
 // chunk_frames = 8 MB worth of worst-case records, at least 1, at most 16 (TM_PLAYER_CHUNK_FRAMES overrides).
 //
 // Refusals are decided on the host before any device call: tm_player_open touches the device only after the header, the index and the
@@ -312,6 +313,10 @@ struct tm_player {
   hipStream_t play = nullptr, copy = nullptr;
   DevBuf d_tiles, d_pal, d_chunk[2], d_kept, d_ring;
   DevBuf d_yuv;               // host YUV destinations: a ring of two packed chunks of planes
+  // an output size (tm_player_set_output; 0, 0: the stream's own): frames are played into the ring and scaled a chunk at a time
+  int out_w = 0, out_h = 0, out_filter = TM_SCALE_LANCZOS3;
+  ScaleTables scale;
+  DevBuf d_scaled;            // host and YUV destinations at an output size: a ring of two scaled chunks
   PinnedBuf h_chunk[2];
   Events2 up, done;
   bool used[2] = {false, false};
@@ -327,7 +332,7 @@ struct tm_player {
       (void)hipSetDevice(device);
       if (play) { (void)hipStreamSynchronize(play); (void)hipStreamDestroy(play); }
       if (copy) { (void)hipStreamSynchronize(copy); (void)hipStreamDestroy(copy); }
-      for (DevBuf *b : {&d_tiles, &d_pal, &d_chunk[0], &d_chunk[1], &d_kept, &d_ring, &d_yuv}) b->release();  // (here: the pool files a block under the current device)
+      for (DevBuf *b : {&d_tiles, &d_pal, &d_chunk[0], &d_chunk[1], &d_kept, &d_ring, &d_yuv, &d_scaled, &scale.dev}) b->release();  // (here: the pool files a block under the current device)
     }
     if (fd >= 0) close(fd);
   }
@@ -438,8 +443,11 @@ struct tm_player {
     return TM_OK;
   }
   int queue_chunks(int count, uint32_t *dev_out, uint32_t *host_out, int *n_done_out, bool *between_chunks, const YuvSink *yuv) {
-    const bool ring = dev_out == nullptr;
+    const bool scaled = out_w > 0 && (dev_out || host_out || yuv);  // (a seek's catching up scales nothing)
+    const int64_t opx = (int64_t)out_w * out_h;
+    const bool ring = dev_out == nullptr || scaled;
     if (ring && count > 0) TM_TRY(d_ring.alloc((size_t)2 * chunk * fpx * 4));
+    if (scaled && !dev_out && count > 0) TM_TRY(d_scaled.alloc((size_t)2 * chunk * opx * 4));
     const bool yuv_host = yuv && yuv->dst->memory == TM_MEM_HOST;
     const size_t yuv_chunk = yuv_host ? (size_t)yuv->plan.frame_bytes() * chunk : 0;
     if (yuv_host && count > 0) TM_TRY(d_yuv.alloc(2 * yuv_chunk));
@@ -472,14 +480,20 @@ struct tm_player {
         TM_TRY(launch_play_frame(d_chunk[b].as<uint8_t>() + (size_t)i * per * sizeof(PlayRec), d_chunk[b].as<uint8_t>() + rb + (size_t)(f0 - i0) * 64, f1 - f0, d_tiles.p,
                                  tileset_tiles, d_pal.p, pal_count, head.pal_size, prev, dst, head.tm_w, head.tm_h, play));
         prev = dst;
-        if (yuv) {
+        if (yuv && !scaled) {
           const YuvDst to = yuv_host ? yuv_dst_packed(yuv->plan, d_yuv.as<uint8_t>() + yuv_chunk * b, chunk, i) : yuv_dst_of(*yuv->dst, n_done + i);
           TM_TRY(launch_rgb32_to_yuv(yuv->plan, dst, head.tm_w * 8, 1, to, play));
         }
       }
       TM_HIP(hipEventRecord(done.ev[b], play));
+      if (scaled) {  // the chunk's frames in one launch, behind them: into the caller's device buffer, or into the scaled ring
+        uint32_t *to = dev_out ? dev_out + (int64_t)n_done * opx : d_scaled.as<uint32_t>() + (int64_t)b * chunk * opx;
+        TM_TRY(launch_scale_rgb32(scale, d_ring.as<uint32_t>() + (int64_t)b * chunk * fpx, head.tm_w * 8, fpx, n, to, out_w, opx, play));
+        if (yuv) TM_TRY(launch_rgb32_to_yuv(yuv->plan, to, out_w, n, yuv_host ? yuv_dst_packed(yuv->plan, d_yuv.as<uint8_t>() + yuv_chunk * b, chunk, 0) : yuv_dst_of(*yuv->dst, n_done), play));
+        if (host_out) TM_HIP(hipMemcpyAsync(host_out + (int64_t)n_done * opx, to, (size_t)n * opx * 4, hipMemcpyDeviceToHost, play));
+      }
       if (yuv_host) TM_TRY(yuv_copy_out(yuv->plan, d_yuv.as<uint8_t>() + yuv_chunk * b, chunk, *yuv->dst, n_done, n, play));
-      if (host_out) TM_HIP(hipMemcpyAsync(host_out + (int64_t)n_done * fpx, d_ring.as<uint32_t>() + (int64_t)b * chunk * fpx, (size_t)n * fpx * 4, hipMemcpyDeviceToHost, play));
+      if (host_out && !scaled) TM_HIP(hipMemcpyAsync(host_out + (int64_t)n_done * fpx, d_ring.as<uint32_t>() + (int64_t)b * chunk * fpx, (size_t)n * fpx * 4, hipMemcpyDeviceToHost, play));
       ms_launch += now_ms() - t0;
       if (first_frame_ms < 0 && (dev_out || host_out || yuv)) {  // (once in a player's life: the wait is part of what is measured)
         TM_HIP(hipStreamSynchronize(play));
@@ -489,6 +503,19 @@ struct tm_player {
       *between_chunks = true;
     }
     return TM_OK;
+  }
+
+  // tm_player_set_output: the tables are made and uploaded before the setting changes, so that a refusal leaves it as it was
+  int set_output(int width, int height, int filter) {
+    if (width == 0 && height == 0) { out_w = out_h = 0; out_filter = TM_SCALE_LANCZOS3; return TM_OK; }
+    ScaleTables next;
+    TM_TRY(next.prepare(head.tm_w * 8, head.tm_h * 8, width, height, filter));
+    DeviceScope scope;
+    TM_HIP(hipSetDevice(device));
+    const int rc = next.upload(play);
+    if (rc == TM_OK) { std::swap(scale, next); out_w = width; out_h = height; out_filter = filter; }
+    next.dev.release();  // (here: the pool files a block under the current device)
+    return rc;
   }
 
   int seek(int frame) {
@@ -572,7 +599,8 @@ int tm_player_info(tm_player *p, tm_gtm_info *info) {
   TM_CHECK(p && info, TM_E_INVAL, "null argument");
   fill_info(p->ix, p->head, p->tileset_tiles, p->pal_count, info);
   info->host_bytes = (int64_t)(p->h_chunk[0].bytes + p->h_chunk[1].bytes + p->peak_records + p->ix.kf.size() * sizeof(KfEntry));
-  info->device_bytes = (int64_t)(p->d_tiles.bytes + p->d_pal.bytes + p->d_chunk[0].bytes + p->d_chunk[1].bytes + p->d_kept.bytes + p->d_ring.bytes + p->d_yuv.bytes);
+  info->device_bytes = (int64_t)(p->d_tiles.bytes + p->d_pal.bytes + p->d_chunk[0].bytes + p->d_chunk[1].bytes + p->d_kept.bytes + p->d_ring.bytes + p->d_yuv.bytes +
+                                   p->d_scaled.bytes + p->scale.dev.bytes);
   return TM_OK;
 }
 
@@ -605,7 +633,7 @@ int tm_player_read_yuv(tm_player *p, int count, const tm_yuv_out *dst, int mode,
   *got = 0;
   TM_CHECK(count >= 0, TM_E_INVAL, "read of %d frames", count);
   YuvSink sink{dst, YuvOutPlan()};
-  TM_TRY(check_yuv_out(dst, p->head.tm_w * 8, p->head.tm_h * 8, mode, &sink.plan));
+  TM_TRY(check_yuv_out(dst, p->out_w > 0 ? p->out_w : p->head.tm_w * 8, p->out_w > 0 ? p->out_h : p->head.tm_h * 8, mode, &sink.plan));
   const int deliver = std::min(count, p->ix.frames - p->pos);  // (as tm_player_read: what is left of the stream is what a call delivers)
   TM_CHECK(deliver <= dst->frames, TM_E_INVAL, "yuv out: %d frames to deliver, room for %d", deliver, dst->frames);
   if (dst->memory == TM_MEM_DEVICE) {
@@ -614,6 +642,19 @@ int tm_player_read_yuv(tm_player *p, int count, const tm_yuv_out *dst, int mode,
   }
   if (count == 0) return TM_OK;
   return p->play_frames(count, nullptr, nullptr, got, &sink);
+}
+
+int tm_player_set_output(tm_player *p, int width, int height, int filter) {
+  TM_CHECK(p, TM_E_INVAL, "null argument");
+  return p->set_output(width, height, filter);
+}
+
+int tm_player_get_output(tm_player *p, int *width, int *height, int *filter) {
+  TM_CHECK(p, TM_E_INVAL, "null argument");
+  if (width) *width = p->out_w;
+  if (height) *height = p->out_h;
+  if (filter) *filter = p->out_filter;
+  return TM_OK;
 }
 
 int tm_player_seek(tm_player *p, int frame) {

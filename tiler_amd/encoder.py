@@ -102,6 +102,8 @@ _ENC_SIGS = {
     "tm_generate_pngs": (c_int, [c_void_p, c_int]),
     "tm_render_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int]),
     "tm_render_frames_yuv": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(YuvClip), c_int]),
+    "tm_render_frames_scaled": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int]),
+    "tm_render_frames_yuv_scaled": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(YuvClip), c_int, c_int]),
     "tm_get_frame_quality": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
     "tm_set_query_shard": (c_int, [c_void_p, c_int, c_int]),
     "tm_set_dither_shard": (c_int, [c_void_p, c_int, c_int]),
@@ -443,12 +445,25 @@ class TilingEncoder:
         """GeneratePNGs (tilingencoder.pas:2075): <OutputFileName>_NNNN.png per frame + the palettes as <OutputFileName>.txt"""
         check(self._L.tm_generate_pngs(c_void_p(self._h), int(bool(input))))
 
-    def RenderFrames(self, first=0, count=None, input=False, device=True):
+    def RenderFrames(self, first=0, count=None, input=False, device=True, size=None, filter="lanczos"):
         """The decoded frames [first, first+count) as Render (tilingencoder.pas:3455-3640) draws them with the constructor's defaults -- or
         the source frames (input=True) -- rendered on the device: [count][tm_h*8][tm_w*8] 0x00RRGGBB (the pushed frames' format, alpha 0),
-        as a torch int32 CUDA tensor (device=True) or a numpy uint32 array"""
+        as a torch int32 CUDA tensor (device=True) or a numpy uint32 array.  size=(width, height): the frames resampled on the device to
+        [count][height][width] (tm_render_frames_scaled); filter: "lanczos" or "nearest", as GtmPlayer.SetOutput takes it"""
         c = self.counts()
         count = c["frames"] - first if count is None else count
+        if size is not None:
+            from ._lib import scale_filter_of
+            w, h, flt = int(size[0]), int(size[1]), scale_filter_of(filter)
+            shape = (max(count, 0), max(h, 0), max(w, 0))
+            if device:
+                import torch
+                out = torch.empty(shape, dtype=torch.int32, device="cuda")
+            else:
+                out = np.empty(shape, np.uint32)
+            ptr = c_void_p(out.data_ptr()) if device else out.ctypes.data_as(c_void_p)
+            check(self._L.tm_render_frames_scaled(c_void_p(self._h), first, count, int(bool(input)), w, h, flt, ptr, int(bool(device))))
+            return out
         shape = (max(count, 0), c["tm_h"] * 8, c["tm_w"] * 8)
         if device:
             import torch
@@ -459,12 +474,20 @@ class TilingEncoder:
         check(self._L.tm_render_frames(c_void_p(self._h), first, count, int(bool(input)), out.ctypes.data_as(c_void_p), 0))
         return out
 
-    def RenderFramesYUV(self, first=0, count=None, input=False, layout="nv12", yuv="auto", device=True, out=None, full_range=False):
+    def RenderFramesYUV(self, first=0, count=None, input=False, layout="nv12", yuv="auto", device=True, out=None, full_range=False, size=None,
+                        filter="lanczos"):
         """RenderFrames' frames as YUV planes (tm_render_frames_yuv), converted on the device behind the render: (y, u, v) as
-        GtmPlayer.ReadYUV returns them (layout, yuv, out and full_range as there)"""
+        GtmPlayer.ReadYUV returns them (layout, yuv, out and full_range as there).  size=(width, height): the frames resampled on the device
+        before the conversion (tm_render_frames_yuv_scaled; with `out`, its planes must have that size); filter: "lanczos" or "nearest", as GtmPlayer.SetOutput takes it"""
         from . import yuv_out
         c = self.counts()
         count = c["frames"] - first if count is None else count
+        if size is not None:
+            from ._lib import scale_filter_of
+            planes, d = yuv_out.destination(layout, count, int(size[1]), int(size[0]), "cuda" if device else None, out, full_range)
+            check(self._L.tm_render_frames_yuv_scaled(c_void_p(self._h), first, count, int(bool(input)), ctypes.byref(d), yuv_out.mode_of(yuv),
+                                                      scale_filter_of(filter)))
+            return yuv_out.first(planes, max(count, 0))
         planes, d = yuv_out.destination(layout, count, c["tm_h"] * 8, c["tm_w"] * 8, "cuda" if device else None, out, full_range)
         check(self._L.tm_render_frames_yuv(c_void_p(self._h), first, count, int(bool(input)), ctypes.byref(d), yuv_out.mode_of(yuv)))
         return yuv_out.first(planes, max(count, 0))

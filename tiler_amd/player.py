@@ -5,7 +5,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import lib, check, c_void_p, c_int, c_int64, c_double, c_char_p
+from ._lib import lib, check, scale_filter_of, SCALE_FILTERS, c_void_p, c_int, c_int64, c_double, c_char_p
 from . import yuv_out
 
 
@@ -32,6 +32,8 @@ _SIGS = {
     "tm_player_read": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(c_int)]),
     "tm_player_read_yuv": (c_int, [c_void_p, c_int, ctypes.POINTER(yuv_out.YuvOut), c_int, ctypes.POINTER(c_int)]),
     "tm_player_seek": (c_int, [c_void_p, c_int]),
+    "tm_player_set_output": (c_int, [c_void_p, c_int, c_int, c_int]),
+    "tm_player_get_output": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "tm_player_tell": (c_int, [c_void_p]),
     "tm_player_timings": (c_int, [c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
     "tm_player_close": (None, [c_void_p]),
@@ -145,12 +147,29 @@ class GtmPlayer:
     def Seek(self, frame):
         check(self._L.tm_player_seek(c_void_p(self._h), int(frame)))
 
+    def SetOutput(self, width, height, filter="lanczos"):
+        """the size Read and ReadYUV deliver at from now on (tm_player_set_output): scaled on the device behind the frames; filter "lanczos"
+        or "nearest".  (0, 0): the stream's own size again.  A refused size leaves the setting as it was"""
+        check(self._L.tm_player_set_output(c_void_p(self._h), int(width), int(height), scale_filter_of(filter)))
+
+    def Output(self):
+        """(width, height, filter) as SetOutput left them; (0, 0, "lanczos"): the stream's own size"""
+        w, h, f = c_int(), c_int(), c_int()
+        check(self._L.tm_player_get_output(c_void_p(self._h), ctypes.byref(w), ctypes.byref(h), ctypes.byref(f)))
+        return w.value, h.value, {v: k for k, v in SCALE_FILTERS.items()}[f.value]
+
+    def _size(self, i):
+        """(height, width) of a delivered frame"""
+        w, h, _ = self.Output()
+        return (h, w) if w > 0 else (i["tm_h"] * 8, i["tm_w"] * 8)
+
     def Read(self, count=None, device=True, out=None):
-        """the next `count` frames (None: to the end) as [got][tm_h*8][tm_w*8] 0x00RRGGBB: a torch int32 CUDA tensor (device=True) or a numpy
-        uint32 array; fewer than count only at the end of the stream.  out: a tensor / array of at least that size to fill instead"""
+        """the next `count` frames (None: to the end) as [got][height][width] 0x00RRGGBB -- tm_h*8 x tm_w*8, or the size SetOutput set: a
+        torch int32 CUDA tensor (device=True) or a numpy uint32 array; fewer than count only at the end of the stream.  out: a tensor /
+        array of at least that size to fill instead"""
         i = self.info()
         count = i["frames"] - self.Tell() if count is None else int(count)
-        shape = (max(count, 0), i["tm_h"] * 8, i["tm_w"] * 8)
+        shape = (max(count, 0),) + self._size(i)
         got = c_int()
         if device:
             import torch
@@ -171,7 +190,8 @@ class GtmPlayer:
         bt601-limited).  out: (y, u, v) of at least that size to fill instead (strides are taken from the arrays)"""
         i = self.info()
         count = i["frames"] - self.Tell() if count is None else int(count)
-        planes, d = yuv_out.destination(layout, count, i["tm_h"] * 8, i["tm_w"] * 8, "cuda:%d" % self._device if device else None, out, full_range)
+        height, width = self._size(i)
+        planes, d = yuv_out.destination(layout, count, height, width, "cuda:%d" % self._device if device else None, out, full_range)
         got = c_int()
         check(self._L.tm_player_read_yuv(c_void_p(self._h), count, ctypes.byref(d), yuv_out.mode_of(yuv), ctypes.byref(got)))
         return yuv_out.first(planes, got.value)

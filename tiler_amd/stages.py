@@ -6,7 +6,7 @@ import ctypes
 
 import torch
 
-from ._lib import lib, check
+from ._lib import lib, check, scale_filter_of
 
 
 def _p(t):
@@ -59,6 +59,22 @@ def yuv_to_rgb32_fmt(y, u, v, chroma, dst_w, dst_h, yuv_mode=0, samples=0, depth
     out = torch.empty((f, dst_h, dst_w), dtype=torch.int32, device=y.device)
     check(lib().tm_stage_yuv_to_rgb32_fmt(_p(y), _p(u), _p(v), (ctypes.c_int64 * 6)(*strides), f, w, h, int(chroma), int(samples), int(depth), dst_w, dst_h,
                                           int(yuv_mode), _p(out), _stream()))
+    return out
+
+
+def scale_rgb32(frames, size, filter="lanczos", out=None):
+    """RGB32 frames at another size (tm_stage_scale_rgb32, the kernel behind GtmPlayer.SetOutput and RenderFrames(size=...)): frames int32
+    [F][H][W'] 0x00RRGGBB with a dense last axis; size (width, height); filter "lanczos" (the Lanczos-3 rule of yuv_to_rgb32, per channel) or
+    "nearest".  out: an int32 CUDA tensor [F][height][width'] to fill (strides are taken from it) -> int32 [F][height][width], top byte 0"""
+    assert frames.is_cuda and frames.dtype == torch.int32 and frames.dim() == 3 and frames.stride(2) == 1
+    f, h, w = frames.shape
+    dw, dh = int(size[0]), int(size[1])
+    if out is None:
+        out = torch.empty((f, max(dh, 0), max(dw, 0)), dtype=torch.int32, device=frames.device)
+    if not (out.is_cuda and out.dtype == torch.int32 and out.dim() == 3 and out.stride(2) == 1 and tuple(out.shape) == (f, dh, dw)):
+        raise ValueError("scale_rgb32: out must be an int32 CUDA tensor of %d frames of %d x %d with a dense last axis" % (f, dw, dh))
+    check(lib().tm_stage_scale_rgb32(_p(frames), frames.stride(1), frames.stride(0), f, w, h, _p(out), out.stride(1), out.stride(0), dw, dh, scale_filter_of(filter),
+                                     _stream()))
     return out
 
 

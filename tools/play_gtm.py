@@ -1,12 +1,15 @@
 """Frames of a .gtm stream, played on the device:
 python tools/play_gtm.py IN.gtm [--start N --frames N] (--info | --raw OUT.rgb | --y4m OUT.y4m [--chroma 444|422|420jpeg|420mpeg2|mono] [--yuv MODE])
+                         [--size WxH [--filter lanczos|nearest]]
 
 --info prints what the stream says about itself (size, frames, key frames, rate, tiles, palettes, the embedded settings) as JSON;
 --raw writes frames [start, start + frames) as packed RGB24, one frame after the other (view with
 `ffplay -f rawvideo -pixel_format rgb24 -video_size WxH OUT.rgb`);
 --y4m writes them as a Y4M file any player, FFmpeg and this library's OpenInput read: the frames are converted to YUV on the device
 (GtmPlayer.ReadYUV) and come to the host as 1 to 3 bytes a pixel.  --yuv: auto (= bt601-limited) bt601-limited bt601-full bt709-limited
-bt709-full tiler (444 and mono only); the header says XCOLORRANGE=FULL for the full-range rules and tiler."""
+bt709-full tiler (444 and mono only); the header says XCOLORRANGE=FULL for the full-range rules and tiler.
+--size WxH (with --raw and --y4m): the frames are scaled on the device to that size before they are delivered (GtmPlayer.SetOutput; --filter
+lanczos, the default, or nearest); the Y4M header carries the output size."""
 import argparse
 import json
 import os
@@ -28,9 +31,20 @@ g.add_argument("--raw")
 g.add_argument("--y4m")
 ap.add_argument("--chroma", default="420jpeg", choices=["444", "422", "420jpeg", "420mpeg2", "mono"])
 ap.add_argument("--yuv", default="auto", choices=["auto", "bt601-limited", "bt601-full", "bt709-limited", "bt709-full", "tiler"])
+ap.add_argument("--size", help="WxH: the size --raw and --y4m deliver at (default: the stream's own)")
+ap.add_argument("--filter", default="lanczos", choices=["lanczos", "nearest"])
 args = ap.parse_args()
+size = None
+if args.size:
+    try:
+        size = tuple(int(v) for v in args.size.lower().split("x"))
+        assert len(size) == 2
+    except (ValueError, AssertionError):
+        ap.error("--size takes WxH, for instance 1920x1080")
 with GtmPlayer(args.input) as p:
     info = p.info()
+    if size and not args.info:
+        p.SetOutput(size[0], size[1], args.filter)
     if args.info:
         info["keyframe_starts"] = p.KeyFrames().tolist()
         info["settings"] = p.SettingsText()
@@ -38,7 +52,7 @@ with GtmPlayer(args.input) as p:
     elif args.y4m:
         p.Seek(args.start)
         left = (args.frames if args.frames > 0 else info["frames"] - args.start)
-        w, h = info["tm_w"] * 8, info["tm_h"] * 8
+        w, h = size if size else (info["tm_w"] * 8, info["tm_h"] * 8)
         full = args.yuv in ("bt601-full", "bt709-full", "tiler")
         with open(args.y4m, "wb") as f:
             f.write(("YUV4MPEG2 W%d H%d F%d:1000000 Ip C%s XCOLORRANGE=%s\n" % (w, h, round(info["fps"] * 1000000), args.chroma, "FULL" if full else "LIMITED")).encode())

@@ -7,7 +7,9 @@
                                                                           the read leg: all frames of one stream as RGB32
                                                                           (tm_player_read) or as YUV planes (tm_player_read_yuv) into device memory
                                                                           or page-locked host memory; wall times and the bytes that cross PCIe.
-                                                                          With --only player: one untimed pass, for rocprofv3
+                                                                          With --only player: one untimed pass, for rocprofv3.
+                                                                          --size WxH --filter lanczos|nearest: the frames are delivered at that
+                                                                          size (GtmPlayer.SetOutput)
 (a) the old way: tm_reload_gtm + tm_render_frames of all frames into device memory;  (b) tm_player_open + tm_player_read of all frames into
 device memory, with the worker thread and (TM_PLAYER_NO_WORKER=1) without.  Wall times are medians of --reps runs after one warm-up, with
 min and max; the player's own split (decode, parse, upload, wait for the worker, launches) and its time to the first frame are its Timings()."""
@@ -79,10 +81,11 @@ def player_way(path, out):
     return r
 
 
-def yuv_leg(path, layout, to, reps):
+def yuv_leg(path, layout, to, reps, size=None, filter="lanczos"):
     """all frames of the stream read `reps` times after one warm-up, each time by a fresh player: wall ms of open + read, of the read alone,
     and the bytes the read sends over PCIe (0 for a device destination)"""
     from tiler_amd import yuv_out
+    W, H = size if size else (globals()["W"], globals()["H"])
     if layout == "rgb32":
         out = torch.empty((F, H, W), dtype=torch.int32, device="cuda") if to == "device" else torch.empty((F, H, W), dtype=torch.int32, pin_memory=True)
         nbytes = out.numel() * 4
@@ -97,6 +100,8 @@ def yuv_leg(path, layout, to, reps):
     def once():
         t0 = time.perf_counter()
         with GtmPlayer(path) as p:
+            if size:
+                p.SetOutput(W, H, filter)
             t1 = time.perf_counter()
             if layout == "rgb32":
                 got = p.Read(F, device=True, out=out) if to == "device" else p.Read(F, device=False, out=out.numpy().view(np.uint32))
@@ -112,7 +117,7 @@ def yuv_leg(path, layout, to, reps):
     if reps <= 0:
         return None
     r = summarise([once() for _ in range(reps)])
-    r.update(layout=layout, to=to, reps=reps, bytes_written=nbytes, pcie_bytes=0 if to == "device" else nbytes, lib=os.environ.get("TM_LIB_VARIANT", ""))
+    r.update(layout=layout, to=to, reps=reps, size="%dx%d" % (W, H), filter=filter if size else None, bytes_written=nbytes, pcie_bytes=0 if to == "device" else nbytes, lib=os.environ.get("TM_LIB_VARIANT", ""))
     return r
 
 
@@ -133,13 +138,18 @@ def main():
     ap.add_argument("--motion", type=int, default=1)
     ap.add_argument("--yuv", help="the read leg: rgb32, or a layout of GtmPlayer.ReadYUV (nv12, p010, 420, ...)")
     ap.add_argument("--to", choices=["host", "device"], default="device")
+    ap.add_argument("--size", help="WxH: the read leg delivers at this size")
+    ap.add_argument("--filter", default="lanczos", choices=["lanczos", "nearest"])
     args = ap.parse_args()
+    size = tuple(int(v) for v in args.size.lower().split("x")) if args.size else None
+    if size and not args.yuv:
+        ap.error("--size belongs to the read leg: give --yuv rgb32 or a layout")
     os.makedirs(args.dir, exist_ok=True)
     paths = {1: os.path.join(args.dir, "bench_motion32.gtm"), 0: os.path.join(args.dir, "bench_motion0.gtm")}
     if args.yuv:
         if not os.path.exists(paths[args.motion]):
             make_stream(paths[args.motion], 32 if args.motion else 0)
-        r = yuv_leg(paths[args.motion], args.yuv, args.to, 0 if args.only else args.reps)
+        r = yuv_leg(paths[args.motion], args.yuv, args.to, 0 if args.only else args.reps, size, args.filter)
         if r is not None:
             print(json.dumps(r))
             if args.json:
