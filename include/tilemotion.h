@@ -32,6 +32,8 @@
  *   TM_KNN_NOPRUNE          the nearest-neighbour scan evaluates every (query, row) pair (bench.py's dense diagnostic launch)
  *   TM_KNN_LIST_ORDER=0     the scan's tile lists stay in run order and are consumed to their ends (default: every list segment sorted by
  *                           its entries' smallest bound, and ended at the first entry no query can want; A/B runs and tests)
+ *   TM_KNN_FIRST_CHUNK=0    the scan runs every listed block's whole chain (default: a block is judged on its 32 widest columns first and
+ *                           ends there when no query of it can gain or tie; A/B runs and tests)
  *   TM_KNN_ARENA_ENTRIES=<n> first size of the scan's tile-list arena (tests: a tiny one, so that a search is repeated with the counted size)
  *   TM_TOPK_BRUTE           the k-nearest search by the VALU brute force (tests compare the pruned scan with it)
  *   TM_EPU_TABLE_GIB=<x>    above this size the (tile, palette) feature table is not built, the pairs asked for are (default 6)
@@ -628,6 +630,9 @@ TM_API int tm_knn_index_last_stats(tm_knn_index *, double *kernel_ms, int *k_byt
 /* diagnostics (tests): entries of the last search's tile lists, and how many of them its consumer took off the lists (fewer where a sorted
  * segment was ended early; equal with TM_KNN_LIST_ORDER=0) */
 TM_API int tm_knn_index_last_list_counts(tm_knn_index *, int64_t *listed, int64_t *popped);
+/* diagnostics (tests): listed blocks (tile x 32 queries) the last search judged on their first chunk of columns, and how many of them ended
+ * there (both 0 with TM_KNN_FIRST_CHUNK=0) */
+TM_API int tm_knn_index_last_chunk_counts(tm_knn_index *, int64_t *looked, int64_t *stopped);
 /* diagnostics (tests): the digit plan of the calling thread's last scan -- 32-column chunks that carry a high digit on the database / query
  * side, 0..6 each, and whether it was the k-nearest collection: together they name the instantiation of the scan's kernels that ran -- and
  * how often a scan of this process has been repeated with a larger tile-list arena (TM_KNN_ARENA_ENTRIES sets the first size) */

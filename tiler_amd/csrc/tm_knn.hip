@@ -43,7 +43,9 @@ struct KnnPlan {
   int tscale = 1;         // database digits are those of tscale * (t - c): 2 lets the scan's chain deliver 2 X without a final doubling
 };
 
-__host__ __device__ inline int knn_tile_bytes(int hch, int with_box) { return (6 + hch) * 1024 + 128 + (with_box ? 64 : 0); }
+// a packed tile of 32 rows: the operand chunks, 32 row terms (norms), the box (database side), 32 row terms over the first chunk's columns
+__host__ __device__ constexpr int knn_tile_bytes(int hch, int with_box) { return (6 + hch) * 1024 + 128 + (with_box ? 64 : 0) + 128; }
+static_assert(knn_tile_bytes(5, 1) == k3_t_bytes(11) && knn_tile_bytes(4, 0) == k3_q_bytes(10), "the scan kernels' view of the packs");
 
 // ---------------------------------------------------------------------------------------------------------------
 // per-column min/max over n rows.  192 threads: thread = (row slot 0..7, 16-byte vector 0..23).
@@ -198,14 +200,20 @@ __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ fe
     {  // |v-c|^2 of every row (the kernel drops the query side's parity bit): eight lanes per row, integer sums (32 threads walking 192
        // values each were the longest leg of a tile)
       const int r = threadIdx.x >> 3, part = threadIdx.x & 7;
-      uint32_t sq = 0;
+      uint32_t sq = 0, sqp = 0;  // over all columns; over the first chunk's (perm[0..31], the 32 widest: k3_chunk_look's lower bound)
 #pragma unroll 8
-      for (int p = part; p < 192; p += 8) { const int v = s_v[r][p]; sq += (uint32_t)(v * v); }
+      for (int p = part; p < 192; p += 8) { const int v = s_v[r][p]; sq += (uint32_t)(v * v); if (p < 32) sqp += (uint32_t)(v * v); }
       sq += __shfl_xor(sq, 1); sq += __shfl_xor(sq, 2); sq += __shfl_xor(sq, 4);
+      sqp += __shfl_xor(sqp, 1); sqp += __shfl_xor(sqp, 2); sqp += __shfl_xor(sqp, 4);
       // what the pack keeps per row is what the scan's chain starts from (k3_chain's `cin`): the query side's |q-c|^2 (the kernel drops its
       // parity), the database side's |t-c|^2 where its digits are those of 2 (t - c), and |t-c|^2 >> 1 where not -- the parities then go
       // into the tile's box (word 14)
-      if (part == 0) { s_norm[r] = sq; reinterpret_cast<uint32_t *>(obase + kch * 1024)[r] = (with_box && scale == 1) ? sq >> 1 : sq; }
+      // ... and the same over the first chunk's columns, in the same form (the query side's whole), behind the box
+      if (part == 0) {
+        s_norm[r] = sq;
+        reinterpret_cast<uint32_t *>(obase + kch * 1024)[r] = (with_box && scale == 1) ? sq >> 1 : sq;
+        reinterpret_cast<uint32_t *>(obase + tile_bytes - 128)[r] = (with_box && scale == 1) ? sqp >> 1 : sqp;
+      }
     }
     __syncthreads();
     if (threadIdx.x == 0) {  // (rows >= n replicate row n - 1: they add no digit the real rows do not have)
@@ -412,7 +420,7 @@ __global__ __launch_bounds__(256) void k_knn_refine(int64_t nq, const uint32_t *
   for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < nq; p += (int64_t)gridDim.x * blockDim.x) {
     const int br = best_row[p];
     const int64_t srow = min((int64_t)(br & 0x3fffffff), nt - 1);  // padded rows replicate row nt-1
-    const uint32_t nqv = reinterpret_cast<const uint32_t *>(qpack + (p >> 5) * (int64_t)q_bytes + q_bytes - 128)[p & 31];
+    const uint32_t nqv = reinterpret_cast<const uint32_t *>(qpack + (p >> 5) * (int64_t)q_bytes + q_bytes - 256)[p & 31];
     const int64_t q = qperm[p];
     out_idx[q] = (int)tperm[srow];
     out_err[q] = (uint32_t)best_key[p] + (nqv & 1u);
@@ -634,6 +642,7 @@ struct tm_knn_index_impl {
   double last_ms = 0;
   int last_kbytes = 0;
   int64_t last_pairs = 0, last_seed_pairs = 0, last_mfma = 0;
+  int64_t last_chunk_looked = 0, last_chunk_stopped = 0, last_stopped_pairs = 0;  // listed blocks judged on their first chunk, and those it stopped
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   ~tm_knn_index_impl() {
     if (ev0) (void)hipEventDestroy(ev0);
@@ -840,7 +849,7 @@ __global__ __launch_bounds__(64) void k_topk_select(int64_t nq, const uint32_t *
     }
     return;
   }
-  const uint32_t parity = reinterpret_cast<const uint32_t *>(qpack + (p >> 5) * (int64_t)q_bytes + q_bytes - 128)[p & 31] & 1u;
+  const uint32_t parity = reinterpret_cast<const uint32_t *>(qpack + (p >> 5) * (int64_t)q_bytes + q_bytes - 256)[p & 31] & 1u;
   int n = 0;
   // (the stored candidates are asked for eight chunks of 64 at a time: a chunk per round trip to memory was most of this kernel -- the sort
   // below is 1.5 ms of the bench clip's 23)
@@ -1057,6 +1066,7 @@ static int launch_scan3(tm_knn_index_impl *ix, int64_t nq, int64_t nqt, int64_t 
   TM_CHECK(ntt < (1 << 24), TM_E_UNSUPPORTED, "knn: %lld database tiles exceed the list entries' 24-bit tile index", (long long)ntt);
   a.ns = ns; a.mode = prune ? K3_MODE_LISTS : K3_MODE_DENSE; a.tdouble = ix->plan.tscale == 2;
   a.list_order = knobs().knn_list_order ? 1 : 0;
+  a.first_chunk = knobs().knn_first_chunk ? 1 : 0;
   a.n_groups = (nqt + ns - 1) / ns;
   a.max_segs = (int)(ntt / (K3_LCAP - K3_LIST_NT) + 2);  // every segment but a list's last holds more than K3_LCAP - K3_LIST_NT entries
   if (prune) {
@@ -1234,7 +1244,7 @@ int knn_index_search(tm_knn_index_impl *ix, const void *queries, int64_t nq, voi
   TM_TRY(ix->best_key.alloc((size_t)nqt * 32 * 4));
   TM_TRY(ix->best_tile.alloc((size_t)nqt * 32 * 4));
   TM_TRY(ix->tie_list.alloc((size_t)nq * 4));
-  TM_TRY(ix->counters.alloc(256 + 2048));  // [4..15]: phase stamps of a diagnostic build; bytes 128..159: the group tickets; bytes 240..247 (stats[28]): list entries popped; bytes 256..: the seed kernel's striped counters
+  TM_TRY(ix->counters.alloc(256 + 2048));  // [4..15]: phase stamps of a diagnostic build, [15] (stats[13]): pairs of the blocks the first chunk stopped; bytes 128..159: the group tickets; bytes 240..247 (stats[28]): list entries popped; bytes 256..: the seed kernel's striped counters
   const int prune = knobs().knn_noprune ? 0 : 1;  // diagnostic: full scan with the same kernel (bench.py roofline_dense)
   int *bt = ix->best_tile.as<int>();
   KnnBoxes bx;
@@ -1307,18 +1317,24 @@ int knn_index_search(tm_knn_index_impl *ix, const void *queries, int64_t nq, voi
   ix->last_visited = (int64_t)cnt[2];
   ix->last_ties = (int64_t)(cnt[0] & 0xffffffffull);
   // pairs actually evaluated: exact (real query, real row) pairs; cnt[12..14]: the seed kernel's blocks, tiles, pairs
-  ix->last_pairs = (int64_t)(cnt[4] + cnt[14]);
+  // (cnt[15]: the pairs of the listed blocks the first-chunk look stopped -- judged, by a lower bound over 32 columns, not evaluated: they are part of what
+  // last_stats reports, as the pairs of a block that ended at its first look always were, and are taken out of what the roofline prices: knn_index_kernel_split)
+  ix->last_stopped_pairs = (int64_t)cnt[15];
+  ix->last_pairs = (int64_t)(cnt[4] + cnt[14] + cnt[15]);
   ix->last_seed_pairs = (int64_t)cnt[14];
   ix->last_mfma = (int64_t)cnt[21];
   ix->last_blocks = (int64_t)(cnt[2] + cnt[12]); ix->last_loads = (int64_t)(cnt[3] + cnt[13]); ix->last_listed = (int64_t)cnt[5]; ix->last_popped = (int64_t)cnt[30];
+  ix->last_chunk_stopped = (int64_t)cnt[31]; ix->last_chunk_looked = prune && knobs().knn_first_chunk ? (int64_t)(cnt[2] + cnt[31]) : 0;
   if (knobs().knn_debug) {
     const int nsg = knn3_sub_tiles(ix->plan.hq);
     const int64_t groups = (nqt + nsg - 1) / nsg;
+    fprintf(stderr, "[tm_knn] first chunk: %lld of %lld listed blocks stopped (%.1f %%)\n", (long long)ix->last_chunk_stopped, (long long)ix->last_chunk_looked,
+            100.0 * (double)ix->last_chunk_stopped / (double)std::max<int64_t>(1, ix->last_chunk_looked));
     fprintf(stderr, "[tm_knn] seeds %.3f ms, lists %.3f ms (%.1f entries per group, arena %.0f %% full), consume %.3f ms, %.2f of %d matrix instructions per block\n", ix->last_seed_ms, ix->last_lists_ms,
             (double)cnt[20] / (double)groups, 100.0 * (double)cnt[20] / (double)std::max<uint64_t>(1, ix->arena_cap), ix->last_consume_ms,
-            (double)cnt[21] / (double)std::max<unsigned long long>(1, cnt[2]), 6 + ix->plan.ht + ix->plan.hq + std::min(ix->plan.ht, ix->plan.hq));
+            (double)cnt[21] / (double)std::max<unsigned long long>(1, cnt[2] + cnt[31]), 6 + ix->plan.ht + ix->plan.hq + std::min(ix->plan.ht, ix->plan.hq));
     fprintf(stderr, "[tm_knn] scan %.3f ms, evaluated %.3f%% of %lld x %lld pairs (%lld blocks; workgroups read %.3f%% of tiles, %.1f per group; %.1f list entries per group, %.1f popped), %lld tie settlements\n",
-            ms, 100.0 * (double)ix->last_pairs / ((double)nq * (double)ix->nt), (long long)nq, (long long)ix->nt, (long long)ix->last_blocks,
+            ms, 100.0 * (double)(ix->last_pairs - ix->last_stopped_pairs) / ((double)nq * (double)ix->nt), (long long)nq, (long long)ix->nt, (long long)ix->last_blocks,
             100.0 * (double)ix->last_loads / ((double)groups * (double)ntt), (double)ix->last_loads / (double)groups, (double)ix->last_listed / (double)groups, (double)ix->last_popped / (double)groups, (long long)ix->last_ties);
   }
 #if TM_KNN3_STAMPS
@@ -1595,13 +1611,19 @@ int knn_index_search_topk(tm_knn_index_impl *ix, const void *queries, int64_t nq
 
 void knn_index_kernel_split(tm_knn_index_impl *ix, double ms[3], int64_t pairs[3]) {
   ms[0] = ix->last_seed_ms; ms[1] = ix->last_lists_ms; ms[2] = ix->last_consume_ms;
-  pairs[0] = ix->last_seed_pairs; pairs[1] = ix->last_pairs - ix->last_seed_pairs; pairs[2] = ix->last_mfma;
+  pairs[0] = ix->last_seed_pairs; pairs[2] = ix->last_mfma;
+  pairs[1] = ix->last_pairs - ix->last_seed_pairs - ix->last_stopped_pairs;  // the consume kernel's blocks that ran to completion: what a roofline may price
 }
 
 void knn_index_stats(tm_knn_index_impl *ix, double *ms, int *kbytes, int64_t *pairs) {
   if (ms) *ms = ix->last_ms;
   if (kbytes) *kbytes = ix->last_kbytes;
   if (pairs) *pairs = ix->last_pairs;
+}
+
+void knn_index_chunk_counts(tm_knn_index_impl *ix, int64_t *looked, int64_t *stopped) {
+  if (looked) *looked = ix->last_chunk_looked;
+  if (stopped) *stopped = ix->last_chunk_stopped;
 }
 
 void knn_index_list_counts(tm_knn_index_impl *ix, int64_t *listed, int64_t *popped) {

@@ -15,7 +15,9 @@
 //                    segment after the other: copied into LDS, consumed by the waves on their own exactly as in the second shape (pop an
 //                    entry, re-judge it against the sub-tiles' bounds AS THEY ARE NOW, tile into registers, one MFMA chain per sub-tile
 //                    that wants it).  An entry judged with the seeds' bound instead of a later, tighter one costs one pop, not a block; a
-//                    sorted segment ends at the first entry whose smallest bound lies above every sub-tile's bound.
+//                    sorted segment ends at the first entry whose smallest bound lies above every sub-tile's bound.  A block is judged on its
+//                    first chunk of columns, the 32 widest, before its chain runs, and ends there nine times in ten (k3_chunk_look, DESIGN.md
+//                    section 23).
 // Arithmetic, operands, boxes, curve and the exactness argument are those of the earlier shapes: a pair is skipped only when its lower
 // bound exceeds the sub-tile's largest best + 1 (both sides of the 16-bit compare rounded the safe way), the minimum VALUE is exact, a
 // second row reaching it raises the tie flag that k_knn_ties settles by original index.
@@ -54,7 +56,12 @@ constexpr int K3_XCD_RUN = 32 * K3_WGS;  // groups dealt to one XCD at a time (n
 #endif
 constexpr int K3_LIST_NT = 256;          // threads of a list-building workgroup
 
-constexpr int k3_lds_bytes(int ns, int kq) { return ns * (kq * 1024 + 576) + 64 + 64 + 64 + K3_LCAP * (4 + 2 * ((ns + 1) & ~1)); }
+// (per sub-tile: operands, norms, bests, tie words, box, the norms over the first chunk's columns; per wave: its tile's 32 row terms over them)
+constexpr int k3_lds_bytes(int ns, int kq) { return ns * (kq * 1024 + 576 + 128) + 64 + 64 + 64 + K3_NW * 128 + K3_LCAP * (4 + 2 * ((ns + 1) & ~1)); }
+// The packs (k_knn_pack): a database tile is KT operand chunks of 1 KB, 32 row terms, the tile's box (64 bytes) and the 32 row terms over the
+// first chunk's columns; a query sub-tile is KQ chunks, 32 norms and the 32 norms over the first chunk's columns.
+constexpr int k3_t_bytes(int kt) { return kt * 1024 + 128 + 64 + 128; }
+constexpr int k3_q_bytes(int kq) { return kq * 1024 + 128 + 128; }
 constexpr int k3_ns(int kq) {
   int ns = 16;
   while (ns > 1 && k3_lds_bytes(ns, kq) > K3_LDS) ns--;
@@ -92,8 +99,9 @@ struct Knn3Args {
   int cand_cap, cand_k;
   int split;                    // workgroups that share one group's tile list (entry j goes to part j mod split)
   int no_seeds;                 // lists: no seed kernel ran (collection mode), so no tile is left out of the lists
+  int first_chunk;              // consume, nearest-neighbour lists: a block is judged on its first chunk's columns before its chain runs (k3_chunk_look; 0: every block runs its chain)
   int list_order;               // lists: a segment leaves sorted by its entries' smallest bound; consume: a segment ends at the first entry nobody can want (0: run order, no stop)
-  unsigned long long *stats;    // consume: [0] blocks evaluated, [1] tiles read, [2] exact (query, row) pairs, [3] list entries consumed, [28] entries popped
+  unsigned long long *stats;    // consume: [0] blocks evaluated, [1] tiles read, [2] exact (query, row) pairs, [3] list entries consumed, [13] (query, row) pairs of the blocks the first chunk stopped, [28] entries popped, [29] those blocks
   unsigned long long *seed_stats;  // [64][4] striped by workgroup: blocks, tiles read, pairs of the seed kernel
   int64_t n_groups;
   int grid_blocks;              // consume: persistent workgroups
@@ -315,6 +323,31 @@ __device__ __forceinline__ void k3_load_tile_masked(const uint8_t *tb, int lane,
   k3_load_rows<KT>(tb, half, cin, pwh);
 }
 
+// ... in two parts for the first-chunk look (k3_chunk_look): chunk 0's low and high digits and row r = lane & 31's term over the chunk's
+// columns (`rowp`; behind the tile's box in the pack) are all the look reads; the other nine KB and the full row terms are asked for right behind
+// them, so that the look need not wait for them.  (Asked for only when a block of the tile gets past its look, as a phase of its own in front of
+// the block loop: 127 registers, 136 bytes of scratch, 12.5 against 8.2 ms -- DESIGN 23.)
+template <int KT>
+__device__ __forceinline__ void k3_load_tile_chunk0(const uint8_t *tb, int lane, unsigned tm, v4i (&T)[KT], unsigned &rowp) {
+  T[0] = *reinterpret_cast<const v4i *>(tb + lane * 16);
+  if constexpr (KT > 6) {
+    T[6] = v4i{0, 0, 0, 0};
+    if (tm & 1u) T[6] = *reinterpret_cast<const v4i *>(tb + (6 * 64 + lane) * 16);
+  }
+  rowp = *reinterpret_cast<const unsigned *>(tb + KT * 1024 + 128 + 64 + (lane & 31) * 4);
+}
+template <int KT>
+__device__ __forceinline__ void k3_load_tile_rest(const uint8_t *tb, int lane, int half, unsigned tm, v4i (&T)[KT], v16i &cin, unsigned &pwh) {
+#pragma unroll
+  for (int kc = 1; kc < 6; kc++) T[kc] = *reinterpret_cast<const v4i *>(tb + (kc * 64 + lane) * 16);
+#pragma unroll
+  for (int kc = 7; kc < KT; kc++) {
+    T[kc] = v4i{0, 0, 0, 0};
+    if ((tm >> (kc - 6)) & 1u) T[kc] = *reinterpret_cast<const v4i *>(tb + (kc * 64 + lane) * 16);
+  }
+  k3_load_rows<KT>(tb, half, cin, pwh);
+}
+
 // the minimum of the chain's sixteen values of a lane: a tree of three-way minima (five, two, one: eight instructions; pairs first cost ten)
 __device__ __forceinline__ int k3_min3(int a, int b, int c) { return min(min(a, b), c); }
 __device__ __forceinline__ int k3_min16(const int (&t)[16]) {
@@ -339,6 +372,77 @@ template <bool TD>
 __device__ __forceinline__ bool k3_may_matter(const v16i &acc, unsigned qn, unsigned bound) {
   const unsigned look = (unsigned)k3_first_look<TD>(acc) + qn + 1u;
   return TD ? look <= bound : (int)look <= (int)min(bound, 0x7FFFFFFFu);
+}
+// A block judged on its first chunk before its chain runs.  The columns are packed widest first, so chunk 0 holds the 32
+// widest, and the sum of squares over them is a lower bound of the sum over all: with the pack's row terms and query norms over those
+// columns (`rows`: the wave's 32 row terms in LDS, in the form the full ones have -- |t-c|^2 with TD, halved without; `qnp_p`: the lane's
+// query's norm, whole) the chain of the chunk's own products -- T_H0 . Q_H0, T_H0 . Q_L0, T_L0 . Q_H0, T_L0 . Q_L0, under k3_chain's
+// predicates, shifted as there, the row term riding in on the second shift -- ends in the pair's SSD over the 32 columns (without TD:
+// that or one less).  The invariant: what a lane compares is <= SSD over the chunk <= SSD <= d'' + 1 for every row of the block, and
+// the compare against the query's best d'' + 1 is inclusive: a row that improves OR ONLY TIES a best always passes, so the bests, the
+// tie words and what k_knn_ties sees are those of a scan that ran every chain.  Returns whether the block can matter to this lane's query.
+template <int HT, int HQ, bool TD>
+__device__ __forceinline__ bool k3_chunk_look(const v4i (&T)[6 + HT], const uint8_t *rows, int half, const uint8_t *q, unsigned tm, unsigned qm, const int *qnp_p,
+                                              unsigned bound) {
+  constexpr int HM = HT < HQ ? HT : HQ;
+  const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  v16i acc = zero;
+  if constexpr (HT + HQ > 0) {
+    constexpr int FA = HT > 0 ? 6 : 0, FQ = HT > 0 ? 0 : 6;  // (k3_chain: the product that always runs)
+    bool hh = false;
+    if constexpr (HM > 0) hh = (tm & qm & 1u) != 0;
+    if (hh) {
+      if constexpr (HM > 0) {
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[6], *reinterpret_cast<const v4i *>(q + 6 * 1024), zero, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[r] = (int)((unsigned)acc[r] << 8);
+      }
+      acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[FA], *reinterpret_cast<const v4i *>(q + FQ * 1024), acc, 0, 0, 0);
+    } else {
+      acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[FA], *reinterpret_cast<const v4i *>(q + FQ * 1024), zero, 0, 0, 0);
+    }
+    if constexpr (HM > 0)
+      if (qm & 1u) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[0], *reinterpret_cast<const v4i *>(q + 6 * 1024), acc, 0, 0, 0);
+  }
+  // The row terms come out of LDS four at a time (k3_load_rows' order: accumulator register r holds row (r&3) + 8*(r>>2) + 4*half), each
+  // read one group ahead of the shift that takes it in, in two buffers in turn like the chain's last operands: all sixteen asked for at
+  // once were eleven more spilled registers.
+  auto term = [&](int q4) { return *reinterpret_cast<const v4i *>(rows + (q4 * 8 + half * 4) * 4); };
+  v4i xa = term(0), xb = term(1);
+  if constexpr (HT + HQ > 0) {
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 4; i++) acc[i] = (int)(((unsigned)acc[i] << 8) + (unsigned)xa[i]);
+    xa = term(2);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 4; i++) acc[4 + i] = (int)(((unsigned)acc[4 + i] << 8) + (unsigned)xb[i]);
+    xb = term(3);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 4; i++) acc[8 + i] = (int)(((unsigned)acc[8 + i] << 8) + (unsigned)xa[i]);
+    xa = *reinterpret_cast<const v4i *>(q);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 4; i++) acc[12 + i] = (int)(((unsigned)acc[12 + i] << 8) + (unsigned)xb[i]);
+  } else {
+    const v4i xc = term(2), xd = term(3);
+#pragma unroll
+    for (int i = 0; i < 4; i++) { acc[i] = xa[i]; acc[4 + i] = xb[i]; acc[8 + i] = xc[i]; acc[12 + i] = xd[i]; }
+    xa = *reinterpret_cast<const v4i *>(q);
+  }
+  acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[0], xa, acc, 0, 0, 0);  // T_L0 . Q_L0
+  const unsigned qnp = (unsigned)*qnp_p;  // (asked for behind the shifts: a register fewer across them)
+  const unsigned look = (unsigned)k3_first_look<TD>(acc) + qnp;  // the SSD over the chunk (without TD: at most one below it, -1 at the least)
+  return TD ? look <= bound : (int)look <= (int)min(bound, 0x7FFFFFFFu);
+}
+// matrix instructions k3_chunk_look issues for a block with these masks
+template <int HT, int HQ>
+__device__ __forceinline__ int k3_chunk_look_products(unsigned tm, unsigned qm) {
+  constexpr int HM = HT < HQ ? HT : HQ;
+  int n = HT + HQ > 0 ? 2 : 1;
+  if (HM > 0) n += ((tm & qm & 1u) ? 1 : 0) + ((qm & 1u) ? 1 : 0);
+  return n;
 }
 // ... and the values themselves (d'' - qn of accumulator register r)
 template <bool TD>
@@ -514,7 +618,7 @@ constexpr int K3_SEED_SLICE = 3;
 template <int HT, int HQ, bool TD, bool UNUSED>
 __global__ __launch_bounds__(K3_SEEDS * 64, 4) void k_knn_seed(const Knn3Args a) {
   constexpr int KT = 6 + HT, KQ = 6 + HQ;
-  constexpr int T_BYTES = KT * 1024 + 128 + 64, Q_BYTES = KQ * 1024 + 128;
+  constexpr int T_BYTES = k3_t_bytes(KT), Q_BYTES = k3_q_bytes(KQ);
   constexpr int SL = (2 * K3_SEED_SLICE * KQ * 1024 + 10 * 1024 > 80 * 1024) ? K3_SEED_SLICE - 1 : K3_SEED_SLICE, NW = K3_SEEDS;  // two workgroups per CU
   __shared__ __attribute__((aligned(16))) uint8_t s_q[2][SL * KQ * 1024];
   __shared__ unsigned long long s_best[16 * 32];
@@ -847,11 +951,12 @@ constexpr int k3_ns_topk(int kq) { return k3_ns(kq) > 1 ? k3_ns(kq) - 1 : 1; }
 template <int HT, int HQ, bool TD, bool TOPK>
 __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
   constexpr int KT = 6 + HT, KQ = 6 + HQ;
-  constexpr int T_BYTES = KT * 1024 + 128 + 64, Q_BYTES = KQ * 1024 + 128;
+  constexpr int T_BYTES = k3_t_bytes(KT), Q_BYTES = k3_q_bytes(KQ);
   constexpr int NS = TOPK ? k3_ns_topk(KQ) : k3_ns(KQ), NSP = (NS + 1) & ~1, NW = K3_NW, NT = K3_NT, LCAP = K3_LCAP;
   // one LDS object, carved by hand (16-byte aligned pieces)
   constexpr int OFF_QN = NS * KQ * 1024, OFF_BEST = OFF_QN + NS * 128, OFF_TIE = OFF_BEST + NS * 256, OFF_QBOX = OFF_TIE + NS * 128,
-                OFF_SMAX = OFF_QBOX + NS * 64, OFF_QMASK = OFF_SMAX + 64, OFF_CTL = OFF_QMASK + 64, OFF_LTILE = OFF_CTL + 64, OFF_LLB = OFF_LTILE + LCAP * 4,
+                OFF_QNP = OFF_QBOX + NS * 64, OFF_SMAX = OFF_QNP + NS * 128, OFF_QMASK = OFF_SMAX + 64, OFF_CTL = OFF_QMASK + 64, OFF_TROW = OFF_CTL + 64,
+                OFF_LTILE = OFF_TROW + NW * 128, OFF_LLB = OFF_LTILE + LCAP * 4,
                 OFF_LAD = OFF_LLB + LCAP * NSP * 2, LDS_TOTAL = OFF_LAD + (TOPK ? NS * 32 * 16 : 0);
   static_assert(OFF_LAD == k3_lds_bytes(NS, KQ) && LDS_TOTAL <= K3_LDS, "LDS carve");
   __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_TOTAL];
@@ -861,6 +966,7 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
   [[maybe_unused]] int *const s_qbox = reinterpret_cast<int *>(lds + OFF_QBOX);             // [NS][16] (kept in the carve: the dense mode's home)
   unsigned *const s_smax = reinterpret_cast<unsigned *>(lds + OFF_SMAX);                    // [16] upper bound of sqrt(largest best + 1)
   unsigned *const s_qmask = reinterpret_cast<unsigned *>(lds + OFF_QMASK);                  // [16] non-zero high-digit chunks of each sub-tile
+  int *const s_qnp = reinterpret_cast<int *>(lds + OFF_QNP);                                // [NS][32] |q-c|^2 over the first chunk's columns
   int *const s_ctl = reinterpret_cast<int *>(lds + OFF_CTL);                                // [0] list length, [1] cursor, [3] group
   unsigned *const s_ltile = reinterpret_cast<unsigned *>(lds + OFF_LTILE);                  // [LCAP]
   uint16_t *const s_llb = reinterpret_cast<uint16_t *>(lds + OFF_LLB);                      // [LCAP][NSP]
@@ -876,8 +982,10 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
   // helps the next one.
   unsigned xcc;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
-  long long nblocks = 0, nloads = 0, npairs = 0, nlisted = 0, npopped = 0, nmfma = 0;
+  long long nblocks = 0, nloads = 0, npairs = 0, nlisted = 0, npopped = 0, nmfma = 0, nstopped = 0, nspairs = 0;
   const bool dense = a.mode == K3_MODE_DENSE, ordered = a.list_order != 0 && !dense;
+  const bool chunk_first = !TOPK && a.first_chunk != 0 && !dense;  // a block is judged on its first chunk before its chain runs (k3_chunk_look)
+  uint8_t *const s_trow = lds + OFF_TROW + wave * 128;  // this wave's tile: its 32 row terms over the first chunk's columns
   const int split = TOPK ? max(1, a.split) : 1;
   const int64_t n_units = a.n_groups * split;  // what the tickets deal: (group, part of its list)
   for (;;) {
@@ -923,6 +1031,7 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
     const int64_t st = min(st0 + (i >> 5), a.n_qtiles - 1);
     const bool real = (i >> 5) < nvalid && !dense;
     s_qn[i] = reinterpret_cast<const int *>(a.qpack + st * (int64_t)Q_BYTES + KQ * 1024)[i & 31] & ~1;
+    if constexpr (!TOPK) s_qnp[i] = reinterpret_cast<const int *>(a.qpack + st * (int64_t)Q_BYTES + KQ * 1024 + 128)[i & 31];
     if constexpr (TOPK) {  // (tau + 1) << 32 | rung spacing; queries that are padding get tau = -1: nothing is within it
       const bool qreal = real && st0 * 32 + i < a.nq;
       const int tau = qreal ? a.tau[st0 * 32 + i] : -1;
@@ -1032,7 +1141,13 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
         v4i T[KT];
         v16i cin;
         unsigned pwh;
-        k3_load_tile_masked<KT>(a.tpack + (int64_t)tile * T_BYTES, lane, half, tm, T, cin, pwh);
+        unsigned rowp = 0;
+        if (chunk_first) {
+          k3_load_tile_chunk0<KT>(a.tpack + (int64_t)tile * T_BYTES, lane, tm, T, rowp);
+          k3_load_tile_rest<KT>(a.tpack + (int64_t)tile * T_BYTES, lane, half, tm, T, cin, pwh);
+        } else {
+          k3_load_tile_masked<KT>(a.tpack + (int64_t)tile * T_BYTES, lane, half, tm, T, cin, pwh);
+        }
         nloads++;
         // the entry after this one is chosen while the loads fly
         int ntile = 0, nlb = 0, nsm = 0;
@@ -1044,6 +1159,8 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
         K3_STAMP(4);  // waiting for the tile's loads (what is left of their latency behind the choice of the next entry)
 #endif
         const int vt = (int)min((int64_t)32, a.nt_rows - (int64_t)tile * 32);
+        // (the wave's own 128 bytes: its looks at the tile before read them in program order, its looks at this one read what is written here)
+        if (chunk_first && lane < 32) reinterpret_cast<unsigned *>(s_trow)[lane] = rowp;
         // a block's epilogue and the refresh of its sub-tile's bound
         auto finish = [&](const v16i &acc, int s, unsigned sm_now, unsigned cur_hi, unsigned qn) {
           unsigned long long *const bp = reinterpret_cast<unsigned long long *>(lds + (a_best + (unsigned)s * 256u));  // &s_best[s * 32 + (lane & 31)]
@@ -1080,6 +1197,17 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
           }
           return -1;
         };
+        // a block's first-chunk look (k3_chunk_look) and its counters: false = the block ends here
+        auto look = [&](int s, unsigned qm, unsigned q_off, unsigned cur_hi) -> bool {
+          const int *const qnp_p = reinterpret_cast<const int *>(lds + (a_qn + (unsigned)(OFF_QNP - OFF_QN) + (unsigned)s * 128u));  // &s_qnp[s * 32 + (lane & 31)]
+          const bool in = k3_chunk_look<HT, HQ, TD>(T, s_trow, half, lds + (a_q + q_off), tm, qm, qnp_p, cur_hi);
+          nmfma += k3_chunk_look_products<HT, HQ>(tm, qm);
+          if (__builtin_amdgcn_ballot_w64(in) != 0) return true;
+          // no query of the sub-tile can gain from the tile, or tie with it
+          nstopped++;
+          nspairs += (long long)vt * (int)min((int64_t)32, a.nq - (st0 + s) * 32);  // (counted apart: `pairs` are those of the blocks that ran to completion)
+          return false;
+        };
         for (;;) {
           unsigned sm0 = 0, sm1 = 0;
           const int s0 = pick(sm0);
@@ -1094,7 +1222,7 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
           const unsigned cur0 = TOPK ? 0u : k3_peek(reinterpret_cast<unsigned *>(lds + (a_best + (unsigned)s0 * 256u)) + 1);
           const int *const qn0_p = reinterpret_cast<const int *>(lds + (a_qn + (unsigned)s0 * 128u));  // &s_qn[s0 * 32 + (lane & 31)]
           unsigned qn0 = 0;
-          if (TM_KNN3_PRE_QN) qn0 = (unsigned)*qn0_p;
+          if (TM_KNN3_PRE_QN && !chunk_first) qn0 = (unsigned)*qn0_p;  // (behind the look where there is one: few blocks get that far)
           const int s1 = (TM_KNN3_DUAL && !TOPK) ? pick(sm1) : -1;
           if (s1 >= 0) {  // two blocks at once
             const unsigned qm1 = (unsigned)__builtin_amdgcn_readlane((int)qmask_v, s1);
@@ -1113,6 +1241,10 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
             // (the sub-tile's operands begin at s0 * KQ KB: a product the compiler makes on the vector unit, a 24-bit multiply, unless told otherwise)
             unsigned q_off;
             asm("s_mul_i32 %0, %1, %2" : "=s"(q_off) : "s"(s0), "n"(KQ * 1024));
+            if (chunk_first) {
+              if (!look(s0, qm0, q_off, cur0)) continue;
+              if (TM_KNN3_PRE_QN) qn0 = (unsigned)*qn0_p;
+            }
             const v16i acc = k3_chain<HT, HQ, TD>(T, cin, lds + (a_q + q_off), tm, qm0);
             nmfma += k3_chain_products<HT, HQ>(tm, qm0);
             K3_STAMP(6);  // the chain, up to the issue of its last matrix instruction
@@ -1165,7 +1297,8 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
     atomicAdd(a.stats + 2, (unsigned long long)npairs);
     if (wave == 0) atomicAdd(a.stats + 3, (unsigned long long)nlisted);
     atomicAdd(a.stats + 28, (unsigned long long)npopped);  // entries the waves took off their lists: short of [3] by what the stops left behind
-    atomicAdd(a.stats + 19, (unsigned long long)nmfma);  // matrix instructions issued (a full chain has 6 + HT + HQ + min(HT, HQ))
+    atomicAdd(a.stats + 19, (unsigned long long)nmfma);  // matrix instructions issued (a full chain has 6 + HT + HQ + min(HT, HQ)), the first-chunk looks' included
+    if (nstopped) { atomicAdd(a.stats + 29, (unsigned long long)nstopped); atomicAdd(a.stats + 13, (unsigned long long)nspairs); }
   }
 }
 

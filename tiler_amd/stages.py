@@ -210,6 +210,12 @@ class KnnIndex:
         check(lib().tm_knn_index_last_list_counts(ctypes.c_void_p(self.h), ctypes.byref(listed), ctypes.byref(popped)))
         return listed.value, popped.value
 
+    def last_chunk_counts(self):
+        """(listed blocks judged on their first chunk, blocks that ended there) of the last search"""
+        looked, stopped = ctypes.c_int64(), ctypes.c_int64()
+        check(lib().tm_knn_index_last_chunk_counts(ctypes.c_void_p(self.h), ctypes.byref(looked), ctypes.byref(stopped)))
+        return looked.value, stopped.value
+
     def close(self):
         if self.h:
             lib().tm_knn_index_destroy(ctypes.c_void_p(self.h))

@@ -8,6 +8,7 @@ named instantiations of k_knn_seed / k_knn_consume (nearest-neighbour mode):
                ends a block for the lanes the first look turns away
   exact        vector instructions of what that branch guards: the minimum's value, its row, the atomics
   nops         s_nop instructions inside `exact` (issue slots that do no work)
+  chunk_look   (consume) vector instructions of the first-chunk look, from its last matrix instruction to the branch that ends the block
 
   python tools/knn_isa_report.py --ht 5 --hq 4 --td 0 [--kernel consume --kernel seed] [--json] [--asm FILE] [--keep FILE]
 """
@@ -70,9 +71,22 @@ def report(lines, sym):
             out[m.group(1)] = int(m.group(2))
         if l.strip() == '.end_amdhsa_kernel':
             break
-    # the first look: the first three-way minimum of the kernel belongs to it; back to the matrix instruction before it, on to the
-    # first branch on the lanes' verdict
-    first_min = next(i for i, l in enumerate(body) if l.startswith('v_min3_i32'))
+    # The looks: each is a tree of three-way minima behind a matrix instruction.  The chain's first look ends in a branch on the LANES'
+    # verdict (s_and_saveexec); the first-chunk look of the consume kernel (k3_chunk_look) comes before it in the code and ends in a
+    # branch on a ballot (s_cbranch): it is reported beside the other two as `chunk_look`.
+    # (An assumption about the code as it is scheduled today: no other scalar branch stands between a tree of minima and the branch on its
+    # verdict.  One that did would be taken for a ballot's and mislabel the look; tests/test_knn_isa.py would then miss `first_look`.)
+    first_min = None
+    i = 0
+    while first_min is None:
+        i = next(j for j in range(i, len(body)) if body[j].startswith('v_min3_i32'))
+        mfma = max(j for j in range(i) if body[j].startswith('v_mfma'))
+        br = next(j for j in range(i, len(body)) if body[j].startswith('s_and_saveexec_b64') or body[j].startswith('s_cbranch'))
+        if body[br].startswith('s_and_saveexec_b64'):
+            first_min = i
+        else:
+            out['chunk_look'] = sum(is_valu(l) for l in body[mfma + 1:br])
+            i = br
     last_mfma = max(i for i in range(first_min) if body[i].startswith('v_mfma'))
     save = next(i for i in range(first_min, len(body)) if body[i].startswith('s_and_saveexec_b64'))
     saved = body[save].split()[1].rstrip(',')
@@ -109,8 +123,9 @@ def main():
         print(json.dumps(res))
     else:
         for k, r in res.items():
-            print('%s: next_free_vgpr %d, private_segment_fixed_size %d, vector instructions: first look %d, exact path %d (+ %d s_nop)' %
-                  (r['instantiation'], r['next_free_vgpr'], r['private_segment_fixed_size'], r['first_look'], r['exact'], r['nops']))
+            print('%s: next_free_vgpr %d, private_segment_fixed_size %d, vector instructions: first look %d, exact path %d (+ %d s_nop)%s' %
+                  (r['instantiation'], r['next_free_vgpr'], r['private_segment_fixed_size'], r['first_look'], r['exact'], r['nops'],
+                   ', first-chunk look %d' % r['chunk_look'] if 'chunk_look' in r else ''))
     return 0
 
 
