@@ -676,6 +676,14 @@ TM_API int tm_stage_quantize_palettes(const void *tiles, const void *pal_idx, in
 /* DoPalettization (:4105-4245): cluster features -> PalIdx_Initial ranked by tile count. */
 TM_API int tm_stage_palettize(const void *feat_i32, const void *use, int64_t n, int npal, int max_iter, void *out_pal_idx,
                               void *stream);
+/* The D^2 seeding of that clustering alone (test seam): the k picked point indices, in pick order, to a host array of k entries (-1 beyond
+ * the centres found); *out_kk = the number of centres found.  feat_i32: [n][192]; use: the points' weights, NULL = 1 each. */
+TM_API int tm_stage_pp_seeds(const void *feat_i32, const void *use /* may be NULL */, int64_t n, int k,
+                             int64_t *out_seeds_host /* k entries, -1 beyond the centres found */, int *out_kk, void *stream);
+/* 1 when the calling thread's last k-means (tm_stage_kmeans*, or the one inside tm_stage_palettize / tm_stage_quantize_palettes) ran through a
+ * resident launch to its end (k_h_resident, k_kmeans3_persistent), 0 when it took one launch per step -- by shape, by TM_KM_LAUNCHES, or
+ * because a barrier of the resident launch gave up and the clustering was repeated (tests tell the two apart with it). */
+TM_API int tm_kmeans_last_resident(void);
 
 /* A17: TKModes.ComputeKModes (kmodes.pas:923-1094; unreachable in the reference snapshot, named by the north star): k-modes on rows
  * of cKModesFeatureCount = 80 bytes (kmodes.pas:15; the reference's asm hard-codes 80, :338-342), dissimilarity = sum |a-b| + 2048 per

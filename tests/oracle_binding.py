@@ -40,6 +40,7 @@ class Oracle:
         L.tmo_palettize_tiles.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
         L.tmo_kmeans_pp_seeds.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
         L.tmo_kmeans_pp_seeds.restype = ctypes.c_int
+        L.tmo_kmeans_pp_i32.argtypes = L.tmo_kmeans_i32.argtypes
 
     # ---- colour
     def rgb_to_lab(self, r, g, b, det=False):
@@ -287,6 +288,17 @@ class Oracle:
         seeds = np.full(k, -1, np.int64)
         kk = self.L.tmo_kmeans_pp_seeds(_p(pts), _p(w), pts.shape[0], pts.shape[1], k, _p(seeds))
         return seeds[:kk]
+
+    def kmeans_pp(self, pts, weights, k, max_iter=300):
+        """the Lloyd iterations of kmeans from the D^2 seeds (what palettize clusters with) -> (live_k, assign, centroids, iterations)"""
+        pts = np.ascontiguousarray(pts, np.int32)
+        n, d = pts.shape
+        w = np.ascontiguousarray(weights, np.uint32) if weights is not None else None
+        assign = np.zeros(n, np.int32)
+        cent = np.zeros((k, d), np.float64)
+        iters = ctypes.c_int()
+        kk = self.L.tmo_kmeans_pp_i32(_p(pts), _p(w), n, d, k, max_iter, _p(assign), _p(cent), ctypes.byref(iters))
+        return kk, assign, cent, iters.value
 
     def palettize(self, feat, use, pal_count, max_iter=300):
         feat = np.ascontiguousarray(feat, np.int32)

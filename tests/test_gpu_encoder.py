@@ -387,7 +387,8 @@ class _FakeDist:
         self.bar.wait()
 
 
-def _sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, pp_sharded, recon_chunk=0):
+def _sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, pp_sharded, recon_chunk=0, size=(64, 48), palette_count=3, tile_count=150,
+                                           palettize_tiles=None):
     import threading
     from tiler_amd import synth, distributed
     from tiler_amd.encoder import TilingEncoder
@@ -397,10 +398,13 @@ def _sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, pp_s
         monkeypatch.setenv("TM_PP_SHARDED", "1")
     else:
         monkeypatch.delenv("TM_PP_SHARDED", raising=False)
-    frames = synth.video(12, 64, 48, cut=3)
-    kw = dict(PaletteCount=3, ShotTransMinSecondsPerKF=0.1, MotionPredictRadius=radius, FrameTilingExtendedPaletteUsage=epu, GlobalTilingTileCount=150)
+    frames = synth.video(12, size[0], size[1], cut=3)
+    kw = dict(PaletteCount=palette_count, ShotTransMinSecondsPerKF=0.1, MotionPredictRadius=radius, FrameTilingExtendedPaletteUsage=epu,
+              GlobalTilingTileCount=tile_count)
     ref = _run_encoder(frames, **kw)
     want = (np.stack([ref.TileMap(f) for f in range(12)]), ref.Tiles())
+    if palettize_tiles is not None:  # the tiles the single run's PreparePalettes clustered
+        assert ref.KmeansIters()["tile_points"] == palettize_tiles
     ref.close()
     if recon_chunk:  # (after the single run: that one stays a single chunk)
         monkeypatch.setenv("TM_RECON_CHUNK_FRAMES", str(recon_chunk))
@@ -416,7 +420,7 @@ def _sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, pp_s
             enc.LoadDefaultSettings()
             for k, v in kw.items():
                 setattr(enc, k, v)
-            enc.SetVideo(64, 48, 24.0, 12)
+            enc.SetVideo(size[0], size[1], 24.0, 12)
             for f in range(12):
                 enc.PushFrame(f, frames[f])
             distributed.run_all(enc, 12, r, world)
@@ -453,6 +457,16 @@ def test_sharded_ranks_merge_to_the_single_run_with_reconstruct_in_chunks(monkey
     """the same with two ranks and TM_RECON_CHUNK_FRAMES=2: every rank's six query frames take three chunks, and the second rank's start at
     a frame > 0 (the chunk offsets into the tile-map arrays, the features computed ahead being the rank's first chunk)"""
     _sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, 2, False, recon_chunk=2)
+
+
+def test_sharded_seeding_with_more_than_one_block_a_rank(monkeypatch):
+    """the data-parallel seeding (k_pp_pick's modes 1 and 2) over three ranks that each hold more than the 512 tiles of a block: every rank sums
+    a whole block and a partial one, and the rank that owns a draw changes between the eight picks.  The tile budget is the smallest with which
+    every one of the three shares passes 512 (3 x 513; the helper asserts that the single run clustered exactly that many), the clip the
+    smallest of the helper's 12-frame clips with that many distinct tiles."""
+    tiles = 3 * 513
+    assert tiles >= 3 * 512 + 1 and all((tiles + r) // 3 > 512 for r in range(3))
+    _sharded_ranks_merge_to_the_single_run(monkeypatch, 0, False, 3, True, size=(112, 96), palette_count=8, tile_count=tiles, palettize_tiles=tiles)
 
 
 @pytest.mark.parametrize("mode", ["keys", "keys-colliding-hashes"])

@@ -172,6 +172,14 @@ int tm_stage_palettize(const void *feat_i32, const void *use, int64_t n, int npa
   return run_palettize(feat_i32, use, n, npal, max_iter, out_pal_idx, (hipStream_t)stream);
 }
 
+int tm_kmeans_last_resident(void) { return kmeans_run_stats().resident; }
+
+int tm_stage_pp_seeds(const void *feat_i32, const void *use, int64_t n, int k, int64_t *out_seeds_host, int *out_kk, void *stream) {
+  knobs_reload();
+  TM_CHECK(feat_i32 && out_seeds_host && out_kk, TM_E_INVAL, "pp_seeds: null argument");
+  return run_pp_seeds(feat_i32, use, n, k, out_seeds_host, out_kk, (hipStream_t)stream);
+}
+
 int tm_stage_render(const void *tile_idx, const void *pal_idx, const void *item_flags, const void *px, const void *py, int tm_w, int tm_h,
                     int nframes, const void *pal_px, int64_t ntiles, const void *palettes, int npal, int pal_size, void *out, void *stream) {
   knobs_reload();

@@ -268,6 +268,8 @@ int run_quantize_palettes(const void *tiles, const void *pal_idx, int64_t n, int
 int run_quantize_palettes_part(const void *tiles, const void *pal_idx, int64_t n, int npal, int pal_size, int max_iter, void *out_palettes,
                                int pal_rank, int pal_world, hipStream_t stream, DevBuf *keep_keys = nullptr, int64_t *keep_n = nullptr);
 int run_palettize(const void *feat, const void *use, int64_t n, int npal, int max_iter, void *out_pal_idx, hipStream_t stream);
+// the seeding of that clustering alone: the k picked indices to the host (-1 beyond the centres found), *out_kk = centres found
+int run_pp_seeds(const void *feat, const void *use, int64_t n, int k, int64_t *out_seeds_host, int *out_kk, hipStream_t stream);
 bool palettize_resident(int64_t n, int npal);  // the clustering above would take the resident launch (then several processes each run it whole)
 // tm_reduce_keys.hip, Reduce over several processes (see there): a 16-byte key per distinct tile (rows[idx[r]], use[r]) and, on the gathered keys of
 // all processes, the tiles that can be among the first `target` of the merged order (in_s: uint32 flags)
@@ -276,7 +278,7 @@ int reduce_select_candidates(const void *keys, int64_t n, int64_t target, void *
 // tm_dl3.hip: dl3quant on device pointers (blocking)
 int run_dl3quant(const void *dev_rgb, int64_t npixels, int quant_to, int lookup_bpc, void *dev_pal, int *out_colors, hipStream_t stream);
 // what the calling thread's last tile -> palette clustering and last colour quantisation ran through (tm_get_kmeans_iters)
-struct KmeansRunStats { int tile_iters = 0; int64_t tile_points = 0; int pixel_iters = 0; int64_t pixel_colours = 0, pixels = 0, pixel_colour_iters = 0; };
+struct KmeansRunStats { int resident = 0 /* the last k-means of all ran in a resident launch to its end */; int tile_iters = 0; int64_t tile_points = 0; int pixel_iters = 0; int64_t pixel_colours = 0, pixels = 0, pixel_colour_iters = 0; };
 KmeansRunStats &kmeans_run_stats();
 
 // tm_kmodes.hip: A17, TKModes.ComputeKModes (kmodes.pas:923-1094); host pointers

@@ -555,11 +555,12 @@ int kmeans_batched(const int32_t *pts, const uint32_t *w, int d, const std::vect
   TM_CHECK(k >= 1 && k <= 65536, TM_E_INVAL, "kmeans: k out of range");
   const int nseg = (int)seg_begin.size();
   if (host_iters) *host_iters = 0;
+  kmeans_run_stats().resident = 0;
   if (nseg == 0) return TM_OK;
   if (d == 3 && !init_idx && !dev_init_idx) {  // the whole clustering in one launch when its workgroups fit the chip together
     int used = 0;
     TM_TRY(kmeans3_persistent(pts, w, seg_begin, seg_count, k, max_iter, assign, cent, host_kk, host_iters, stream, &used));
-    if (used) return TM_OK;
+    if (used) { kmeans_run_stats().resident = 1; return TM_OK; }
   }
   for (bool allow_resident = true;; allow_resident = false) {  // a resident launch that gave up: once more, from the seeds, without it
     KmRun r;
@@ -577,6 +578,7 @@ int kmeans_batched(const int32_t *pts, const uint32_t *w, int d, const std::vect
       continue;
     }
     if (leg == Resident::not_applicable) TM_TRY(km_launches(r, &it));
+    else kmeans_run_stats().resident = 1;
     TM_HIP(hipGetLastError());
     if (host_iters) *host_iters = it;
     {

@@ -1025,7 +1025,8 @@ __global__ __launch_bounds__(HR_NT) void k_h_resident(const int32_t *__restrict_
       // the buffer of the iteration after next: read for the last time before the barrier just passed, added to again only behind the next one
       const int b2 = (it + 2) % 3;
       const int per = (HR_E + (int)G - 1) / (int)G;
-      if (tid < per && g * per + tid < HR_E) __hip_atomic_store(&st->delta[b2][g * per + tid], (u64)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      // (with fewer than four workgroups a share is longer than the workgroup: up to HR_E = 3 088 entries with one, 1 544 with two, 1 030 with three)
+      for (int e = g * per + tid; e < min(HR_E, (g + 1) * per); e += HR_NT) __hip_atomic_store(&st->delta[b2][e], (u64)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (g == 0 && tid == 0) __hip_atomic_store(&st->changed[b2], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
       for (int u = 0; u < 4; u++) { const int e = u * HR_NT + tid; if (e < HR_E && dv[u]) s_sum[e] += dv[u]; }

@@ -314,6 +314,18 @@ static int pp_seeds(const int32_t *pts, const uint32_t *w, int64_t n, int k, std
   return TM_OK;
 }
 
+int run_pp_seeds(const void *feat, const void *use, int64_t n, int k, int64_t *out_seeds_host, int *out_kk, hipStream_t stream) {
+  TM_TRY(require_device());
+  TM_CHECK(k >= 1 && k <= 65536, TM_E_INVAL, "PaletteCount %d outside 1..65536 (tilingencoder.pas:2959)", k);
+  std::vector<int64_t> seeds((size_t)k, -1);
+  if (n > 0) TM_TRY(pp_seeds((const int32_t *)feat, (const uint32_t *)use, n, k, &seeds, stream));
+  int kk = 0;
+  while (kk < k && seeds[kk] >= 0) kk++;
+  std::copy(seeds.begin(), seeds.end(), out_seeds_host);
+  *out_kk = kk;
+  return TM_OK;
+}
+
 // would run_palettize put the clustering through the resident launch?  (one process per GPU: then every process clusters ALL global tiles
 // itself -- 6 ms, no collective -- instead of a share of them with an all-reduce per Lloyd iteration)
 bool palettize_resident(int64_t n, int npal) { return !knobs().km_launches && resident_plan(n, npal, cu_count()).rounds != 0; }

@@ -288,6 +288,24 @@ def palettize(feat, use, npal, max_iter=300):
     return out
 
 
+def kmeans_last_resident():
+    """did this thread's last k-means (kmeans, kmeans_seeded, or the one inside palettize / quantize_palettes) run through a resident launch
+    to its end?  False: one launch per step -- by shape, by TM_KM_LAUNCHES, or after a barrier of the resident launch gave up"""
+    return bool(lib().tm_kmeans_last_resident())
+
+
+def pp_seeds(feat, use, k):
+    """the D^2 seeding of palettize alone (test seam): feat int32 [n][192], use uint32-as-int32 [n] or None ->
+    (centres found, numpy int64 [k]: the picked point indices in pick order, -1 beyond the centres found)"""
+    import numpy as np
+    assert feat.is_cuda and feat.dtype == torch.int32 and feat.is_contiguous() and feat.dim() == 2 and feat.shape[1] == 192
+    assert use is None or (use.is_cuda and use.dtype == torch.int32 and use.is_contiguous() and use.numel() == feat.shape[0])
+    seeds = np.full(k, -1, np.int64)
+    kk = ctypes.c_int()
+    check(lib().tm_stage_pp_seeds(_p(feat), _p(use), feat.shape[0], k, seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(kk), _stream()))
+    return kk.value, seeds
+
+
 def kmodes(rows, num_clusters, num_init=0, num_modalities=256, max_iter=-1):
     """TKModes.ComputeKModes (kmodes.pas:923-1094): rows uint8 numpy [n][80] (host, like the Pascal arrays) ->
     (labels int32 [n], centroids uint8 [k][80], cost, iterations of the best run)"""
