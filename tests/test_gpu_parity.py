@@ -372,7 +372,7 @@ def test_knn_dense_mode_large(monkeypatch):
 
 def _plan_data(rng, nq, nt, ct, cq):
     """rows whose first ct (database) / cq (query) columns need a second int8 digit and whose other columns fit one: the digit plan becomes
-    HT = ceil(ct / 32), HQ = ceil(cq / 32) (tm_knn.hip: make_plan_scaled)"""
+    HT = ceil(ct / 32), HQ = ceil(cq / 32) (tm_knn_plan.hip: make_plan_scaled)"""
     db = rng.integers(-25, 26, size=(nt, 192)).astype(np.int32)
     q = rng.integers(-25, 26, size=(nq, 192)).astype(np.int32)
     if ct:
@@ -427,6 +427,34 @@ def test_knn_plans_covered():
         pytest.skip("the plan tests did not run in this session")
     assert {(a, b, 0) for a in range(7) for b in range(7)} <= _SEEN_PLANS
     assert (6, 6, 1) in _SEEN_PLANS
+
+
+def test_knn_one_index_several_batches():
+    """one index searched by three batches: narrow queries, queries with 91 wide columns (the plan widens and the database is packed
+    again), then a fresh narrow batch (the widened plan still covers it and is kept).  Every batch against the fp64 brute force, the
+    third also against a fresh index, and the plans named by tm_knn_last_plan."""
+    from tiler_amd import stages
+    rng = np.random.default_rng(2024)
+    nq, nt = 700, 4200
+    db, q1 = _plan_data(rng, nq, nt, 59, 0)
+    _, q2 = _plan_data(rng, nq, nt, 0, 91)
+    _, q3 = _plan_data(rng, nq, nt, 0, 0)
+    ddb = _dev(db)
+    ix = stages.KnnIndex(ddb)
+    plans, results = [], []
+    for q in (q1, q2, q3):
+        idx, err = ix.search(_dev(q))
+        plans.append(stages.knn_last_plan()[:3])
+        results.append((idx.cpu().numpy(), err.cpu().numpy().view(np.uint32)))
+        eidx, eerr = _torch_nn(q, db)
+        assert np.array_equal(results[-1][1], eerr) and np.array_equal(results[-1][0], eidx), "batch %d" % len(plans)
+    ix.close()
+    fresh = stages.KnnIndex(ddb)
+    fidx, ferr = fresh.search(_dev(q3))
+    fresh.close()
+    assert np.array_equal(fidx.cpu().numpy(), results[2][0]) and np.array_equal(ferr.cpu().numpy().view(np.uint32), results[2][1])
+    assert plans[1][1] > plans[0][1], "the wide batch did not widen the query side: %r" % (plans,)
+    assert plans[2][:2] == plans[1][:2], "a built index keeps a plan that still covers the queries: %r" % (plans,)
 
 
 @pytest.mark.parametrize("mode", ["nearest", "topk"])
@@ -1054,7 +1082,7 @@ def test_motion_search_matrix_path(oracle, monkeypatch, tm_w, tm_h, radius, amp)
 @pytest.fixture(params=["by-size", "sampled", "bound"])
 def topk_thresholds(request, monkeypatch):
     """where the k-nearest search's first thresholds come from: the shipped rule (a sample of the database for many queries against a database
-    of some size, tm_knn.hip: knn_index_search_topk), the sample whenever the database has rows enough for one (TM_TOPK_ESTIMATE=1: queries that
+    of some size, tm_knn_topk.hip: knn_index_search_topk), the sample whenever the database has rows enough for one (TM_TOPK_ESTIMATE=1: queries that
     find fewer than k rows within their estimate are searched again), never (=0: the curve window's bound)"""
     monkeypatch.delenv("TM_TOPK_ESTIMATE", raising=False)
     if request.param != "by-size":

@@ -41,7 +41,7 @@ int launch_epu_rerank_ondemand(const void *queries, int64_t nq, const void *knn_
 int launch_epu_rerank(const void *queries, int64_t nq, const void *knn_idx, int k, const void *tile_pal, int64_t ntiles, int npal,
                       const void *table, void *out_tile, void *out_pal, void *out_err, hipStream_t stream);
 
-// tm_knn.hip
+// tm_knn.hip (index, nearest neighbour, the stats of the last search) and tm_knn_topk.hip (k nearest rows); tm_knn.h is their own header
 struct tm_knn_index_impl;
 int knn_index_create(const void *db, int64_t nt, hipStream_t stream, tm_knn_index_impl **out);
 void knn_index_destroy(tm_knn_index_impl *ix);

@@ -22,6 +22,7 @@
 // bound exceeds the sub-tile's largest best + 1 (both sides of the 16-bit compare rounded the safe way), the minimum VALUE is exact, a
 // second row reaching it raises the tie flag that k_knn_ties settles by original index.
 #pragma once
+#include <cstddef>
 #include <type_traits>
 #include "tm_knn_kernel.h"
 
@@ -101,12 +102,40 @@ struct Knn3Args {
   int no_seeds;                 // lists: no seed kernel ran (collection mode), so no tile is left out of the lists
   int first_chunk;              // consume, nearest-neighbour lists: a block is judged on its first chunk's columns before its chain runs (k3_chunk_look; 0: every block runs its chain)
   int list_order;               // lists: a segment leaves sorted by its entries' smallest bound; consume: a segment ends at the first entry nobody can want (0: run order, no stop)
-  unsigned long long *stats;    // consume: [0] blocks evaluated, [1] tiles read, [2] exact (query, row) pairs, [3] list entries consumed, [13] (query, row) pairs of the blocks the first chunk stopped, [28] entries popped, [29] those blocks
-  unsigned long long *seed_stats;  // [64][4] striped by workgroup: blocks, tiles read, pairs of the seed kernel
+  unsigned long long *stats;    // K3Counters::stats, indexed by K3Stat
+  unsigned long long *seed_stats;  // K3Counters::seed: [64][4] striped by workgroup: blocks, tiles read, pairs of the seed kernel
   int64_t n_groups;
   int grid_blocks;              // consume: persistent workgroups
   unsigned *tickets;            // [8] zeroed before the consume launch: next run-slot of each XCD's share of the groups
 };
+
+// The counter block of a search: one buffer the host zeroes before the scan and reads back after it.  The kernels reach it through
+// Knn3Args::stats (+ a K3Stat), ::arena_cursor, ::tickets and ::seed_stats; the host through this struct and nothing else.
+enum K3Stat {
+  K3S_BLOCKS = 0,          // consume: blocks evaluated
+  K3S_TILES = 1,           // consume: tiles read
+  K3S_PAIRS = 2,           // consume: exact (query, row) pairs
+  K3S_LISTED = 3,          // list entries listed
+  K3S_STAMPS = 4,          // [4..9] a diagnostic build's (TM_KNN3_STAMPS) spans of the consume kernel's phases, the last one the total
+  K3S_STAMPS_IN = 10,      // [10..12] ... and inside "consume": pick, chain, epilogue
+  K3S_STOPPED_PAIRS = 13,  // (query, row) pairs of the blocks the first chunk stopped
+  K3S_TICKETS = 14,        // [14..17] these 32 bytes are Knn3Args::tickets: eight u32
+  K3S_CURSOR = 18,         // Knn3Args::arena_cursor
+  K3S_MFMA = 19,           // matrix instructions issued
+  K3S_SEED_STAMPS = 20,    // [20..26] a diagnostic build's spans of the seed kernel's phases, the last one the total
+  K3S_GUARD = 27,          // consume: a tile index or a segment out of range (0: none)
+  K3S_POPPED = 28,         // entries the waves took off their lists: short of K3S_LISTED by what the stops left behind
+  K3S_STOPPED = 29,        // blocks the first chunk stopped
+  K3S_COUNT = 30
+};
+enum K3SeedStat { K3SEED_BLOCKS = 0, K3SEED_TILES = 1, K3SEED_PAIRS = 2, K3SEED_WORDS = 4 };  // a stripe of the seed kernel's counters (the fourth word is spare)
+struct K3Counters {
+  unsigned tie_count, pad_[3];              // k_knn_refine counts the queries it hands to k_knn_ties
+  unsigned long long stats[K3S_COUNT];
+  unsigned long long seed[64][K3SEED_WORDS];  // the seed kernel's, striped by workgroup
+  unsigned *tickets() { return reinterpret_cast<unsigned *>(stats + K3S_TICKETS); }
+};
+static_assert(offsetof(K3Counters, stats) == 16 && offsetof(K3Counters, seed) == 256 && sizeof(K3Counters) == 2304, "the counter block's layout");
 
 __device__ __forceinline__ unsigned k3_wave_umax(unsigned x) {  // max over lanes 0..31 (every lane of a row of 16 ends with its row's)
   x = max(x, (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xf, 0xf, true));
@@ -694,23 +723,23 @@ __global__ __launch_bounds__(K3_SEEDS * 64, 4) void k_knn_seed(const Knn3Args a)
 #if TM_KNN3_STAMPS
   K3_STAMP(5);  // results
   if (a.stats && lane == 0) {
-    for (int i = 0; i < 6; i++) atomicAdd(a.stats + 20 + i, st_acc[i]);
-    atomicAdd(a.stats + 26, __builtin_amdgcn_s_memtime() - st_begin);
+    for (int i = 0; i < 6; i++) atomicAdd(a.stats + K3S_SEED_STAMPS + i, st_acc[i]);
+    atomicAdd(a.stats + K3S_SEED_STAMPS + 6, __builtin_amdgcn_s_memtime() - st_begin);
   }
 #endif
   // The seeds' own counters (blocks, tiles read, pairs), one set of atomics per WORKGROUP into one of 64 striped slots: 90 000 waves adding to
   // three words of one cache line took their turns at the L2 and held every other request of the kernel up behind them (2.5 of its 3.3 ms).
   if (a.seed_stats) {
-    __shared__ unsigned long long s_cnt[2];
-    if (tid < 2) s_cnt[tid] = 0;
+    __shared__ unsigned long long s_sum[2];  // blocks, pairs
+    if (tid < 2) s_sum[tid] = 0;
     __syncthreads();
-    if (lane == 0 && active) { atomicAdd(&s_cnt[0], (unsigned long long)nblocks); atomicAdd(&s_cnt[1], (unsigned long long)npairs); }
+    if (lane == 0 && active) { atomicAdd(&s_sum[0], (unsigned long long)nblocks); atomicAdd(&s_sum[1], (unsigned long long)npairs); }
     __syncthreads();
     if (tid == 0) {
-      unsigned long long *slot = a.seed_stats + (blockIdx.x & 63) * 4;
-      atomicAdd(slot, s_cnt[0]);
-      atomicAdd(slot + 1, (unsigned long long)n_seed);
-      atomicAdd(slot + 2, s_cnt[1]);
+      unsigned long long *slot = a.seed_stats + (blockIdx.x & 63) * K3SEED_WORDS;
+      atomicAdd(slot + K3SEED_BLOCKS, s_sum[0]);
+      atomicAdd(slot + K3SEED_TILES, (unsigned long long)n_seed);
+      atomicAdd(slot + K3SEED_PAIRS, s_sum[1]);
     }
   }
 }
@@ -722,7 +751,7 @@ __global__ __launch_bounds__(K3_SEEDS * 64, 4) void k_knn_seed(const Knn3Args a)
 // in the arena with one atomic add and is copied out, sorted by its entries' smallest bound (sort_segment; a.list_order = 0: as collected).
 // The segments of a list keep the outward order among themselves.  Past the arena's capacity nothing is written and the segment's count is 0: the
 // cursor keeps counting, the host sees the overflow with the scan's other counters and repeats the search with a larger arena.
-#ifdef TM_KNN3_WITH_LISTS  // (not a template: defined in one translation unit, tm_knn.hip)
+#ifdef TM_KNN3_WITH_LISTS  // (not templates: defined in one translation unit, tm_knn.hip, and launched by its host functions)
 __global__ __launch_bounds__(K3_LIST_NT) void k_knn_lists(const Knn3Args a) {
   constexpr int ND = KNN_ND, NT = K3_LIST_NT, LCAP = K3_LCAP;
   constexpr int RB = NT / 16, RS = NT / KNN_GROUP;  // runs per batch, runs per tile-test step
@@ -1076,7 +1105,7 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
       const uint2 sg = a.segs[g * a.max_segs + seg];
       list_n = (int)sg.y;
       if (list_n != 0 && ((unsigned long long)sg.x + sg.y > a.arena_cap || list_n > LCAP)) {  // never by construction (a segment that did not fit the arena has 0 entries): a guard against a corrupted segment table
-        if (tl == 0) atomicMax(a.stats + 27, 0x100000000ull | sg.y);
+        if (tl == 0) atomicMax(a.stats + K3S_GUARD, 0x100000000ull | sg.y);
         list_n = 0;
       }
       for (int i = tl; i < list_n; i += NT) s_ltile[i] = a.ltile[sg.x + i];
@@ -1135,7 +1164,7 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
       while (have) {
         const unsigned tm = tmw;
         if (tile >= n_ttiles) {  // never by construction: a list entry outside the database (a guard: the loads below must not follow it)
-          if (lane == 0) atomicMax(a.stats + 27, 0x200000000ull | (unsigned)tile);
+          if (lane == 0) atomicMax(a.stats + K3S_GUARD, 0x200000000ull | (unsigned)tile);
           break;
         }
         v4i T[KT];
@@ -1286,19 +1315,19 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
   }  // next query group
 #if TM_KNN3_STAMPS
   if (a.stats && lane == 0) {
-    for (int i = 0; i < 5; i++) atomicAdd(a.stats + 4 + i, st_acc[i]);
-    atomicAdd(a.stats + 9, __builtin_amdgcn_s_memtime() - st_begin);
-    for (int i = 5; i < 8; i++) atomicAdd(a.stats + 5 + i, st_acc[i]);  // [10..12]: inside "consume" (the host reads them before it reuses the slots)
+    for (int i = 0; i < 5; i++) atomicAdd(a.stats + K3S_STAMPS + i, st_acc[i]);
+    atomicAdd(a.stats + K3S_STAMPS + 5, __builtin_amdgcn_s_memtime() - st_begin);
+    for (int i = 5; i < 8; i++) atomicAdd(a.stats + K3S_STAMPS_IN + (i - 5), st_acc[i]);  // inside "consume"
   }
 #endif
   if (a.stats && lane == 0) {
-    atomicAdd(a.stats, (unsigned long long)nblocks);
-    atomicAdd(a.stats + 1, (unsigned long long)nloads);
-    atomicAdd(a.stats + 2, (unsigned long long)npairs);
-    if (wave == 0) atomicAdd(a.stats + 3, (unsigned long long)nlisted);
-    atomicAdd(a.stats + 28, (unsigned long long)npopped);  // entries the waves took off their lists: short of [3] by what the stops left behind
-    atomicAdd(a.stats + 19, (unsigned long long)nmfma);  // matrix instructions issued (a full chain has 6 + HT + HQ + min(HT, HQ)), the first-chunk looks' included
-    if (nstopped) { atomicAdd(a.stats + 29, (unsigned long long)nstopped); atomicAdd(a.stats + 13, (unsigned long long)nspairs); }
+    atomicAdd(a.stats + K3S_BLOCKS, (unsigned long long)nblocks);
+    atomicAdd(a.stats + K3S_TILES, (unsigned long long)nloads);
+    atomicAdd(a.stats + K3S_PAIRS, (unsigned long long)npairs);
+    if (wave == 0) atomicAdd(a.stats + K3S_LISTED, (unsigned long long)nlisted);
+    atomicAdd(a.stats + K3S_POPPED, (unsigned long long)npopped);
+    atomicAdd(a.stats + K3S_MFMA, (unsigned long long)nmfma);  // matrix instructions issued (a full chain has 6 + HT + HQ + min(HT, HQ)), the first-chunk looks' included
+    if (nstopped) { atomicAdd(a.stats + K3S_STOPPED, (unsigned long long)nstopped); atomicAdd(a.stats + K3S_STOPPED_PAIRS, (unsigned long long)nspairs); }
   }
 }
 

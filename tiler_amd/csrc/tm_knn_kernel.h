@@ -1,6 +1,7 @@
 // tm_knn_kernel.h -- what the KNN stage's kernels and its host code share (see tm_knn.hip for the scheme, tm_knn3_kernel.h for the scan).
 #pragma once
 #include <climits>
+#include <cstdint>
 #include <type_traits>
 
 #include "tm_common.h"
@@ -34,6 +35,15 @@ struct KnnBoxes {
   const uint32_t *tkey; // [n_ttiles] curve key of each tile's first row (ascending)
   int col[KNN_NC];      // source feature column of each box dimension
   int cen[KNN_NC];      // the digit plan's centre of that column (the radial dimension is measured from the centres)
+};
+
+// where a row lies on the Morton curve both sides are sorted along (k_row_radial, k_curve_keys), and the box columns (k_knn_pack)
+struct CurveSpec {
+  int col[KNN_NC];
+  int lo[3], range[3];      // the three curve columns: union range
+  float scale[4], off[4];   // quantised coordinate of dimension d (three columns, radial) = (value - off) * scale, clamped to its bits
+  int bits[4];
+  int rlog;                 // radial coordinate taken as log2(R + 1) instead of R
 };
 
 }  // namespace tmx
