@@ -17,21 +17,30 @@ __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ fe
                                                   int *__restrict__ box_lo, int *__restrict__ box_hi, uint8_t *__restrict__ out,
                                                   int *__restrict__ err_flag, int *__restrict__ qmeta /* query side: [ntiles][16] box, home tile, high-chunk mask */,
                                                   uint8_t *__restrict__ hmask /* database side: [ntiles] which high-digit chunks of the tile hold a non-zero digit */) {
-  __shared__ int16_t s_c[192], s_p[192];
-  __shared__ __attribute__((aligned(16))) int s_v[32][196];  // (pitch 196: a row's 16-value groups are 16-byte aligned, and sixteen rows' groups cover the 64 banks once)
+  __shared__ __attribute__((aligned(16))) int16_t s_c[192];  // centre of the column at packed position p
+  __shared__ int16_t s_inv[192];                             // source column -> packed position
   __shared__ uint32_t s_norm[32];
   __shared__ unsigned s_hm;  // bit kc: high-digit chunk kc of this tile is not all zero
   __shared__ long long s_bsq[32];  // query side: squared distance of each row from the centres over the box columns
-  __shared__ __attribute__((aligned(16))) int16_t s_raw[32][200];  // the tile's rows as they lie in memory (pitch 400 B)
-  for (int i = threadIdx.x; i < 192; i += 256) { s_p[i] = perm[i]; s_c[i] = centre[perm[i]]; }
+  __shared__ __attribute__((aligned(16))) int16_t s_perm[32][200];  // the tile's rows, raw values in PACKED column order (pitch 400 B)
+  for (int i = threadIdx.x; i < 192; i += 256) { s_c[i] = centre[perm[i]]; s_inv[perm[i]] = (int16_t)i; }
+  __syncthreads();
   const int kch = 6 + hch, tile_bytes = knn_tile_bytes(hch, with_box);
-  // the 32 rows of a tile come in as 16-byte vectors (three per thread) and are permuted out of LDS (the column permutation would otherwise
-  // turn the read into 6 144 two-byte loads per tile); the NEXT tile's vectors are fetched while this one is worked on, and the row
-  // numbers (curve order) of the one after: a workgroup walks its tiles one after the other, and two dependent round trips to memory per
-  // tile were most of the kernel
+  // The 32 rows of a tile come in as 16-byte vectors (three per thread: the column permutation would otherwise turn the read into 6 144
+  // two-byte loads per tile) and go into LDS already permuted, two bytes at a time to places the thread knows for good (its vectors cover the
+  // same columns of every tile); digits and norms are then made from 16-byte reads of the permuted rows.  (A copy in memory order, a second,
+  // centred int32 copy in packed order and a barrier between them were 38 KB of LDS -- four workgroups a CU -- and a third of a tile's time.)
+  // The NEXT tile's vectors are fetched while this one is worked on, and the row numbers (curve order) of the one after: a workgroup walks
+  // its tiles one after the other, and two dependent round trips to memory per tile were most of the kernel.
   int pr[3], pv[3];
+  uint16_t dst[3][8];  // where the eight values of vector u go in s_perm
 #pragma unroll
-  for (int u = 0; u < 3; u++) { const int i = threadIdx.x + u * 256; pr[u] = i / 24; pv[u] = i - pr[u] * 24; }
+  for (int u = 0; u < 3; u++) {
+    const int i = threadIdx.x + u * 256;
+    pr[u] = i / 24; pv[u] = i - pr[u] * 24;
+#pragma unroll
+    for (int j = 0; j < 8; j++) dst[u][j] = (uint16_t)(pr[u] * 200 + s_inv[pv[u] * 8 + j]);
+  }
   auto row_of = [&](int64_t tile, int r) -> int64_t {
     int64_t row = std::min<int64_t>(tile * 32 + r, n - 1);
     return rowperm ? (int64_t)rowperm[row] : row;  // rows are packed in curve order
@@ -50,7 +59,11 @@ __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ fe
     __syncthreads();
     if (threadIdx.x == 0) s_hm = 0;
 #pragma unroll
-    for (int u = 0; u < 3; u++) *reinterpret_cast<uint4 *>(&s_raw[pr[u]][pv[u] * 8]) = nvec[u];
+    for (int u = 0; u < 3; u++) {
+      const uint32_t w[4] = {nvec[u].x, nvec[u].y, nvec[u].z, nvec[u].w};
+#pragma unroll
+      for (int j = 0; j < 8; j++) (&s_perm[0][0])[dst[u][j]] = (int16_t)(w[j >> 1] >> ((j & 1) * 16));
+    }
     {
       const int64_t t1 = tile + gridDim.x, t2 = tile + 2 * (int64_t)gridDim.x;
 #pragma unroll
@@ -60,16 +73,15 @@ __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ fe
       }
     }
     __syncthreads();
-    // centred, permuted values of the 32 rows
     if (qmeta && threadIdx.x >= 192 && threadIdx.x < 224) {
       // the sub-tile's bounding box over the box columns, as the first scan shape computed it in its prologue: the rows are in LDS here (a
-      // kernel of its own gathered six scattered columns of every row again, 0.33 ms for 3.2 M rows), and these lanes have nothing else to do
+      // kernel of its own gathered six scattered columns of every row again, 0.33 ms for 3.2 M rows)
       const int r = threadIdx.x - 192;
       int lo[KNN_NC], hi[KNN_NC];
       long long boxsq = 0;
 #pragma unroll
       for (int d = 0; d < KNN_NC; d++) {
-        const int v = s_raw[r][cs.col[d]];
+        const int v = s_perm[r][s_inv[cs.col[d]]];
         lo[d] = hi[d] = v;
         const long long c = v - (int)centre[cs.col[d]];
         boxsq += c * c;
@@ -82,50 +94,60 @@ __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ fe
 #pragma unroll
         for (int d = 0; d < KNN_NC; d++) { qmeta[tile * 16 + d] = lo[d]; qmeta[tile * 16 + 8 + d] = hi[d]; }
     }
-    if (threadIdx.x < 192) {  // a thread per (permuted) column: no index arithmetic in the loop; the fourth wave's lanes beyond 192 sit it out
-      const int p = threadIdx.x, sp = s_p[p], c = s_c[p];
-#pragma unroll 8
-      for (int r = 0; r < 32; r++) {
-        const int v = (int)s_raw[r][sp] - c;
-        s_v[r][p] = negate ? -v : v;
-      }
-    }
-    __syncthreads();
     uint8_t *obase = out + tile * (int64_t)tile_bytes;
     bool bad = false;
+    const int mult = negate ? -scale : scale;  // the digits are those of mult * (v - c)
     for (int piece = threadIdx.x; piece < kch * 64; piece += 256) {
-      const int kc = piece >> 6, ln = piece & 63, half = ln >> 5, r = ln & 31;
-      // the piece's sixteen values as four 16-byte LDS reads (sixteen 4-byte ones were most of this loop's instructions)
-      const int kpos0 = kc * 32 + half * 16;  // byte position along K of the piece's first value
-      const bool high = kpos0 >= 192;         // (uniform in the piece: 192 is a multiple of 16)
-      const int4 *src = reinterpret_cast<const int4 *>(&s_v[r][high ? kpos0 - 192 : kpos0]);
-      const int4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-      const int vals[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
-      const bool must_fit = !high && kpos0 >= hch * 32;  // columns without a high digit (hch * 32 is a multiple of 16 too)
-      uint32_t w[4] = {0, 0, 0, 0};
+      // a wave's 64 pieces are one chunk's (kc is the same for them, and known to be: the cases below are branches, not masks)
+      const int kc = __builtin_amdgcn_readfirstlane(piece >> 6), ln = piece & 63, half = ln >> 5, r = ln & 31;
+      const bool high = kc >= 6;                // a chunk of high digits, of the columns of chunk kc - 6
+      const bool must_fit = !high && kc >= hch;  // columns without a high digit
+      const int kp = (high ? kc - 6 : kc) * 32 + half * 16;  // packed position of the piece's first value
+      // the piece's sixteen values and their centres as two 16-byte LDS reads each (the centres' are the same for the 32 rows: a broadcast)
+      const int4 *src = reinterpret_cast<const int4 *>(&s_perm[r][kp]), *cen = reinterpret_cast<const int4 *>(&s_c[kp]);
+      const int4 q0 = src[0], q1 = src[1], c0 = cen[0], c1 = cen[1];
+      const int qw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w}, cw[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+      // v = mult * (value - centre), |v| < 2^18 (a 24-bit multiply is exact).  Balanced base 256, v = 256 h + l with l in [-128, 127]: l's byte
+      // is v's low byte and h = (v + 128) >> 8; a digit d fits int8 where (unsigned)(d + 128) <= 255, so the OR of those sums over the piece
+      // has a bit above the eighth exactly where some digit does not fit.
+      uint32_t w[4] = {0, 0, 0, 0}, over = 0;
 #pragma unroll
       for (int b = 0; b < 16; b++) {
-        const int v = vals[b] * scale;
-        const int lo = ((v + 128) & 255) - 128;  // low digit in [-128,127]
-        int digit;
-        if (!high) {
-          digit = lo;
-          if (must_fit && v != lo) bad = true;
+        const int raw = (b & 1) ? (qw[b >> 1] >> 16) : (int)(int16_t)(qw[b >> 1] & 0xffff);
+        const int c = (b & 1) ? (cw[b >> 1] >> 16) : (int)(int16_t)(cw[b >> 1] & 0xffff);
+        const int v = __mul24(raw - c, mult);
+        if (high) {
+          const int h = (v + 128) >> 8;
+          over |= (uint32_t)(h + 128);
+          w[b >> 2] |= (uint32_t)(h & 255) << ((b & 3) * 8);
         } else {
-          digit = (v - lo) >> 8;
-          if (digit < -128 || digit > 127) bad = true;
+          if (must_fit) over |= (uint32_t)(v + 128);
+          w[b >> 2] |= (uint32_t)(v & 255) << ((b & 3) * 8);
         }
-        w[b >> 2] |= (uint32_t)(digit & 255) << ((b & 3) * 8);
       }
+      if (over > 255u) bad = true;
       *reinterpret_cast<uint4 *>(obase + piece * 16) = make_uint4(w[0], w[1], w[2], w[3]);
       if (high && (w[0] | w[1] | w[2] | w[3])) atomicOr(&s_hm, 1u << (kc - 6));
     }
-    {  // |v-c|^2 of every row (the kernel drops the query side's parity bit): eight lanes per row, integer sums (32 threads walking 192
-       // values each were the longest leg of a tile)
+    {  // |v-c|^2 of every row (the kernel drops the query side's parity bit): eight lanes per row, 24 packed positions each, integer sums
+       // mod 2^32 (their order does not matter; 32 threads walking 192 values each were the longest leg of a tile)
       const int r = threadIdx.x >> 3, part = threadIdx.x & 7;
       uint32_t sq = 0, sqp = 0;  // over all columns; over the first chunk's (perm[0..31], the 32 widest: k3_chunk_look's lower bound)
-#pragma unroll 8
-      for (int p = part; p < 192; p += 8) { const int v = s_v[r][p]; sq += (uint32_t)(v * v); if (p < 32) sqp += (uint32_t)(v * v); }
+      const int4 *src = reinterpret_cast<const int4 *>(&s_perm[r][part * 24]), *cen = reinterpret_cast<const int4 *>(&s_c[part * 24]);
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        const int4 q = src[k], c = cen[k];
+        const int qw[4] = {q.x, q.y, q.z, q.w}, cw[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const int p = part * 24 + k * 8 + 2 * j;
+          const int v0 = (int)(int16_t)(qw[j] & 0xffff) - (int)(int16_t)(cw[j] & 0xffff), v1 = (qw[j] >> 16) - (cw[j] >> 16);
+          const uint32_t s0 = (uint32_t)__mul24(v0, v0), s1 = (uint32_t)__mul24(v1, v1);  // (the low 32 bits of the product, as a 32-bit multiply's)
+          sq += s0 + s1;
+          if (p < 32) sqp += s0;
+          if (p + 1 < 32) sqp += s1;
+        }
+      }
       sq += __shfl_xor(sq, 1); sq += __shfl_xor(sq, 2); sq += __shfl_xor(sq, 4);
       sqp += __shfl_xor(sqp, 1); sqp += __shfl_xor(sqp, 2); sqp += __shfl_xor(sqp, 4);
       // what the pack keeps per row is what the scan's chain starts from (k3_chain's `cin`): the query side's |q-c|^2 (the kernel drops its
