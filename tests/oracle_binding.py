@@ -8,6 +8,12 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
 
 
+class Plan(ctypes.Structure):
+    """tmo_plan of oracle/tm_oracle.h"""
+    _fields_ = [("count", ctypes.c_int), ("luma", ctypes.c_int32 * 64), ("y2", (ctypes.c_int32 * 4) * 64), ("remap", ctypes.c_uint8 * 64),
+                ("y2_mixed_colors", ctypes.c_int)]
+
+
 class Oracle:
     def __init__(self, so):
         self.L = ctypes.CDLL(so)
@@ -205,6 +211,23 @@ class Oracle:
         self.L.tmo_dither_tiles(_p(tiles), _p(f), _p(pal_idx), tiles.shape[0], _p(palettes), palettes.shape[1], int(use_tk), y2_mixed,
                                 _p(out))
         return out
+
+    def prepare_plan(self, palette, y2_mixed=4):
+        """PreparePlan (tilingencoder.pas:2268-2301) of one palette -> Plan"""
+        palette = np.ascontiguousarray(palette, np.int32)
+        plan = Plan()
+        self.L.tmo_prepare_plan.argtypes = [ctypes.POINTER(Plan), ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        self.L.tmo_prepare_plan.restype = None
+        self.L.tmo_prepare_plan(ctypes.byref(plan), _p(palette), palette.shape[0], y2_mixed)
+        return plan
+
+    def mixing_plan_yliluoma(self, plan, col):
+        """DeviseBestMixingPlanYliluoma of one colour -> the sorted list of plan indices (uint8 [count])"""
+        lst = np.zeros(256, np.uint8)
+        self.L.tmo_mixing_plan_yliluoma.argtypes = [ctypes.POINTER(Plan), ctypes.c_uint32, ctypes.c_void_p]
+        self.L.tmo_mixing_plan_yliluoma.restype = ctypes.c_int
+        n = self.L.tmo_mixing_plan_yliluoma(ctypes.byref(plan), int(col) & 0xFFFFFFFF, _p(lst))
+        return lst[:n].copy()
 
     # ---- dedup
     def dedup(self, rows, use_in=None):

@@ -15,7 +15,7 @@ def _to_screen(tiles_u32, tm_w, tm_h):
 
 
 def run(oracle, frames, fps=24.0, palette_size=16, palette_count=1, dithering_mode=4, quality_tc=7.0, tile_count=0,
-        max_s=15.0, min_s=1.0, lo=0.8, stop_after=None, timings=None, motion_radius=0, epu=False):
+        max_s=15.0, min_s=1.0, lo=0.8, stop_after=None, timings=None, motion_radius=0, epu=False, use_tk=True, y2_mixed=4):
     import time
     nf, h, w = frames.shape
     tm_w, tm_h = (w - 1) // 8 + 1, (h - 1) // 8 + 1
@@ -112,7 +112,7 @@ def run(oracle, frames, fps=24.0, palette_size=16, palette_count=1, dithering_mo
         timings["palettes"] = time.time() - t0
     # Dither
     t0 = time.time()
-    pal_px = oracle.dither(gtiles, gflags, pal_idx, palettes, True)
+    pal_px = oracle.dither(gtiles, gflags, pal_idx, palettes, use_tk, y2_mixed)
     out.update(pal_px=pal_px)
     if timings is not None:
         timings["dither"] = time.time() - t0

@@ -21,6 +21,37 @@ def _run_encoder(frames, **settings):
     return enc
 
 
+def _assert_run_equals_oracle(oracle, enc, exp, nf):
+    """what Run(esAll) left in the encoder against the oracle pipeline's tables"""
+    c = enc.counts()
+    assert np.array_equal(enc.FrameCorrelations().view(np.uint32), exp["correl"].view(np.uint32))
+    assert np.array_equal(enc.KeyFrames(), exp["keyframes"])
+    assert c["tiles"] == exp["final_T"]
+    hdr, pal, rgb = enc.Tiles()
+    assert np.array_equal(pal, exp["final_pal_px"])
+    assert np.array_equal(hdr["UseCount"], exp["final_use"])
+    assert np.array_equal(hdr["PalIdx_Initial"], exp["final_pal_idx"])
+    assert np.array_equal(rgb, exp["final_rgb"])
+    assert np.array_equal(enc.Palettes(), exp["palettes"])
+    per = exp["per"]
+    for f in range(nf):
+        tm = enc.TileMap(f)
+        sl = slice(f * per, (f + 1) * per)
+        assert np.array_equal(tm["TileIdx"], exp["final_tm_tile"][sl])
+        assert np.array_equal(tm["PalIdx"], exp["tm_pal"][sl])
+        assert np.array_equal(tm["Flags"] & 3, exp["flags"][sl])
+        assert np.array_equal((tm["Flags"] >> 2) & 1, exp["is_predicted"][sl])
+        assert np.array_equal(tm["PredictedX"], exp["pred_x"][sl]) and np.array_equal(tm["PredictedY"], exp["pred_y"][sl])
+        psnr = np.array([oracle.L.tmo_euclidean_to_psnr(int(e)) for e in exp["tm_err"][sl]], np.float32)
+        assert np.allclose(tm["PSNR"], psnr, rtol=1e-6)  # PSNR goes through log10: tolerance 1e-6 relative
+    # TKeyFrame.LogPSNR (1006-1028): mean PSNR by tile per key frame and over the clip
+    q = enc.PSNR()
+    allp = np.array([oracle.L.tmo_euclidean_to_psnr(int(e)) for e in exp["tm_err"]], np.float64)
+    kf = list(exp["keyframes"]) + [nf]
+    assert np.allclose(q["per_keyframe"], [allp[a * per:b * per].mean() for a, b in zip(kf[:-1], kf[1:])], rtol=1e-6)
+    assert np.isclose(q["global"], allp.mean(), rtol=1e-6)
+
+
 @pytest.mark.parametrize("shape,pc,radius,tc,epu", [((10, 64, 64), 1, 0, 0, False), ((6, 52, 100), 3, 0, 0, False), ((10, 64, 64), 1, 32, 0, False),
                                                       ((10, 64, 64), 2, 32, 150, False), ((7, 52, 100), 3, 5, 300, False),
                                                       ((1, 32, 32), 1, 32, 0, False), ((6, 52, 100), 3, 0, 0, True),
@@ -36,34 +67,102 @@ def test_run_all_matches_oracle(oracle, shape, pc, radius, tc, epu):
     exp = oracle_pipeline.run(oracle, frames, palette_count=pc, min_s=0.1, motion_radius=radius, tile_count=tc, epu=epu)
     kw = dict(GlobalTilingTileCount=tc) if tc else {}
     enc = _run_encoder(frames, PaletteCount=pc, ShotTransMinSecondsPerKF=0.1, MotionPredictRadius=radius, FrameTilingExtendedPaletteUsage=epu, **kw)
-    c = enc.counts()
-    assert np.array_equal(enc.FrameCorrelations().view(np.uint32), exp["correl"].view(np.uint32))
-    assert np.array_equal(enc.KeyFrames(), exp["keyframes"])
-    assert c["tiles"] == exp["final_T"]
-    hdr, pal, rgb = enc.Tiles()
-    assert np.array_equal(pal, exp["final_pal_px"])
-    assert np.array_equal(hdr["UseCount"], exp["final_use"])
-    assert np.array_equal(hdr["PalIdx_Initial"], exp["final_pal_idx"])
-    assert np.array_equal(rgb, exp["final_rgb"])
-    assert np.array_equal(enc.Palettes(), exp["palettes"])
-    per = exp["per"]
-    for f in range(shape[0]):
-        tm = enc.TileMap(f)
-        sl = slice(f * per, (f + 1) * per)
-        assert np.array_equal(tm["TileIdx"], exp["final_tm_tile"][sl])
-        assert np.array_equal(tm["PalIdx"], exp["tm_pal"][sl])
-        assert np.array_equal(tm["Flags"] & 3, exp["flags"][sl])
-        assert np.array_equal((tm["Flags"] >> 2) & 1, exp["is_predicted"][sl])
-        assert np.array_equal(tm["PredictedX"], exp["pred_x"][sl]) and np.array_equal(tm["PredictedY"], exp["pred_y"][sl])
-        psnr = np.array([oracle.L.tmo_euclidean_to_psnr(int(e)) for e in exp["tm_err"][sl]], np.float32)
-        assert np.allclose(tm["PSNR"], psnr, rtol=1e-6)  # PSNR goes through log10: tolerance 1e-6 relative
-    # TKeyFrame.LogPSNR (1006-1028): mean PSNR by tile per key frame and over the clip
-    q = enc.PSNR()
-    allp = np.array([oracle.L.tmo_euclidean_to_psnr(int(e)) for e in exp["tm_err"]], np.float64)
-    kf = list(exp["keyframes"]) + [shape[0]]
-    assert np.allclose(q["per_keyframe"], [allp[a * per:b * per].mean() for a, b in zip(kf[:-1], kf[1:])], rtol=1e-6)
-    assert np.isclose(q["global"], allp.mean(), rtol=1e-6)
+    _assert_run_equals_oracle(oracle, enc, exp, shape[0])
     enc.close()
+
+
+_NULL_COLOR = -65281  # cDitheringNullColor $FFFF00FF as int32
+
+
+@pytest.mark.parametrize("shape,pc,ps,radius,tc,epu,tk,mixed,post,moved",
+                         [((6, 52, 100), 3, 2, 0, 0, False, True, None, None, None), ((6, 52, 100), 3, 16, 0, 0, False, False, 4, None, None),
+                          ((6, 52, 100), 3, 64, 0, 0, True, False, 16, 0xC0C0C0, 10), ((6, 52, 100), 3, 64, 0, 0, True, True, None, 0xC0C0C0, 10),
+                          ((10, 64, 64), 2, 5, 32, 150, True, False, 3, None, 145), ((10, 64, 64), 4, 64, 32, 150, True, True, None, 0xE0E0C0, 99),
+                          ((3, 24, 24), 2, 3, 32, 0, True, False, 1, None, 0)])
+def test_run_all_matches_oracle_off_the_defaults(oracle, shape, pc, ps, radius, tc, epu, tk, mixed, post, moved):
+    """test_run_all_matches_oracle's assertions with the [Dither] settings off PaletteSize = 16 / Thomas-Knoll: ps = PaletteSize, tk =
+    DitheringUseThomasKnoll, mixed = DitheringYliluoma2MixedColors (tk off).  post: an AND mask on the clip's pixels, so few colours that
+    the quantiser leaves null slots in the palettes (PreparePalettes, OptimizePalettes, the re-rank over every palette and features_pal
+    then walk palettes with holes).  moved: the oracle's number of items the extended-palette re-rank gave a palette other than their
+    tile's own.  It is 0 for the (3, 24, 24) clip -- 22 global tiles, two thirds of its items motion predicted; that case is here for
+    the padded k = 64 list at a 3-colour palette with one mixed colour.
+    Every condition a case is run for is asserted from the oracle's result before the encoder is compared with it."""
+    from tiler_amd import synth
+    from tests import oracle_pipeline
+    frames = synth.video(*shape[:1], shape[2], shape[1], cut=4)
+    if post is not None:
+        frames = frames & np.uint32(post)
+    okw = {} if tk else dict(use_tk=False, y2_mixed=mixed)
+    exp = oracle_pipeline.run(oracle, frames, palette_size=ps, palette_count=pc, min_s=0.1, motion_radius=radius, tile_count=tc, epu=epu, **okw)
+    nulls = (exp["palettes"] == _NULL_COLOR).sum(axis=1)
+    assert exp["palettes"].shape == (pc, ps)
+    if post == 0xC0C0C0:
+        assert (nulls > 0).all(), nulls
+    elif post is not None:
+        assert (nulls > 0).any(), nulls
+    if epu:
+        live = exp["tm_tile_recon"] >= 0
+        assert int((exp["tm_pal"][live] != exp["pal_idx"][exp["tm_tile_recon"][live]]).sum()) == moved
+        assert moved >= 1 or shape == (3, 24, 24)  # (see the docstring: that clip's re-rank moves nothing)
+    if radius == 32:
+        assert exp["is_predicted"].any() and not exp["is_predicted"].all()
+    kw = dict(GlobalTilingTileCount=tc) if tc else {}
+    if not tk:
+        kw.update(DitheringYliluoma2MixedColors=mixed)
+    enc = _run_encoder(frames, PaletteCount=pc, PaletteSize=ps, DitheringUseThomasKnoll=tk, ShotTransMinSecondsPerKF=0.1, MotionPredictRadius=radius,
+                       FrameTilingExtendedPaletteUsage=epu, **kw)
+    assert enc.PaletteSize == ps and enc.DitheringUseThomasKnoll == tk
+    _assert_run_equals_oracle(oracle, enc, exp, shape[0])
+    enc.close()
+
+
+def test_stream_render_and_reload_off_the_defaults_yliluoma(oracle, tmp_path):
+    """PaletteSize = 5 with the Yliluoma planner (3 mixed colours), motion prediction and the extended palette usage: the saved stream, played
+    with the reference player's semantics, shows RenderFrames' frames; ReloadGTM into a fresh encoder brings PaletteSize = 5, the palettes
+    and the tile pixels back (test_reload_gtm_round_trip's comparisons)"""
+    from tiler_amd import synth
+    from tiler_amd.encoder import TilingEncoder
+    from tests import gtm_reader
+    nf = 10
+    frames = synth.video(nf, 64, 64, cut=4)
+    a = str(tmp_path / "a.gtm")
+    enc = _run_encoder(frames, PaletteCount=2, PaletteSize=5, DitheringUseThomasKnoll=False, DitheringYliluoma2MixedColors=3, ShotTransMinSecondsPerKF=0.1,
+                       MotionPredictRadius=32, GlobalTilingTileCount=150, FrameTilingExtendedPaletteUsage=True)
+    enc.Save(a)
+    _, player = gtm_reader.play(oracle, open(a, "rb").read())
+    assert "PaletteSize=5" in player.settings and "DitheringUseThomasKnoll=0" in player.settings and "DitheringYliluoma2MixedColors=3" in player.settings
+    shown = np.stack([np.asarray(f, np.uint32) & 0xFFFFFF for f in player.frames])
+    got = enc.RenderFrames(device=False)
+    assert got.shape == (nf, 64, 64)
+    assert np.array_equal(got, ((shown & 0xFF) << 16) | (shown & 0xFF00) | (shown >> 16))  # the player's 0x00BBGGRR as the pushed frames' 0x00RRGGBB
+    enc2 = TilingEncoder()
+    enc2.LoadDefaultSettings()
+    assert enc2.PaletteSize == 16
+    enc2.PaletteCount = 2
+    enc2.SetVideo(64, 64, 24.0, nf)
+    enc2.ReloadGTM(a)
+    assert enc2.PaletteSize == 5
+    assert np.array_equal(enc2.KeyFrames(), enc.KeyFrames())
+    pal = enc.Palettes().copy()
+    assert pal.shape == (2, 5)
+    pal[pal == _NULL_COLOR] = 0xFFFFFF  # the stream stores the null colour as white (5284-5285)
+    assert np.array_equal(enc2.Palettes(), pal)
+    px1, px2 = enc.Tiles()[1], enc2.Tiles()[1]
+    assert px1.shape == px2.shape and px1.max() < 5
+    some_pred = False
+    for f in range(nf):
+        t1, t2 = enc.TileMap(f), enc2.TileMap(f)
+        pred = ((t1["Flags"] >> 2) & 1).astype(bool)
+        some_pred |= bool(pred.any())
+        assert np.array_equal(pred, ((t2["Flags"] >> 2) & 1).astype(bool))
+        assert np.array_equal(t1["Flags"][~pred], t2["Flags"][~pred])  # a predicted item's mirrors are not in the stream
+        assert np.array_equal(t1["PredictedX"][pred], t2["PredictedX"][pred]) and np.array_equal(t1["PredictedY"][pred], t2["PredictedY"][pred])
+        assert np.array_equal(t1["PalIdx"][~pred], t2["PalIdx"][~pred])
+        assert np.array_equal(px1[t1["TileIdx"][~pred]], px2[t2["TileIdx"][~pred]])  # same pixels, possibly under another index
+    assert some_pred
+    assert np.array_equal(enc2.RenderFrames(device=False), got)
+    enc.close()
+    enc2.close()
 
 
 def test_reference_default_palette_count_with_extended_palette_usage(oracle):
@@ -388,7 +487,7 @@ class _FakeDist:
 
 
 def _sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, pp_sharded, recon_chunk=0, size=(64, 48), palette_count=3, tile_count=150,
-                                           palettize_tiles=None):
+                                           palettize_tiles=None, extra=None):
     import threading
     from tiler_amd import synth, distributed
     from tiler_amd.encoder import TilingEncoder
@@ -400,7 +499,7 @@ def _sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, pp_s
         monkeypatch.delenv("TM_PP_SHARDED", raising=False)
     frames = synth.video(12, size[0], size[1], cut=3)
     kw = dict(PaletteCount=palette_count, ShotTransMinSecondsPerKF=0.1, MotionPredictRadius=radius, FrameTilingExtendedPaletteUsage=epu,
-              GlobalTilingTileCount=tile_count)
+              GlobalTilingTileCount=tile_count, **(extra or {}))  # extra: further settings, the same for the single run and every rank
     ref = _run_encoder(frames, **kw)
     want = (np.stack([ref.TileMap(f) for f in range(12)]), ref.Tiles())
     if palettize_tiles is not None:  # the tiles the single run's PreparePalettes clustered
@@ -450,6 +549,15 @@ def test_sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, 
     through the library's collective callback, and must end with exactly the single-process result.  With 6 ranks on 4 key frames some
     ranks own no frame at all; with 5 ranks on 3 palettes some own no palette."""
     _sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, pp_sharded)
+
+
+@pytest.mark.parametrize("world,pp_sharded,extra", [(2, True, dict(PaletteSize=5, DitheringUseThomasKnoll=False, DitheringYliluoma2MixedColors=3)),
+                                                      (3, False, dict(PaletteSize=64))], ids=["2-yliluoma-5", "3-size-64"])
+def test_sharded_ranks_merge_to_the_single_run_off_the_defaults(monkeypatch, world, pp_sharded, extra):
+    """the same with motion prediction (radius 8) and the extended palette usage at a PaletteSize other than 16: five colours dithered by
+    the Yliluoma planner over two ranks, 64 colours over three -- the sharded quantisation, the merge of the ranks' Dither shares and the
+    re-rank's palette tables all take their width from the setting"""
+    _sharded_ranks_merge_to_the_single_run(monkeypatch, 8, True, world, pp_sharded, extra=extra)
 
 
 @pytest.mark.parametrize("radius,epu", [(0, False), (8, True)])
