@@ -583,6 +583,11 @@ TM_API int tm_stage_rgb_to_lab(const void *rgb, int64_t n, void *out_lab, void *
  * mirror_flags may be NULL (no un-mirroring). */
 TM_API int tm_stage_features_rgb(const void *tiles, int64_t n, const void *mirror_flags, int mode, int use_lab,
                                  void *out_i16, void *stream);
+/* The same for a list of rows, as Reconstruct asks for its queries: out row i = the features of tile rows[i] (i32 [n], repeats allowed; no
+ * un-mirroring).  colmm may be NULL; else i32 [384] on the device, preset by the caller to 192 x INT_MAX, then 192 x INT_MIN: the minimum and the
+ * maximum of each of the 192 output columns are folded in (what the nearest-neighbour search's digit plan reads). */
+TM_API int tm_stage_features_rgb_rows(const void *tiles, const void *rows, int64_t n, int mode, int use_lab, void *out_i16,
+                                      void *colmm_or_null, void *stream);
 /* FromPal=True variant (PrepareReconstruct.DoPsyV, :4570-4583): pal_px u8 [n][64], pal_idx i32 [n],
  * palettes i32 [npal][pal_size]. */
 TM_API int tm_stage_features_pal(const void *pal_px, const void *pal_idx, int64_t n, const void *palettes, int pal_size,

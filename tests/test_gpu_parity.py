@@ -82,7 +82,7 @@ def test_features_rgb_extremes(oracle):
 @pytest.mark.parametrize("mode,use_lab", [(1, False), (0, False), (3, False), (4, True), (4, False), (3, True)])
 def test_features_first_look_agrees_with_reference_order(mode, use_lab, monkeypatch):
     """The int16 features take a separable first look at every coefficient and sum it in the reference's order only when the rounding
-    is in doubt (tm_features.hip): over 300 000 tiles of every kind -- noise, flat, two-colour, ramps, near-black -- both forms give the
+    is in doubt (tm_dct.h): over 300 000 tiles of every kind -- noise, flat, two-colour, ramps, near-black -- both forms give the
     same 57.6 M integers (TM_FEATURES_PLAIN=1 sums every coefficient the reference's way; that form is the one checked against the
     oracle above, at the oracle's sizes)."""
     from tiler_amd import stages
@@ -217,6 +217,32 @@ def test_features_eight_tiles_a_wave_against_a_tile_at_a_time(monkeypatch, mode,
                 monkeypatch.delenv("TM_FEATURES_BY_TILE")
                 monkeypatch.setenv("TM_FEATURES_PLAIN", "1")
                 assert torch.equal(stages.features_rgb(td[:n].contiguous(), fl, mode, use_lab), got), (n, fl is not None)
+
+
+@pytest.mark.parametrize("mode,by_tile", [(1, False), (1, True), (3, False)])
+def test_features_of_a_row_list_with_column_ranges(monkeypatch, mode, by_tile):
+    """Reconstruct's form of the int16 features (launch_features_rgb_rows): a list of rows with repeats instead of the tiles themselves, and
+    the output columns' ranges folded in by the kernel -- k_features_tiles8 (the default), k_features_i16<0> (TM_FEATURES_BY_TILE=1) and a
+    special DCT mode (always k_features_i16<0>) -- against the features of the gathered tiles, at list lengths of one lane group, a ragged
+    wave, one full run, a run and one, and several workgroups with a ragged tail.  (In the special mode both sides run k_features_i16<0>: that
+    case checks the row gather and the ranges, not the arithmetic, which test_features_rgb holds against the oracle.)"""
+    from tiler_amd import stages
+    t, _ = _tile_kinds(600, 4242)
+    td = _dev(t)
+    g = torch.Generator(device="cuda").manual_seed(99 + mode)
+    monkeypatch.delenv("TM_FEATURES_PLAIN", raising=False)
+    for n in (1, 7, 8, 9, 4099):
+        rows = torch.randint(0, 600, (n,), generator=g, device="cuda", dtype=torch.int32)
+        if n > 1:
+            rows[n // 2] = rows[0]  # (a repeat even where chance gives none)
+        monkeypatch.delenv("TM_FEATURES_BY_TILE", raising=False)
+        exp = stages.features_rgb(td[rows.long()].contiguous(), None, mode, False)
+        if by_tile:
+            monkeypatch.setenv("TM_FEATURES_BY_TILE", "1")
+        out, colmm = stages.features_rgb_rows(td, rows, mode, False)
+        assert torch.equal(out, exp), n
+        assert torch.equal(colmm, torch.stack([exp.min(0).values, exp.max(0).values]).int()), n
+        assert torch.equal(stages.features_rgb_rows(td, rows, mode, False, with_colmm=False)[0], exp), n
 
 
 def test_features_pal_and_cluster(tiles_flags, oracle):

@@ -42,6 +42,7 @@ SIGNATURES = {
     "tm_set_devices": (c_int, [c_void_p, ctypes.POINTER(c_int), c_int]),
     "tm_stage_load": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tm_stage_features_rgb": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "tm_stage_features_rgb_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tm_stage_features_pal": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "tm_stage_features_cluster": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "tm_stage_window_dcts": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),

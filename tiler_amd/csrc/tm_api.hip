@@ -35,6 +35,12 @@ int tm_stage_features_rgb(const void *tiles, int64_t n, const void *mirror_flags
   return launch_features_rgb(tiles, n, mirror_flags, mode, use_lab, out_i16, (hipStream_t)stream);
 }
 
+int tm_stage_features_rgb_rows(const void *tiles, const void *rows, int64_t n, int mode, int use_lab, void *out_i16, void *colmm_or_null,
+                               void *stream) {
+  knobs_reload();
+  return launch_features_rgb_rows(tiles, rows, n, mode, use_lab, out_i16, (hipStream_t)stream, colmm_or_null);
+}
+
 int tm_stage_features_pal(const void *pal_px, const void *pal_idx, int64_t n, const void *palettes, int pal_size, int mode,
                           void *out_i16, void *stream) {
   knobs_reload();

@@ -165,5 +165,9 @@ inline bool mode_weighted(int mode) { return mode == TM_PVS_WEIGHTED_DCT || mode
 
 // workgroups of 256 for a grid-stride loop over n items: one per 256 items, at most 4096
 inline int gridn(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 16)); }
+// the load and feature kernels' grids: one workgroup per per_block items (what its waves take in one pass of their loop), at most 2048
+inline int grid_for(int64_t work_items, int per_block) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>((work_items + per_block - 1) / per_block, 256 * 8));
+}
 
 }  // namespace tmx

@@ -8,17 +8,26 @@
 
 namespace tmx {
 
-// tm_features.hip
+// tm_load.hip: the load stage (A1-A3)
 int launch_load(const void *frames, int nframes, int img_w, int img_h, int tm_w, int tm_h, void *tiles, void *flags,
                 void *lab_means, hipStream_t stream);
 int launch_rgb_to_lab(const void *rgb, int64_t n, void *out, hipStream_t stream);
 int launch_pearson(const void *lab, int nframes, int per, void *correl, hipStream_t stream);
+
+// tm_features.hip: the int16 features of tiles (A4 + A5)
 int launch_features_rgb(const void *tiles, int64_t n, const void *mirror_flags, int mode, int use_lab, void *out, hipStream_t stream);
 // colmm (optional): [384] ints on the device, mn[192] preset to INT_MAX and mx[192] to INT_MIN: the kernel folds the output columns' ranges in
 int launch_features_rgb_rows(const void *tiles, const void *rows, int64_t n, int mode, int use_lab, void *out, hipStream_t stream, void *colmm = nullptr);
 int launch_features_pal(const void *pal_px, const void *pal_idx, int64_t n, const void *palettes, int pal_size, int mode, void *out,
                         hipStream_t stream);
+// int16 features of the (tile, palette) pairs pairs[i] = tile << 32 | palette (the rows the extended-palette re-rank asks for)
+int launch_features_pairs(const void *pal_px, const void *pairs, int64_t n, const void *palettes, int pal_size, void *out, hipStream_t stream);
+int launch_features_table(const void *pal_px, int64_t ntiles, const void *palettes, int npal, int pal_size, void *out, hipStream_t stream);
+
+// tm_features_cluster.hip: the clustering's int32 features (A6)
 int launch_features_cluster(const void *tiles, int64_t n, int mode, void *out, hipStream_t stream);
+
+// tm_window_dcts.hip: the features of every 8 x 8 window of a frame buffer (motion prediction)
 int launch_window_dcts(const void *fb, int w, int h, void *out, hipStream_t stream, const int *only_if = nullptr);
 // The windows' features straight into the matrix layout of the motion search (tm_motion.hip: what k_mo_pack_win makes of the int16 rows) -- the
 // int16 rows are then never written.  Per block of 32 consecutive window positions of a row: [12 chunks][64 lanes][16 B] digits (low digits of the
@@ -30,9 +39,6 @@ constexpr int MM_BLK_BYTES = MM_QUIRK + 32 * 16;                     // 12928
 constexpr int MM_LIMIT6 = 10922;                                     // |coefficient| bound of blocks 5 and 6 under which a6 - b5 - b6 cannot saturate
 constexpr int MM_LIMIT = 16383;                                      // |coefficient| bound under which no plain difference saturates
 int launch_window_dcts_packed(const void *fb, int w, int h, const void *cur, int ntiles, void *packed, int *flag, hipStream_t stream);
-// int16 features of the (tile, palette) pairs pairs[i] = tile << 32 | palette (the rows the extended-palette re-rank asks for)
-int launch_features_pairs(const void *pal_px, const void *pairs, int64_t n, const void *palettes, int pal_size, void *out, hipStream_t stream);
-int launch_features_table(const void *pal_px, int64_t ntiles, const void *palettes, int npal, int pal_size, void *out, hipStream_t stream);
 
 // tm_epu.hip: FrameTilingExtendedPaletteUsage (tilingencoder.pas:1559-1610)
 int launch_knn_topk(const void *queries, int64_t nq, const void *db, int64_t nt, int k, void *out_idx, void *out_err, hipStream_t stream);

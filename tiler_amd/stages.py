@@ -112,6 +112,21 @@ def features_rgb(tiles, mirror_flags=None, mode=1, use_lab=False):
     return out
 
 
+def features_rgb_rows(tiles, rows, mode=1, use_lab=False, with_colmm=True):
+    """features_rgb of tiles[rows] without the gather (Reconstruct's queries: rows int32 [n], repeats allowed) -> int16 [n][192] and, with_colmm,
+    int32 [2][192]: the minimum and the maximum of every output column, folded in by the kernel (None otherwise)"""
+    assert tiles.is_cuda and tiles.dtype == torch.int32 and tiles.is_contiguous()
+    assert rows.is_cuda and rows.dtype == torch.int32 and rows.is_contiguous()
+    n = rows.shape[0]
+    out = torch.empty((n, 192), dtype=torch.int16, device=tiles.device)
+    colmm = None
+    if with_colmm:  # the kernel's atomics start from the empty range
+        info = torch.iinfo(torch.int32)
+        colmm = torch.tensor([[info.max], [info.min]], dtype=torch.int32, device=tiles.device).repeat(1, 192)
+    check(lib().tm_stage_features_rgb_rows(_p(tiles), _p(rows), n, mode, int(use_lab), _p(out), _p(colmm), _stream()))
+    return out, colmm
+
+
 def features_pal(pal_px, pal_idx, palettes, mode=1):
     """PrepareReconstruct.DoPsyV (tilingencoder.pas:4570-4583) -> int16 [n][192]"""
     n = pal_px.shape[0]
