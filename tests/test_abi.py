@@ -77,3 +77,21 @@ def test_optimize_palettes_host_matches_oracle(built, oracle):
         sweeps = oracle.L.tmo_optimize_palettes(b.ctypes.data_as(ctypes.c_void_p), pc, ps)
         assert np.array_equal(a, b) and sw.value == sweeps
         assert all(sorted(x) == sorted(y) for x, y in zip(a.tolist(), pals.tolist()))  # a permutation of each palette
+
+
+def _settings_round_trip(built, text):
+    """LoadSettings then SaveSettings on text (tm_settings_text_host: no encoder, no device) -> the `Key=Value` pairs written back"""
+    built.tm_settings_text_host.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    built.tm_last_error.restype = ctypes.c_char_p
+    n = ctypes.c_int64()
+    buf = ctypes.create_string_buffer(4096)
+    assert built.tm_settings_text_host(text.encode("latin-1"), buf, 4096, ctypes.byref(n)) == 0, built.tm_last_error()
+    return dict(l.split("=", 1) for l in buf.raw[:n.value].decode("latin-1").split("\r\n") if "=" in l)
+
+
+def test_dithering_mode_setting_loads_clamps_and_is_written_back(built):
+    """DitheringMode through LoadSettings, its setter (0..4, TPsyVisMode) and the settings text, on the host"""
+    assert _settings_round_trip(built, "")["DitheringMode"] == "4"  # the default: pvsWeightedSpeDCT
+    for text, want in (("3", "3"), ("0", "0"), ("1", "1"), ("2", "2"), ("4", "4"), ("5", "4"), ("77", "4"), ("-1", "0"), ("-9", "0")):
+        got = _settings_round_trip(built, "[Dither]\r\nPaletteCount=7\r\nDitheringMode=%s\r\n" % text)
+        assert got["DitheringMode"] == want and got["PaletteCount"] == "7", (text, got)

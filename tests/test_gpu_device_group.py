@@ -94,6 +94,25 @@ def test_group_equals_the_single_encoder(monkeypatch, tmp_path, tmp_path_factory
     enc.close()
 
 
+def test_group_equals_the_single_encoder_at_another_dithering_mode(monkeypatch, tmp_path, tmp_path_factory):
+    """test_group_equals_the_single_encoder with DitheringMode = 3 on three shards, the clustering sharded (every shard makes the clustering
+    features of its own share of the tiles): the setting reaches every shard, and it matters on this clip"""
+    monkeypatch.setenv("TM_PP_SHARDED", "1")
+    kw = dict(MotionPredictRadius=8, FrameTilingExtendedPaletteUsage=True)
+    default, _ = _reference(tmp_path_factory, **kw)
+    want, want_gtm = _reference(tmp_path_factory, DitheringMode=3, **kw)
+    a, b = want["hdr"]["PalIdx_Initial"], default["hdr"]["PalIdx_Initial"]
+    assert a.shape != b.shape or (a != b).any(), "DitheringMode=3 changes no tile's palette here"
+    monkeypatch.chdir(tmp_path)
+    enc = _encoder([0, 0, 0], _clip(), DitheringMode=3, OutputFileName="clip.gtm", **kw)
+    assert enc.DitheringMode == 3
+    enc.Run()
+    _assert_same(_state(enc), want)
+    assert open("clip.gtm", "rb").read() == want_gtm
+    assert enc.CollectiveStats()["bytes"] > 0
+    enc.close()
+
+
 def test_group_from_host_clips_and_prefetch(tmp_path_factory):
     """the host-clip Load (every shard loads the whole clip) and a second clip queued by PrefetchFramesHost"""
     a, b = _clip(), _clip(seed=7)

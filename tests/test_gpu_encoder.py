@@ -502,6 +502,11 @@ def _sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, pp_s
               GlobalTilingTileCount=tile_count, **(extra or {}))  # extra: further settings, the same for the single run and every rank
     ref = _run_encoder(frames, **kw)
     want = (np.stack([ref.TileMap(f) for f in range(12)]), ref.Tiles())
+    if "DitheringMode" in kw:  # the setting must matter on this clip: a single run at the default mode clusters the tiles otherwise
+        base = _run_encoder(frames, **dict(kw, DitheringMode=4))
+        a, b = want[1][0]["PalIdx_Initial"], base.Tiles()[0]["PalIdx_Initial"]
+        base.close()
+        assert a.shape != b.shape or (a != b).any(), "DitheringMode=%d changes no tile's palette here" % kw["DitheringMode"]
     if palettize_tiles is not None:  # the tiles the single run's PreparePalettes clustered
         assert ref.KmeansIters()["tile_points"] == palettize_tiles
     ref.close()
@@ -552,11 +557,14 @@ def test_sharded_ranks_merge_to_the_single_run(monkeypatch, radius, epu, world, 
 
 
 @pytest.mark.parametrize("world,pp_sharded,extra", [(2, True, dict(PaletteSize=5, DitheringUseThomasKnoll=False, DitheringYliluoma2MixedColors=3)),
-                                                      (3, False, dict(PaletteSize=64))], ids=["2-yliluoma-5", "3-size-64"])
+                                                      (3, False, dict(PaletteSize=64)), (2, True, dict(DitheringMode=1)), (3, False, dict(DitheringMode=0))],
+                         ids=["2-yliluoma-5", "3-size-64", "2-dithering-mode-1", "3-dithering-mode-0"])
 def test_sharded_ranks_merge_to_the_single_run_off_the_defaults(monkeypatch, world, pp_sharded, extra):
     """the same with motion prediction (radius 8) and the extended palette usage at a PaletteSize other than 16: five colours dithered by
     the Yliluoma planner over two ranks, 64 colours over three -- the sharded quantisation, the merge of the ranks' Dither shares and the
-    re-rank's palette tables all take their width from the setting"""
+    re-rank's palette tables all take their width from the setting.  And at a DitheringMode other than 4: with the clustering sharded every
+    rank makes the clustering features of its own share of the tiles, otherwise every rank makes all of them, under the mode of the
+    settings either way (the helper first asserts that the mode changes the single run's clustering of this clip)"""
     _sharded_ranks_merge_to_the_single_run(monkeypatch, 8, True, world, pp_sharded, extra=extra)
 
 

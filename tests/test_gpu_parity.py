@@ -3,6 +3,8 @@ Bit-exact everywhere (integer/byte/index outputs, and floats because the build o
 import numpy as np
 import pytest
 
+from tests.tile_kinds import tile_kinds as _tile_kinds
+
 torch = pytest.importorskip("torch")
 
 pytestmark = pytest.mark.gpu
@@ -113,20 +115,6 @@ def test_features_first_look_agrees_with_reference_order(mode, use_lab, monkeypa
         cplain = stages.features_cluster(t, mode)
         monkeypatch.delenv("TM_FEATURES_PLAIN", raising=False)
         assert torch.equal(cfast, cplain)
-
-
-def _tile_kinds(n, seed):
-    """noise, flat, two-colour, grey ramps, near-black and plain noise again: the kinds test_features_first_look_agrees_with_reference_order builds"""
-    rng = np.random.default_rng(seed)
-    t = rng.integers(0, 1 << 24, size=(n, 64), dtype=np.uint32)
-    k = n // 6
-    t[k:2 * k] = t[k:2 * k, :1]
-    two = rng.integers(0, 1 << 24, size=(k, 2), dtype=np.uint32)
-    t[2 * k:3 * k] = np.take_along_axis(two, rng.integers(0, 2, size=(k, 64)), axis=1)
-    v = np.clip((np.arange(64) % 8)[None, :] * rng.integers(0, 32, size=(k, 1)) + rng.integers(0, 32, size=(k, 1)), 0, 255).astype(np.uint32)
-    t[3 * k:4 * k] = v | (v << 8) | (v << 16)
-    t[4 * k:5 * k] &= 0x070707
-    return t, rng.integers(0, 4, size=n).astype(np.uint8)
 
 
 def test_features_default_path_against_the_oracle_at_scale(oracle):

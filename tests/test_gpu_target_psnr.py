@@ -134,6 +134,35 @@ def test_gtm_settings_carry_the_flag(oracle, tmp_path):
     assert "GlobalTilingUseTargetPSNR=1" in lines and "GlobalTilingTargetPSNR=36.5" in lines
 
 
+def test_gtm_settings_carry_the_dithering_mode(oracle, tmp_path):
+    """a stream saved with DitheringMode = 1 says so in its settings text, and LoadSettings of that text brings the 1 back.  ReloadGTM
+    itself leaves the setting alone, as the reference does: LoadStream seeks past the settings record (tilingencoder.pas:5057-5060)
+    and takes only what the stream's commands carry -- the palettes' size and count."""
+    from tests import gtm_reader
+    from tiler_amd.encoder import TilingEncoder
+    frames = _frames()
+    nf, h, w = frames.shape
+    path = str(tmp_path / "dm.gtm")
+    enc = run_encoder(frames, PaletteCount=2, ShotTransMinSecondsPerKF=0.1, MotionPredictRadius=0, FrameTilingExtendedPaletteUsage=False,
+                      DitheringMode=1, OutputFileName=path)
+    enc.close()
+    _, pl = gtm_reader.play(oracle, open(path, "rb").read())
+    assert "DitheringMode=1" in pl.settings.split("\r\n")
+    ini = tmp_path / "dm.ini"
+    ini.write_bytes(pl.settings.encode("latin-1"))
+    enc = TilingEncoder()
+    enc.LoadDefaultSettings()
+    assert enc.DitheringMode == 4
+    enc.LoadSettings(ini)
+    assert enc.DitheringMode == 1 and enc.PaletteCount == 2
+    enc.LoadDefaultSettings()
+    enc.DitheringMode = 3
+    enc.SetVideo(w, h, 24.0, nf)
+    enc.ReloadGTM(path)
+    assert enc.PaletteCount == 2 and enc.DitheringMode == 3
+    enc.close()
+
+
 def test_target_psnr_at_full_size(oracle):
     """the 720p x 300 clip at radius 32 with a target above the one the default budget lands on: more global tiles than the
     budget (320 705) has ever carried through PreparePalettes, Dither, Reconstruct and Reindex"""
