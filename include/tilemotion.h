@@ -390,6 +390,58 @@ TM_API int tm_render_frames_yuv_scaled(tm_encoder *, int first_frame, int frame_
  * sums: no frame is materialised.  Any pointer may be NULL.  Errors as tm_render_frames (both renders are needed). */
 TM_API int tm_get_frame_quality(tm_encoder *, int first_frame, int frame_count, uint64_t *sse /* [count][3] */, double *psnr /* [count] */,
                                 double *ssim_y /* [count] */, double *clip_psnr, double *clip_ssim_y);
+/* ---- Render's other views (Render :3455-3736 with its switches; tm_render_view.hip) ---------------------------------
+ * tm_render_frames draws with the constructor's switches.  A tm_render_view names the others: the page, and FRenderPredicted,
+ * FRenderMirrored, FRenderOutputDithered, FRenderUseGamma, FRenderPaletteIndex and RenderGammaValue.  Pixels are 0x00RRGGBB, background
+ * is 0 (the GUI's hatched brush, its motion-vector lines and its texts are not drawn).  THE RULE:
+ *   DrawTile (:3457-3506).  The colour starts as magenta, 0x00FF00FF.  With a palette and the tile's HasPalPixels flag it is
+ * palette[pal_px[mirrored (ty, tx)]] with R and B swapped -- 0 for a colour index at or beyond the palette size; without a palette and with
+ * the tile's HasRGBPixels flag it is the tile's RGB pixel with R and B swapped.  Then, with use_gamma, every channel c becomes lut[c]
+ * (tm_render_gamma_lut_host; also the magenta and the 0 of a colour index out of range: they are DrawTile's).  Background and aqua are not
+ * DrawTile's and stay as they are.  The Output page ignores the tile's Active flag, as tm_render_frames does; the Tiles page honours it
+ * (an inactive tile is magenta).
+ *   Output page (:3574-3634), per item.  Predicted and view.predicted: the previous frame's picture under the same view at the offset,
+ * clamped per pixel (before frame 0: background).  Otherwise -- predicted items too when view.predicted is 0 -- the item is drawn as its
+ * stored TileIdx / PalIdx say: a TileIdx out of range is background; dithered and palette_index < 0: the item's own palette, a PalIdx out
+ * of range is background; dithered and palette_index >= 0: drawn where PalIdx == palette_index, background elsewhere; dithered 0: no
+ * palette and no filter, the tile's RGB pixels.  mirrored 0 drops the item's two mirror flags.  A predicted pixel follows its chain to
+ * the first drawn item and takes that item's colour under the view (background where the filter skips it), so gamma is applied once.
+ *   Input page (:3538-3570).  The frame tiles, un-mirrored by their initial flags (mirrored) or in their stored orientation (mirrored 0);
+ * gamma applies; every other switch is ignored.
+ *   Tiles page (:3678-3707).  Page p is a picture of the frame's size whose cell (sy, sx) shows tile tm_w*sy + sx + tm_w*tm_h*p, aqua
+ * (0x0000FFFF) beyond the last tile; ceil(tiles / (tm_w*tm_h)) pages.  With dithered and at least one palette the palette is
+ * palette_index if >= 0, else max(0, PalIdx_Initial) -- background where that is beyond the palettes (the reference would index past
+ * FPalettes); otherwise the RGB pixels.  Mirrors are the tile's HMirror_Initial / VMirror_Initial when mirrored is set.
+ * With tm_render_view_default the Output page is tm_render_frames(input = 0) bit for bit and the Input page is input = 1. */
+enum { TM_RENDER_PAGE_INPUT = 0, TM_RENDER_PAGE_OUTPUT = 1, TM_RENDER_PAGE_TILES = 2 };   /* TRenderPage: rpInput, rpOutput, rpTilesPalette */
+typedef struct {
+  int32_t page;           /* TM_RENDER_PAGE_* */
+  int32_t predicted;      /* FRenderPredicted */
+  int32_t mirrored;       /* FRenderMirrored */
+  int32_t dithered;       /* FRenderOutputDithered */
+  int32_t use_gamma;      /* FRenderUseGamma */
+  int32_t palette_index;  /* FRenderPaletteIndex; < 0: every palette */
+  double  gamma;          /* RenderGammaValue = FGamma[1]; the constructor's 0.6 */
+} tm_render_view;         /* 32 bytes; offsets 0, 4, 8, 12, 16, 20, 24 */
+/* Host only, no device.  tm_render_view_default: the constructor's values (:5495-5509) -- page OUTPUT, predicted, mirrored and dithered 1,
+ * gamma off at 0.6, palette_index -1.  tm_probe_render_view_host: TM_E_INVAL for a null struct, an unknown page, a NaN gamma, or
+ * palette_index >= pal_count (the reference would index past FPalettes there); a negative gamma is not refused, it counts as 0
+ * (SetRenderGammaValue, :3024-3027).  tm_render_gamma_lut_host: the table DrawTile applies (:3490-3495 with InitLuts :1689-1694),
+ * lut[i] = RoundHalfEven(pow(i / 255.0, max(0, gamma)) * 255.0) in double; gamma 1 is the identity, gamma 0 is 255 everywhere
+ * (pow(0, 0) = 1).  The device only looks the table up. */
+TM_API int tm_render_view_default(tm_render_view *view);
+TM_API int tm_probe_render_view_host(const tm_render_view *view, int pal_count);
+TM_API int tm_render_gamma_lut_host(double gamma, uint8_t lut[256]);
+/* Pages INPUT and OUTPUT of frames [first_frame, first_frame+frame_count): out, out_on_device and the refusals as tm_render_frames, plus
+ * the probe's (pal_count = the encoder's palettes); page TILES here is TM_E_INVAL.  tm_render_tile_pages: pages [first_page,
+ * first_page+page_count) of the Tiles page, [page_count][tm_h*8][tm_w*8]; the tiles must exist (after Reduce or ReloadGTM), a page range
+ * outside tm_get_tile_page_count's is TM_E_INVAL; view->page is not looked at.  All refusals come before any device call and write
+ * nothing.  In a device group the calls read shard 0, like the exports and tm_render_frames_yuv (page INPUT: a range shard 0 did not load
+ * is TM_E_INVAL).  After tm_reload_gtm the tiles carry no RGB pixels (HasRGBPixels false): an undithered view is magenta where an item
+ * is drawn, as in the reference.  Blocking. */
+TM_API int tm_render_view_frames(tm_encoder *, const tm_render_view *view, int first_frame, int frame_count, void *out, int out_on_device);
+TM_API int tm_render_tile_pages(tm_encoder *, const tm_render_view *view, int first_page, int page_count, void *out, int out_on_device);
+TM_API int tm_get_tile_page_count(tm_encoder *, int *pages);
 /* ReloadGTM, :2059 -> LoadStream, :4880-5175: replaces the encoder's tiles (palette indices only), palettes, tile maps and key
  * frames with the file's; the video set with tm_set_video must match the file's header (:5021-5032) or TM_E_INVAL comes back.
  * Afterwards the read-back views and tm_save_gtm work on the loaded state. */
@@ -648,6 +700,13 @@ TM_API int tm_knn_last_plan(int *ht, int *hq, int *topk, int64_t *arena_retries)
  * palettes i32 [npal][pal_size] 0x00BBGGRR -> out u32 [nframes][tm_h*8][tm_w*8] 0x00RRGGBB, as tm_render_frames draws them. */
 TM_API int tm_stage_render(const void *tile_idx, const void *pal_idx, const void *item_flags, const void *px, const void *py, int tm_w, int tm_h,
                            int nframes, const void *pal_px, int64_t ntiles, const void *palettes, int npal, int pal_size, void *out, void *stream);
+/* Render's other views (tm_render_view above) from caller-held tables: the pointers of tm_stage_render, plus rgb_px u32 [ntiles][64]
+ * 0x00BBGGRR (16-byte aligned; pal_px 4-byte aligned), tile_flags u32 [ntiles] (the tm_tile_hdr.Flags bits) and pal_idx_initial i32 [ntiles].
+ * Pages OUTPUT (nframes frames) and TILES (nframes pages from page 0, at most the tiles' page count; the tile-map pointers may be null) ->
+ * out u32 [nframes][tm_h*8][tm_w*8]; page INPUT and what tm_probe_render_view_host(view, npal) refuses are TM_E_INVAL.  Queued on `stream`. */
+TM_API int tm_stage_render_view(const tm_render_view *view, const void *tile_idx, const void *pal_idx, const void *item_flags, const void *px,
+                                const void *py, int tm_w, int tm_h, int nframes, const void *pal_px, const void *rgb_px, const void *tile_flags,
+                                const void *pal_idx_initial, int64_t ntiles, const void *palettes, int npal, int pal_size, void *out, void *stream);
 /* The sums behind tm_get_frame_quality for two stacks of frames a (source) and b (decoded), u32 0x00RRGGBB [nframes][h][stride_px]
  * (w, h multiples of 4, at least 8): sse_u64 [nframes][3] (R, G, B), ssim_f64 [nframes], both device pointers. */
 TM_API int tm_stage_frame_quality(const void *a, const void *b, int nframes, int w, int h, int64_t stride_px, void *sse_u64, void *ssim_f64,

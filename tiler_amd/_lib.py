@@ -30,6 +30,24 @@ class YuvClip(ctypes.Structure):  # tm_yuv_clip: a YUV clip lent in memory (tm_s
                 ("chroma", c_int), ("samples", c_int), ("depth", c_int), ("full_range", c_int), ("memory", c_int)]
 
 
+class RenderViewDesc(ctypes.Structure):  # tm_render_view: Render's switches (32 bytes)
+    _fields_ = [("page", ctypes.c_int32), ("predicted", ctypes.c_int32), ("mirrored", ctypes.c_int32), ("dithered", ctypes.c_int32),
+                ("use_gamma", ctypes.c_int32), ("palette_index", ctypes.c_int32), ("gamma", c_double)]
+
+
+RENDER_PAGES = {"input": 0, "output": 1, "tiles": 2}  # TM_RENDER_PAGE_*
+
+
+def render_view_desc(page="output", predicted=True, mirrored=True, dithered=True, gamma=None, palette=-1):
+    """tm_render_view from the keywords RenderView / stages.render_view take; gamma=None: off (the value stays the constructor's 0.6)"""
+    if isinstance(page, str):
+        if page not in RENDER_PAGES:
+            raise ValueError("unknown render page %r (one of %s)" % (page, " ".join(RENDER_PAGES)))
+        page = RENDER_PAGES[page]
+    return RenderViewDesc(int(page), int(bool(predicted)), int(bool(mirrored)), int(bool(dithered)), int(gamma is not None), int(palette),
+                          0.6 if gamma is None else float(gamma))
+
+
 # name -> (restype, argtypes); mirrors include/tilemotion.h one to one
 SIGNATURES = {
     "tm_last_error": (c_char_p, []),
@@ -72,6 +90,11 @@ SIGNATURES = {
     "tm_stage_render": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_int,
                                 c_void_p, c_void_p]),
     "tm_stage_frame_quality": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "tm_render_view_default": (c_int, [ctypes.POINTER(RenderViewDesc)]),
+    "tm_probe_render_view_host": (c_int, [ctypes.POINTER(RenderViewDesc), c_int]),
+    "tm_render_gamma_lut_host": (c_int, [c_double, c_void_p]),
+    "tm_stage_render_view": (c_int, [ctypes.POINTER(RenderViewDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "tm_stage_yuv_to_rgb32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "tm_stage_yuv_to_rgb32_fmt": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                           c_void_p]),

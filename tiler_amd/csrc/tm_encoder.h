@@ -195,3 +195,7 @@ std::vector<Piece> group_pieces(tm_encoder *e, int first, int count);
 
 // tm_export.hip
 int save_to(tm_encoder *e, const char *path);
+// what the device renders check and read (tm_render_frames and its kin there, the views of tm_render_view.hip); no device call
+int render_range_ok(tm_encoder *e, int first, int count);
+int render_output_map(tm_encoder *e, RenderMap *m);
+int render_input_src(tm_encoder *e, int first, int count, RenderInput *in);

@@ -30,12 +30,12 @@ int save_to(tm_encoder *e, const char *path) {  // Save, tilingencoder.pas:2040-
 }
 
 // ---- the decoded frames on the device (tm_render.hip): what tm_render_frames, tm_get_frame_quality and the exports draw
-static int render_range_ok(tm_encoder *e, int first, int count) {
+int render_range_ok(tm_encoder *e, int first, int count) {
   TM_CHECK(e->nframes > 0 && first >= 0 && count >= 0 && (int64_t)first + count <= e->nframes, TM_E_INVAL, "frame range [%d,+%d) outside 0..%d",
            first, count, e->nframes);
   return TM_OK;
 }
-static int render_output_map(tm_encoder *e, RenderMap *m) {
+int render_output_map(tm_encoder *e, RenderMap *m) {
   TM_CHECK(e->has_pal_px && (e->steps_done & (1 << TM_STEP_RECONSTRUCT)) && e->tm_tile.p && e->tm_pal.p && e->fflags.p && e->palettes_dev.p, TM_E_INVAL,
            "output frames: Reconstruct (or ReloadGTM) has not been run");
   const bool pm = e->has_pm && e->tm_pred.p && e->tm_px.p && e->tm_py.p;
@@ -46,7 +46,7 @@ static int render_output_map(tm_encoder *e, RenderMap *m) {
                  e->palettes_dev.as<int32_t>(), npal, e->s.PaletteSize, e->tm_w, e->tm_h};
   return TM_OK;
 }
-static int render_input_src(tm_encoder *e, int first, int count, RenderInput *in) {
+int render_input_src(tm_encoder *e, int first, int count, RenderInput *in) {
   TM_CHECK(e->src_tiles && (e->steps_done & (1 << TM_STEP_LOAD)) && e->ftiles.p && e->fflags.p, TM_E_INVAL,
            "source frames: the frame tiles are not in memory (run Load; ReloadGTM does not bring them)");
   TM_CHECK(!e->load_sharded || (first >= e->load_first && first + count <= e->load_first + e->load_count), TM_E_INVAL,

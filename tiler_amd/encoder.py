@@ -10,7 +10,7 @@ import enum
 
 import numpy as np
 
-from ._lib import lib, check, TileMotionError, YuvClip, c_void_p, c_int, c_int64, c_double, c_char_p
+from ._lib import lib, check, TileMotionError, YuvClip, RenderViewDesc, c_void_p, c_int, c_int64, c_double, c_char_p
 
 
 class TEncoderStep(enum.IntEnum):  # tilingencoder.pas:18
@@ -105,6 +105,9 @@ _ENC_SIGS = {
     "tm_render_frames_scaled": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int]),
     "tm_render_frames_yuv_scaled": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(YuvClip), c_int, c_int]),
     "tm_get_frame_quality": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
+    "tm_render_view_frames": (c_int, [c_void_p, ctypes.POINTER(RenderViewDesc), c_int, c_int, c_void_p, c_int]),
+    "tm_render_tile_pages": (c_int, [c_void_p, ctypes.POINTER(RenderViewDesc), c_int, c_int, c_void_p, c_int]),
+    "tm_get_tile_page_count": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "tm_set_query_shard": (c_int, [c_void_p, c_int, c_int]),
     "tm_set_dither_shard": (c_int, [c_void_p, c_int, c_int]),
     "tm_set_collective": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -473,6 +476,44 @@ class TilingEncoder:
         out = np.empty(shape, np.uint32)
         check(self._L.tm_render_frames(c_void_p(self._h), first, count, int(bool(input)), out.ctypes.data_as(c_void_p), 0))
         return out
+
+    def _view_pictures(self, fn, view, first, count, device):
+        c = self.counts()
+        shape = (max(count, 0), c["tm_h"] * 8, c["tm_w"] * 8)
+        if device:
+            import torch
+            out = torch.empty(shape, dtype=torch.int32, device="cuda")
+            check(fn(c_void_p(self._h), ctypes.byref(view), first, count, c_void_p(out.data_ptr()), 1))
+            return out
+        out = np.empty(shape, np.uint32)
+        check(fn(c_void_p(self._h), ctypes.byref(view), first, count, out.ctypes.data_as(c_void_p), 0))
+        return out
+
+    def RenderView(self, first=0, count=None, page="output", predicted=True, mirrored=True, dithered=True, gamma=None, palette=-1, device=False):
+        """Frames [first, first+count) as Render (tilingencoder.pas:3455-3736) draws its Output or Input page (page="output" / "input") under
+        its switches (tm_render_view_frames; the rule: include/tilemotion.h): predicted = FRenderPredicted, mirrored = FRenderMirrored,
+        dithered = FRenderOutputDithered, gamma = RenderGammaValue with FRenderUseGamma on (None: off), palette = FRenderPaletteIndex
+        (-1: every palette).  [count][tm_h*8][tm_w*8] 0x00RRGGBB, a numpy uint32 array or (device=True) a torch int32 CUDA tensor; the
+        defaults give RenderFrames' pictures"""
+        from ._lib import render_view_desc
+        count = self.counts()["frames"] - first if count is None else count
+        view = render_view_desc(page, predicted, mirrored, dithered, gamma, palette)
+        return self._view_pictures(self._L.tm_render_view_frames, view, first, count, device)
+
+    def TilePageCount(self):
+        """pages of the Tiles page: ceil(tiles / (tm_w * tm_h)); the tiles must exist (after Reduce or ReloadGTM)"""
+        n = c_int()
+        check(self._L.tm_get_tile_page_count(c_void_p(self._h), ctypes.byref(n)))
+        return n.value
+
+    def RenderTilePages(self, first=0, count=None, mirrored=True, dithered=True, gamma=None, palette=-1, device=False):
+        """Pages [first, first+count) of Render's Tiles page (tm_render_tile_pages): cell (sy, sx) of page p shows tile
+        tm_w*sy + sx + tm_w*tm_h*p through palette `palette`, or its own first palette (-1), or as RGB pixels (dithered=False); aqua
+        beyond the last tile.  Shapes and switches as RenderView"""
+        from ._lib import render_view_desc
+        count = self.TilePageCount() - first if count is None else count
+        view = render_view_desc("tiles", True, mirrored, dithered, gamma, palette)
+        return self._view_pictures(self._L.tm_render_tile_pages, view, first, count, device)
 
     def RenderFramesYUV(self, first=0, count=None, input=False, layout="nv12", yuv="auto", device=True, out=None, full_range=False, size=None,
                         filter="lanczos"):

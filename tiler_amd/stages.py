@@ -385,6 +385,35 @@ def render(tile_idx, pal_idx, item_flags, px, py, tm_w, tm_h, pal_px, palettes):
     return out
 
 
+def render_view(tile_idx, pal_idx, item_flags, px, py, tm_w, tm_h, pal_px, rgb_px, tile_flags, pal_idx_initial, palettes, page="output", predicted=True,
+                mirrored=True, dithered=True, gamma=None, palette=-1, pages=None):
+    """Render's Output or Tiles page under its switches (tm_stage_render_view; the rule: include/tilemotion.h) from caller-held tables: those of
+    render(), plus rgb_px int32 [T][64] 0x00BBGGRR, tile_flags int32 [T] (the tm_tile_hdr Flags bits: 0 Active, 1 HasRGBPixels, 2 HasPalPixels,
+    3 / 4 H / VMirror_Initial) and pal_idx_initial int32 [T].  page="output": the F frames of the tile maps; page="tiles": `pages` pages from page 0
+    (default: all, ceil(T / (tm_w*tm_h)); the tile-map tensors may be None).  Switches as TilingEncoder.RenderView -> int32 [F][tm_h*8][tm_w*8]"""
+    from ._lib import render_view_desc
+    per = tm_w * tm_h
+    for t, dt in ((pal_px, torch.uint8), (rgb_px, torch.int32), (tile_flags, torch.int32), (pal_idx_initial, torch.int32), (palettes, torch.int32)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous()
+    ntiles = tile_flags.numel()
+    assert pal_px.numel() == ntiles * 64 and rgb_px.numel() == ntiles * 64 and pal_idx_initial.numel() == ntiles
+    view = render_view_desc(page, predicted, mirrored, dithered, gamma, palette)
+    if view.page == 2:
+        nf = -(-ntiles // per) if pages is None else int(pages)
+        maps = [None] * 5
+    else:
+        maps = [tile_idx, pal_idx, item_flags, px, py]
+        for t, dt in zip(maps, (torch.int32, torch.int32, torch.uint8, torch.int8, torch.int8)):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous()
+        n = tile_idx.numel()
+        assert n % per == 0 and all(t.numel() == n for t in maps)
+        nf = n // per
+    out = torch.empty((nf, tm_h * 8, tm_w * 8), dtype=torch.int32, device=pal_px.device)
+    check(lib().tm_stage_render_view(view, *[None if t is None else _p(t) for t in maps], tm_w, tm_h, nf, _p(pal_px), _p(rgb_px), _p(tile_flags),
+                                     _p(pal_idx_initial), ntiles, _p(palettes), palettes.shape[0], palettes.shape[1], _p(out), _stream()))
+    return out
+
+
 def _mean_in_order(v):
     acc = 0.0
     for x in v.tolist():  # frame order, as tm_get_frame_quality sums
