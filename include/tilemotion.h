@@ -694,6 +694,11 @@ TM_API int tm_knn_index_last_chunk_counts(tm_knn_index *, int64_t *looked, int64
  * side, 0..6 each, and whether it was the k-nearest collection: together they name the instantiation of the scan's kernels that ran -- and
  * how often a scan of this process has been repeated with a larger tile-list arena (TM_KNN_ARENA_ENTRIES sets the first size) */
 TM_API int tm_knn_last_plan(int *ht, int *hq, int *topk, int64_t *arena_retries);
+/* diagnostics for the tests: the database's row order as the scan of a searched index sees it (host memory, uint32 [nt]: tile t holds rows
+ * out[32 t .. 32 t + 31]: the rows the curve sort put there, in ascending index) */
+TM_API int tm_knn_index_row_order(tm_knn_index *, void *out_rows_u32, void *stream);
+/* ... and the step that orders them, on its own: every run of 32 entries of perm (device memory, uint32 [n]) into ascending order, in place */
+TM_API int tm_stage_knn_tile_order(void *perm_u32, int64_t n, void *stream);
 
 /* Render (:3455-3640) of nframes frames from their tile maps, on device pointers: tile_idx / pal_idx i32 [nframes][tm_h*tm_w],
  * item_flags u8 (bit 0 H mirror, bit 1 V mirror, bit 2 predicted), px / py int8 (PredictedX / PredictedY), pal_px u8 [ntiles][64],

@@ -15,7 +15,7 @@ int tm_device_count(void) {
 }
 
 // the trailing token names the build of the KNN scan kernel: PMC passes under profiles/ are keyed by it (bench.py reads `traffic` from them)
-const char *tm_version(void) { return "tilemotion-mi355x 0.3 (gfx950) knn-scan3-r08"; }
+const char *tm_version(void) { return "tilemotion-mi355x 0.3 (gfx950) knn-scan3-r11"; }
 
 int tm_stage_load(const void *frames, int nframes, int img_w, int img_h, int tm_w, int tm_h, void *tiles, void *flags,
                   void *lab_means, void *stream) {
@@ -123,6 +123,17 @@ int tm_knn_index_last_chunk_counts(tm_knn_index *ix, int64_t *looked, int64_t *s
   TM_CHECK(ix != nullptr, TM_E_INVAL, "null index");
   knn_index_chunk_counts(reinterpret_cast<tm_knn_index_impl *>(ix), looked, stopped);
   return TM_OK;
+}
+
+int tm_knn_index_row_order(tm_knn_index *ix, void *out_rows_u32, void *stream) {
+  TM_CHECK(ix != nullptr && out_rows_u32 != nullptr, TM_E_INVAL, "null index or output");
+  return knn_index_row_order(reinterpret_cast<tm_knn_index_impl *>(ix), out_rows_u32, (hipStream_t)stream);
+}
+
+int tm_stage_knn_tile_order(void *perm_u32, int64_t n, void *stream) {
+  TM_TRY(require_device());
+  TM_CHECK(perm_u32 != nullptr && n >= 0, TM_E_INVAL, "knn tile order: null rows or a negative count");
+  return launch_tile_order((uint32_t *)perm_u32, n, (hipStream_t)stream);
 }
 
 int tm_knn_last_plan(int *ht, int *hq, int *topk, int64_t *arena_retries) {

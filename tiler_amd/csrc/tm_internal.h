@@ -57,6 +57,11 @@ void knn_index_stats(tm_knn_index_impl *ix, double *ms, int *kbytes, int64_t *pa
 void knn_index_list_counts(tm_knn_index_impl *ix, int64_t *listed, int64_t *popped);
 void knn_index_chunk_counts(tm_knn_index_impl *ix, int64_t *looked, int64_t *stopped);
 void knn_last_plan(int *ht, int *hq, int *topk, long long *arena_retries);
+// diagnostics for the tests: the database's row order as the scan sees it (host, [nt]: tile t holds rows out[32 t ..]), of an index that has searched
+int knn_index_row_order(tm_knn_index_impl *ix, void *out_rows, hipStream_t stream);
+// tm_knn_prepare.hip: every run of 32 entries of perm (device, [n]) into ascending order, in place (what a built index does to its curve order;
+// pack: the database's pack, whose tiles' last 128 bytes take the ordered indices)
+int launch_tile_order(uint32_t *perm, int64_t n, hipStream_t stream, uint8_t *pack = nullptr, int tile_bytes = 0);
 // the last search's three kernels on their own: ms of seeds / lists / consume; pairs evaluated by seeds / consume, matrix instructions the consume kernel issued
 void knn_index_kernel_split(tm_knn_index_impl *ix, double ms[3], int64_t pairs[3]);
 // grp_off / grp_members (optional): the index was built over DISTINCT rows; results are expanded to the original rows (member lists

@@ -25,13 +25,13 @@ struct KnnPlan {
 };
 inline int knn_kbytes(const KnnPlan &p) { return 192 + 32 * (p.ht + p.hq + std::min(p.ht, p.hq)); }  // K of the distance GEMM
 
-// a packed tile of 32 rows: the operand chunks, 32 row terms (norms), the box (database side), 32 row terms over the first chunk's columns
-__host__ __device__ constexpr int knn_tile_bytes(int hch, int with_box) { return (6 + hch) * 1024 + 128 + (with_box ? 64 : 0) + 128; }
+// a packed tile of 32 rows: the operand chunks, 32 row terms (norms), the box (database side), 32 row terms over the first chunk's columns,
+// the rows' 32 original indices (database side)
+__host__ __device__ constexpr int knn_tile_bytes(int hch, int with_box) { return (6 + hch) * 1024 + 128 + (with_box ? 64 : 0) + 128 + (with_box ? 128 : 0); }
 static_assert(knn_tile_bytes(5, 1) == k3_t_bytes(11) && knn_tile_bytes(4, 0) == k3_q_bytes(10), "the scan kernels' view of the packs");
 
 // what the last nearest-neighbour search's counters said (K3Counters, read once per attempt)
 struct KnnCounts {
-  unsigned long long ties = 0;                                   // queries handed to k_knn_ties
   unsigned long long blocks = 0, tiles = 0, pairs = 0;           // the consume kernel's
   unsigned long long seed_blocks = 0, seed_tiles = 0, seed_pairs = 0;  // the seed kernel's, summed over its stripes
   unsigned long long listed = 0, popped = 0, cursor = 0;         // list entries written / taken off / asked of the arena
@@ -51,17 +51,16 @@ struct tm_knn_index_impl {
   DevBuf qperm, qkey, skey, skey2, sidx, sort_tmp;  // queries sorted along the curve
   DevBuf rrange, tradial, qradial;                  // radial coordinate of the rows (curve key) and its range
   CurveSpec curve;
-  DevBuf tie_list, counters;                        // counters: one K3Counters (tm_knn3_kernel.h)
+  DevBuf counters;                                  // one K3Counters (tm_knn3_kernel.h)
   DevBuf tccol, qccol;                              // the rows' three curve columns (k_row_radial -> k_curve_keys)
   DevBuf qmeta;                                     // per query sub-tile: box, home tile, high-chunk mask
-  // third scan shape: what the seed kernel leaves for the other two (bests, tie values, bounds) and the groups' tile lists
-  DevBuf gbest, gtie, gsmax, segs, nsegs, arena_tile, arena_lb;
+  // third scan shape: what the seed kernel leaves for the other two (bests, bounds) and the groups' tile lists
+  DevBuf gbest, gsmax, segs, nsegs, arena_tile, arena_lb;
   DevBuf thmask;                                    // per database tile: which of its high-digit chunks are not all zero
   uint64_t arena_cap = 0, arena_want = 0;           // list entries the arena holds / the largest cursor a search has reported
   hipEvent_t ev_seed = nullptr, ev_lists = nullptr;
   double last_seed_ms = 0, last_lists_ms = 0, last_consume_ms = 0;
   int64_t last_blocks = 0, last_loads = 0, last_listed = 0, last_popped = 0;
-  int64_t last_ties = 0;
   double last_ms = 0;
   int last_kbytes = 0;
   int64_t last_pairs = 0, last_seed_pairs = 0, last_mfma = 0;

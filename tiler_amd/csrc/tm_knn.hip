@@ -13,10 +13,10 @@
 //   = three int32 MFMA accumulators fed by v_mfma_i32_32x32x32_i8, K = 192 + 32 (HT + HQ + min(HT,HQ)) <= 768 bytes.
 //   The query digits are stored NEGATED, so one lane computes, with nq2 = 2 * (|q-c|^2 >> 1),
 //      d'' = |t-c|^2 + 2 * (acc2<<16 + acc1<<8 + acc0) + nq2  ==  SSD - (|q-c|^2 & 1)   (exact mod 2^32, SSD < 2^31)
-//   with three v_lshl_add_u32 + one add per element, and keeps a running (min d'', first tile) per lane.  Database rows ride
-//   the MFMA A operand (accumulator rows), queries the B operand (accumulator columns = lanes), so the argmin of a
-//   query never leaves its lane until the final 2-lane merge.  A second tiny kernel rescans the winning 32-row
-//   tile with the plain int16 SSD to produce (index, error) under the lowest-index rule.
+//   with three v_lshl_add_u32 + one add per element, and keeps a running (min d'', lowest original index) per query.  Database
+//   rows ride the MFMA A operand (accumulator rows), queries the B operand (accumulator columns = lanes), so the argmin of a
+//   query never leaves its lane until the 64-bit atomic minimum where the half-waves, the waves and the seeds meet.  A second
+//   tiny kernel puts (index, error) back in the caller's order.
 //
 // Files: tm_knn_plan.hip (column ranges, digit plan), tm_knn_prepare.hip (curve order, packs, boxes), this file (the index, the scan's
 // host side, the nearest-neighbour search), tm_knn_topk.hip (the k nearest rows); tm_knn.h is what the four share.
@@ -28,116 +28,16 @@
 namespace tmx {
 
 // ---------------------------------------------------------------------------------------------------------------
-// Rescan the winning 32-row tile of each query with the plain SSD (CompareEuclideanDCTPtr, utils.pas:541-557) and
-// apply the lowest-ORIGINAL-index rule inside it.  One wave per (sorted) query, lanes 0..31 = rows of the tile.
-// Queries whose minimum was reached by a second tile (tie flag) are queued for k_knn_ties.
-__device__ __forceinline__ uint32_t ssd_rows(const int16_t *__restrict__ a, const int16_t *__restrict__ b) {
-  const v4i *qp = reinterpret_cast<const v4i *>(a);
-  const v4i *tp = reinterpret_cast<const v4i *>(b);
-  uint32_t ssd = 0;
-#pragma unroll 4
-  for (int v = 0; v < 24; v++) {
-    const v4i x = qp[v], y = tp[v];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int d0 = (int)(int16_t)(x[i] & 0xffff) - (int)(int16_t)(y[i] & 0xffff);
-      const int d1 = (x[i] >> 16) - (y[i] >> 16);
-      ssd += (uint32_t)(d0 * d0) + (uint32_t)(d1 * d1);
-    }
-  }
-  return ssd;
-}
-
-__global__ __launch_bounds__(256) void k_knn_refine(int64_t nq, const uint32_t *__restrict__ qperm, int64_t nt,
-                                                    const uint32_t *__restrict__ tperm, const uint8_t *__restrict__ qpack, int q_bytes,
-                                                    const int *__restrict__ best_key, const int *__restrict__ best_row,
-                                                    int *__restrict__ out_idx, uint32_t *__restrict__ out_err,
-                                                    uint32_t *__restrict__ tie_list, unsigned int *__restrict__ tie_count) {
-  // The kernel already knows the sorted row of the (first) minimum and d'' = SSD - (|q-c|^2 & 1): undo both mappings.
+// What the scan leaves per sorted query -- d'' = SSD - (|q-c|^2 & 1) and the winner's ORIGINAL index, equal distances already settled to the
+// lowest one inside the scan (k3_epilogue) -- back in the caller's order, the parity put back.
+__global__ __launch_bounds__(256) void k_knn_refine(int64_t nq, const uint32_t *__restrict__ qperm, const uint8_t *__restrict__ qpack, int q_bytes,
+                                                    const int *__restrict__ best_key, const int *__restrict__ best_idx,
+                                                    int *__restrict__ out_idx, uint32_t *__restrict__ out_err) {
   for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < nq; p += (int64_t)gridDim.x * blockDim.x) {
-    const int br = best_row[p];
-    const int64_t srow = min((int64_t)(br & 0x3fffffff), nt - 1);  // padded rows replicate row nt-1
     const uint32_t nqv = reinterpret_cast<const uint32_t *>(qpack + (p >> 5) * (int64_t)q_bytes + q_bytes - 256)[p & 31];
     const int64_t q = qperm[p];
-    out_idx[q] = (int)tperm[srow];
+    out_idx[q] = best_idx[p];
     out_err[q] = (uint32_t)best_key[p] + (nqv & 1u);
-    if ((br & (1 << 30)) || (int64_t)(br & 0x3fffffff) >= nt) tie_list[atomicAdd(tie_count, 1u)] = (uint32_t)p;
-  }
-}
-
-// Tie settlement: another tile reached the same minimum.  Every row with SSD == best lives in a tile whose box is
-// within sqrt(best) of the query, so a box test over all tiles finds the candidates; keep the lowest original index.
-// One workgroup per tie, thread = tile.
-__global__ __launch_bounds__(256) void k_knn_ties(const int16_t *__restrict__ queries, const uint32_t *__restrict__ qperm,
-                                                  const int16_t *__restrict__ db, int64_t nt, int64_t n_ttiles,
-                                                  const uint32_t *__restrict__ tperm, KnnBoxes bx,
-                                                  const uint32_t *__restrict__ tie_list, const unsigned int *__restrict__ tie_count,
-                                                  int *__restrict__ out_idx, const uint32_t *__restrict__ out_err) {
-  __shared__ unsigned int s_min;
-  __shared__ int s_nt, s_tlist[2048], s_ng, s_glist[256];
-  for (unsigned int k = blockIdx.x; k < *tie_count; k += gridDim.x) {
-    const uint32_t p = tie_list[k];
-    const int64_t q = qperm[p];
-    const int16_t *qrow = queries + q * 192;
-    const uint32_t best = out_err[q];
-    int qv[KNN_NC];  // the tie rescan prunes with the column boxes only
-#pragma unroll
-    for (int d = 0; d < KNN_NC; d++) qv[d] = qrow[bx.col[d]];
-    if (threadIdx.x == 0) { s_min = 0xffffffffu; s_nt = 0; s_ng = 0; }
-    __syncthreads();
-    // (the scan's winner reaches the minimum: only rows of a LOWER original index can replace it, the others are not even read)
-    unsigned int mine = (unsigned int)out_idx[q];
-    auto rows = [&](int64_t t, int r0, int r1) {
-      for (int r = r0; r < r1; r++) {
-        const int64_t sr = t * 32 + r;
-        if (sr >= nt) break;
-        const uint32_t orow = tperm[sr];
-        if (orow < mine && ssd_rows(qrow, db + (int64_t)orow * 192) == best) mine = orow;
-      }
-    };
-    // The runs of KNN_GROUP tiles whose box admits the minimum first (a few of them: the minimum is the NEAREST row's distance), then the
-    // tiles of those runs; the surviving tiles go on a list and their rows are spread over the threads.  (One box test per tile of the
-    // whole database was 2 ms of the literal bench clip's step: 92 000 ties x 5 300 tiles.)
-    auto tile_test = [&](int64_t t) {
-      long long lb = 0;
-#pragma unroll
-      for (int d = 0; d < KNN_NC; d++) {
-        const long long g = max(0, max(bx.lo[(int64_t)d * n_ttiles + t] - qv[d], qv[d] - bx.hi[(int64_t)d * n_ttiles + t]));
-        lb += g * g;
-      }
-      if (lb > (long long)best) return;
-      const int slot = atomicAdd(&s_nt, 1);
-      if (slot < 2048) s_tlist[slot] = (int)t;
-      else rows(t, 0, 32);  // list full: this thread takes the tile's rows itself
-    };
-    const int64_t n_runs = (n_ttiles + KNN_GROUP - 1) / KNN_GROUP;
-    for (int64_t g = threadIdx.x; g < n_runs; g += 256) {
-      long long lb = 0;
-#pragma unroll
-      for (int d = 0; d < KNN_NC; d++) {
-        const long long e = max(0, max(bx.glo[(int64_t)d * n_runs + g] - qv[d], qv[d] - bx.ghi[(int64_t)d * n_runs + g]));
-        lb += e * e;
-      }
-      if (lb > (long long)best) continue;
-      const int slot = atomicAdd(&s_ng, 1);
-      if (slot < 256) s_glist[slot] = (int)g;
-      else for (int64_t t = g * KNN_GROUP; t < min(n_ttiles, (g + 1) * KNN_GROUP); t++) tile_test(t);  // list full: the thread walks the run itself
-    }
-    __syncthreads();
-    {
-      const int runs = min(s_ng, 256);
-      for (int e = threadIdx.x; e < runs * KNN_GROUP; e += 256) {
-        const int64_t t = (int64_t)s_glist[e / KNN_GROUP] * KNN_GROUP + e % KNN_GROUP;
-        if (t < n_ttiles) tile_test(t);
-      }
-    }
-    __syncthreads();
-    const int total = min(s_nt, 2048) * 32;
-    for (int e = threadIdx.x; e < total; e += 256) rows(s_tlist[e >> 5], e & 31, (e & 31) + 1);
-    if (mine != (unsigned int)out_idx[q]) atomicMin(&s_min, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_min != 0xffffffffu) out_idx[q] = (int)s_min;
-    __syncthreads();
   }
 }
 
@@ -323,11 +223,11 @@ static int launch_scan3(tm_knn_index_impl *ix, int64_t nq, int prune, hipStream_
   a.mode = prune ? K3_MODE_LISTS : K3_MODE_DENSE;
   a.first_chunk = knobs().knn_first_chunk ? 1 : 0;
   if (prune) {
-    TM_TRY(ix->gbest.alloc((size_t)a.n_qtiles * 32 * 8)); TM_TRY(ix->gtie.alloc((size_t)a.n_qtiles * 32 * 4));
+    TM_TRY(ix->gbest.alloc((size_t)a.n_qtiles * 32 * 8));
     TM_TRY(ensure_list_buffers(ix, &a));
     TM_TRY(ensure_arena(ix, 1.0, &a));
   }
-  a.gbest = ix->gbest.as<unsigned long long>(); a.gtie = ix->gtie.as<unsigned>();
+  a.gbest = ix->gbest.as<unsigned long long>();
   a.best_key = ix->best_key.as<int>(); a.best_tile = ix->best_tile.as<int>();
   a.seed_stats = &ix->dev_counters()->seed[0][0];
   a.grid_blocks = scan_grid_blocks(a.n_groups);
@@ -360,7 +260,6 @@ static int read_counts(tm_knn_index_impl *ix, KnnCounts *n, int *flag, hipStream
     TM_TRY(hr_.wait());
   }
   *n = KnnCounts();
-  n->ties = c.tie_count;
   n->blocks = c.stats[K3S_BLOCKS]; n->tiles = c.stats[K3S_TILES]; n->pairs = c.stats[K3S_PAIRS];
   n->listed = c.stats[K3S_LISTED]; n->popped = c.stats[K3S_POPPED]; n->cursor = c.stats[K3S_CURSOR];
   n->stopped = c.stats[K3S_STOPPED]; n->stopped_pairs = c.stats[K3S_STOPPED_PAIRS];
@@ -381,7 +280,6 @@ static int record_counts(tm_knn_index_impl *ix, const KnnCounts &n, int prune) {
   TM_HIP(hipEventElapsedTime(&c_, ix->ev_lists, ix->ev1));
   ix->last_ms = ms; ix->last_seed_ms = a_; ix->last_lists_ms = b_; ix->last_consume_ms = c_;
   ix->last_kbytes = knn_kbytes(ix->plan);
-  ix->last_ties = (int64_t)n.ties;
   // pairs actually evaluated: exact (real query, real row) pairs.  (The pairs of the listed blocks the first-chunk look stopped were judged, by a
   // lower bound over 32 columns, not evaluated: they are part of what last_stats reports, as the pairs of a block that ended at its first look always
   // were, and are taken out of what the roofline prices: knn_index_kernel_split)
@@ -402,9 +300,9 @@ static void print_counts(const tm_knn_index_impl *ix, const KnnCounts &n, int64_
   fprintf(stderr, "[tm_knn] seeds %.3f ms, lists %.3f ms (%.1f entries per group, arena %.0f %% full), consume %.3f ms, %.2f of %d matrix instructions per block\n", ix->last_seed_ms, ix->last_lists_ms,
           (double)n.cursor / (double)groups, 100.0 * (double)n.cursor / (double)std::max<uint64_t>(1, ix->arena_cap), ix->last_consume_ms,
           (double)n.mfma / (double)std::max<unsigned long long>(1, n.blocks + n.stopped), knn_kbytes(ix->plan) / 32);
-  fprintf(stderr, "[tm_knn] scan %.3f ms, evaluated %.3f%% of %lld x %lld pairs (%lld blocks; workgroups read %.3f%% of tiles, %.1f per group; %.1f list entries per group, %.1f popped), %lld tie settlements\n",
+  fprintf(stderr, "[tm_knn] scan %.3f ms, evaluated %.3f%% of %lld x %lld pairs (%lld blocks; workgroups read %.3f%% of tiles, %.1f per group; %.1f list entries per group, %.1f popped)\n",
           ix->last_ms, 100.0 * (double)(ix->last_pairs - ix->last_stopped_pairs) / ((double)nq * (double)ix->nt), (long long)nq, (long long)ix->nt, (long long)ix->last_blocks,
-          100.0 * (double)ix->last_loads / ((double)groups * (double)ntt), (double)ix->last_loads / (double)groups, (double)ix->last_listed / (double)groups, (double)ix->last_popped / (double)groups, (long long)ix->last_ties);
+          100.0 * (double)ix->last_loads / ((double)groups * (double)ntt), (double)ix->last_loads / (double)groups, (double)ix->last_listed / (double)groups, (double)ix->last_popped / (double)groups);
 }
 
 #if TM_KNN3_STAMPS
@@ -419,19 +317,15 @@ static void print_stamps(const KnnCounts &n, int64_t groups) {
 }
 #endif
 
-// one attempt: the scan between its events, then the winners' rescan and the tie settlement
-static int search_attempt(tm_knn_index_impl *ix, const void *queries, int64_t nq, void *out_idx, void *out_err, int prune, const KnnBoxes &bx, hipStream_t stream) {
+// one attempt: the scan between its events, then its results in the caller's order
+static int search_attempt(tm_knn_index_impl *ix, int64_t nq, void *out_idx, void *out_err, int prune, hipStream_t stream) {
   K3Counters *c = ix->dev_counters();
   TM_HIP(hipMemsetAsync(c, 0, sizeof(K3Counters), stream));
   TM_HIP(hipEventRecord(ix->ev0, stream));
   TM_TRY(launch_scan3(ix, nq, prune, stream));
   TM_HIP(hipEventRecord(ix->ev1, stream));
-  hipLaunchKernelGGL(k_knn_refine, dim3(gridn(nq)), dim3(256), 0, stream, nq, ix->qperm.as<uint32_t>(), ix->nt, ix->tperm.as<uint32_t>(),
-                     ix->qpack.as<uint8_t>(), knn_tile_bytes(ix->plan.hq, 0), ix->best_key.as<int>(), ix->best_tile.as<int>(), (int *)out_idx,
-                     (uint32_t *)out_err, ix->tie_list.as<uint32_t>(), &c->tie_count);
-  TM_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_knn_ties, dim3(1024), dim3(256), 0, stream, (const int16_t *)queries, ix->qperm.as<uint32_t>(), ix->db, ix->nt, knn_tiles(ix->nt),
-                     ix->tperm.as<uint32_t>(), bx, ix->tie_list.as<uint32_t>(), &c->tie_count, (int *)out_idx, (const uint32_t *)out_err);
+  hipLaunchKernelGGL(k_knn_refine, dim3(gridn(nq)), dim3(256), 0, stream, nq, ix->qperm.as<uint32_t>(), ix->qpack.as<uint8_t>(), knn_tile_bytes(ix->plan.hq, 0),
+                     ix->best_key.as<int>(), ix->best_tile.as<int>(), (int *)out_idx, (uint32_t *)out_err);
   TM_HIP(hipGetLastError());
   return TM_OK;
 }
@@ -449,7 +343,6 @@ int knn_index_search(tm_knn_index_impl *ix, const void *queries, int64_t nq, voi
   const int64_t nqt = knn_tiles(nq), ntt = knn_tiles(ix->nt);
   TM_TRY(ix->best_key.alloc((size_t)nqt * 32 * 4));
   TM_TRY(ix->best_tile.alloc((size_t)nqt * 32 * 4));
-  TM_TRY(ix->tie_list.alloc((size_t)nq * 4));
   TM_TRY(ix->counters.alloc(sizeof(K3Counters)));
   const int prune = knobs().knn_noprune ? 0 : 1;  // diagnostic: full scan with the same kernel (bench.py roofline_dense)
   const KnnBoxes bx = knn_boxes(ix);
@@ -459,7 +352,7 @@ int knn_index_search(tm_knn_index_impl *ix, const void *queries, int64_t nq, voi
   int flag = 0;
   KnnCounts n;
   for (int attempt = 0;; attempt++) {
-    TM_TRY(search_attempt(ix, queries, nq, out_idx, out_err, prune, bx, stream));
+    TM_TRY(search_attempt(ix, nq, out_idx, out_err, prune, stream));
     TM_TRY(read_counts(ix, &n, &flag, stream));
     if (prune) note_list_entries(n.cursor, groups);
     TM_CHECK(n.guard == 0, TM_E_HIP, "knn: the scan met a corrupted tile list (guard word %llx)", n.guard);
@@ -473,6 +366,13 @@ int knn_index_search(tm_knn_index_impl *ix, const void *queries, int64_t nq, voi
   print_stamps(n, groups);
 #endif
   return TM_OK;
+}
+
+int knn_index_row_order(tm_knn_index_impl *ix, void *out_rows, hipStream_t stream) {
+  TM_CHECK(ix != nullptr && ix->packed, TM_E_INVAL, "knn: the index has not searched yet");
+  HostRead hr_(stream);
+  TM_TRY(hr_.get(out_rows, ix->tperm.p, (size_t)ix->nt * 4));
+  return hr_.wait();
 }
 
 void knn_index_kernel_split(tm_knn_index_impl *ix, double ms[3], int64_t pairs[3]) {

@@ -5,7 +5,7 @@
 // showed 21 % of the wave time in phases where the matrix pipe has nothing to do (list building 10.8 %, the wait for the slowest wave at
 // every list's end 6.8 %, prologue 3.7 %).  Here each phase is a kernel of its own, shaped for what it does:
 //   1. k_knn_seed    every query sub-tile against the K3_SEEDS database tiles around its group's position on the curve: bests (one 64-bit
-//                    word per query), tie values, and the sub-tile's bound sqrt(largest best) -- MFMA work with no list in sight, several
+//                    word per query) and the sub-tile's bound sqrt(largest best) -- MFMA work with no list in sight, several
 //                    workgroups per CU.
 //   2. k_knn_lists   the tile list of every query group, judged against the seeds' bounds: runs of KNN_GROUP tiles first, then the tiles of
 //                    surviving runs; per entry the box lower bound of each (tile, sub-tile) pair as a 16-bit square root.  No MFMA, no query
@@ -19,8 +19,11 @@
 //                    first chunk of columns, the 32 widest, before its chain runs, and ends there nine times in ten (k3_chunk_look, DESIGN.md
 //                    section 23).
 // Arithmetic, operands, boxes, curve and the exactness argument are those of the earlier shapes: a pair is skipped only when its lower
-// bound exceeds the sub-tile's largest best + 1 (both sides of the 16-bit compare rounded the safe way), the minimum VALUE is exact, a
-// second row reaching it raises the tie flag that k_knn_ties settles by original index.
+// bound exceeds the sub-tile's largest best + 1 (both sides of the 16-bit compare rounded the safe way), the minimum VALUE is exact, and
+// among the rows reaching it the lowest ORIGINAL index wins inside the scan: a query's best is (d'' + 1) << 32 | original index, every row
+// that reaches or ties it arrives at k3_epilogue's 64-bit atomic minimum (the inclusive compares of next_entry, pick, k3_chunk_look and the
+// epilogue), and a tile's rows stand in ascending original index (k_knn_tile_order), so a lane's lowest winning row is its lowest index
+// (DESIGN.md section 27).
 #pragma once
 #include <cstddef>
 #include <type_traits>
@@ -57,11 +60,14 @@ constexpr int K3_XCD_RUN = 32 * K3_WGS;  // groups dealt to one XCD at a time (n
 #endif
 constexpr int K3_LIST_NT = 256;          // threads of a list-building workgroup
 
-// (per sub-tile: operands, norms, bests, tie words, box, the norms over the first chunk's columns; per wave: its tile's 32 row terms over them)
-constexpr int k3_lds_bytes(int ns, int kq) { return ns * (kq * 1024 + 576 + 128) + 64 + 64 + 64 + K3_NW * 128 + K3_LCAP * (4 + 2 * ((ns + 1) & ~1)); }
-// The packs (k_knn_pack): a database tile is KT operand chunks of 1 KB, 32 row terms, the tile's box (64 bytes) and the 32 row terms over the
-// first chunk's columns; a query sub-tile is KQ chunks, 32 norms and the 32 norms over the first chunk's columns.
-constexpr int k3_t_bytes(int kt) { return kt * 1024 + 128 + 64 + 128; }
+// (per sub-tile: operands, norms, bests, box, the norms over the first chunk's columns; per wave: its tile's 32 row terms over them and its
+// 32 original indices)
+constexpr int k3_lds_bytes(int ns, int kq) { return ns * (kq * 1024 + 576) + 64 + 64 + 64 + K3_NW * (128 + 128) + K3_LCAP * (4 + 2 * ((ns + 1) & ~1)); }
+// The packs (k_knn_pack): a database tile is KT operand chunks of 1 KB, 32 row terms, the tile's box (64 bytes), the 32 row terms over the
+// first chunk's columns and the rows' 32 original indices (ascending; padding rows carry the last real row's); a query sub-tile is KQ
+// chunks, 32 norms and the 32 norms over the first chunk's columns.
+constexpr int k3_t_bytes(int kt) { return kt * 1024 + 128 + 64 + 128 + 128; }
+constexpr int k3_t_idx_off(int kt) { return kt * 1024 + 128 + 64 + 128; }  // where a tile's original indices begin
 constexpr int k3_q_bytes(int kq) { return kq * 1024 + 128 + 128; }
 constexpr int k3_ns(int kq) {
   int ns = 16;
@@ -81,8 +87,7 @@ struct Knn3Args {
   int mode;                     // consume: K3_MODE_LISTS / K3_MODE_DENSE (every tile, every sub-tile; no seeds, no lists)
   int tdouble;                  // the database pack holds the digits of 2 (t - c)
   // between the kernels (HBM)
-  unsigned long long *gbest;    // [n_qtiles * 32] (d'' + 1) << 32 | sorted row
-  unsigned *gtie;               // [n_qtiles * 32] smallest d'' + 1 seen twice
+  unsigned long long *gbest;    // [n_qtiles * 32] (d'' + 1) << 32 | original index
   unsigned *gsmax;              // [n_qtiles] upper bound of sqrt(largest best + 1) of the sub-tile, 0xFFFE = some query has none
   uint2 *segs;                  // [n_groups][max_segs] (first entry, entries) of each list segment
   int *nsegs;                   // [n_groups]
@@ -130,7 +135,7 @@ enum K3Stat {
 };
 enum K3SeedStat { K3SEED_BLOCKS = 0, K3SEED_TILES = 1, K3SEED_PAIRS = 2, K3SEED_WORDS = 4 };  // a stripe of the seed kernel's counters (the fourth word is spare)
 struct K3Counters {
-  unsigned tie_count, pad_[3];              // k_knn_refine counts the queries it hands to k_knn_ties
+  unsigned pad_[4];
   unsigned long long stats[K3S_COUNT];
   unsigned long long seed[64][K3SEED_WORDS];  // the seed kernel's, striped by workgroup
   unsigned *tickets() { return reinterpret_cast<unsigned *>(stats + K3S_TICKETS); }
@@ -408,8 +413,8 @@ __device__ __forceinline__ bool k3_may_matter(const v16i &acc, unsigned qn, unsi
 // query's norm, whole) the chain of the chunk's own products -- T_H0 . Q_H0, T_H0 . Q_L0, T_L0 . Q_H0, T_L0 . Q_L0, under k3_chain's
 // predicates, shifted as there, the row term riding in on the second shift -- ends in the pair's SSD over the 32 columns (without TD:
 // that or one less).  The invariant: what a lane compares is <= SSD over the chunk <= SSD <= d'' + 1 for every row of the block, and
-// the compare against the query's best d'' + 1 is inclusive: a row that improves OR ONLY TIES a best always passes, so the bests, the
-// tie words and what k_knn_ties sees are those of a scan that ran every chain.  Returns whether the block can matter to this lane's query.
+// the compare against the query's best d'' + 1 is inclusive: a row that improves OR ONLY TIES a best always passes, so the bests,
+// their original indices included, are those of a scan that ran every chain.  Returns whether the block can matter to this lane's query.
 template <int HT, int HQ, bool TD>
 __device__ __forceinline__ bool k3_chunk_look(const v4i (&T)[6 + HT], const uint8_t *rows, int half, const uint8_t *q, unsigned tm, unsigned qm, const int *qnp_p,
                                               unsigned bound) {
@@ -530,6 +535,38 @@ __device__ __forceinline__ unsigned k3_equal_mask(const v16i &acc, int ym) {
   return e;
 }
 
+// A tile's 32 original indices into the wave's own 128 bytes of LDS (consume): one LDS-DMA load by lanes 0..31, `src` = the indices in the
+// tile's pack and `lds_dst` = the slot's LDS address, both wave-uniform.  The load has no register destination -- the block loop has none to
+// spare -- and the compiler does not count it: whoever reads the slot waits for it (k3_tile_idx_staged).  M0, the LDS base of
+// such a load, is the compiler's and is put back.  (The wait states in front of the load cover a base the compiler may have made on the
+// vector unit and M0's own.)  The wave's reads of the slot for the tile before are retired by then: each fed an atomic already issued.
+__device__ __forceinline__ void k3_stage_tile_idx(const uint8_t *src, unsigned lds_dst, int lane) {
+  if (lane < 32) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\t"
+                 "s_mov_b32 m0, %3\n\t"
+                 "s_nop 2\n\t"
+                 "global_load_lds_dword %1, %2\n\t"
+                 "s_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(lane * 4), "s"(src), "s"(lds_dst)
+                 : "memory");
+  }
+}
+// ... and one of them read back by the wave that staged them.  Nothing orders an LDS read behind an LDS-DMA load but the issuing wave's own
+// wait for its memory counter, so the wait stands in the statement that reads.  It waits for nothing else: the read is made behind a
+// block's chain, which has taken in every load of the tile, and the next tile's are not asked for before the block loop ends.
+__device__ __forceinline__ unsigned k3_tile_idx_staged(const unsigned *p) {
+  unsigned v;
+  asm volatile("s_waitcnt vmcnt(0)\n\t"
+               "ds_read_b32 %0, %1\n\t"
+               "s_waitcnt lgkmcnt(0)"
+               : "=&v"(v)
+               : "v"((unsigned)(size_t)(const __attribute__((address_space(3))) unsigned *)p)
+               : "memory");
+  return v;
+}
+
 // A block's epilogue: the row minimum of each query (lane & 31; the two half-waves hold 16 rows each) against its running best in LDS.
 // d'' = 2 X + |t-c|^2 + 2 (|q-c|^2 >> 1) = SSD - parity.  Returns true in lanes whose improvement may have lowered the sub-tile's largest
 // best (the caller refreshes the bound when any lane says so); `sm_now` = the sub-tile's published bound, or 0 to ask for a refresh on
@@ -538,8 +575,12 @@ __device__ __forceinline__ unsigned k3_equal_mask(const v16i &acc, int ym) {
 // and a row with Y_r >= ym + 1 is worth at least 2 ym + 2: so the minimum is 2 ym + p, p the smallest parity among the rows with Y_r = ym,
 // and the rows reaching it are those with Y_r = ym and parity p.  With TD the values are the Y_r (p = 0).  Neither the sixteen values nor a
 // second minimum are made, and the row is named by a bit scan: k3_prow grows with r, so the lowest set bit is the first register's row.
-template <bool TD>
-__device__ __forceinline__ bool k3_epilogue(const v16i &acc, unsigned pwh, int tile, int half, unsigned qn, unsigned long long *best, unsigned *tie,
+// The key's low word is the row's ORIGINAL index (`tidx`: the 32 indices of the wave's tile in LDS), so the atomic minimum settles equal
+// distances by the rule of CompareEuclideanDCTPtr's callers where they meet: among a lane's rows the lowest set bit of `win` is the lowest
+// index (a tile's rows ascend in it: k_knn_tile_order), the other half-wave, the other waves and the seeds meet through the atomic.
+// DMA: the indices came by k3_stage_tile_idx and are waited for here (k3_tile_idx_staged).
+template <bool TD, bool DMA>
+__device__ __forceinline__ bool k3_epilogue(const v16i &acc, unsigned pwh, const unsigned *tidx, int half, unsigned qn, unsigned long long *best,
                                             unsigned sm_now, unsigned cur_hi /* the query's best as read BEFORE the chain: stale only on the safe side (a best only falls) */) {
   bool refresh = false;
   int y[16];
@@ -556,11 +597,11 @@ __device__ __forceinline__ bool k3_epilogue(const v16i &acc, unsigned pwh, int t
       key_hi = look + (even ? 0u : 1u);
     }
     if (key_hi <= cur_hi) {
-      const int row = __builtin_ctz(win) + 4 * half;  // the first row reaching the minimum
-      const unsigned long long key = ((unsigned long long)key_hi << 32) | (unsigned)((tile << 5) | row);
+      const int row = __builtin_ctz(win) + 4 * half;  // the first row reaching the minimum: of this lane's, the one of the lowest original index
+      const unsigned idx = DMA ? k3_tile_idx_staged(tidx + row) : tidx[row];
+      const unsigned long long key = ((unsigned long long)key_hi << 32) | idx;
       const unsigned long long pre = atomicMin(best, key);
       const unsigned pre_hi = (unsigned)(pre >> 32);
-      if (pre_hi == key_hi || (win & (win - 1u)) != 0) atomicMin(tie, key_hi);  // the value was reached a second time
       // The sub-tile's largest best can only have moved if this query held it: its old best is then no smaller than what the published
       // bound was made from ((bound - 3)^2; a bound of 0xFFFE stands for "some query has no best yet").  A refresh skipped by a race only
       // leaves the bound loose (and is made good at the end of the segment).
@@ -642,7 +683,8 @@ __device__ __forceinline__ bool k3_epilogue_topk(const v16i &acc, unsigned pwh, 
 // ------------------------------------------------------------------------------------------------------------------ 1. seeds
 // One workgroup (8 waves) per query group: wave w holds seed tile w in registers; the group's sub-tiles pass through LDS three at a time
 // (double buffered, LDS-DMA), every wave scoring each against its tile.  Bests meet in LDS (64-bit atomic minimum per query) and leave as
-// gbest / gtie / gsmax.  ~62 KB of LDS: two workgroups per CU, 100 registers per wave.
+// gbest / gsmax.  A wave keeps its tile's 32 original indices in LDS of its own for its whole life (s_tidx: plain stores before the first
+// barrier).  ~61 KB of LDS: two workgroups per CU, 100 registers per wave.
 constexpr int K3_SEED_SLICE = 3;
 template <int HT, int HQ, bool TD, bool UNUSED>
 __global__ __launch_bounds__(K3_SEEDS * 64, 4) void k_knn_seed(const Knn3Args a) {
@@ -651,7 +693,7 @@ __global__ __launch_bounds__(K3_SEEDS * 64, 4) void k_knn_seed(const Knn3Args a)
   constexpr int SL = (2 * K3_SEED_SLICE * KQ * 1024 + 10 * 1024 > 80 * 1024) ? K3_SEED_SLICE - 1 : K3_SEED_SLICE, NW = K3_SEEDS;  // two workgroups per CU
   __shared__ __attribute__((aligned(16))) uint8_t s_q[2][SL * KQ * 1024];
   __shared__ unsigned long long s_best[16 * 32];
-  __shared__ unsigned s_tie[16 * 32];
+  __shared__ unsigned s_tidx[NW * 32];
   __shared__ int s_qn[16 * 32];
   __shared__ unsigned s_qm[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), half = lane >> 5;
@@ -679,7 +721,6 @@ __global__ __launch_bounds__(K3_SEEDS * 64, 4) void k_knn_seed(const Knn3Args a)
     const int64_t st = min(st0 + (i >> 5), a.n_qtiles - 1);
     s_qn[i] = reinterpret_cast<const int *>(a.qpack + st * (int64_t)Q_BYTES + KQ * 1024)[i & 31] & ~1;
     s_best[i] = ~0ull;
-    s_tie[i] = ~0u;
   }
   if (tid < 16) s_qm[tid] = tid < nvalid ? (unsigned)a.qmeta[(st0 + tid) * 16 + 15] : 0u;
   const bool active = wave < n_seed;
@@ -689,6 +730,7 @@ __global__ __launch_bounds__(K3_SEEDS * 64, 4) void k_knn_seed(const Knn3Args a)
   v16i cin;
   unsigned pwh;
   k3_load_tile<KT>(a.tpack + (int64_t)tile * T_BYTES, lane, half, T, cin, pwh);
+  if (lane < 32) s_tidx[wave * 32 + lane] = reinterpret_cast<const unsigned *>(a.tpack + (int64_t)tile * T_BYTES + k3_t_idx_off(KT))[lane];
   const int n_slices = (nvalid + SL - 1) / SL;
   long long nblocks = 0, npairs = 0;
   const int vt = (int)min((int64_t)32, a.nt_rows - (int64_t)tile * 32);
@@ -703,7 +745,7 @@ __global__ __launch_bounds__(K3_SEEDS * 64, 4) void k_knn_seed(const Knn3Args a)
         const int qi = s * 32 + (lane & 31);
         const unsigned cur_hi = k3_peek(reinterpret_cast<unsigned *>(&s_best[qi]) + 1), qn = (unsigned)s_qn[qi];  // (asked for before the chain: they arrive under it)
         const v16i acc = k3_chain<HT, HQ, TD>(T, cin, &s_q[sl & 1][j * KQ * 1024] + lane * 16, tm, (unsigned)__builtin_amdgcn_readfirstlane((int)s_qm[s]));
-        k3_epilogue<TD>(acc, pwh, tile, half, qn, &s_best[qi], &s_tie[qi], 0u, cur_hi);
+        k3_epilogue<TD, false>(acc, pwh, &s_tidx[wave * 32], half, qn, &s_best[qi], 0u, cur_hi);
         nblocks++;
         npairs += (long long)vt * (int)min((int64_t)32, a.nq - (st0 + s) * 32);
       }
@@ -712,10 +754,7 @@ __global__ __launch_bounds__(K3_SEEDS * 64, 4) void k_knn_seed(const Knn3Args a)
   }
   __syncthreads();
   K3_STAMP(4);
-  for (int i = tid; i < nvalid * 32; i += NW * 64) {
-    a.gbest[st0 * 32 + i] = s_best[i];
-    a.gtie[st0 * 32 + i] = s_tie[i];
-  }
+  for (int i = tid; i < nvalid * 32; i += NW * 64) a.gbest[st0 * 32 + i] = s_best[i];
   for (int s = wave; s < nvalid; s += NW) {
     const unsigned mx = k3_wave_umax((unsigned)(s_best[s * 32 + (lane & 31)] >> 32));
     if (lane == 0) a.gsmax[st0 + s] = k3_bound_of(mx);
@@ -983,15 +1022,16 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
   constexpr int T_BYTES = k3_t_bytes(KT), Q_BYTES = k3_q_bytes(KQ);
   constexpr int NS = TOPK ? k3_ns_topk(KQ) : k3_ns(KQ), NSP = (NS + 1) & ~1, NW = K3_NW, NT = K3_NT, LCAP = K3_LCAP;
   // one LDS object, carved by hand (16-byte aligned pieces)
-  constexpr int OFF_QN = NS * KQ * 1024, OFF_BEST = OFF_QN + NS * 128, OFF_TIE = OFF_BEST + NS * 256, OFF_QBOX = OFF_TIE + NS * 128,
+  // (the collection mode's ladder base stands between the bests and the boxes; the nearest-neighbour scan has nothing there)
+  constexpr int OFF_QN = NS * KQ * 1024, OFF_BEST = OFF_QN + NS * 128, OFF_BASE = OFF_BEST + NS * 256, OFF_QBOX = OFF_BASE + (TOPK ? NS * 128 : 0),
                 OFF_QNP = OFF_QBOX + NS * 64, OFF_SMAX = OFF_QNP + NS * 128, OFF_QMASK = OFF_SMAX + 64, OFF_CTL = OFF_QMASK + 64, OFF_TROW = OFF_CTL + 64,
-                OFF_LTILE = OFF_TROW + NW * 128, OFF_LLB = OFF_LTILE + LCAP * 4,
+                OFF_TIDX = OFF_TROW + NW * 128, OFF_LTILE = OFF_TIDX + NW * 128, OFF_LLB = OFF_LTILE + LCAP * 4,
                 OFF_LAD = OFF_LLB + LCAP * NSP * 2, LDS_TOTAL = OFF_LAD + (TOPK ? NS * 32 * 16 : 0);
-  static_assert(OFF_LAD == k3_lds_bytes(NS, KQ) && LDS_TOTAL <= K3_LDS, "LDS carve");
+  static_assert(OFF_LAD == k3_lds_bytes(NS, KQ) + (TOPK ? NS * 128 : 0) && LDS_TOTAL <= K3_LDS, "LDS carve");
   __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_TOTAL];
   int *const s_qn = reinterpret_cast<int *>(lds + OFF_QN);                                  // [NS][32] 2 * (|q-c|^2 >> 1)
-  unsigned long long *const s_best = reinterpret_cast<unsigned long long *>(lds + OFF_BEST);  // [NS][32] (d'' + 1) << 32 | sorted row
-  unsigned *const s_tie = reinterpret_cast<unsigned *>(lds + OFF_TIE);                      // [NS][32] smallest d'' + 1 seen twice
+  unsigned long long *const s_best = reinterpret_cast<unsigned long long *>(lds + OFF_BEST);  // [NS][32] (d'' + 1) << 32 | original index
+  [[maybe_unused]] unsigned *const s_base = reinterpret_cast<unsigned *>(lds + OFF_BASE);   // TOPK: [NS][32] the ladder's base
   [[maybe_unused]] int *const s_qbox = reinterpret_cast<int *>(lds + OFF_QBOX);             // [NS][16] (kept in the carve: the dense mode's home)
   unsigned *const s_smax = reinterpret_cast<unsigned *>(lds + OFF_SMAX);                    // [16] upper bound of sqrt(largest best + 1)
   unsigned *const s_qmask = reinterpret_cast<unsigned *>(lds + OFF_QMASK);                  // [16] non-zero high-digit chunks of each sub-tile
@@ -1002,6 +1042,7 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
   [[maybe_unused]] unsigned *const s_lad = reinterpret_cast<unsigned *>(lds + OFF_LAD);     // TOPK: [NS][32][4] the ladder's 7 x 16-bit counters
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), half = lane >> 5;
+  [[maybe_unused]] const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) uint8_t *)lds;  // the carve's own LDS address (0 where it is the kernel's only object)
 #if TM_KNN3_STAMPS
   unsigned long long st_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = __builtin_amdgcn_s_memtime();
   const unsigned long long st_begin = st_last;
@@ -1015,6 +1056,7 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
   const bool dense = a.mode == K3_MODE_DENSE, ordered = a.list_order != 0 && !dense;
   const bool chunk_first = !TOPK && a.first_chunk != 0 && !dense;  // a block is judged on its first chunk before its chain runs (k3_chunk_look)
   uint8_t *const s_trow = lds + OFF_TROW + wave * 128;  // this wave's tile: its 32 row terms over the first chunk's columns
+  [[maybe_unused]] const unsigned *const s_tidx = reinterpret_cast<const unsigned *>(lds + OFF_TIDX + wave * 128);  // ... and its 32 original indices
   const int split = TOPK ? max(1, a.split) : 1;
   const int64_t n_units = a.n_groups * split;  // what the tickets deal: (group, part of its list)
   for (;;) {
@@ -1067,11 +1109,10 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
       int stp = tau > 0 ? tau >> 3 : 0;  // (seven rungs fit below the threshold whatever the host asks for)
       if (a.step && qreal && stp > 0) stp = min(stp, max(1, a.step[st0 * 32 + i]));
       s_best[i] = ((unsigned long long)(unsigned)(tau + 1) << 32) | (unsigned)stp;
-      s_tie[i] = (unsigned)(tau + 1);  // the ladder's base (the nearest-neighbour scan's tie words are not used in this mode)
+      s_base[i] = (unsigned)(tau + 1);  // the ladder's base
       for (int w = 0; w < 4; w++) s_lad[i * 4 + w] = 0;
     } else {
       s_best[i] = real ? a.gbest[st0 * 32 + i] : ~0ull;
-      s_tie[i] = real ? a.gtie[st0 * 32 + i] : ~0u;
     }
   }
   if (tp < 16) {
@@ -1171,6 +1212,8 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
         v16i cin;
         unsigned pwh;
         unsigned rowp = 0;
+        if constexpr (!TOPK)  // (asked for first: whatever later load of the tile the wave waits for, this one is older)
+          k3_stage_tile_idx(a.tpack + (int64_t)tile * T_BYTES + k3_t_idx_off(KT), (unsigned)(OFF_TIDX + wave * 128) + lds_base, lane);
         if (chunk_first) {
           k3_load_tile_chunk0<KT>(a.tpack + (int64_t)tile * T_BYTES, lane, tm, T, rowp);
           k3_load_tile_rest<KT>(a.tpack + (int64_t)tile * T_BYTES, lane, half, tm, T, cin, pwh);
@@ -1199,9 +1242,9 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
             const int64_t q = (st0 + s) * 32 + (lane & 31);
             // (the last database tile pads with copies of its last row: they are candidates like any row -- the select stage drops them --
             // but must not count towards a rung)
-            refresh = k3_epilogue_topk<TD>(acc, pwh, tile, tile != (int)n_ttiles - 1, half, qn, &s_best[qi], &s_lad[qi * 4], &s_tie[qi], q < a.nq, q, a, sm_now);
+            refresh = k3_epilogue_topk<TD>(acc, pwh, tile, tile != (int)n_ttiles - 1, half, qn, &s_best[qi], &s_lad[qi * 4], &s_base[qi], q < a.nq, q, a, sm_now);
           } else {
-            refresh = k3_epilogue<TD>(acc, pwh, tile, half, qn, bp, reinterpret_cast<unsigned *>(lds + (a_qn + (unsigned)(OFF_TIE - OFF_QN) + (unsigned)s * 128u)), sm_now, cur_hi);
+            refresh = k3_epilogue<TD, true>(acc, pwh, s_tidx, half, qn, bp, sm_now, cur_hi);
           }
           if (__builtin_amdgcn_ballot_w64(refresh)) {  // refresh the sub-tile's largest best (bests only go down: a late writer is only loose)
             const unsigned mx = k3_wave_umax(k3_peek(reinterpret_cast<unsigned *>(bp) + 1));  // = largest d'' + 1
@@ -1295,7 +1338,7 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
     K3_STAMP(3);  // waiting for the other waves at the end of a segment
   }
 
-  // ---- results, in the format k_knn_refine / k_knn_ties read
+  // ---- results, in the format k_knn_refine reads
   int tr = threadIdx.x;
   asm volatile("" : "+v"(tr));
   for (int i = tr; i < NS * 32; i += NT) {
@@ -1308,7 +1351,7 @@ __global__ __launch_bounds__(K3_NT) void k_knn_consume(const Knn3Args a) {
       if (q < a.nq && hi > 0) atomicMin(&a.tau[q], (int)(hi - 1u));
     } else {
       a.best_key[q] = (int)(hi - 1u);
-      a.best_tile[q] = (int)(((unsigned)k & 0x3fffffffu) | (s_tie[i] == hi ? (1u << 30) : 0u));
+      a.best_tile[q] = (int)(unsigned)k;  // the winner's original index
     }
   }
   K3_STAMP(0);  // results (counted with the prologue)

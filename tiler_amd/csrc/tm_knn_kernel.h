@@ -20,8 +20,8 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 // Pruning.  Both sides arrive sorted along a Morton curve of the three widest feature columns (the Y/U/V DC terms for tile features) and
 // the radial coordinate below, so 32 consecutive rows form a compact box.  For ND dimensions the database keeps per-tile bounding boxes
 // (and boxes of runs of KNN_GROUP tiles); the squared box-to-box distance is a lower bound of every SSD between a query sub-tile's
-// queries and a tile's rows.  Exactness: the minimum VALUE is exact (a tile is only skipped when bound > best + 1); when a second row
-// reaches the same value the tie flag is raised and k_knn_ties settles the lowest-index rule.
+// queries and a tile's rows.  Exactness: the minimum VALUE is exact (a tile is only skipped when bound > best + 1), and a row that
+// only ties a best is never skipped either: the scan's atomic minimum, keyed by (value, original index), settles the lowest-index rule.
 constexpr int KNN_NC = 6;        // bounding-box columns
 // One more box dimension, radial: R = |v - c| over all the OTHER columns.  |R(q) - R(t)|^2 <= the squared distance over those
 // columns (reverse triangle inequality), so its gap adds to the lower bound like a column's; it tells a noisy tile from a smooth
@@ -32,7 +32,7 @@ constexpr int KNN_GROUP = 128;   // tiles per second-level box
 struct KnnBoxes {
   const int *lo, *hi;   // [KNN_ND][n_ttiles] bounding boxes of the database tiles
   const int *glo, *ghi; // [KNN_ND][ceil(n_ttiles / KNN_GROUP)] boxes of runs of KNN_GROUP tiles: a run no sub-tile can use is skipped whole
-  const uint32_t *tkey; // [n_ttiles] curve key of each tile's first row (ascending)
+  const uint32_t *tkey; // [n_ttiles] each tile's smallest curve key: that of its first row in curve order (ascending)
   int col[KNN_NC];      // source feature column of each box dimension
   int cen[KNN_NC];      // the digit plan's centre of that column (the radial dimension is measured from the centres)
 };

@@ -9,7 +9,8 @@ namespace tmx {
 // ---------------------------------------------------------------------------------------------------------------
 // Pack n rows into MFMA fragment order: per 32-row tile [kc][64 lanes][16 B] (lane = half*32 + row) followed by
 // 32 u32 norms.  negate=1 (query side): digits of (c - v) and norm >> 1; negate=0 (database): digits of (v - c).
-// Rows >= n replicate row n-1 (ties resolve to the lower, real index).  err_flag is set if a digit overflows int8.
+// Rows >= n replicate row n-1 (database side: the tile's box and the row terms over the first chunk's columns follow the norms, and the
+// tile's last 128 bytes, the rows' original indices, are k_knn_tile_order's: knn_tile_bytes).  err_flag is set if a digit overflows int8.
 // scale (database side, KnnPlan::tscale): the digits are those of scale * (v - c); the norms stay those of v - c.
 __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ feat, int64_t n, int64_t ntiles, int hch, int negate, int scale,
                                                   const int16_t *__restrict__ centre, const int16_t *__restrict__ perm,
@@ -157,7 +158,7 @@ __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ fe
       if (part == 0) {
         s_norm[r] = sq;
         reinterpret_cast<uint32_t *>(obase + kch * 1024)[r] = (with_box && scale == 1) ? sq >> 1 : sq;
-        reinterpret_cast<uint32_t *>(obase + tile_bytes - 128)[r] = (with_box && scale == 1) ? sqp >> 1 : sqp;
+        reinterpret_cast<uint32_t *>(obase + kch * 1024 + 128 + (with_box ? 64 : 0))[r] = (with_box && scale == 1) ? sqp >> 1 : sqp;
       }
     }
     __syncthreads();
@@ -212,6 +213,33 @@ __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ fe
       tb[KNN_ND + d] = b;
       box_lo[(int64_t)d * ntiles + tile] = a;
       box_hi[(int64_t)d * ntiles + tile] = b;
+    }
+  }
+}
+
+// The rows of every tile in ascending original index.  The curve sort decides WHICH 32 rows form a tile (boxes, masks and the tiles' keys
+// are functions of that set); inside the tile the order is free, and this one lets the scan settle equal distances by original index where
+// it finds them: the lowest of a lane's winning rows is then the one of the lowest index (k3_epilogue).  One half-wave per tile, a bitonic
+// network over its 32 lanes; the last tile's missing rows sort behind the real ones and are not written.  `pack` (the database's pack,
+// tile_bytes a tile; null: none): the tile's 32 indices go into its last 128 bytes, where the scan reads the low word of its atomic minimum's
+// key (k3_epilogue); a padding row carries the index of the row it replicates, row n - 1 (k_knn_pack wrote them, and needed a 129th register).
+__global__ __launch_bounds__(256) void k_knn_tile_order(uint32_t *__restrict__ perm, int64_t n, int64_t ntiles, uint8_t *__restrict__ pack, int tile_bytes) {
+  const int i = threadIdx.x & 31;
+  for (int64_t tile = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5); tile < ntiles; tile += (int64_t)gridDim.x * 8) {
+    const int64_t row = tile * 32 + i;
+    const int real = (int)min((int64_t)32, n - tile * 32);  // rows of the tile that exist
+    uint32_t v = row < n ? perm[row] : 0xFFFFFFFFu;
+#pragma unroll
+    for (int k = 2; k <= 32; k <<= 1)
+#pragma unroll
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        const uint32_t w = (uint32_t)__shfl_xor((int)v, j);
+        v = (((i & k) == 0) == ((i & j) == 0)) ? min(v, w) : max(v, w);
+      }
+    if (row < n) perm[row] = v;
+    if (pack) {
+      const uint32_t last = (uint32_t)__shfl((int)v, real - 1, 32);
+      reinterpret_cast<uint32_t *>(pack + (tile + 1) * (int64_t)tile_bytes - 128)[i] = row < n ? v : last;
     }
   }
 }
@@ -345,6 +373,14 @@ static int sort_by_curve(tm_knn_index_impl *ix, const DevBuf &ccol, int64_t n, c
   return TM_OK;
 }
 
+int launch_tile_order(uint32_t *perm, int64_t n, hipStream_t stream, uint8_t *pack, int tile_bytes) {
+  if (n <= 0) return TM_OK;
+  const int64_t ntiles = knn_tiles(n);
+  hipLaunchKernelGGL(k_knn_tile_order, dim3((unsigned)std::min<int64_t>((ntiles + 7) / 8, 2048)), dim3(256), 0, stream, perm, n, ntiles, pack, tile_bytes);
+  TM_HIP(hipGetLastError());
+  return TM_OK;
+}
+
 static int run_pack(tm_knn_index_impl *ix, const void *feat, int64_t n, int negate, int hch, const DevBuf &perm, int with_box,
                     DevBuf &out, hipStream_t stream) {
   const int scale = negate ? 1 : ix->plan.tscale;
@@ -447,7 +483,9 @@ static int build_database_side(tm_knn_index_impl *ix, hipStream_t stream) {
   ix->tccol.release();
   ix->tradial.release();
   TM_TRY(ix->tkey.alloc((size_t)ntt * 4));
-  TM_HIP(hipMemcpy2DAsync(ix->tkey.p, 4, ix->skey2.p, 128, 4, (size_t)ntt, hipMemcpyDeviceToDevice, stream));  // key of each tile's first row
+  TM_HIP(hipMemcpy2DAsync(ix->tkey.p, 4, ix->skey2.p, 128, 4, (size_t)ntt, hipMemcpyDeviceToDevice, stream));  // each tile's smallest key (the sorted keys stay in curve order)
+  TM_TRY(ix->tpack.alloc((size_t)ntt * knn_tile_bytes(ix->plan.ht, 1)));  // (the pack's own allocation below finds it there)
+  TM_TRY(launch_tile_order(ix->tperm.as<uint32_t>(), ix->nt, stream, ix->tpack.as<uint8_t>(), knn_tile_bytes(ix->plan.ht, 1)));
   TM_TRY(ix->box_lo.alloc((size_t)ntt * KNN_ND * 4));
   TM_TRY(ix->box_hi.alloc((size_t)ntt * KNN_ND * 4));
   TM_TRY(run_pack(ix, ix->db, ix->nt, 0, ix->plan.ht, ix->tperm, 1, ix->tpack, stream));

@@ -4,6 +4,7 @@ Each function names the reference routine it stands for; tensors must live on th
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from ._lib import lib, check, scale_filter_of
@@ -191,6 +192,12 @@ def knn(queries, db):
     return idx, err
 
 
+def knn_tile_order(perm):
+    """every run of 32 entries of perm (int32 / uint32 bit patterns on the device) into ascending unsigned order, in place"""
+    check(lib().tm_stage_knn_tile_order(_p(perm), perm.shape[0], _stream()))
+    return perm
+
+
 def knn_last_plan():
     """(ht, hq, topk, arena_retries): the digit plan and mode of this thread's last scan, and the process's count of repeated scans (tests)"""
     ht, hq, tk, r = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
@@ -230,6 +237,12 @@ class KnnIndex:
         looked, stopped = ctypes.c_int64(), ctypes.c_int64()
         check(lib().tm_knn_index_last_chunk_counts(ctypes.c_void_p(self.h), ctypes.byref(looked), ctypes.byref(stopped)))
         return looked.value, stopped.value
+
+    def row_order(self):
+        """the database's row order as the scan sees it (numpy uint32 [nt]; tile t = rows [32 t, 32 t + 32)), after a search"""
+        out = np.empty((self.db.shape[0],), dtype=np.uint32)
+        check(lib().tm_knn_index_row_order(ctypes.c_void_p(self.h), out.ctypes.data_as(ctypes.c_void_p), _stream()))
+        return out
 
     def close(self):
         if self.h:
