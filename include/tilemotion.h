@@ -446,7 +446,7 @@ TM_API int tm_get_tile_page_count(tm_encoder *, int *pages);
  * frames with the file's; the video set with tm_set_video must match the file's header (:5021-5032) or TM_E_INVAL comes back.
  * Afterwards the read-back views and tm_save_gtm work on the loaded state. */
 TM_API int tm_reload_gtm(tm_encoder *, const char *path);
-/* ---- The .gtm player: an object of its own, no encoder behind it (tm_player.hip) --------------------------------
+/* ---- The .gtm player: an object of its own, no encoder behind it (tm_player.hip, tm_player_parse.hip, tm_play_frame.hip) --------------------------------
  * tm_player_open reads the GTMv header and the GTMk index and decodes the FIRST key frame's stream only (it carries the settings text,
  * SetDimensions, the TileSet and the palettes); frames then come out in order, key frame by key frame, each frame one kernel launch that
  * reads the frame before it.  A frame is, bit for bit, what tm_render_frames(first, count, input = 0) gives after tm_reload_gtm of the same

@@ -5,7 +5,7 @@
  * at many lengths (large one), and with bytes flipped.  Every variant sits in an allocation of its exact size, so a read past its end is
  * seen.  Each call must return TM_OK or a negative code with a message; the intact streams must parse.
  *
- * Build and run: tools/asan_player_parse.sh (the program AND the host code it calls -- tm_player.hip, tm_gtm.hip, tm_tables.hip -- carry the
+ * Build and run: tools/asan_player_parse.sh (the program AND the host code it calls -- tm_player_parse.hip, tm_gtm.hip, tm_lzma.hip, tm_tables.hip -- carry the
  * sanitizers: clang -fsanitize=address,undefined for this file, hipcc -Xarch_host -fsanitize=address,undefined for those; no device is touched).
  * An optional second and further arguments feed one more stream:  player_parse DIR STREAM.lzma TM_W TM_H TILE_COUNT
  * (tests/golden/football_cif_kf1.lzma 44 36 83460).  DESIGN.md section 19 records the result. */

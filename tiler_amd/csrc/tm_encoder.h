@@ -7,6 +7,7 @@
 
 #include "tm_common.h"
 #include "tm_internal.h"
+#include "tm_input.h"
 
 struct ncclComm;  // (RCCL's header: tm_shard.hip only)
 struct tm_encoder;
@@ -48,7 +49,7 @@ struct tm_encoder {
   // device state
   DevBuf frames_owned;
   const void *frames = nullptr;  // [nframes][height][width] RGB32
-  // the frame source "file" (tm_open_input): Load decodes InputFileName into a clip the encoder owns (tm_input.hip)
+  // the frame source "file" (tm_open_input): Load decodes InputFileName into a clip the encoder owns (tm_input.hip, tm_input.h)
   InputInfo input;
   int input_yuv = TM_YUV_AUTO;
   InputTables input_tables;

@@ -4,6 +4,7 @@
 #include <fstream>
 
 #include "tm_encoder.h"
+#include "tm_gtm.h"
 
 int save_to(tm_encoder *e, const char *path) {  // Save, tilingencoder.pas:2040-2058 -> SaveStream, 5177
   TM_TRY(need(e, TM_STEP_REINDEX, "Reindex"));

@@ -1,7 +1,7 @@
 // tm_gtm_walk.h -- the command grammar of a .gtm key frame's decoded stream (TGTMCommand, tilingencoder.pas:53-86; LoadStream, 4880-5175),
 // stated once.  walk_gtm_keyframe reads 16-bit commands (data << 4 | cmd) with their operands up to the FrameEnd that closes the key frame,
 // checks that every operand lies inside the stream, and hands each command to a sink.  What a command MEANS -- where an item lands, which
-// tile an intra item becomes -- is the sink's: tm_reload_gtm's tables (tm_gtm.hip) and the player's records (tm_player.hip) are two sinks.
+// tile an intra item becomes -- is the sink's: tm_reload_gtm's tables (tm_gtm_reload.hip) and the player's records (tm_player_parse.hip) are two sinks.
 //
 // A sink has (each returns TM_OK or an error, which ends the walk):
 //   int settings(uint32_t kind, const uint8_t *text, size_t n)        ExtendedCommand; kind 0 is the settings text
@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "tm_common.h"
+#include "tm_gtm.h"
 
 namespace tmx {
 
@@ -41,14 +42,24 @@ inline int settings_palette_size(const uint8_t *text, size_t n) {
   }
   return 0;
 }
+// what both sinks make of the settings text (ExtendedCommand 0): kept, and the palette size until a TileSet says it -- a stream of intra
+// and predicted items has none
+inline void take_settings_text(const uint8_t *text, size_t n, std::string *settings, int *pal_size) {
+  settings->assign((const char *)text, n);
+  if (*pal_size == 0) *pal_size = settings_palette_size(text, n);
+}
+// what both sinks make of a LoadPalette's n words 0xAABBGGRR: the alpha is stripped (4951)
+inline void take_palette_words(const uint8_t *c, size_t n, int32_t *out) {
+  for (size_t k = 0; k < n; k++) out[k] = (int32_t)(load_u32(c + 4 * k) & 0xffffffu);
+}
 
 template <class Sink>
 int walk_gtm_keyframe(const uint8_t *kf, size_t n, const char *name, Sink &s, size_t *end = nullptr) {
   size_t p = 0;
   auto need = [&](size_t k) { return k <= n - p; };  // (p <= n always)
   auto u8 = [&]() { return (uint32_t)kf[p++]; };
-  auto u16 = [&]() { const uint32_t v = kf[p] | (kf[p + 1] << 8); p += 2; return v; };
-  auto u32 = [&]() { const uint32_t v = (uint32_t)kf[p] | ((uint32_t)kf[p + 1] << 8) | ((uint32_t)kf[p + 2] << 16) | ((uint32_t)kf[p + 3] << 24); p += 4; return v; };
+  auto u16 = [&]() { const uint32_t v = load_u16(kf + p); p += 2; return v; };
+  auto u32 = [&]() { const uint32_t v = load_u32(kf + p); p += 4; return v; };
   bool kf_end = false;
   while (!kf_end) {
     TM_CHECK(need(2), TM_E_IO, "%s: truncated command stream", name);

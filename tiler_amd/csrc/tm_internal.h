@@ -154,45 +154,12 @@ uint32_t crc32_ieee(const uint8_t *p, size_t n);
 int inflate_zlib(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *out_n);
 int read_png(const char *path, uint32_t *out, int64_t cap_px, int *w, int *h);
 
-// tm_input.hip: Load's input.  What the probe half of Load (tilingencoder.pas:1764-1820) finds out about InputFileName.
-constexpr int INPUT_YUV_CLIP = 3;  // InputInfo::kind of a YUV clip lent in memory (tm_set_frames_yuv), beside TM_INPUT_Y4M / TM_INPUT_PNGS
-constexpr int INPUT_GTM = TM_INPUT_GTM;  // a .gtm stream ('GTMv'): Load plays its frames into the device clip (tm_player.hip)
-// tm_player.hip (host only): a .gtm file's picture size (tm_w * 8 x tm_h * 8), rate and frame count, from its header and first key frame
-int probe_gtm(const char *path, int *width, int *height, double *fps, int *frames);
-struct InputInfo {
-  int kind = 0;  // 0: RGB32 frames from memory (pushed or lent); TM_INPUT_Y4M / TM_INPUT_PNGS: from the file; INPUT_YUV_CLIP: lent planes
-  std::string name;
-  tm_yuv_clip clip{};               // INPUT_YUV_CLIP: the descriptor as it was lent
-  bool lent = false;                // its planes are still borrowed: no Load has read them yet
-  int start = 0, frames = 0, src_w = 0, src_h = 0, dst_w = 0, dst_h = 0, chroma = 0, full_range = 0;
-  double fps = 0;
-  int64_t frame_bytes = 0;
-  std::vector<int64_t> frame_off;   // Y4M: where every whole frame's planes start in the file
-  std::vector<int32_t> manual_kf;   // PNGs: frame 0 and the frames a .kf file marks (3380-3384)
-  bool decoded = false;             // the device clip holds frames [dec_first, +dec_count) converted with dec_mode
-  int dec_first = 0, dec_count = 0, dec_mode = 0;
-};
-struct PinnedBuf {  // page-locked host memory that only grows
-  void *p = nullptr;
-  size_t bytes = 0;
-  PinnedBuf() = default;
-  PinnedBuf(const PinnedBuf &) = delete;
-  PinnedBuf &operator=(const PinnedBuf &) = delete;
-  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-  int alloc(size_t n) {
-    if (p && n <= bytes) return TM_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; bytes = 0;
-    TM_HIP(hipHostMalloc(&p, n, hipHostMallocDefault));
-    bytes = n;
-    return TM_OK;
-  }
-};
-int probe_input(const std::string &name, int start_frame, int frame_count, double scaling, InputInfo *in);
-// the resampling tables of one conversion on the device: per axis first [m], count [m], coef [tap][m] (the lanes of a wave read neighbouring
+// tm_input.h: Load's input -- InputInfo and probe_input, the staging helpers (PinnedBuf, StagingRing), the YUV planes' way in (InputTables)
+
+// tm_resample.hip (host only): the rule's tables, shared by tm_yuv_in.hip (YUV planes in) and tm_scale.hip (RGB32 frames out).
+// The resampling tables of one conversion on the device: per axis first [m], count [m], coef [tap][m] (the lanes of a wave read neighbouring
 // words); a vertical axis also has, per tile of th output rows, the source rows its samples reach as (first row, number of rows)
 struct AxisTaps { const int32_t *first, *count, *coef; const int2 *span; };
-// tm_resample.hip (host only): the rule's tables, shared by tm_input.hip (YUV planes in) and tm_scale.hip (RGB32 frames out)
 int resample_taps(int n, int m, int np, int s, int o_halves, int32_t *first, int32_t *count, int32_t *coef, int64_t *sum_abs_max);
 constexpr int RESAMPLE_TH_MAX = 16;  // output rows per workgroup, at most
 struct AxisTable {  // one axis on the host: first / count [m], coef [m][TM_RESAMPLE_MAX_TAPS], the largest sum of |coefficients| of a sample
@@ -207,11 +174,6 @@ int check_resample_sums(const AxisTable &h, const AxisTable &v, int src_w, int s
 int resample_tile_rows(const AxisTable *const *vertical, int nplanes, int max_rows);  // th (0: not even one row's taps fit)
 // the axes in the device layout above; odd ones are vertical and get the spans of tiles of th rows (none may reach more than max_rows)
 int upload_axis_tables(const AxisTable *const *axes, int naxes, int th, int max_rows, DevBuf *dev, AxisTaps *out, hipStream_t stream);
-struct InputTables {
-  int src_w = 0, src_h = 0, chroma = -1, dst_w = 0, dst_h = 0, th = 0;  // th: output rows per workgroup
-  DevBuf dev;
-  AxisTaps lh{}, lv{}, ch{}, cv{};  // luma / chroma, horizontal / vertical
-};
 
 // tm_scale.hip: RGB32 frames [n][h][stride] 0x00RRGGBB at another size.  probe_scale: the sizes and the filter;
 // check_scale_args: those, the pointers, the strides in pixels and the overlap -- neither makes a device call.
@@ -299,34 +261,6 @@ int run_kmodes(const uint8_t *rows, int64_t n, int k, int num_init, int nmod, in
 // tm_optpal.hip (host only)
 int optimize_palettes_host(std::vector<int32_t> &pals, int pal_count, int pal_size, int *sweeps_out);
 
-
-// tm_gtm.hip (host only): SaveStream restatement, tilingencoder.pas:5177-5482
-struct GtmInput {
-  int tm_w = 0, tm_h = 0, nframes = 0;
-  double fps = 0;
-  std::vector<int32_t> kf_start;
-  const uint8_t *pal_px = nullptr;   // [ntiles][64], final (Reindex) order
-  std::vector<uint32_t> use;         // [ntiles]
-  const int32_t *palettes = nullptr; // [pal_count][pal_size]
-  int pal_count = 0, pal_size = 0;
-  const tm_tilemap_item *tilemap = nullptr;  // [nframes][tm_h*tm_w]
-  std::string settings;
-};
-int write_gtm(const char *path, const GtmInput &in);
-void lz_compress(const std::vector<uint8_t> &raw, std::vector<uint8_t> &dst);
-int lz_decompress(const uint8_t *src, size_t n, std::vector<uint8_t> &dst, size_t *consumed, size_t max_out = (size_t)-1);  // max_out: TM_E_IO once the output passes it
-// LoadStream (tilingencoder.pas:4880-5175)
-struct GtmLoaded {
-  int header_w = 0, header_h = 0, header_frames = -1;  // from the GTMv header (-1: headerless stream)
-  int tm_w = 0, tm_h = 0, nframes = 0, pal_size = 0, pal_count = 0;
-  double fps = 0;
-  std::vector<int32_t> kf_start;
-  std::vector<uint8_t> pal_px;      // [tiles][64]
-  std::vector<uint32_t> use;        // UseCount as SetTMI counts it (4968-4969)
-  std::vector<int32_t> palettes;    // [pal_count][pal_size], alpha stripped (4951)
-  std::vector<tm_tilemap_item> tilemap;  // [nframes][tm_h*tm_w]
-  std::string settings;
-};
-int read_gtm(const char *path, GtmLoaded *out);
+// tm_gtm.h: the .gtm container, write_gtm / read_gtm / probe_gtm, lz_compress / lz_decompress; tm_player.h: the player's host side
 
 }  // namespace tmx

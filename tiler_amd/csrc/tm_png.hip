@@ -1,5 +1,5 @@
 // tm_png.hip -- host only: the PNG reader behind a numbered PNG sequence (LoadInputVideo, tilingencoder.pas:3340-3353) and the inflate it
-// needs.  Like the LZMA coder of tm_gtm.hip and the PNG writer of tm_export.hip it links nothing: stored, fixed and dynamic Huffman
+// needs.  Like the LZMA coder of tm_lzma.hip and the PNG writer of tm_export.hip it links nothing: stored, fixed and dynamic Huffman
 // blocks (RFC 1951), the zlib wrapper with its Adler-32 (RFC 1950), chunk CRCs and the five row filters (PNG 1.2, sections 3, 6).
 // Every read is checked against the end of its buffer; a stream that is cut short or damaged is refused, never followed.
 #include "tm_common.h"

@@ -1,5 +1,5 @@
 // tm_resample.hip -- the Lanczos-3 resampling tables (host only): the one place the rule of DESIGN.md section 17 is stated.  Its two users are
-// the kernel that reads YUV planes on the way in (tm_input.hip) and the kernel that scales RGB32 frames on the way out (tm_scale.hip):
+// the kernel that reads YUV planes on the way in (tm_yuv_in.hip) and the kernel that scales RGB32 frames on the way out (tm_scale.hip):
 //   r = n / m;  f = max(1, r / s);  u_j = ((j + 0.5) r - 0.5 - o) / s;  taps ceil(u_j - 3f) .. floor(u_j + 3f) inside the plane
 //   c_k = RoundHalfEven(16384 w_k / sum w), the remainder to the tap of largest w;  h = (sum c p + 64) >> 7;  v = clamp((sum c h + 2^20) >> 21)
 // for a plane whose samples sit at luma positions s k + o (s = 2 for subsampled chroma, o = 0.5 where it is centred).
@@ -134,3 +134,8 @@ int upload_axis_tables(const AxisTable *const *axes, int naxes, int th, int max_
 }
 
 }  // namespace tmx
+
+extern "C" int tm_resample_taps_host(int n, int m, int np, int s, int o_halves, int32_t *first, int32_t *count, int32_t *coef) {
+  TM_CHECK(first && count && coef, TM_E_INVAL, "null argument");
+  return tmx::resample_taps(n, m, np, s, o_halves, first, count, coef, nullptr);
+}

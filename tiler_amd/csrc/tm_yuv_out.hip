@@ -1,5 +1,5 @@
 // tm_yuv_out.hip -- decoded frames leave as YUV: the forward colour rules, the checks of a destination (tm_yuv_out), and the kernel that
-// turns RGB32 frames into planes of Y, U, V on the device (the mirror image of tm_input.hip's k_yuv_to_rgb32).
+// turns RGB32 frames into planes of Y, U, V on the device (the mirror image of tm_yuv_in.hip's k_yuv_to_rgb32).
 //
 // One sample, one rounding.  A sample at depth d is ((c . S + half) >> s) + off, clamped to 0 .. 2^d - 1: c the row of the 16-bit matrix, S the
 // weighted sum of R, G, B over the sample's footprint (weights totalling 2^lw), s = 16 - (d - 8) + lw, half = 1 << (s - 1).  Footprints: the

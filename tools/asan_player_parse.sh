@@ -1,5 +1,5 @@
 #!/bin/bash
-# tests/c/player_parse.c and the host code it calls (tm_player.hip, tm_gtm.hip, tm_tables.hip; tm_yuv_out.hip for the player's YUV read) under AddressSanitizer and
+# tests/c/player_parse.c and the host code it calls (tm_player_parse.hip, tm_gtm.hip, tm_lzma.hip, tm_tables.hip) under AddressSanitizer and
 # UndefinedBehaviorSanitizer, as one stand-alone program; CPU only, no device is touched.  usage: tools/asan_player_parse.sh [BUILD_DIR]
 set -euo pipefail
 ROOT="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
@@ -10,7 +10,7 @@ S="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
 mkdir -p "$OUT"
 "$CLANG" -O1 -g $S -Wall -I"$ROOT/include" -c "$ROOT/tests/c/player_parse.c" -o "$OUT/player_parse.o"
 objs=("$OUT/player_parse.o")
-for f in tm_player tm_gtm tm_tables tm_yuv_out; do
+for f in tm_player_parse tm_gtm tm_lzma tm_tables; do
   "$HIPCC" --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
     -c "$ROOT/tiler_amd/csrc/$f.hip" -o "$OUT/$f.o" &
   objs+=("$OUT/$f.o")
