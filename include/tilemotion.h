@@ -73,8 +73,8 @@
  *                           other processes or shards (120)
  *   TM_GROUP_FAIL_SHARD=<r> shard r of a device group fails with TM_E_INVAL ("forced") at the start of its next step, before it queues any work
  *                           (tests: the other shards must leave their collectives at once)
- *   TM_INPUT_CHUNK_FRAMES=<n> Load reads a Y4M file, or stages a lent YUV clip, n frames at a time instead of 16 MB worth (tests: 1, so that a small
- *                           clip walks the two staging buffers many times)
+ *   TM_INPUT_CHUNK_FRAMES=<n> Load reads a Y4M file, or stages a lent YUV or RGB clip, n frames at a time instead of 16 MB worth (tests: 1, so that
+ *                           a small clip walks the two staging buffers many times)
  *   TM_RECON_CHUNK_FRAMES=<n> Reconstruct computes and searches its query features n frames at a time instead of 8 GiB worth (2 GiB with the
  *                           extended palette usage); the features computed ahead during PreparePalettes are then those of the first n frames
  *                           (tests: a small clip takes several chunks)
@@ -187,8 +187,8 @@ TM_API int tm_prefetch_frames_host(tm_encoder *, const uint32_t *host_frames);
 /* The probe half of Load (:1764-1820): reads InputFileName, StartFrame, FrameCount and Scaling, does what tm_set_video(DstWidth, DstHeight,
  * fps, frames) does and makes the file the encoder's frame source; tm_run(TM_STEP_LOAD) then decodes it into a device clip the encoder owns
  * and goes on as if that clip had been set with tm_set_frames_device (a second Load without a new tm_open_input reads that clip again).
- * With no video described yet and InputFileName set, Load calls it itself.  tm_set_video, tm_push_frame_rgb32 and tm_set_frames_* switch
- * the source back to memory (and the key frames back to the automatic rule).
+ * With no video described yet and InputFileName set, Load calls it itself.  tm_set_video, tm_push_frame_rgb32 and tm_set_frames_* (_device,
+ * _host, _yuv, _rgb) switch the source back to memory (and the key frames back to the automatic rule).
  *   An existing file must be Y4M ('YUV4MPEG2 '): W, H, F num:den (fps = num / den), I and C tags, XCOLORRANGE=FULL|LIMITED; frames are
  * found by walking their 'FRAME...' headers, a last frame cut short does not count.  8-bit C444, C422, C420jpeg (also no C tag), C420mpeg2,
  * Cmono; Ip, I? or no I tag.  Anything else -- other layouts, deeper samples, interlaced video, a file that is not Y4M (FFmpeg stays out of
@@ -199,7 +199,7 @@ TM_API int tm_prefetch_frames_host(tm_encoder *, const uint32_t *host_frames);
  * YUV -> RGB run on the device (tm_stage_yuv_to_rgb32).
  *   An existing file that starts with 'GTMv' is a .gtm stream: Load plays frames [StartFrame, StartFrame + FrameCount) with the player
  * (tm_player_*) into the device clip; the video is tm_w*8 x tm_h*8 at the stream's rate.  Key frames follow the automatic rule: the stream's
- * own are not taken over.  Scaling != 1 is TM_E_UNSUPPORTED (the resampler takes YUV planes), refused here, before the stream is read.
+ * own are not taken over.  Scaling != 1 is TM_E_UNSUPPORTED (played frames are not resampled on the way in), refused here, before the stream is read.
  *   Otherwise the name is a Format pattern with one %d or %.Nd (%% = '%'): the PNG sequence Format(name, [i + StartFrame])
  * (LoadInputVideo, :3340-3353), fps 24 (:1791), FrameCount <= 0 counts files up to the first gap (:1797-1806), the size is the first
  * file's (:1813-1814; a later file of another size: TM_E_INVAL at Load), Scaling is ignored (:3347-3348).  Key frames are manual: frame 0
@@ -244,7 +244,8 @@ typedef struct {
  * of the next tm_run(TM_STEP_LOAD), which converts it on the device as it does a Y4M file's planes.  StartFrame and FrameCount do not apply;
  * the key frames follow the automatic rule.  The planes are BORROWED until that Load has returned; from then on the encoder reads its own
  * RGB32 clip: a second Load with the same tm_set_input_yuv mode reads that clip again, one with another mode (or a larger share of the frames)
- * is TM_E_INVAL -- lend the clip again.  tm_set_video, tm_push_frame_rgb32, tm_set_frames_* and tm_open_input switch the source away.
+ * is TM_E_INVAL -- lend the clip again.  tm_set_video, tm_push_frame_rgb32, tm_set_frames_* (tm_set_frames_rgb among them) and tm_open_input
+ * switch the source away.
  *   Planes on the encoder's own device (TM_MEM_DEVICE; the owner is asked of the runtime) are converted where they are.  Planes in host
  * memory or on another device of a group go through two staging buffers in chunks (TM_INPUT_CHUNK_FRAMES applies), straight from page-locked
  * memory, through the encoder's own page-locked buffers from pageable memory.
@@ -255,6 +256,42 @@ typedef struct {
  *   tm_probe_yuv_clip_host is the host-only seam: the same checks and the size tm_set_frames_yuv would describe (pointers may be NULL). */
 TM_API int tm_set_frames_yuv(tm_encoder *, const tm_yuv_clip *clip);
 TM_API int tm_probe_yuv_clip_host(const tm_yuv_clip *clip, double scaling, int *dst_width, int *dst_height);
+/* An RGB clip LENT in memory, as its producer leaves it (tm_rgb_in.hip): three pointers and one step describe every
+ * layout -- RGB24 (g = r + 1, b = r + 2, step 3), BGRA (b = base, g = base + 1, r = base + 2, step 4), RGB48 (step 6, words), gbrp (three
+ * planes, step 1), [N,3,H,W] (pointers one plane apart, frame = three planes), grey (r = g = b).  Alpha and padding bytes are never read as
+ * samples.
+ *   Sample: the sample of channel c at (f, y, x) is the byte or word at c + f frame + y row + x step; words become bytes by tm_yuv_clip's
+ * rule, bit for bit: U16_LOW p_d = word & (2^d - 1), U16_HIGH p_d = word >> (16 - d), then p = min(255, (p_d + 2^(d-9)) >> (d - 8)).
+ *   Pixel: the unscaled pixel is R << 16 | G << 8 | B, top byte 0.
+ *   Size: the video is Round(width Scaling) x Round(height Scaling), as tm_set_frames_yuv describes it.  At that size equal to the source's
+ * the clip is the unscaled pixels; otherwise every frame is TM_SCALE_LANCZOS3 of the unscaled frame, exactly as tm_scale_rgb32_host computes it.
+ * The struct is 88 bytes: r 0, g 8, b 16, step 24, row 32, frame 40, width 48, height 52, frames 56, fps 64, samples 72, depth 76, memory 80. */
+typedef struct {
+  const void *r, *g, *b;      /* the R, G, B sample of pixel (0, 0) of frame 0; may be equal (grey) */
+  int64_t step, row, frame;   /* bytes from a channel's sample to its right neighbour, to the row below, to the next frame; shared by the three channels */
+  int width, height, frames; double fps;
+  int samples, depth;         /* TM_SAMPLES_U8: depth 8.  TM_SAMPLES_U16_LOW / _HIGH: little-endian words, depth 9 .. 16 */
+  int memory;                 /* TM_MEM_HOST, TM_MEM_DEVICE */
+} tm_rgb_clip;
+/* tm_set_frames_yuv's twin in every respect but the samples: reads Scaling, describes the video, and makes the clip the frame source of the
+ * next tm_run(TM_STEP_LOAD).  StartFrame and FrameCount do not apply; the key frames follow the automatic rule.  The clip is BORROWED until
+ * that Load has returned; a second Load reads the encoder's own RGB32 clip again, one that needs a larger share of the frames is TM_E_INVAL
+ * -- lend the clip again.  tm_set_input_yuv plays no part.  tm_set_video, tm_push_frame_rgb32, tm_set_frames_* and tm_open_input switch the
+ * source away.  A clip on the encoder's own device is converted where it is; host memory and other devices go through the two staging
+ * buffers (TM_INPUT_CHUNK_FRAMES applies): an interleaved clip -- the three pointers within one step of the lowest -- as one plane from the
+ * lowest pointer, otherwise every distinct channel pointer as a plane of its own.
+ *   TM_E_INVAL, before anything is stored and before any device call: a null struct or channel; width or height outside 1 .. 65536;
+ * frames < 1; fps <= 0; an unknown samples or memory value; depth != 8 with U8 or outside 9 .. 16 with words; step < bytes per sample;
+ * row < (width - 1) step + bytes; a negative frame; an odd pointer, step or stride with words.  TM_MEM_DEVICE pointers that are not device
+ * memory are TM_E_INVAL at Load.  TM_E_UNSUPPORTED: a shrink beyond 8.  A refused call leaves the encoder as it was.
+ *   tm_probe_rgb_clip_host: the same checks and the size, with no device; pointers are only compared, never read.  tm_rgb_to_rgb32_host:
+ * the rule in plain loops on host memory -- frames [first_frame, +frame_count) unpacked, then scaled as tm_scale_rgb32_host scales them,
+ * into out [frame_count][dst_h][dst_w].  tm_stage_rgb_to_rgb32 (k_rgb_unpack / k_rgb_to_rgb32): the kernel alone on device pointers, every
+ * frame of the clip, on the current device, queued on `stream`; it returns after the launch at equal size and drains the stream otherwise. */
+TM_API int tm_set_frames_rgb(tm_encoder *, const tm_rgb_clip *clip);
+TM_API int tm_probe_rgb_clip_host(const tm_rgb_clip *clip, double scaling, int *dst_width, int *dst_height);
+TM_API int tm_rgb_to_rgb32_host(const tm_rgb_clip *clip, int first_frame, int frame_count, int dst_w, int dst_h, uint32_t *out);
+TM_API int tm_stage_rgb_to_rgb32(const tm_rgb_clip *clip, int dst_w, int dst_h, void *out_rgb32, void *stream);
 /* ---- Frames delivered as YUV (tm_yuv_out.hip): the mirror image of the above ----------------------------------------
  * A destination has tm_yuv_clip's field layout (same offsets, 120 bytes); its plane pointers are WRITTEN.  `frames` is its capacity, fps is
  * not read, v == NULL means u takes interleaved (U, V) pairs, memory is TM_MEM_HOST or TM_MEM_DEVICE (the device of the player / encoder).

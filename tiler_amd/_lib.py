@@ -30,6 +30,11 @@ class YuvClip(ctypes.Structure):  # tm_yuv_clip: a YUV clip lent in memory (tm_s
                 ("chroma", c_int), ("samples", c_int), ("depth", c_int), ("full_range", c_int), ("memory", c_int)]
 
 
+class RgbClip(ctypes.Structure):  # tm_rgb_clip: an RGB clip lent in memory (tm_set_frames_rgb; rgb_in.py describes arrays with it), 88 bytes
+    _fields_ = [("r", c_void_p), ("g", c_void_p), ("b", c_void_p), ("step", c_int64), ("row", c_int64), ("frame", c_int64),
+                ("width", c_int), ("height", c_int), ("frames", c_int), ("fps", c_double), ("samples", c_int), ("depth", c_int), ("memory", c_int)]
+
+
 class RenderViewDesc(ctypes.Structure):  # tm_render_view: Render's switches (32 bytes)
     _fields_ = [("page", ctypes.c_int32), ("predicted", ctypes.c_int32), ("mirrored", ctypes.c_int32), ("dithered", ctypes.c_int32),
                 ("use_gamma", ctypes.c_int32), ("palette_index", ctypes.c_int32), ("gamma", c_double)]
@@ -106,6 +111,9 @@ SIGNATURES = {
     "tm_yuv_out_matrix_host": (c_int, [c_int, ctypes.POINTER(ctypes.c_int32)]),
     "tm_rgb32_to_yuv_host": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tm_probe_yuv_clip_host": (c_int, [ctypes.POINTER(YuvClip), c_double, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "tm_probe_rgb_clip_host": (c_int, [ctypes.POINTER(RgbClip), c_double, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "tm_rgb_to_rgb32_host": (c_int, [ctypes.POINTER(RgbClip), c_int, c_int, c_int, c_int, c_void_p]),
+    "tm_stage_rgb_to_rgb32": (c_int, [ctypes.POINTER(RgbClip), c_int, c_int, c_void_p, c_void_p]),
     "tm_probe_input_host": (c_int, [c_char_p, c_int, c_int, c_double] + [ctypes.POINTER(c_int)] * 5 + [ctypes.POINTER(c_double)] + [ctypes.POINTER(c_int)] * 2),
     "tm_read_png_host": (c_int, [c_char_p, c_void_p, c_int64, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "tm_inflate_host": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),

@@ -55,7 +55,7 @@ struct Knobs {
   int topk_estimate = -1;  // TM_TOPK_ESTIMATE: the k-nearest search's first thresholds from a sample of the database: -1 by size, 0 never, 1 whenever possible
   double epu_table_gib = 6.0, comm_timeout_s = 120.0;
   long long knn_arena_entries = 0, dedup_radix_min = 1ll << 20;
-  int input_chunk_frames = 0;  // TM_INPUT_CHUNK_FRAMES: frames per chunk of Load's read of a Y4M file or of a lent YUV clip (0: 16 MB worth; tests: 1, so that small clips take many chunks)
+  int input_chunk_frames = 0;  // TM_INPUT_CHUNK_FRAMES: frames per chunk of Load's read of a Y4M file or of a lent YUV or RGB clip (0: 16 MB worth; tests: 1, so that small clips take many chunks)
   int recon_chunk_frames = 0;  // TM_RECON_CHUNK_FRAMES: frames per chunk of Reconstruct's query features (0: 8 GiB worth, 2 GiB with the extended palette usage; tests: small, so that a clip takes several chunks)
   bool player_no_worker = false;  // TM_PLAYER_NO_WORKER: the player decodes the next key frame on the calling thread, when the last one has been played
   int player_chunk_frames = 0;    // TM_PLAYER_CHUNK_FRAMES: frames per chunk of the player's record upload (0: 8 MB worth, at most 16)

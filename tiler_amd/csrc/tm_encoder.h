@@ -53,6 +53,7 @@ struct tm_encoder {
   InputInfo input;
   int input_yuv = TM_YUV_AUTO;
   InputTables input_tables;
+  ScaleTables rgb_in_tables;         // the same for an RGB clip lent at another size (tm_set_frames_rgb)
   PinnedBuf input_pinned[2];         // the two staging buffers of a Y4M file's chunks
   std::vector<uint32_t> input_clip;  // a PNG sequence, decoded on the host, until Load has uploaded it
   const void *frames_host = nullptr;  // the same in HOST memory (tm_set_frames_host): Load copies it over in chunks beside its own kernel

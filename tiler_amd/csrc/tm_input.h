@@ -14,11 +14,13 @@ namespace tmx {
 // ---- what the probe half of Load (tilingencoder.pas:1764-1820) finds out about InputFileName
 constexpr int INPUT_YUV_CLIP = 3;  // InputInfo::kind of a YUV clip lent in memory (tm_set_frames_yuv), beside TM_INPUT_Y4M / TM_INPUT_PNGS
 constexpr int INPUT_GTM = TM_INPUT_GTM;  // a .gtm stream: Load plays its frames into the device clip (tm_player.hip)
+constexpr int INPUT_RGB_CLIP = 5;  // an RGB clip lent in memory (tm_set_frames_rgb)
 struct InputInfo {
-  int kind = 0;  // 0: RGB32 frames from memory (pushed or lent); TM_INPUT_Y4M / TM_INPUT_PNGS: from the file; INPUT_YUV_CLIP: lent planes
+  int kind = 0;  // 0: RGB32 frames from memory (pushed or lent); TM_INPUT_Y4M / TM_INPUT_PNGS: from the file; INPUT_YUV_CLIP / INPUT_RGB_CLIP: a lent clip
   std::string name;
   tm_yuv_clip clip{};               // INPUT_YUV_CLIP: the descriptor as it was lent
-  bool lent = false;                // its planes are still borrowed: no Load has read them yet
+  tm_rgb_clip rgb_clip{};           // INPUT_RGB_CLIP: the same
+  bool lent = false;                // the clip's memory is still borrowed: no Load has read it yet
   int start = 0, frames = 0, src_w = 0, src_h = 0, dst_w = 0, dst_h = 0, chroma = 0, full_range = 0;
   double fps = 0;
   int64_t frame_bytes = 0;
@@ -97,6 +99,17 @@ struct SampleFmt {
   bool pairs = false;
   int bytes() const { return samples == TM_SAMPLES_U8 ? 1 : 2; }
 };
+// the deep-sample rule (tm_yuv_clip) as the kernels take it: p_d = (word >> rshift) & mask;  p = min(255, (p_d + half) >> nshift), half = 2^(nshift - 1)
+struct DeepRule { int rshift, mask, half, nshift; };
+inline DeepRule deep_rule_of(const SampleFmt &fmt) {
+  if (fmt.bytes() == 1) return DeepRule{0, 0xff, 0, 0};
+  const int d = fmt.depth;
+  return fmt.samples == TM_SAMPLES_U16_HIGH ? DeepRule{16 - d, 0xffff, 1 << (d - 9), d - 8} : DeepRule{0, (1 << d) - 1, 1 << (d - 9), d - 8};
+}
+__host__ __device__ __forceinline__ int narrow_word(int word, const DeepRule &d) {
+  const int pd = (word >> d.rshift) & d.mask, p = (pd + d.half) >> d.nshift;
+  return p < 255 ? p : 255;
+}
 // the checks of tm_set_frames_yuv and of the stage seam, with no device call; what they find out about the planes
 struct ClipPlanes {
   SampleFmt fmt;
@@ -117,5 +130,23 @@ int build_input_tables(int src_w, int src_h, int chroma, int dst_w, int dst_h, I
 int launch_yuv_to_rgb32(const InputTables &t, const void *y, const void *u, const void *v, const int64_t strides[6], const SampleFmt &fmt, int nframes, int yuv_mode,
                         void *out, hipStream_t stream);
 inline int resolve_yuv_mode(int mode, int full_range) { return mode == TM_YUV_AUTO ? (full_range ? TM_YUV_BT601_FULL : TM_YUV_BT601_LIMITED) : mode; }
+
+// ---- tm_rgb_in.hip: an RGB clip lent in memory (tm_rgb_clip) into RGB32 frames
+// The checks of tm_set_frames_rgb and of the stage seam, with no device call, and what they find out.  A clip is "interleaved" when its three
+// pointers lie within one step of the lowest and a row holds its last pixel whole: a pixel is then `span` bytes from the lowest pointer on,
+// fetched once for the three channels, and the clip stages as one plane of pixel_row_bytes per row.  Otherwise each channel is read sample
+// by sample, and each distinct pointer stages as a plane of sample_row_bytes per row.
+struct RgbPlan {
+  SampleFmt fmt;
+  bool interleaved = false;
+  const uint8_t *base = nullptr;   // the lowest of the three pointers
+  int64_t off[3] = {0, 0, 0};      // interleaved: R, G, B from base, in bytes
+  int span = 0;                    // interleaved: off's largest + bytes per sample
+  int64_t sample_row_bytes = 0, pixel_row_bytes = 0;  // (width - 1) step + bytes, + off's largest
+};
+int check_rgb_clip(const tm_rgb_clip *c, RgbPlan *out);
+// frames [0, nframes) of the clip as described (device pointers) into out [nframes][dst_h][dst_w]; tables: null at the source's size, else
+// prepared for (width, height) -> (dst_w, dst_h), TM_SCALE_LANCZOS3, and uploaded
+int launch_rgb_to_rgb32(const tm_rgb_clip &c, const RgbPlan &plan, const ScaleTables *tables, int nframes, int dst_w, int dst_h, void *out, hipStream_t stream);
 
 }  // namespace tmx

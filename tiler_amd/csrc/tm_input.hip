@@ -201,6 +201,100 @@ static int convert_yuv_clip(tm_encoder *e, int a, int b) {
   return convert_staged(e, a, b, src);
 }
 
+// frames [a, b) of the lent RGB clip into the encoder's device clip (convert_yuv_clip's twin)
+static int convert_rgb_clip(tm_encoder *e, int a, int b) {
+  const tm_rgb_clip &c = e->input.rgb_clip;
+  RgbPlan pl;
+  TM_TRY(check_rgb_clip(&c, &pl));
+  const ScaleTables *tables = nullptr;
+  if (e->width != c.width || e->height != c.height) {
+    TM_TRY(e->rgb_in_tables.prepare(c.width, c.height, e->width, e->height, TM_SCALE_LANCZOS3));
+    TM_TRY(e->rgb_in_tables.upload(e->stream));
+    tables = &e->rgb_in_tables;
+  }
+  uint8_t *const out = e->frames_owned.as<uint8_t>();
+  const size_t out_fb = (size_t)e->width * e->height * 4;
+  const uint8_t *const ptr[3] = {(const uint8_t *)c.r, (const uint8_t *)c.g, (const uint8_t *)c.b};
+  // the planes a chunk is staged as: the pixels from the lowest pointer on, or every distinct channel pointer; which plane a channel reads
+  int nplanes = 0, plane_of[3] = {0, 0, 0};
+  const uint8_t *plane[3] = {nullptr, nullptr, nullptr};
+  if (pl.interleaved) { plane[nplanes++] = pl.base; }
+  else
+    for (int i = 0; i < 3; i++) {
+      int j = 0;
+      while (j < nplanes && plane[j] != ptr[i]) j++;
+      if (j == nplanes) plane[nplanes++] = ptr[i];
+      plane_of[i] = j;
+    }
+  bool in_place = false;
+  if (c.memory == TM_MEM_DEVICE) {
+    for (int i = 0; i < nplanes; i++) {
+      hipPointerAttribute_t at;
+      TM_CHECK(hipPointerGetAttributes(&at, plane[i]) == hipSuccess && at.type == hipMemoryTypeDevice, TM_E_INVAL, "rgb clip: a channel pointer is not device memory");
+      if (i == 0) in_place = at.device == e->device;
+    }
+  }
+  if (in_place) {  // the clip is converted where it is
+    tm_rgb_clip part = c;
+    part.r = ptr[0] + c.frame * a; part.g = ptr[1] + c.frame * a; part.b = ptr[2] + c.frame * a;
+    RgbPlan pp = pl;
+    pp.base = pl.base + c.frame * a;
+    TM_TRY(launch_rgb_to_rgb32(part, pp, tables, b - a, e->width, e->height, out + out_fb * a, e->stream));
+    TM_HIP(hipStreamSynchronize(e->stream));  // the clip is the caller's again when Load returns
+    return TM_OK;
+  }
+  // Staged: a chunk holds nf frames of the first plane, then of the second, then of the third; steps and offsets stay as they are.
+  // Rows that are all but dense (alpha or padding bytes, at most 1/16 of the row) keep their stride: a frame -- a whole chunk, where the
+  // frames follow one another -- then travels as one linear copy from its first described byte to its last, and no byte behind that is
+  // read.  (As a 2-D copy of 5119 of every 5120 bytes the 720p x 300 BGRA clip took 2.2 s to stage instead of 21 ms.)  Other rows are packed.
+  const int64_t row_bytes = pl.interleaved ? pl.pixel_row_bytes : pl.sample_row_bytes;
+  const bool keep_rows = (c.row - row_bytes) * 16 <= c.row, keep_frames = keep_rows && c.frame == c.row * c.height;
+  const int64_t srow = keep_rows ? c.row : row_bytes, plane_bytes = srow * c.height, frame_bytes = srow * (c.height - 1) + row_bytes;  // frame_bytes: first to last described byte
+  bool pinned = c.memory == TM_MEM_DEVICE;  // (another device of the group: copied by the runtime as page-locked memory is)
+  if (!pinned) {
+    pinned = true;
+    for (int i = 0; i < nplanes; i++) pinned = pinned && is_page_locked(plane[i]);
+  }
+  StagedSource src;
+  src.fb = (size_t)(plane_bytes * nplanes);
+  if (pinned)
+    src.copy_in = [&](int f0, int nf, uint8_t *dst, hipStream_t stream) -> int {
+      for (int i = 0; i < nplanes; i++) {
+        uint8_t *to = dst + plane_bytes * nf * i;
+        const uint8_t *from = plane[i] + c.frame * f0;
+        if (keep_frames) TM_HIP(hipMemcpyAsync(to, from, (size_t)(plane_bytes * (nf - 1) + frame_bytes), hipMemcpyDefault, stream));
+        else if (keep_rows)
+          for (int f = 0; f < nf; f++) TM_HIP(hipMemcpyAsync(to + plane_bytes * f, from + c.frame * f, (size_t)frame_bytes, hipMemcpyDefault, stream));
+        else TM_TRY(copy_plane_async(to, from, c.row, c.frame, row_bytes, c.height, nf, stream));
+      }
+      return (int)TM_OK;
+    };
+  else
+    src.fill_host = [&](int f0, int nf, uint8_t *host) -> int {
+      return parallel_for(nf, [&](int f) -> int {
+        for (int i = 0; i < nplanes; i++) {
+          uint8_t *dst = host + plane_bytes * nf * i + plane_bytes * f;
+          const uint8_t *from = plane[i] + c.frame * (f0 + f);
+          if (keep_rows) memcpy(dst, from, (size_t)frame_bytes);
+          else
+            for (int r = 0; r < c.height; r++) memcpy(dst + row_bytes * r, from + c.row * r, (size_t)row_bytes);
+        }
+        return (int)TM_OK;
+      });
+    };
+  src.convert = [&](const uint8_t *base, int f0, int nf) -> int {
+    tm_rgb_clip part = c;
+    RgbPlan pp = pl;
+    const uint8_t *ch[3];
+    for (int i = 0; i < 3; i++) ch[i] = pl.interleaved ? base + pl.off[i] : base + plane_bytes * nf * plane_of[i];
+    part.r = ch[0]; part.g = ch[1]; part.b = ch[2];
+    part.row = srow; part.frame = plane_bytes; part.frames = nf; part.memory = TM_MEM_DEVICE;
+    pp.base = base;
+    return launch_rgb_to_rgb32(part, pp, tables, nf, e->width, e->height, out + out_fb * f0, e->stream);
+  };
+  return convert_staged(e, a, b, src);
+}
+
 // the PNG sequence, decoded on the host into a clip the encoder keeps until Load's chunked host-clip upload has taken it
 static int decode_pngs(tm_encoder *e) {
   InputInfo &in = e->input;
@@ -247,8 +341,11 @@ int load_from_input(tm_encoder *e) {
     a = std::max<int64_t>(a - 1, 0);
   }
   const int mode = resolve_yuv_mode(e->input_yuv, in.full_range);
-  if (in.decoded && e->frames == e->frames_owned.p && e->frames_owned.p && in.dec_first <= a && b <= in.dec_first + in.dec_count && in.dec_mode == mode) return TM_OK;
-  const bool lent_clip = in.kind == INPUT_YUV_CLIP;
+  const bool rgb_clip = in.kind == INPUT_RGB_CLIP;  // (no YUV rule takes part in its conversion: dec_mode is not compared)
+  if (in.decoded && e->frames == e->frames_owned.p && e->frames_owned.p && in.dec_first <= a && b <= in.dec_first + in.dec_count && (rgb_clip || in.dec_mode == mode))
+    return TM_OK;
+  const bool lent_clip = in.kind == INPUT_YUV_CLIP || rgb_clip;
+  TM_CHECK(!rgb_clip || in.lent, TM_E_INVAL, "the RGB clip was given back when the last Load returned: lend the clip again (tm_set_frames_rgb) for more frames");
   TM_CHECK(!lent_clip || in.lent, TM_E_INVAL,
            "the YUV planes were given back when the last Load returned: lend the clip again (tm_set_frames_yuv) to convert it with another InputYUV or for more frames");
   TM_HIP(hipStreamSynchronize(e->stream));  // the destination may have been handed out by the pool a moment ago
@@ -257,7 +354,7 @@ int load_from_input(tm_encoder *e) {
   e->frames_host = nullptr;
   e->hclip_cur = -1;
   in.decoded = false;
-  if (b > a) TM_TRY(lent_clip ? convert_yuv_clip(e, (int)a, (int)b) : in.kind == INPUT_GTM ? play_gtm(e, (int)a, (int)b) : decode_y4m(e, (int)a, (int)b));
+  if (b > a) TM_TRY(rgb_clip ? convert_rgb_clip(e, (int)a, (int)b) : lent_clip ? convert_yuv_clip(e, (int)a, (int)b) : in.kind == INPUT_GTM ? play_gtm(e, (int)a, (int)b) : decode_y4m(e, (int)a, (int)b));
   in.lent = false;  // (a lent clip is borrowed until this Load has returned: from here on the encoder reads its own RGB32 clip)
   in.decoded = true; in.dec_first = (int)a; in.dec_count = (int)(b - a); in.dec_mode = mode;
   return TM_OK;
@@ -289,6 +386,24 @@ int tm_set_frames_yuv(tm_encoder *e, const tm_yuv_clip *clip) {  // what tm_open
   in.lent = true;
   in.frames = clip->frames; in.src_w = clip->width; in.src_h = clip->height; in.dst_w = dw; in.dst_h = dh;
   in.chroma = clip->chroma; in.full_range = clip->full_range ? 1 : 0; in.fps = clip->fps;
+  e->input = std::move(in);
+  e->input_clip.clear();
+  return TM_OK;
+}
+
+int tm_set_frames_rgb(tm_encoder *e, const tm_rgb_clip *clip) {  // tm_set_frames_yuv's twin
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_TRY(check_rgb_clip(clip, nullptr));
+  int dw = 0, dh = 0;
+  TM_TRY(scaled_size(clip->width, clip->height, e->s.Scaling, &dw, &dh));
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_set_frames_rgb(s, clip); });  // every shard converts what its Load reads
+  TM_TRY(tm_set_video(e, dw, dh, clip->fps, clip->frames));
+  InputInfo in;
+  in.kind = INPUT_RGB_CLIP;
+  in.rgb_clip = *clip;
+  in.lent = true;
+  in.frames = clip->frames; in.src_w = clip->width; in.src_h = clip->height; in.dst_w = dw; in.dst_h = dh;
+  in.chroma = TM_CHROMA_444; in.fps = clip->fps;
   e->input = std::move(in);
   e->input_clip.clear();
   return TM_OK;

@@ -180,6 +180,7 @@ int upload_axis_tables(const AxisTable *const *axes, int naxes, int th, int max_
 int probe_scale(int src_w, int src_h, int dst_w, int dst_h, int filter);
 int check_scale_args(const void *src, int64_t src_stride_px, int64_t src_frame_px, int nframes, int src_w, int src_h, const void *dst, int64_t dst_stride_px,
                      int64_t dst_frame_px, int dst_w, int dst_h, int filter);
+constexpr int SC_TW = 64, SC_HROWS = 80;  // a Lanczos workgroup's tile width, and the most source rows its tile may reach (ScaleTables::th is chosen for it)
 struct ScaleTables {  // the tables of one (source size, output size, filter), kept until another is asked for
   int src_w = 0, src_h = 0, dst_w = 0, dst_h = 0, filter = 0, th = 0;  // th: output rows per workgroup
   bool ready = false, on_device = false;

@@ -14,7 +14,7 @@ namespace tmx {
 // is fetched once and feeds the three channels' sums.  Then every lane runs the vertical pass for four neighbouring pixels of one row out of
 // LDS, for the three channels at once, and stores them as 16 bytes.  Nothing goes to HBM between the passes.  The host picks th so that the
 // rows a tile reaches fit SC_HROWS (resample_tile_rows); 3 x 80 x 64 x 4 bytes = 60 KB of LDS, two workgroups to a CU.
-constexpr int SC_TW = 64, SC_HROWS = 80;
+// (SC_TW = 64, SC_HROWS = 80: tm_internal.h, beside the tables that are sized for them; tm_rgb_in.hip's kernel shares both)
 struct ScaleGeom { int64_t src_row, src_frame, dst_row, dst_frame; int src_w, src_h, dst_w, dst_h, th, vec_ok; };  // strides in pixels
 
 __device__ __forceinline__ int sc_clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }

@@ -32,15 +32,11 @@ int chroma_geom(int chroma, int w, int h, ChromaGeom *g) {
 constexpr int IN_TW = 64, IN_HROWS = 96;
 static_assert(RESAMPLE_TH_MAX * 16 == 256, "a workgroup's 256 lanes: 16 per output row of the tile");
 struct PlaneSrc { const uint8_t *p; int64_t row, frame; };  // strides in bytes
-struct DeepRule { int rshift, mask, half, nshift; };  // p_d = (word >> rshift) & mask;  p = min(255, (p_d + half) >> nshift), half = 2^(nshift - 1)
 
 template <int BYTES>
 __device__ __forceinline__ int fetch_sample(const uint8_t *at, const DeepRule &d) {
   if constexpr (BYTES == 1) return (int)*at;
-  else {
-    const int pd = ((int)*reinterpret_cast<const uint16_t *>(at) >> d.rshift) & d.mask;
-    return min(255, (pd + d.half) >> d.nshift);
-  }
+  else return narrow_word((int)*reinterpret_cast<const uint16_t *>(at), d);
 }
 
 __device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
@@ -180,11 +176,7 @@ int launch_yuv_to_rgb32(const InputTables &t, const void *y, const void *u, cons
   const bool has_c = t.chroma != TM_CHROMA_MONO, pairs = has_c && fmt.pairs;
   const PlaneSrc sy{(const uint8_t *)y, strides[0], strides[1]}, su{has_c ? (const uint8_t *)u : nullptr, strides[2], strides[3]},
       sv{has_c ? (pairs ? (const uint8_t *)u + fmt.bytes() : (const uint8_t *)v) : nullptr, strides[pairs ? 2 : 4], strides[pairs ? 3 : 5]};
-  DeepRule deep{0, 0xff, 0, 0};
-  if (fmt.bytes() == 2) {
-    const int d = fmt.depth;
-    deep = fmt.samples == TM_SAMPLES_U16_HIGH ? DeepRule{16 - d, 0xffff, 1 << (d - 9), d - 8} : DeepRule{0, (1 << d) - 1, 1 << (d - 9), d - 8};
-  }
+  const DeepRule deep = deep_rule_of(fmt);
   const int vec_ok = (t.dst_w % 4 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
   const dim3 grid((unsigned)((t.dst_w + IN_TW - 1) / IN_TW), (unsigned)((t.dst_h + t.th - 1) / t.th), (unsigned)nframes);
   TM_CHECK(grid.y <= 65535 && grid.z <= 65535, TM_E_UNSUPPORTED, "yuv_to_rgb32: %d rows x %d frames in one launch", t.dst_h, nframes);

@@ -10,7 +10,7 @@ import enum
 
 import numpy as np
 
-from ._lib import lib, check, TileMotionError, YuvClip, RenderViewDesc, c_void_p, c_int, c_int64, c_double, c_char_p
+from ._lib import lib, check, TileMotionError, YuvClip, RgbClip, RenderViewDesc, c_void_p, c_int, c_int64, c_double, c_char_p
 
 
 class TEncoderStep(enum.IntEnum):  # tilingencoder.pas:18
@@ -82,6 +82,7 @@ _ENC_SIGS = {
     "tm_set_frames_host": (c_int, [c_void_p, c_void_p]),
     "tm_prefetch_frames_host": (c_int, [c_void_p, c_void_p]),
     "tm_set_frames_yuv": (c_int, [c_void_p, ctypes.POINTER(YuvClip)]),
+    "tm_set_frames_rgb": (c_int, [c_void_p, ctypes.POINTER(RgbClip)]),
     "tm_open_input": (c_int, [c_void_p]),
     "tm_get_video": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_double), ctypes.POINTER(c_int)]),
     "tm_set_input_yuv": (c_int, [c_void_p, c_int]),
@@ -281,6 +282,19 @@ class TilingEncoder:
         self._yuv_ref = given
         return self.VideoInfo()
 
+    def SetFramesRGB(self, frames, layout="rgb24", *, fps, depth=None, samples=None):
+        """An RGB clip lent in memory as its producer leaves it (tm_set_frames_rgb): SetFramesYUV's twin for RGB sources.  frames: a numpy
+        array or a torch tensor (CPU tensors are lent as host memory, cuda tensors as device memory); layout: rgb24, bgr24, rgba, bgra, argb,
+        abgr ([N,H,W,C] uint8), rgb48, bgr48, rgba64, bgra64 ([N,H,W,C] uint16), rgbp ([N,3,H,W] in R, G, B order), gbrp (the same shape in
+        G, B, R order; both uint8, or uint16 with depth), gray ([N,H,W]).  Step, row and frame are the array's own strides, so sliced and
+        padded views work; depth: bits per 16-bit sample (default 16; samples: TSamples, default u16Low).  Scaling applies as for a file.
+        The array is borrowed (and kept alive here) until the Run that loads it has returned.  Returns VideoInfo()."""
+        from . import rgb_in
+        clip = rgb_in.describe(frames, layout, depth, samples, fps)
+        check(self._L.tm_set_frames_rgb(c_void_p(self._h), ctypes.byref(clip)))
+        self._yuv_ref = [frames]
+        return self.VideoInfo()
+
     def SaveSettings(self, path):
         self._L.tm_save_settings_ini.restype = c_int
         self._L.tm_save_settings_ini.argtypes = [c_void_p, c_char_p]
@@ -296,7 +310,7 @@ class TilingEncoder:
     def Run(self, step=TEncoderStep.esAll):
         check(self._L.tm_run(c_void_p(self._h), int(step)))
         if int(step) in (TEncoderStep.esAll, TEncoderStep.esLoad):
-            self._yuv_ref = None  # planes lent with SetFramesYUV are the caller's again once Load has returned
+            self._yuv_ref = None  # a clip lent with SetFramesYUV / SetFramesRGB is the caller's again once Load has returned
 
     # -- read-back
     def counts(self):

@@ -79,6 +79,23 @@ def scale_rgb32(frames, size, filter="lanczos", out=None):
     return out
 
 
+def rgb_to_rgb32(frames, layout="rgb24", size=None, depth=None, out=None, samples=None):
+    """An RGB clip in device memory -> RGB32 frames (tm_stage_rgb_to_rgb32, the kernels behind SetFramesRGB's Load): frames and layout as
+    SetFramesRGB takes them (a CUDA tensor; strides are its own); size (width, height): the output's, default the clip's (a pure unpack;
+    otherwise the Lanczos-3 rule of scale_rgb32 on the unpacked pixels).  out: a contiguous int32 CUDA tensor [N][height][width] to fill
+    -> int32 [N][height][width] 0x00RRGGBB"""
+    from . import rgb_in
+    assert frames.is_cuda
+    clip = rgb_in.describe(frames, layout, depth, samples)
+    dw, dh = (clip.width, clip.height) if size is None else (int(size[0]), int(size[1]))
+    if out is None:
+        out = torch.empty((clip.frames, max(dh, 0), max(dw, 0)), dtype=torch.int32, device=frames.device)
+    if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (clip.frames, dh, dw)):
+        raise ValueError("rgb_to_rgb32: out must be a contiguous int32 CUDA tensor of %d frames of %d x %d" % (clip.frames, dw, dh))
+    check(lib().tm_stage_rgb_to_rgb32(ctypes.byref(clip), dw, dh, _p(out), _stream()))
+    return out
+
+
 def rgb32_to_yuv(rgb, layout="nv12", yuv="auto", out=None, width=None):
     """RGB32 frames -> YUV planes (tm_stage_rgb32_to_yuv_fmt, the kernel behind GtmPlayer.ReadYUV): rgb int32 [F][H][W'] 0x00RRGGBB with a
     dense last axis, of which `width` columns (default: all) are converted; layout and yuv as ReadYUV takes them (auto = bt601-limited).

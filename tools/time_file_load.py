@@ -1,13 +1,15 @@
 """Wall time of Load from a Y4M file against Load of the same clip as RGB32 in page-locked host memory, and of the same clip lent as YUV planes.
 
-    python tools/time_file_load.py [--mode file|host|both|yuv|all] [--frames 300 --width 1280 --height 720] [--scaling 1.0] [--passes 7] [--dir /dev/shm]
+    python tools/time_file_load.py [--mode file|host|both|yuv|rgb|all] [--frames 300 --width 1280 --height 720] [--scaling 1.0] [--passes 7] [--dir /dev/shm]
 
 The clip is bench.py's (SURVEY.md 8d's generator).  `file`: it is written as a 4:2:0 Y4M into --dir (memory-backed by default, so that the
 figure is the pipeline's and not a disk's) and every pass is OpenInput + Run(esLoad).  `host`: the RGB32 clip sits in pinned memory and every
 pass is SetFramesHost + Run(esLoad) -- the path a caller had before Load could read a file; it uses no call newer than that, so the same
 script times an older build of the library.  `yuv` (`all`: every leg): the planes are lent with SetFramesYUV and every pass is SetFramesYUV +
 Run(esLoad) -- (d) planar 4:2:0 in page-locked host memory, (e) NV12 in device memory, (f) P010 in device memory (the bytes in the high
-bits of 10-bit samples).  One warm-up pass, then the median of --passes passes with their spread; one JSON line."""
+bits of 10-bit samples).  `rgb` (and `all`): the clip is lent with SetFramesRGB and every pass is SetFramesRGB + Run(esLoad) -- rgb24 and bgra in
+page-locked host memory, rgb24 and gbrp 10-bit in device memory, rgb24 in device memory at Scaling 0.5; the device legs also time the
+conversion alone (stages.rgb_to_rgb32) between two events.  One warm-up pass, then the median of --passes passes with their spread; one JSON line."""
 import argparse
 import json
 import os
@@ -38,7 +40,7 @@ def stats(ms):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["file", "host", "both", "yuv", "all"], default="both")
+    ap.add_argument("--mode", choices=["file", "host", "both", "yuv", "rgb", "all"], default="both")
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=720)
@@ -93,6 +95,43 @@ def main():
                 ms.append((time.perf_counter() - t0) * 1e3)
             enc.close()
             out[name] = dict(stats(ms[1:]), video=info)
+
+    if args.mode in ("rgb", "all"):
+        from tiler_amd import stages
+        px = torch.from_numpy(clip.view(np.uint8).reshape(F, H, W, 4))  # little-endian 0xAARRGGBB: bytes B, G, R, A
+        rgb24 = torch.empty((F, H, W, 3), dtype=torch.uint8, pin_memory=True)
+        rgb24.copy_(px[..., [2, 1, 0]])
+        bgra = host.view(torch.uint8).view(F, H, W, 4)  # (the yardstick's own memory, lent as it lies)
+        rgb24_dev = rgb24.cuda()
+        gbrp10 = (rgb24_dev.permute(0, 3, 1, 2)[:, [1, 2, 0]].to(torch.int16) << 2).contiguous()  # the bytes in 10-bit samples, low bits of the word
+        legs = (("load_rgb24_host_pinned", rgb24, "rgb24", None, args.scaling), ("load_bgra_host_pinned", bgra, "bgra", None, args.scaling),
+                ("load_rgb24_device", rgb24_dev, "rgb24", None, args.scaling), ("load_gbrp10_device", gbrp10, "gbrp", 10, args.scaling),
+                ("load_rgb24_device_half", rgb24_dev, "rgb24", None, 0.5))
+        for name, lent, layout, depth, scaling in legs:
+            enc = TilingEncoder()
+            enc.LoadDefaultSettings()
+            enc.Scaling = scaling
+            ms = []
+            for p in range(args.passes + 1):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                info = enc.SetFramesRGB(lent, layout, fps=24.0, depth=depth)
+                enc.Run(S.esLoad)
+                ms.append((time.perf_counter() - t0) * 1e3)
+            enc.close()
+            out[name] = dict(stats(ms[1:]), video=info)
+            if lent.is_cuda:  # the conversion alone, between two events on the stream (the tables of a scaled pass are made inside: see kernel_ms of a trace)
+                size, kms = (info["width"], info["height"]), []
+                dst = torch.empty((F, size[1], size[0]), dtype=torch.int32, device="cuda")
+                for p in range(args.passes + 1):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    stages.rgb_to_rgb32(lent, layout, size=size, depth=depth, out=dst)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    kms.append(e0.elapsed_time(e1))
+                out[name]["convert_events"] = stats(kms[1:])
+                del dst
 
     if args.mode in ("file", "both", "all"):
         path = os.path.join(args.dir, "time_file_load_%d.y4m" % os.getpid())
