@@ -1218,19 +1218,35 @@ def _kmodes_rows(case, rng):
         return np.tile(rng.integers(0, 8, size=(1, 80)), (2500, 1)).astype(np.uint8), 5, 8
     if case == "few-points":  # fewer points than clusters: the farthest-first pick runs out of unused points
         return rng.integers(0, 4, size=(3, 80)).astype(np.uint8), 6, 4
+    if case == "many-owned":  # more clusters than owners (64): owners 0 and 1 hold three clusters each, the rest two; exactly three bins
+        return rng.integers(0, 16, size=(2880, 80)).astype(np.uint8), 130, 16
+    if case == "handover":
+        # Two clusters, five whole bins.  From point 0 the rows N of bin 1 start in P's cluster (55 differing bytes against 65 to R) and are
+        # nearer R (65) than M (80) once the initial modes stand: all of bin 1 moves in the first iteration, and with two clusters
+        # every move concerns both owners, so each stages more moves than its row buffer holds at once (768) and stages a second time.
+        # (The oracle, counting per bin, with this seed: 960 moves in bin 1 of iteration 1 for num_init 0 and 3, none from point 7.)
+        a = np.arange(80)
+        P, M, R = np.where(a < 40, 1, 4), np.full(80, 1), np.full(80, 2)
+        N = np.where(a < 40, 5, np.where(a < 65, 4, 2))
+        rows = np.concatenate([np.tile(M, (960, 1)), np.tile(N, (960, 1)), np.tile(R, (960, 1)), np.tile(M, (960, 1)), np.tile(R, (960, 1))])
+        noise = rng.random(rows.shape) < 0.03
+        rows[noise] = rng.integers(0, 8, size=int(noise.sum()))
+        rows[0] = P
+        return rows.astype(np.uint8), 2, 8
     raise ValueError(case)
 
 
 @pytest.mark.parametrize("path", ["fast-leg", "fast-leg-always", "binwise"])
 @pytest.mark.parametrize("num_init", [0, -7, 3])
-@pytest.mark.parametrize("case", ["clusters", "uniform", "identical", "few-points"])
+@pytest.mark.parametrize("case", ["clusters", "uniform", "identical", "few-points", "many-owned", "handover"])
 def test_kmodes(oracle, case, num_init, path, monkeypatch):
     """A17: TKModes.ComputeKModes (kmodes.pas:923-1094) -- labels, modes, cost and the best run's iteration count equal the oracle's
     restatement on structured, structureless and degenerate inputs, from point 0, from point 7 and over three spread starting points;
     with the later iterations' fast leg (all remaining points scored at once, the bins walked by one launch until a mode changes: it
     runs to the end on "clusters", stops at once on "uniform" and hands over to the bin-by-bin launches in the middle of the iteration when
     TM_KMODES_FAST_ALWAYS has it tried there, meets the empty-cluster repairs on "identical") and with every iteration bin by bin
-    (TM_KMODES_BINWISE)"""
+    (TM_KMODES_BINWISE).  "many-owned" has owners that hold two and three clusters each; in "handover" a whole bin moves at once, so every
+    owner stages its moves' rows in two passes"""
     from tiler_amd import stages
     monkeypatch.delenv("TM_KMODES_BINWISE", raising=False)
     monkeypatch.delenv("TM_KMODES_FAST_ALWAYS", raising=False)

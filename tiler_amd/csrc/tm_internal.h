@@ -255,7 +255,7 @@ int run_dl3quant(const void *dev_rgb, int64_t npixels, int quant_to, int lookup_
 struct KmeansRunStats { int resident = 0 /* the last k-means of all ran in a resident launch to its end */; int tile_iters = 0; int64_t tile_points = 0; int pixel_iters = 0; int64_t pixel_colours = 0, pixels = 0, pixel_colour_iters = 0; };
 KmeansRunStats &kmeans_run_stats();
 
-// tm_kmodes.hip: A17, TKModes.ComputeKModes (kmodes.pas:923-1094); host pointers
+// tm_kmodes.hip (the driver of tm_kmodes_init.hip and tm_kmodes_iter.hip): A17, TKModes.ComputeKModes (kmodes.pas:923-1094); host pointers
 int run_kmodes(const uint8_t *rows, int64_t n, int k, int num_init, int nmod, int max_iter, int32_t *labels_out, uint8_t *cent_out, uint64_t *cost_out,
                int *iters_out, hipStream_t stream);
 

@@ -12,7 +12,7 @@ pids=(); objs=()
 for src in "$HERE"/*.hip; do
   obj="$OBJ/$(basename "${src%.hip}").o"; objs+=("$obj")
   case "$(basename "$src")" in
-    tm_knn*.hip|tm_kmeans*.hip|tm_palettize.hip|tm_load.hip|tm_features*.hip|tm_window_dcts.hip|tm_kmodes.hip) $HIPCC $FLAGS -c "$src" -o "$obj" & pids+=($!) ;;
+    tm_knn*.hip|tm_kmeans*.hip|tm_palettize.hip|tm_load.hip|tm_features*.hip|tm_window_dcts.hip|tm_kmodes*.hip) $HIPCC $FLAGS -c "$src" -o "$obj" & pids+=($!) ;;
     *) cp "$HERE/.obj/$(basename "${src%.hip}").o" "$obj" ;;   # unaffected by the shape macros (TM_LT_BATCH lives in tm_load.hip)
   esac
 done

@@ -22,7 +22,9 @@ def kernels(src):
         desc = dict(re.findall(r"\.amdhsa_(\w+) (\d+)", m.group(2)))
         begin = lines.index(name + ":")
         end = next(i for i in range(begin, len(lines)) if lines[i].startswith(".Lfunc_end"))
-        body = "\n".join(l for l in lines[begin + 1:end] if l.strip())
+        # (the kernel's own name, which its descriptor and section lines repeat, stays out of the hash: a parameter type that moves to
+        # another namespace renames the kernel and nothing else)
+        body = "\n".join(l.replace(name, "<kernel>") for l in lines[begin + 1:end] if l.strip())
         yield name, [desc[f] for f in FIELDS] + [str(body.count("\n") + 1), hashlib.sha256(body.encode()).hexdigest()[:16]]
 
 
