@@ -50,6 +50,8 @@
  *                           compare the two forms)
  *   TM_KM_LAUNCHES          the tile -> palette k-means runs its skipping iterations as three launches each instead of one resident launch
  *                           for all of them (tests compare the two)
+ *   TM_KM_FIRST_LOOK=0      the plain iterations of the tile -> palette k-means score every point with the double-precision chain -- without
+ *                           the single-precision first look that leaves the chain to the points it cannot decide (A/B runs; tests compare the two)
  *   TM_KMODES_BINWISE       every k-modes iteration bin by bin (two launches per 960 points) -- without the leg that scores all remaining points
  *                           at once and walks the bins in one launch for as long as no mode changes (tests compare the two);
  *                           TM_KMODES_FAST_ALWAYS: that leg is tried in every iteration after the first, also behind an iteration that moved many
@@ -790,6 +792,10 @@ TM_API int tm_stage_pp_seeds(const void *feat_i32, const void *use /* may be NUL
  * resident launch to its end (k_h_resident, k_kmeans3_persistent), 0 when it took one launch per step -- by shape, by TM_KM_LAUNCHES, or
  * because a barrier of the resident launch gave up and the clustering was repeated (tests tell the two apart with it). */
 TM_API int tm_kmeans_last_resident(void);
+/* The first look of the calling thread's last tile k-means (D = 192; tm_stage_kmeans*, or the one inside tm_stage_palettize): how many
+ * point-scorings (a point against all its centroids, once per plain iteration) were looked at in single precision, and how many of those
+ * the look could not decide and handed to the double-precision chain.  Both 0 under TM_KM_FIRST_LOOK=0.  Either pointer may be NULL. */
+TM_API void tm_kmeans_last_first_look(int64_t *looked, int64_t *exact);
 
 /* A17: TKModes.ComputeKModes (kmodes.pas:923-1094; unreachable in the reference snapshot, named by the north star): k-modes on rows
  * of cKModesFeatureCount = 80 bytes (kmodes.pas:15; the reference's asm hard-codes 80, :338-342), dissimilarity = sum |a-b| + 2048 per

@@ -91,6 +91,7 @@ SIGNATURES = {
     "tm_stage_quantize_palettes": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
     "tm_stage_palettize": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "tm_kmeans_last_resident": (c_int, []),
+    "tm_kmeans_last_first_look": (None, [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     "tm_stage_pp_seeds": (c_int, [c_void_p, c_void_p, c_int64, c_int, ctypes.POINTER(c_int64), ctypes.POINTER(c_int), c_void_p]),
     "tm_stage_kmodes": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(c_int), c_void_p]),
     "tm_stage_dither": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

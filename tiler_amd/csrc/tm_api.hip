@@ -190,6 +190,10 @@ int tm_stage_palettize(const void *feat_i32, const void *use, int64_t n, int npa
 }
 
 int tm_kmeans_last_resident(void) { return kmeans_run_stats().resident; }
+void tm_kmeans_last_first_look(int64_t *looked, int64_t *exact) {
+  if (looked) *looked = kmeans_run_stats().look_scored;
+  if (exact) *exact = kmeans_run_stats().look_exact;
+}
 
 int tm_stage_pp_seeds(const void *feat_i32, const void *use, int64_t n, int k, int64_t *out_seeds_host, int *out_kk, void *stream) {
   knobs_reload();

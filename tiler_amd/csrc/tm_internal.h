@@ -252,7 +252,7 @@ int reduce_select_candidates(const void *keys, int64_t n, int64_t target, void *
 // tm_dl3.hip: dl3quant on device pointers (blocking)
 int run_dl3quant(const void *dev_rgb, int64_t npixels, int quant_to, int lookup_bpc, void *dev_pal, int *out_colors, hipStream_t stream);
 // what the calling thread's last tile -> palette clustering and last colour quantisation ran through (tm_get_kmeans_iters)
-struct KmeansRunStats { int resident = 0 /* the last k-means of all ran in a resident launch to its end */; int tile_iters = 0; int64_t tile_points = 0; int pixel_iters = 0; int64_t pixel_colours = 0, pixels = 0, pixel_colour_iters = 0; };
+struct KmeansRunStats { int resident = 0 /* the last k-means of all ran in a resident launch to its end */; int tile_iters = 0; int64_t tile_points = 0; int pixel_iters = 0; int64_t pixel_colours = 0, pixels = 0, pixel_colour_iters = 0; int64_t look_scored = 0, look_exact = 0 /* the last D = 192 clustering's first look: point-scorings looked at, and those of them the double-precision chain settled */; };
 KmeansRunStats &kmeans_run_stats();
 
 // tm_kmodes.hip (the driver of tm_kmodes_init.hip and tm_kmodes_iter.hip): A17, TKModes.ComputeKModes (kmodes.pas:923-1094); host pointers

@@ -122,11 +122,37 @@ int kmeans3_persistent(const int32_t *pts, const uint32_t *w, const std::vector<
 // ---- tm_kmeans_tile.hip: D = 192 --------------------------------------------------------------------------------------------------
 void launch_chunk_major(const int32_t *pts, int64_t n, int32_t *out, hipStream_t stream);  // [n][192] -> [24][n][8]
 
+// ---- the first look of the plain iterations: decide in single precision, the double-precision chain only where in doubt ----------------
+// The assignment step needs the DECISIONS of the reference's 192-term double-precision chains, not their values.  Per point p (an int32
+// row) and centroid c (doubles), with c^ the Single nearest to c in every coordinate:
+//   s(c)  = the Single sum over the dimensions of (float(p_j) - c^_j)^2: one subtraction and one fused multiply-add per term, in any
+//           order and any number of partial sums.  Its terms are non-negative, so its relative error against the exact sum over (p_j - c^_j)^2
+//           is below (2 + 192) * 2^-24 = 194 * 2^-24 when every float(p_j) is exact; the Single root adds 2^-24 and halves the rest.
+//           FL_GAMMA = 2^-16 is taken as the bound on the ROOT's relative error, more than twice what it needs.
+//   E(c)  = FL_CENT * |c| = 2^-23 |c| >= |c^ - c| (rounding a coordinate to Single moves it by at most 2^-24 of itself; no centroid of
+//           integer rows leaves Single's normal range: a quotient of an int64 sum and a count, zero or at least 2^-64 in magnitude),
+//           computed in double and rounded up.  By the triangle inequality | |p - c^| - |p - c| | <= E(c).
+// The true distance d(c) therefore lies in [lo(c), hi(c)] = [sqrt(s(c)) (1 - FL_GAMMA) - E(c), sqrt(s(c)) (1 + FL_GAMMA) + E(c)].
+// With c* the Single argmin, a point is DECIDED iff lo(c) (1 - FL_ETA) > hi(c*) (1 + FL_ETA) for every other c: the reference's computed
+// squared distances (within 1e-13 of the true ones) are then strictly ordered the same way, no tie can occur, c* is the reference's
+// answer.  Otherwise, or when some |p_j| >= 2^24 (its conversion may round), the point is IN DOUBT and goes through the chain itself:
+// double, terms in order, ties to the lowest index, against all its centroids (those that are no contenders lie strictly behind c*, so
+// scoring them as well changes nothing).
+// Bounds for the skipping iterations: ub = hi(c*), lb = the smallest lo(c) among the others, each moved outwards by FL_ETA; the exact
+// roots with k_assign192's own margins where the chain ran.
+constexpr double FL_GAMMA = 1.0 / 65536.0;    // 2^-16
+constexpr double FL_CENT = 1.0 / 8388608.0;   // 2^-23
+constexpr double FL_ETA = 1e-9;                // the margin of the comparison, the one of the skip test (H_ETA)
+constexpr float FL_INT_EXACT = 16777216.0f;    // 2^24: below it int32 -> Single is exact
+
 // k_assign192's launch: slices of the largest segment sized so that one round of workgroups fills the chip evenly
 struct Assign192Shape { int ppt, nblk, rows, lds_delta; size_t lds; };
 Assign192Shape assign192_shape(int64_t maxcount, int nseg, int k, int cus);
+// look_stats: two counters on the device (point-scorings looked at, those that went to the chain) the launch adds to, or null; the first
+// look itself is taken unless TM_KM_FIRST_LOOK=0
 void launch_assign192(const Assign192Shape &sh, int nseg, hipStream_t stream, const int32_t *pts, const int32_t *ptsc, int64_t ntot, const uint32_t *w, Seg *ds,
-                      int k, const double *cent, int32_t *assign, u64 *sums, u64 *cnts, const int *quiet, double *ub = nullptr, double *lb = nullptr);
+                      int k, const double *cent, int32_t *assign, u64 *sums, u64 *cnts, const int *quiet, double *ub = nullptr, double *lb = nullptr,
+                      u64 *look_stats = nullptr);
 
 // Would one segment of n points and k centroids go through k_h_resident on a device of `cus` compute units?  rounds == 0: no.
 struct ResidentPlan { int grid, rounds; size_t lds; };
@@ -145,6 +171,7 @@ struct TileRun {
   int32_t *assign;
   u64 *sums, *cnts;
   int *quiet;
+  u64 *look = nullptr;  // the first look's two counters (launch_assign192)
   Assign192Shape a192;
   hipStream_t stream;
   // the skipping iterations' own state (tile_skip_setup)

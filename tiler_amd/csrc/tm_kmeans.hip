@@ -398,7 +398,7 @@ struct KmRun {  // one clustering from its seeds: what the steps below share
   std::vector<Seg> hs;
   int nblk;     // workgroups of the 1-D grids over all segments
   bool skipping;
-  DevBuf dsegs, mind, partial, sums, cnts, ptsc, quiet;
+  DevBuf dsegs, mind, partial, sums, cnts, ptsc, quiet, look;
 };
 
 // the segments' table, zeroed sums, the initial centres (the caller's or farthest-first picks) and, for D = 192, what the tile kernels need
@@ -468,6 +468,9 @@ static int km_setup(KmRun &r, const std::vector<int64_t> &seg_begin, const std::
   TM_TRY(r.quiet.alloc(4));
   TM_HIP(hipMemsetAsync(r.quiet.p, 0xff, 4, stream));
   t.quiet = r.quiet.as<int>();
+  TM_TRY(r.look.alloc(16));
+  TM_HIP(hipMemsetAsync(r.look.p, 0, 16, stream));
+  t.look = r.look.as<u64>();
   r.skipping = d == 192 && nseg == 1 && k <= H_MAXK;
   if (r.skipping) TM_TRY(tile_skip_setup(t));
   return TM_OK;
@@ -515,7 +518,7 @@ static int km_launches(KmRun &r, int *iters) {
           hipLaunchKernelGGL(k_accumulate<3>, dim3(nblk), dim3(256), lds_acc, stream, t.pts, t.w, t.ds, k, t.assign, t.sums, t.cnts, t.quiet);
         }
       } else {
-        launch_assign192(t.a192, nseg, stream, t.pts, t.ptsc, t.n, t.w, t.ds, k, t.cent, t.assign, t.sums, t.cnts, t.quiet);
+        launch_assign192(t.a192, nseg, stream, t.pts, t.ptsc, t.n, t.w, t.ds, k, t.cent, t.assign, t.sums, t.cnts, t.quiet, nullptr, nullptr, t.look);
       }
       hipLaunchKernelGGL(k_update_all, dim3(1), dim3(1024), 0, stream, t.ds, nseg, k, d, (d == 192 || fuse3) ? 1 : 0, t.sums, t.cnts, t.cent, issued, t.quiet, pin_dev);
     }
@@ -556,6 +559,7 @@ int kmeans_batched(const int32_t *pts, const uint32_t *w, int d, const std::vect
   const int nseg = (int)seg_begin.size();
   if (host_iters) *host_iters = 0;
   kmeans_run_stats().resident = 0;
+  if (d == 192) kmeans_run_stats().look_scored = kmeans_run_stats().look_exact = 0;
   if (nseg == 0) return TM_OK;
   if (d == 3 && !init_idx && !dev_init_idx) {  // the whole clustering in one launch when its workgroups fit the chip together
     int used = 0;
@@ -581,10 +585,16 @@ int kmeans_batched(const int32_t *pts, const uint32_t *w, int d, const std::vect
     else kmeans_run_stats().resident = 1;
     TM_HIP(hipGetLastError());
     if (host_iters) *host_iters = it;
+    u64 look[2] = {0, 0};
     {
       HostRead hr_(stream);
       TM_TRY(hr_.get(r.hs.data(), r.dsegs.p, sizeof(Seg) * nseg));
+      TM_TRY(hr_.get(look, r.look.p, 16));
       TM_TRY(hr_.wait());
+    }
+    if (d == 192) {
+      kmeans_run_stats().look_scored = (int64_t)look[0];
+      kmeans_run_stats().look_exact = (int64_t)look[1];
     }
     if (host_kk) {
       host_kk->resize(nseg);

@@ -14,35 +14,203 @@ namespace tmx {
 // The exact integer sums are carried from iteration to iteration: a point that changes cluster adds its row to the new
 // cluster and subtracts it from the old one (u64 arithmetic: exact and order-free), all threads of the workgroup
 // cooperating on one moved row at a time (coalesced read, one dimension per thread), accumulated in LDS and flushed once.
+// LOOK: the first look of tm_kmeans.h -- the same passes with Single accumulators in pairs (packed subtractions and fused multiply-adds:
+// a quarter of the chain's issue time), the centroids staged as Singles, their norms summed on the way; the points the look cannot
+// decide are listed in LDS and go through the chain itself, a lane per (point, centroid) pair, before anything is written.
 constexpr int A_DCH = 8;   // dimensions staged per pass
-template <int PPT>
+constexpr int A_MU = 8;    // moved rows a wave has in flight
+typedef float a_f2 __attribute__((ext_vector_type(2)));
+template <int PPT, bool LOOK>
 __global__ __launch_bounds__(256) void k_assign192(const int32_t *__restrict__ pts, const int32_t *__restrict__ pts_chunked, int64_t n_total,
                                                    const uint32_t *__restrict__ w, Seg *__restrict__ segs,
                                                    int k, const double *__restrict__ cent, int32_t *__restrict__ assign,
                                                    u64 *__restrict__ sums, u64 *__restrict__ cnts, int rows_per_block, int lds_delta,
-                                                   const int *__restrict__ quiet, double *__restrict__ ub = nullptr, double *__restrict__ lb = nullptr) {
+                                                   const int *__restrict__ quiet, double *__restrict__ ub, double *__restrict__ lb,
+                                                   u64 *__restrict__ look_stats) {
   if (*quiet >= 0) return;  // converged earlier in this batch of launches
   constexpr int D = 192, ROWS = 256 * PPT, PITCH = A_DCH + 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
   double(*s_cent)[KCH] = reinterpret_cast<double(*)[KCH]>(s_raw);                       // [A_DCH][KCH]
+  float(*s_centf)[KCH] = reinterpret_cast<float(*)[KCH]>(s_raw);                        // LOOK: the same as Singles, in its first half
   int32_t *s_pts = reinterpret_cast<int32_t *>(s_raw + A_DCH * KCH * 8);               // [ROWS][PITCH]
   int32_t *s_moved = s_pts + ROWS * PITCH;                                             // [ROWS][3]: row, old, new
   u64 *s_delta = reinterpret_cast<u64 *>(s_moved + ROWS * 3 + (ROWS & 1));             // [kk][D+1] when lds_delta
-  __shared__ int s_nmoved;
+  // LOOK, once the passes are over, in s_pts' place (24 of its 36 bytes per row): what the chain found for a row in doubt, and their list
+  double *s_xd = reinterpret_cast<double *>(s_pts);                                     // [ROWS][2]: smallest, second smallest
+  int32_t *s_xc = s_pts + ROWS * 4;                                                     // [ROWS]: whose the smallest is
+  int32_t *s_doubt = s_xc + ROWS;                                                       // [ROWS]
+  __shared__ int s_nmoved, s_ndoubt;
+  __shared__ double s_nrm[A_DCH * KCH], s_E[KCH];  // LOOK: the centroids' norms in partial sums, then E(c)
   const int seg = blockIdx.y;
   const Seg sg = segs[seg];
   const int kk = sg.kk, tid = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.x * rows_per_block;
   const int nrows = (int)max((int64_t)0, min((int64_t)rows_per_block, sg.count - row0));
   if (nrows <= 0) return;
-  if (tid == 0) s_nmoved = 0;
+  if (tid == 0) { s_nmoved = 0; s_ndoubt = 0; }
   if (lds_delta)
     for (int e = tid; e < kk * (D + 1); e += 256) s_delta[e] = 0;
   double bd[PPT], bd2[PPT];  // smallest and second smallest distance (the second only feeds the bounds of the later iterations)
   int bc[PPT];
+  double ubv[PPT], lbv[PPT];  // the bounds the later iterations start from
 #pragma unroll
-  for (int m = 0; m < PPT; m++) { bd[m] = 0.0; bd2[m] = 1.0e300; bc[m] = -1; }
+  for (int m = 0; m < PPT; m++) { bd[m] = 0.0; bd2[m] = 1.0e300; bc[m] = -1; ubv[m] = 0.0; lbv[m] = 0.0; }
   const int4 zero4 = make_int4(0, 0, 0, 0);
+  if constexpr (LOOK) {
+    float bs[PPT], mx[PPT];            // the smallest Single sum; the row's largest magnitude as a Single
+    double bhi[PPT], blo[PPT], olo[PPT];  // hi and lo of the Single argmin; the smallest lo among the others
+#pragma unroll
+    for (int m = 0; m < PPT; m++) { bs[m] = 0.0f; mx[m] = 0.0f; bhi[m] = 0.0; blo[m] = 0.0; olo[m] = 1.0e150; }
+#pragma unroll 1
+    for (int c0 = 0; c0 < kk; c0 += KCH) {
+      a_f2 s[PPT][KCH / 2];
+#pragma unroll
+      for (int m = 0; m < PPT; m++)
+#pragma unroll
+        for (int c = 0; c < KCH / 2; c++) s[m][c] = a_f2{0.0f, 0.0f};
+      int4 pre[2 * PPT];
+      double pre_c = 0.0, nrm = 0.0;
+      // as below, but a slot beyond the slice reads the slice's last row (nothing of such a slot is used) instead of choosing between the load
+      // and a zero: that choice makes the loads flat ones (one of the two addresses is private memory), and a flat load counts as an LDS
+      // operation as well, so the scoring's first wait for its LDS reads waits for the whole prefetch
+      auto fetch = [&](int j0) {
+#pragma unroll
+        for (int m = 0; m < 2 * PPT; m++) {
+          const int r = min((tid >> 1) + 128 * m, nrows - 1);
+          pre[m] = *reinterpret_cast<const int4 *>(pts_chunked + ((int64_t)(j0 / A_DCH) * n_total + sg.begin + row0 + r) * A_DCH + (tid & 1) * 4);
+        }
+        if (tid < A_DCH * KCH) {
+          const int j = tid / KCH, c = tid - j * KCH;
+          pre_c = c0 + c < kk ? cent[((int64_t)seg * k + c0 + c) * D + j0 + j] : 0.0;
+        }
+      };
+      auto stage = [&]() {
+#pragma unroll
+        for (int m = 0; m < 2 * PPT; m++) {
+          int32_t *dst = s_pts + ((tid >> 1) + 128 * m) * PITCH + (tid & 1) * 4;
+          dst[0] = pre[m].x; dst[1] = pre[m].y; dst[2] = pre[m].z; dst[3] = pre[m].w;
+        }
+        if (tid < A_DCH * KCH) { s_centf[tid / KCH][tid % KCH] = (float)pre_c; nrm = __fma_rn(pre_c, pre_c, nrm); }
+      };
+      fetch(0);
+      __syncthreads();  // previous pass (or the zeroing above) done with the buffers
+      stage();
+      __syncthreads();
+#pragma unroll 1
+      for (int j0 = 0; j0 < D; j0 += A_DCH) {
+        if (j0 + A_DCH < D) fetch(j0 + A_DCH);
+#pragma unroll 2
+        for (int j = 0; j < A_DCH; j++) {
+          a_f2 pj[PPT];
+#pragma unroll
+          for (int m = 0; m < PPT; m++) {
+            const float v = (float)s_pts[(tid + 256 * m) * PITCH + j];
+            mx[m] = __builtin_fmaxf(mx[m], __builtin_fabsf(v));
+            pj[m] = a_f2{v, v};
+          }
+#pragma unroll
+          for (int c = 0; c < KCH; c += 4) {
+            const float4 cv = *reinterpret_cast<const float4 *>(&s_centf[j][c]);
+            const a_f2 c01{cv.x, cv.y}, c23{cv.z, cv.w};
+#pragma unroll
+            for (int m = 0; m < PPT; m++) {
+              const a_f2 t0 = pj[m] - c01, t1 = pj[m] - c23;
+              s[m][c / 2] = __builtin_elementwise_fma(t0, t0, s[m][c / 2]);
+              s[m][c / 2 + 1] = __builtin_elementwise_fma(t1, t1, s[m][c / 2 + 1]);
+            }
+          }
+        }
+        __syncthreads();
+        if (j0 + A_DCH < D) stage();
+        __syncthreads();
+      }
+      // E(c) of this pass's centroids: eight partial sums of squares each (any order: rounded up by FL_ETA, nine orders above their rounding)
+      if (tid < A_DCH * KCH) s_nrm[tid] = nrm;
+      __syncthreads();
+      if (tid < KCH) {
+        double q = 0.0;
+#pragma unroll
+        for (int j = 0; j < A_DCH; j++) q += s_nrm[j * KCH + tid];
+        s_E[tid] = sqrt(q) * (FL_CENT * (1.0 + FL_ETA)) + 1.0e-30;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int c = 0; c < KCH; c++) {
+        if (c0 + c >= kk) break;  // (uniform)
+        const double e = s_E[c];
+#pragma unroll
+        for (int m = 0; m < PPT; m++) {
+          const float sv = s[m][c >> 1][c & 1];
+          const double rt = (double)sqrtf(sv);
+          const double hi = __fma_rn(rt, 1.0 + FL_GAMMA, e), lo = __fma_rn(rt, 1.0 - FL_GAMMA, -e);
+          if (bc[m] < 0 || sv < bs[m]) {
+            if (bc[m] >= 0) olo[m] = fmin(olo[m], blo[m]);
+            bs[m] = sv; bc[m] = c0 + c; bhi[m] = hi; blo[m] = lo;
+          } else olo[m] = fmin(olo[m], lo);
+        }
+      }
+    }
+    // decided, or in doubt -> the list
+    bool doubt[PPT];
+#pragma unroll
+    for (int m = 0; m < PPT; m++) {
+      const int r = tid + 256 * m;
+      const bool decided = olo[m] * (1.0 - FL_ETA) > bhi[m] * (1.0 + FL_ETA) && mx[m] < FL_INT_EXACT;
+      doubt[m] = r < nrows && !decided;
+      ubv[m] = bhi[m] * (1.0 + FL_ETA);
+      lbv[m] = olo[m] - fabs(olo[m]) * FL_ETA;
+      if (doubt[m]) s_doubt[atomicAdd(&s_ndoubt, 1)] = r;  // (s_pts has been read for the last time: the barriers behind the last pass)
+    }
+    __syncthreads();
+    const int ndoubt = s_ndoubt;
+    if (ndoubt) {  // (uniform in the workgroup) the chain: 16 points per step, a lane per (point, centroid) pair, every accumulator its 192 terms in order
+      const int cl = tid & 15;
+#pragma unroll 1
+      for (int t0 = 0; t0 < ndoubt; t0 += 16) {
+        const int t = t0 + (tid >> 4);
+        const bool act = t < ndoubt;
+        const int r = s_doubt[act ? t : 0];
+        const int32_t *rp = pts + (sg.begin + row0 + r) * D;
+        double xd = 1.0e300, xd2 = 1.0e300;
+        int xc = 0x7fffffff;
+#pragma unroll 1
+        for (int c0 = 0; c0 < kk; c0 += KCH) {
+          const int ci = c0 + cl;
+          const double *cp = cent + ((int64_t)seg * k + min(ci, kk - 1)) * D;
+          double sacc = 0.0;
+#pragma unroll 8
+          for (int j = 0; j < D; j++) { const double d0 = __dsub_rn((double)rp[j], cp[j]); sacc = __fma_rn(d0, d0, sacc); }
+          if (ci < kk) {  // this lane's centroids come in ascending order: strict `<` keeps the lowest index among equals
+            if (sacc < xd) { xd2 = xd; xd = sacc; xc = ci; }
+            else if (sacc < xd2) xd2 = sacc;
+          }
+        }
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {  // the 16 lanes of a point: the best by (distance, index); the second best distance = the smallest of the rest
+          const double od = __shfl_xor(xd, o), od2 = __shfl_xor(xd2, o);
+          const int oc = __shfl_xor(xc, o);
+          const bool take = od < xd || (od == xd && oc < xc);
+          const double loser = take ? xd : od;
+          xd2 = fmin(fmin(xd2, od2), loser);
+          if (take) { xd = od; xc = oc; }
+        }
+        if (act && cl == 0) { s_xd[r * 2] = xd; s_xd[r * 2 + 1] = xd2; s_xc[r] = xc; }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int m = 0; m < PPT; m++)
+        if (doubt[m]) {
+          const int r = tid + 256 * m;
+          bc[m] = s_xc[r];
+          ubv[m] = sqrt(s_xd[r * 2]) * (1.0 + 1e-12);
+          lbv[m] = sqrt(s_xd[r * 2 + 1]) * (1.0 - 1e-12);
+        }
+    }
+    if (look_stats && tid == 0) {  // one add per workgroup
+      atomicAdd(&look_stats[0], (u64)nrows);
+      if (ndoubt) atomicAdd(&look_stats[1], (u64)ndoubt);
+    }
+  } else {
 #pragma unroll 1
   for (int c0 = 0; c0 < kk; c0 += KCH) {
     double s[PPT][KCH];
@@ -109,14 +277,17 @@ __global__ __launch_bounds__(256) void k_assign192(const int32_t *__restrict__ p
           else if (s[m][c] < bd2[m]) bd2[m] = s[m][c];
         }
   }
+#pragma unroll
+  for (int m = 0; m < PPT; m++) { ubv[m] = sqrt(bd[m]) * (1.0 + 1e-12); lbv[m] = sqrt(bd2[m]) * (1.0 - 1e-12); }
+  }
   if (ub) {  // Euclidean bounds for the skipping iterations, rounded the safe way: ub >= the distance to the own centroid, lb <= to any other
 #pragma unroll
     for (int m = 0; m < PPT; m++) {
       const int r = tid + 256 * m;
       if (r >= nrows) continue;
       const int64_t gi = sg.begin + row0 + r;
-      ub[gi] = sqrt(bd[m]) * (1.0 + 1e-12);
-      lb[gi] = sqrt(bd2[m]) * (1.0 - 1e-12);
+      ub[gi] = ubv[m];
+      lb[gi] = lbv[m];
     }
   }
   // moved points -> list
@@ -135,22 +306,43 @@ __global__ __launch_bounds__(256) void k_assign192(const int32_t *__restrict__ p
   const int nmoved = s_nmoved;
   if (nmoved == 0) return;
   if (tid == 0) atomicAdd(&segs[seg].changed, nmoved);
-#pragma unroll 2
-  for (int e = tid >> 6; e < nmoved; e += 4) {  // a wave per moved row (four rows in flight, eight with the unrolling): lane -> dimensions lane, +64, +128; 192 = the weight
-    const int r = s_moved[e * 3], old = s_moved[e * 3 + 1], nw = s_moved[e * 3 + 2];
-    const int64_t gi = sg.begin + row0 + r;
-    const long long wi = w ? (long long)w[gi] : 1;
+  // a wave per moved row: lane -> dimensions lane, +64, +128; 192 = the weight.  A wave asks for A_MU rows before it adds the first (32 rows
+  // of the workgroup in flight): the first iteration moves every row of the slice, and with eight rows in flight its 768 rows were 96
+  // round trips to memory one behind the other
+#pragma unroll 1
+  for (int e0 = tid >> 6; e0 < nmoved; e0 += 4 * A_MU) {
+    int pv[A_MU][3], oldv[A_MU], nwv[A_MU];
+    long long wv[A_MU];
 #pragma unroll
-    for (int j = tid & 63; j <= D; j += 64) {
-      const u64 v = j < D ? (u64)(wi * pts[gi * D + j]) : (u64)wi;
-      if (lds_delta) {
-        atomicAdd(&s_delta[nw * (D + 1) + j], v);
-        if (old >= 0) atomicAdd(&s_delta[old * (D + 1) + j], (u64)0 - v);
-      } else {
-        u64 *base = j < D ? sums + (int64_t)seg * k * D : cnts + (int64_t)seg * k;
-        const int64_t stride = j < D ? D : 1, off = j < D ? j : 0;
-        atomicAdd(&base[nw * stride + off], v);
-        if (old >= 0) atomicAdd(&base[old * stride + off], (u64)0 - v);
+    for (int u = 0; u < A_MU; u++) {
+      const int e = e0 + 4 * u;
+      const bool ok = e < nmoved;
+      const int ee = ok ? e : e0;
+      const int64_t gi = sg.begin + row0 + s_moved[ee * 3];
+      oldv[u] = s_moved[ee * 3 + 1];
+      nwv[u] = ok ? s_moved[ee * 3 + 2] : -1;
+      wv[u] = w ? (long long)w[gi] : 1;
+#pragma unroll
+      for (int q = 0; q < 3; q++) pv[u][q] = pts[gi * D + (tid & 63) + 64 * q];
+    }
+#pragma unroll
+    for (int u = 0; u < A_MU; u++) {
+      const int old = oldv[u], nw = nwv[u];
+      if (nw < 0) continue;  // (uniform in the wave)
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int j = (tid & 63) + 64 * q;
+        if (j > D) break;
+        const u64 v = q < 3 ? (u64)(wv[u] * pv[u][q < 3 ? q : 0]) : (u64)wv[u];
+        if (lds_delta) {
+          atomicAdd(&s_delta[nw * (D + 1) + j], v);
+          if (old >= 0) atomicAdd(&s_delta[old * (D + 1) + j], (u64)0 - v);
+        } else {
+          u64 *base = j < D ? sums + (int64_t)seg * k * D : cnts + (int64_t)seg * k;
+          const int64_t stride = j < D ? D : 1, off = j < D ? j : 0;
+          atomicAdd(&base[nw * stride + off], v);
+          if (old >= 0) atomicAdd(&base[old * stride + off], (u64)0 - v);
+        }
       }
     }
   }
@@ -194,22 +386,29 @@ Assign192Shape assign192_shape(int64_t maxcount, int nseg, int k, int cus) {
   return sh;
 }
 
-template <int PPT>
+template <int PPT, bool LOOK>
 static void launch_assign192_t(const Assign192Shape &sh, int nseg, hipStream_t stream, const int32_t *pts, const int32_t *ptsc, int64_t ntot, const uint32_t *w, Seg *ds,
-                               int k, const double *cent, int32_t *assign, u64 *sums, u64 *cnts, const int *quiet, double *ub, double *lb) {
+                               int k, const double *cent, int32_t *assign, u64 *sums, u64 *cnts, const int *quiet, double *ub, double *lb, u64 *look_stats) {
   static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_assign192<PPT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512); attr_set = true; }
-  hipLaunchKernelGGL(k_assign192<PPT>, dim3(sh.nblk, nseg), dim3(256), sh.lds, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, sh.rows, sh.lds_delta, quiet, ub, lb);
+  if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_assign192<PPT, LOOK>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048); attr_set = true; }
+  hipLaunchKernelGGL((k_assign192<PPT, LOOK>), dim3(sh.nblk, nseg), dim3(256), sh.lds, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, sh.rows, sh.lds_delta, quiet, ub, lb,
+                     look_stats);
+}
+template <bool LOOK>
+static void launch_assign192_l(const Assign192Shape &sh, int nseg, hipStream_t stream, const int32_t *pts, const int32_t *ptsc, int64_t ntot, const uint32_t *w, Seg *ds,
+                               int k, const double *cent, int32_t *assign, u64 *sums, u64 *cnts, const int *quiet, double *ub, double *lb, u64 *look_stats) {
+  switch (sh.ppt) {
+    case 1: launch_assign192_t<1, LOOK>(sh, nseg, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, quiet, ub, lb, look_stats); break;
+    case 2: launch_assign192_t<2, LOOK>(sh, nseg, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, quiet, ub, lb, look_stats); break;
+    case 3: launch_assign192_t<3, LOOK>(sh, nseg, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, quiet, ub, lb, look_stats); break;
+    case 4: launch_assign192_t<4, LOOK>(sh, nseg, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, quiet, ub, lb, look_stats); break;
+    default: launch_assign192_t<5, LOOK>(sh, nseg, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, quiet, ub, lb, look_stats); break;
+  }
 }
 void launch_assign192(const Assign192Shape &sh, int nseg, hipStream_t stream, const int32_t *pts, const int32_t *ptsc, int64_t ntot, const uint32_t *w, Seg *ds,
-                      int k, const double *cent, int32_t *assign, u64 *sums, u64 *cnts, const int *quiet, double *ub, double *lb) {
-  switch (sh.ppt) {
-    case 1: launch_assign192_t<1>(sh, nseg, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, quiet, ub, lb); break;
-    case 2: launch_assign192_t<2>(sh, nseg, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, quiet, ub, lb); break;
-    case 3: launch_assign192_t<3>(sh, nseg, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, quiet, ub, lb); break;
-    case 4: launch_assign192_t<4>(sh, nseg, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, quiet, ub, lb); break;
-    default: launch_assign192_t<5>(sh, nseg, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, quiet, ub, lb); break;
-  }
+                      int k, const double *cent, int32_t *assign, u64 *sums, u64 *cnts, const int *quiet, double *ub, double *lb, u64 *look_stats) {
+  if (knobs().km_first_look) launch_assign192_l<true>(sh, nseg, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, quiet, ub, lb, look_stats);
+  else launch_assign192_l<false>(sh, nseg, stream, pts, ptsc, ntot, w, ds, k, cent, assign, sums, cnts, quiet, ub, lb, nullptr);
 }
 
 // ---- D = 192: iterations that skip what cannot change (Hamerly's bounds, made exact) ------------------------------------------
@@ -1128,7 +1327,7 @@ void tile_skip_iteration(TileRun &t, int iter, int *pin_dev) {
   if (iter < H_WARM) {
     const bool last_plain = iter == H_WARM - 1;  // it leaves the bounds the skipping iterations start from
     launch_assign192(t.a192, 1, t.stream, t.pts, t.ptsc, t.n, t.w, t.ds, t.k, t.cent, t.assign, t.sums, t.cnts, t.quiet, last_plain ? t.ub.as<double>() : nullptr,
-                     last_plain ? t.lb.as<double>() : nullptr);
+                     last_plain ? t.lb.as<double>() : nullptr, t.look);
   } else {
     hipLaunchKernelGGL(k_h_bounds, dim3((int)((t.n + H_SLICE - 1) / H_SLICE)), dim3(256), 0, t.stream, t.pts, t.n, t.ds, (const double *)t.cent, t.assign, t.ub.as<double>(),
                        t.lb.as<double>(), t.move.as<double>(), t.half.as<double>(), t.k, t.need.as<int32_t>(), t.cnt.as<unsigned>(), t.quiet);

@@ -339,6 +339,14 @@ def kmeans_last_resident():
     return bool(lib().tm_kmeans_last_resident())
 
 
+def kmeans_last_first_look():
+    """the first look of this thread's last tile k-means (D = 192): (point-scorings looked at in single precision, those of them that went
+    to the double-precision chain); (0, 0) under TM_KM_FIRST_LOOK=0"""
+    looked, exact = ctypes.c_int64(0), ctypes.c_int64(0)
+    lib().tm_kmeans_last_first_look(ctypes.byref(looked), ctypes.byref(exact))
+    return int(looked.value), int(exact.value)
+
+
 def pp_seeds(feat, use, k):
     """the D^2 seeding of palettize alone (test seam): feat int32 [n][192], use uint32-as-int32 [n] or None ->
     (centres found, numpy int64 [k]: the picked point indices in pick order, -1 beyond the centres found)"""
