@@ -643,6 +643,15 @@ TM_API int tm_get_kmeans_iters(tm_encoder *, int *tile_iters, int64_t *tile_poin
 TM_API int tm_stage_load(const void *frames, int nframes, int img_w, int img_h, int tm_w, int tm_h,
                          void *tiles, void *flags, void *lab_means, void *stream);
 
+/* PearsonCorrelation (:2201-2228) of consecutive frames, the correlation Load finds its key frames with, in two seams.
+ * tm_pearson_finish_host (host only, no device call): its last lines (:2221-2227) on the raw sums (num, sum dx^2, sum dy^2) of n frames ->
+ * correl[f] = num / (sqrt(sum dx^2) * sqrt(sum dy^2)) in IEEE Single arithmetic, 1 where that denominator is 0; correl[0] = 0 (frame 0
+ * has no predecessor; its sums are not read).  Load's own tail calls it.
+ * tm_stage_pearson: the sums of [nframes][per] Singles in DEVICE memory (per >= 1: Load passes 3 x the tile count), read back and finished
+ * with the function above -> HOST float32 [nframes].  Blocking. */
+TM_API int tm_pearson_finish_host(const float *sums /* [n][3] */, int n, float *correl /* [n] */);
+TM_API int tm_stage_pearson(const void *lab_f32, int nframes, int per, void *correl_f32_host, void *stream);
+
 /* Planes of 8-bit Y, U, V -> RGB32 frames [nframes][dst_h][dst_w] 0x00RRGGBB, the format frames are pushed in: chroma upsampling, the
  * Lanczos-3 resize to dst_w x dst_h and the colour conversion in one kernel (what tm_open_input's Load runs per chunk of frames).  strides
  * (HOST array): row and frame stride in bytes of y, u, v -- {y_row, y_frame, u_row, u_frame, v_row, v_frame}; chroma: TM_CHROMA_* (MONO: u,
@@ -710,6 +719,12 @@ TM_API int tm_stage_window_dcts(const void *frame_buffer, int width, int height,
  * minimum in raster order.  out_err u32, out_px / out_py int8 (PredictedX / PredictedY). */
 TM_API int tm_stage_motion_search(const void *cur_i16, int tm_w, int tm_h, const void *window_dcts, int radius, void *out_err,
                                   void *out_px, void *out_py, void *stream);
+/* The two in one, as PredictMotion runs them per frame: the search of cur in frame buffer fb_rgb32 ([tm_h*8][tm_w*8] u32 0x00BBGGRR), whose
+ * window features are made straight in the search's matrix layout; the int16 rows (allocated inside) are written only when the frame falls
+ * back to the VALU search.  TM_MOTION_PACK_SEPARATE, TM_MOTION_FORCE_FLAG, TM_MOTION_VALU and TM_WINDOW_DCTS_BY_TILE pick its other forms.
+ * Blocking. */
+TM_API int tm_stage_motion_search_fb(const void *cur_i16, int tm_w, int tm_h, const void *fb_rgb32, int radius, void *out_err,
+                                     void *out_px, void *out_py, void *stream);
 
 /* A13+A14 (KNN branch): exact nearest neighbour of every query in the database, both int16 [.][192];
  * what ann_kdtree_short_search(eps=0) answers (:1547).  Ties: lowest database index.

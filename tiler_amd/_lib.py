@@ -64,12 +64,15 @@ SIGNATURES = {
     "tm_set_device_mask": (c_int, [c_void_p, ctypes.c_uint32]),
     "tm_set_devices": (c_int, [c_void_p, ctypes.POINTER(c_int), c_int]),
     "tm_stage_load": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tm_pearson_finish_host": (c_int, [c_void_p, c_int, c_void_p]),
+    "tm_stage_pearson": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "tm_stage_features_rgb": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "tm_stage_features_rgb_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tm_stage_features_pal": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "tm_stage_features_cluster": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "tm_stage_window_dcts": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "tm_stage_motion_search": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tm_stage_motion_search_fb": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tm_stage_knn_topk": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "tm_stage_epu_rerank": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),

@@ -1,5 +1,7 @@
 // tm_api.hip -- extern "C" surface of libtilemotion.so: stage seam + KNN index + misc (include/tilemotion.h).
+#include <cmath>
 #include <cstdlib>
+#include <vector>
 
 #include "tm_common.h"
 #include "tm_internal.h"
@@ -21,6 +23,35 @@ int tm_stage_load(const void *frames, int nframes, int img_w, int img_h, int tm_
                   void *lab_means, void *stream) {
   knobs_reload();
   return launch_load(frames, nframes, img_w, img_h, tm_w, tm_h, tiles, flags, lab_means, (hipStream_t)stream);
+}
+
+// the tail of PearsonCorrelation (tilingencoder.pas:2221-2227) in host IEEE arithmetic: the device's square root is not correctly rounded
+int tm_pearson_finish_host(const float *sums, int n, float *correl) {
+  TM_CHECK(n >= 0 && (n == 0 || (sums && correl)), TM_E_INVAL, "tm_pearson_finish_host: bad arguments");
+  for (int f = 0; f < n; f++) {
+    if (f == 0) { correl[0] = 0.0f; continue; }
+    const float denx = std::sqrt(sums[f * 3 + 1]), deny = std::sqrt(sums[f * 3 + 2]);
+    const float den = denx * deny;
+    correl[f] = den != 0.0f ? sums[f * 3] / den : 1.0f;
+  }
+  return TM_OK;
+}
+
+int tm_stage_pearson(const void *lab_f32, int nframes, int per, void *correl_f32_host, void *stream) {
+  knobs_reload();
+  TM_TRY(require_device());
+  TM_CHECK(nframes >= 0 && per >= 1 && (nframes == 0 || (lab_f32 && correl_f32_host)), TM_E_INVAL, "tm_stage_pearson: bad arguments");
+  if (nframes == 0) return TM_OK;
+  DevBuf dsums;
+  TM_TRY(dsums.alloc((size_t)nframes * 12));
+  TM_TRY(launch_pearson(lab_f32, nframes, per, dsums.p, (hipStream_t)stream));
+  std::vector<float> sums((size_t)nframes * 3);
+  {
+    HostRead hr_((hipStream_t)stream);
+    TM_TRY(hr_.get(sums.data(), dsums.p, sums.size() * 4));
+    TM_TRY(hr_.wait());
+  }
+  return tm_pearson_finish_host(sums.data(), nframes, (float *)correl_f32_host);
 }
 
 int tm_stage_rgb_to_lab(const void *rgb, int64_t n, void *out_lab, void *stream) {
@@ -63,6 +94,18 @@ int tm_stage_motion_search(const void *cur_i16, int tm_w, int tm_h, const void *
   knobs_reload();
   TM_TRY(require_device());
   return launch_motion_search(cur_i16, tm_w, tm_h, window_dcts, radius, out_err, out_px, out_py, (hipStream_t)stream);
+}
+
+int tm_stage_motion_search_fb(const void *cur_i16, int tm_w, int tm_h, const void *fb_rgb32, int radius, void *out_err, void *out_px,
+                              void *out_py, void *stream) {
+  knobs_reload();
+  TM_TRY(require_device());
+  TM_CHECK(tm_w > 0 && tm_h > 0 && cur_i16 && fb_rgb32 && out_err && out_px && out_py, TM_E_INVAL, "tm_stage_motion_search_fb: bad arguments");
+  DevBuf win;  // the int16 rows of the fallback
+  TM_TRY(win.alloc((size_t)(tm_w * 8 - 7) * (size_t)(tm_h * 8 - 7) * 384));
+  TM_TRY(launch_motion_search_fb(cur_i16, tm_w, tm_h, fb_rgb32, win.p, radius, out_err, out_px, out_py, (hipStream_t)stream));
+  TM_HIP(hipStreamSynchronize((hipStream_t)stream));  // the rows are freed on return
+  return TM_OK;
 }
 
 int tm_stage_knn_topk(const void *queries_i16, int64_t nq, const void *db_i16, int64_t nt, int k, void *out_idx, void *out_err, void *stream) {

@@ -168,11 +168,7 @@ int load_tail(tm_encoder *e, hipStream_t st) {  // st: the stream the sums sit b
   }
   e->load_tail_pending = false;  // only now: a failed read-back leaves the tail to the next caller instead of stale key frames
   e->correl.assign(e->nframes, 0.0f);
-  for (int f = 1; f < e->nframes; f++) {  // tail of PearsonCorrelation (2221-2227) in host IEEE arithmetic
-    const float denx = std::sqrt(sums[f * 3 + 1]), deny = std::sqrt(sums[f * 3 + 2]);
-    const float den = denx * deny;
-    e->correl[f] = den != 0.0f ? sums[f * 3] / den : 1.0f;
-  }
+  TM_TRY(tm_pearson_finish_host(sums.data(), e->nframes, e->correl.data()));  // tail of PearsonCorrelation (2221-2227) in host IEEE arithmetic
   e->kf_start.clear();
   if (e->kf_manual) {  // FindKeyFrames, manual mode (3380-3384): the thresholds and the spacing play no part
     e->kf_start = e->kf_manual_list;

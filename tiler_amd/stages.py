@@ -31,6 +31,16 @@ def load(frames, tm_w, tm_h):
     return tiles, flags, lab
 
 
+def pearson(lab):
+    """PearsonCorrelation (tilingencoder.pas:2201-2228) of consecutive rows, as Load runs it on the frames' Lab tile means: lab float32
+    [nframes][per] on the device -> numpy float32 [nframes] (entry 0 is 0)"""
+    assert lab.is_cuda and lab.dtype == torch.float32 and lab.is_contiguous() and lab.dim() == 2
+    nframes, per = lab.shape
+    out = np.zeros((nframes,), np.float32)
+    check(lib().tm_stage_pearson(_p(lab), nframes, per, out.ctypes.data_as(ctypes.c_void_p), _stream()))
+    return out
+
+
 def yuv_to_rgb32(y, u, v, chroma, dst_w, dst_h, yuv_mode=0):
     """Planes of a Y4M clip -> RGB32 frames (tm_stage_yuv_to_rgb32): chroma upsampling, the Lanczos-3 resize and the colour conversion in
     one kernel.  y uint8 [F][H][W]; u, v uint8 [F][ch][cw] (None for chroma 4 = mono); chroma: TM_CHROMA_* (0 444, 1 422, 2 420jpeg,
@@ -177,6 +187,19 @@ def motion_search(cur, tm_w, tm_h, win, radius):
     px = torch.empty((n,), dtype=torch.int8, device=cur.device)
     py = torch.empty((n,), dtype=torch.int8, device=cur.device)
     check(lib().tm_stage_motion_search(_p(cur), tm_w, tm_h, _p(win), radius, _p(err), _p(px), _p(py), _stream()))
+    return err, px, py
+
+
+def motion_search_fb(cur, tm_w, tm_h, fb, radius):
+    """the same search in a frame buffer (int32 [tm_h*8][tm_w*8] 0x00BBGGRR), whose window features are made in the search's own layout:
+    what PredictMotion runs per frame (tm_stage_motion_search_fb) -> (err int32-as-uint32, px int8, py int8), one per tile"""
+    assert fb.is_cuda and fb.dtype == torch.int32 and fb.is_contiguous() and tuple(fb.shape) == (tm_h * 8, tm_w * 8)
+    assert cur.is_cuda and cur.dtype == torch.int16 and cur.is_contiguous() and tuple(cur.shape) == (tm_w * tm_h, 192)
+    n = tm_w * tm_h
+    err = torch.empty((n,), dtype=torch.int32, device=cur.device)
+    px = torch.empty((n,), dtype=torch.int8, device=cur.device)
+    py = torch.empty((n,), dtype=torch.int8, device=cur.device)
+    check(lib().tm_stage_motion_search_fb(_p(cur), tm_w, tm_h, _p(fb), radius, _p(err), _p(px), _p(py), _stream()))
     return err, px, py
 
 
