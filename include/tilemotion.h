@@ -86,6 +86,13 @@
  *                           so that a small clip walks the two staging buffers many times)
  *   TM_POOL_GIB=<x>         cap of the device-memory pool a thread keeps (96); TM_HOST_THREADS=<n>: OptimizePalettes' helper threads
  *                           (both read once per process)
+ *   TM_HOST_THREADS=<n>     also: the threads Save codes its key frames' streams on, at most one per key frame and at most 16 (default: the
+ *                           machine's, at most 16); this use is read at each Save.  1: one stream after the other on the calling thread
+ *   TM_SAVE_FINDER=host|device  where Save's coder takes its match lists from: its own finder on the parser threads, or the device finder
+ *                           (tm_lz_matches.hip) on the encoder's device with the parsers one window behind; read at each Save.  The file
+ *                           is the same bytes either way.  Default: device for tm_save_gtm / esSave, host for tm_write_gtm_host (no device)
+ *   TM_LZ_WINDOW=<n>        the device finder works in windows of n positions instead of 262144; read at each call (tests: small, so that
+ *                           window edges fall inside matches)
  */
 #ifndef TILEMOTION_H
 #define TILEMOTION_H
@@ -369,6 +376,48 @@ TM_API int tm_write_gtm_host(const char *path, int tm_w, int tm_h, int nframes, 
 /* LZCompress, extern.pas:420-439 (LZMA-alone: lc 8, lp 0, pb 2, 4 MiB dictionary, unknown size, end marker), host
  * buffers.  *out_n = compressed size; TM_E_INVAL (with *out_n set) when cap is too small. */
 TM_API int tm_lz_compress_host(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *out_n);
+/* The coder's match finder on its own.  The list of position i of a stream is a function of (src, n, i): the
+ * records of the running maximum of the match length over the nearest earlier position with the same two bytes, the nearest with the same
+ * 3-byte hash, then up to 96 positions of the 4-byte hash chain, nearest first, all within 4 MiB; lengths strictly increase, end at
+ * min(273, n - i), and a list holds at most 98 pairs.  A table of lists is CSR: a uint8 count per position, the pairs of all positions in a row.
+ * tm_lz_matches_host: the lists of positions [first, first + count); *npairs = pairs needed/written, TM_E_INVAL (with *npairs set) when
+ * cap_pairs is too small, TM_E_UNSUPPORTED for n >= 2^31.
+ * tm_lz_compress_from_matches_host: the parser and range coder of tm_lz_compress_host on lists the caller supplies for all n positions
+ * (the same capacity convention); with the finder's lists it writes tm_lz_compress_host's bytes. */
+typedef struct tm_lz_pair {
+  uint16_t len;
+  uint16_t zero; /* padding, written as 0 */
+  uint32_t dist; /* distance - 1 */
+} tm_lz_pair;
+TM_API int tm_lz_matches_host(const uint8_t *src, size_t n, size_t first, size_t count, uint8_t *counts_u8, tm_lz_pair *pairs, size_t cap_pairs,
+                              size_t *npairs);
+TM_API int tm_lz_compress_from_matches_host(const uint8_t *src, size_t n, const uint8_t *counts_u8, const tm_lz_pair *pairs, uint8_t *dst, size_t cap,
+                                            size_t *out_n);
+/* The same finder on the device (tm_lz_matches.hip: three stable key sorts of the positions, then one lane per position over its chain's
+ * stretch of the sorted order).  tm_stage_lz_matches: dev_src = the stream's n bytes in DEVICE memory; the counts and pairs of positions
+ * [first, first + count) into DEVICE memory, exactly tm_lz_matches_host's; *host_npairs = pairs needed/written, TM_E_INVAL (with
+ * *host_npairs set, nothing written to dev_pairs) when cap_pairs is too small, TM_E_UNSUPPORTED for n >= 2^31.  It returns synchronised.
+ * tm_stage_lz_compress: HOST bytes in, tm_lz_compress_host's bytes out (the same capacity convention): the bytes are uploaded, the device
+ * finder runs window by window and the host parser follows one window behind on a helper thread.  TM_LZ_WINDOW=<n> (read at each call)
+ * sets the window to n positions instead of 262144 (tests: small, so that window edges fall inside matches). */
+TM_API int tm_stage_lz_matches(const uint8_t *dev_src, size_t n, size_t first, size_t count, uint8_t *dev_counts_u8, tm_lz_pair *dev_pairs,
+                               size_t cap_pairs, size_t *host_npairs, void *stream);
+TM_API int tm_stage_lz_compress(const uint8_t *host_src, size_t n, uint8_t *dst, size_t cap, size_t *out_n);
+/* What the encoder's last Save did (tm_save_gtm): TM_E_INVAL before the first one.  Save codes the key frames' streams side by side on up
+ * to min(key frames, TM_HOST_THREADS, 16) helper threads, with the match lists from the device finder (TM_SAVE_FINDER=device, the default:
+ * DESIGN.md section 33 has the measurement behind it) or from the coder's own (TM_SAVE_FINDER=host); both switches are read at each Save,
+ * and TM_SAVE_FINDER=host with TM_HOST_THREADS=1 is the one-thread writer of before.  The file is the same bytes in every case. */
+typedef struct tm_save_stats {
+  int64_t raw_bytes, comp_bytes; /* the sums of the GTMk entries */
+  int32_t key_frames, threads;   /* threads: the parser threads that ran */
+  int32_t finder, reserved;      /* TM_SAVE_FINDER_* */
+  double ms_commands;            /* building the command bytes */
+  double ms_finder;              /* the device finder: upload, sorts, windows, read-back, each timed behind a synchronise (0 with the host finder) */
+  double ms_parse;               /* parser + range coder (with the host finder: its finder too), summed over the threads */
+  double ms_wall;                /* the whole Save */
+} tm_save_stats;
+enum { TM_SAVE_FINDER_HOST = 0, TM_SAVE_FINDER_DEVICE = 1 };
+TM_API int tm_get_save_stats(tm_encoder *, tm_save_stats *out);
 /* LZDecompress, extern.pas:441-458: one stream; *out_n = decoded size (set even when cap is too small -> TM_E_INVAL),
  * *consumed (optional) = bytes of src the stream occupied, so that the next key frame's stream can follow. */
 TM_API int tm_lz_decompress_host(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *out_n, size_t *consumed);

@@ -124,6 +124,11 @@ SIGNATURES = {
     "tm_resample_taps_host": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tm_probe_scale_host": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "tm_scale_rgb32_host": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int]),
+    "tm_lz_matches_host": (c_int, [c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, c_void_p, c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "tm_lz_compress_from_matches_host": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "tm_stage_lz_matches": (c_int, [c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, c_void_p, c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                    c_void_p]),
+    "tm_stage_lz_compress": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "tm_stage_scale_rgb32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p]),
 }
 

@@ -96,6 +96,8 @@ struct tm_encoder {
   std::vector<int32_t> palettes_host;
   std::vector<uint8_t> h_fflags;
   double stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  tm_save_stats save_stats{};  // of the last Save (tm_get_save_stats)
+  bool has_save_stats = false;
   int shard_first = 0, shard_count = -1;  // query frames this process matches in Reconstruct (multi-GPU: one shard per rank)
   DevBuf pair_keys;          // the distinct pixel keys PreparePalettes' quantisation sorted out, for Dither (valid while pair_keys_n > 0:
   int64_t pair_keys_n = 0;   // every step that rewrites the global tiles zeroes it)

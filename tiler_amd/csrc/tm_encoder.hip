@@ -510,6 +510,13 @@ int tm_get_stage_ms(tm_encoder *e, double ms[8]) {
   return TM_OK;
 }
 
+int tm_get_save_stats(tm_encoder *e, tm_save_stats *out) {
+  TM_CHECK(e && out, TM_E_INVAL, "null argument");
+  TM_CHECK(e->has_save_stats, TM_E_INVAL, "save stats: this encoder has not saved a stream");
+  *out = e->save_stats;
+  return TM_OK;
+}
+
 void *tm_get_stream(tm_encoder *e) { return e ? (void *)e->stream : nullptr; }
 
 int tm_get_device_array(tm_encoder *e, int which, void **ptr, int64_t *count) {

@@ -27,7 +27,12 @@ int save_to(tm_encoder *e, const char *path) {  // Save, tilingencoder.pas:2040-
   TM_TRY(tm_get_tilemaps(e, 0, e->nframes, tmi.data()));
   in.tilemap = tmi.data();
   in.settings = settings_text(e->s);
-  return write_gtm(path, in);
+  // the key frames' streams are coded side by side, their match lists found on this encoder's device unless TM_SAVE_FINDER says otherwise
+  in.has_device = true; in.stream = e->stream; in.stats = &e->save_stats;
+  e->has_save_stats = false;
+  TM_TRY(write_gtm(path, in));
+  e->has_save_stats = true;
+  return TM_OK;
 }
 
 // ---- the decoded frames on the device (tm_render.hip): what tm_render_frames, tm_get_frame_quality and the exports draw

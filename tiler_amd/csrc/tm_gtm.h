@@ -62,6 +62,9 @@ struct GtmInput {
   int pal_count = 0, pal_size = 0;
   const tm_tilemap_item *tilemap = nullptr;  // [nframes][tm_h*tm_w]
   std::string settings;
+  bool has_device = false;          // the caller has set a device for this thread: the device match finder may run (TM_SAVE_FINDER)
+  void *stream = nullptr;           // its hipStream_t
+  tm_save_stats *stats = nullptr;   // filled when the file has been written
 };
 int write_gtm(const char *path, const GtmInput &in);
 // tm_lzma.hip (host only): LZCompress / LZDecompress, extern.pas:420-458

@@ -4,12 +4,20 @@
 // per key frame one LZMA stream (lz_compress, tm_lzma.hip) of 16-bit commands (data << 4 | cmd; 53-86, 5200-5206; the grammar: tm_gtm_walk.h):
 // ExtendedCommand(settings) + SetDimensions + TileSet(tiles with UseCount > 1) + LoadPalette x P in the first
 // keyframe, then per frame tile-map items / SkipBlocks (5392-5437) and FrameEnd.
+//
+// The command bytes of every key frame are built first, on the calling thread; the key frames' streams are independent, so they are then
+// coded side by side (lz_compress_jobs, tm_lz_matches.hip) and laid into the file in key-frame order.  Two switches, read at each Save:
+// TM_HOST_THREADS (parser threads, at most one per key frame and at most 16) and TM_SAVE_FINDER (host | device: where the match lists
+// are made; device only where the caller has one).  The file does not depend on either.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <thread>
 #include <vector>
 
 #include "tm_gtm_walk.h"
+#include "tm_lz_matches.h"
 
 namespace tmx {
 namespace {
@@ -23,10 +31,28 @@ struct Stream {
   void cmd(int c, uint32_t data) { u16((data << 4) | (uint32_t)c); }  // DoCmd, 5200-5206
 };
 
+// What Save's measurement on the MI355X decided: the finder an encoder with a device uses when TM_SAVE_FINDER is not set.
+constexpr bool kDeviceFinderByDefault = true;
+
+int save_threads() {  // TM_HOST_THREADS, or the machine's threads, at most 16
+  const char *env = getenv("TM_HOST_THREADS");
+  const int n = env ? atoi(env) : (int)std::thread::hardware_concurrency();
+  return std::max(1, std::min(16, n));
+}
+bool save_device_finder(bool has_device) {  // TM_SAVE_FINDER
+  if (!has_device) return false;
+  const char *env = getenv("TM_SAVE_FINDER");
+  if (env && !strcmp(env, "host")) return false;
+  if (env && !strcmp(env, "device")) return true;
+  return kDeviceFinderByDefault;
+}
+double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
 }  // namespace
 
 int write_gtm(const char *path, const GtmInput &in) {
   TM_CHECK(path && in.tm_w > 0 && in.tm_h > 0 && in.nframes > 0 && in.fps > 0 && !in.kf_start.empty(), TM_E_INVAL, "write_gtm: bad input");
+  const auto t_start = std::chrono::steady_clock::now();
   const int tm_size = in.tm_w * in.tm_h, nkf = (int)in.kf_start.size();
   const int64_t ntiles = (int64_t)in.use.size();
   std::vector<uint8_t> file(GTM_HEADER_BYTES + GTM_KF_BYTES * (size_t)nkf, 0);  // (filled in at the end: the sizes are known then)
@@ -67,9 +93,7 @@ int write_gtm(const char *path, const GtmInput &in) {
       z.u32(col | 0xff000000u);
     }
   }
-  double avg_bytes = 0;
-  uint32_t kf_max = 0;
-  int last_kf = 0;
+  std::vector<std::vector<uint8_t>> raw((size_t)nkf);  // the key frames' command bytes
   for (int k = 0; k < nkf; k++) {
     const int f0 = in.kf_start[k], f1 = (k + 1 < nkf ? in.kf_start[k + 1] : in.nframes) - 1;
     for (int f = f0; f <= f1; f++) {
@@ -125,19 +149,32 @@ int write_gtm(const char *path, const GtmInput &in) {
       TM_CHECK(cs == tm_size && skip == 0, TM_E_INVAL, "write_gtm: incomplete tile map (frame %d)", f);
       const bool is_kf_end = f == f1;
       z.cmd(gtFrameEnd, is_kf_end ? 1 : 0);
-      if (is_kf_end) {
-        const int kf_count = f1 - last_kf + 1;
-        last_kf = f1 + 1;
-        const size_t before = file.size();
-        lz_compress(z.b, file);
-        const uint32_t kf_size = (uint32_t)(file.size() - before);
-        entries[(size_t)k].raw_size = (uint32_t)z.b.size();
-        entries[(size_t)k].comp_size = kf_size;
-        if (k > 0 || nkf == 1) kf_max = std::max(kf_max, (uint32_t)llrint(kf_size * in.fps / kf_count));
-        avg_bytes += kf_size;
-        z.b.clear();
-      }
+      if (is_kf_end) { raw[(size_t)k].swap(z.b); z.b.clear(); }
     }
+  }
+  const double ms_commands = ms_since(t_start);
+  std::vector<LzJob> jobs((size_t)nkf);
+  for (int k = 0; k < nkf; k++) { jobs[(size_t)k].src = raw[(size_t)k].data(); jobs[(size_t)k].n = raw[(size_t)k].size(); }
+  const bool device_finder = save_device_finder(in.has_device);
+  LzJobsReport report;
+  TM_TRY(lz_compress_jobs(jobs, save_threads(), device_finder, in.stream, &report));
+  double avg_bytes = 0;
+  uint32_t kf_max = 0;
+  int last_kf = 0;
+  int64_t raw_sum = 0, comp_sum = 0;
+  for (int k = 0; k < nkf; k++) {
+    const int f1 = (k + 1 < nkf ? in.kf_start[k + 1] : in.nframes) - 1;
+    const int kf_count = f1 - last_kf + 1;
+    last_kf = f1 + 1;
+    const std::vector<uint8_t> &lz = jobs[(size_t)k].out;
+    file.insert(file.end(), lz.begin(), lz.end());
+    const uint32_t kf_size = (uint32_t)lz.size();
+    entries[(size_t)k].raw_size = (uint32_t)raw[(size_t)k].size();
+    entries[(size_t)k].comp_size = kf_size;
+    if (k > 0 || nkf == 1) kf_max = std::max(kf_max, (uint32_t)llrint(kf_size * in.fps / kf_count));
+    avg_bytes += kf_size;
+    raw_sum += (int64_t)raw[(size_t)k].size();
+    comp_sum += kf_size;
   }
   head.avg_bytes_per_s = (uint32_t)llrint(avg_bytes * in.fps / in.nframes);
   head.kf_max_bytes_per_s = kf_max;
@@ -148,6 +185,9 @@ int write_gtm(const char *path, const GtmInput &in) {
   const size_t w = fwrite(file.data(), 1, file.size(), fp);
   fclose(fp);
   TM_CHECK(w == file.size(), TM_E_IO, "short write to %s", path);
+  if (in.stats)
+    *in.stats = tm_save_stats{raw_sum, comp_sum, nkf, report.threads, device_finder ? TM_SAVE_FINDER_DEVICE : TM_SAVE_FINDER_HOST, 0, ms_commands, report.finder_ms,
+                              report.parse_ms, ms_since(t_start)};
   return TM_OK;
 }
 

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "tm_gtm.h"
+#include "tm_lz_matches.h"
 
 namespace tmx {
 namespace {
@@ -61,12 +62,83 @@ struct LenCoder {
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// The incremental match finder: the rule of tm_lz_matches.h as a forward pass.  An exact 2-byte table, 3-byte and 4-byte hash heads and a
+// chain on the latter; find(i) first inserts every position below i, so what it returns depends on (src, n, i) alone.  The two quick rejects
+// in the chain walk (the byte at `best`, the first byte) drop only candidates that could not have set a record.
+class IncrementalFinder : public lzm::MatchSource {
+ public:
+  IncrementalFinder(const uint8_t *src, size_t n)
+      : src_(src), n_(n), head2_((size_t)1 << lzm::kBits2, -1), head3_((size_t)1 << lzm::kBits3, -1), head4_((size_t)1 << lzm::kBits4, -1), chain_(n ? n : 1, -1) {}
+  // (length, distance - 1) pairs at position i, lengths strictly increasing; inserts i.  Positions must come in order.
+  int find(size_t i, uint32_t *lens, uint32_t *dists) override {
+    if (mf_pos_ == i + 1 && last_i_ == i) {  // asked again for the position a parse ended on: the lists it got then
+      for (int q = 0; q < last_np_; q++) { lens[q] = last_lens_[q]; dists[q] = last_dists_[q]; }
+      return last_np_;
+    }
+    while (mf_pos_ < i) insert(mf_pos_++);
+    const size_t max_len = lzm::max_len_at(n_, i);
+    int np = 0;
+    size_t best = 1;
+    if (max_len >= 2) {
+      const int32_t c2 = head2_[lzm::key2(src_ + i)];
+      if (c2 >= 0 && i - (size_t)c2 <= lzm::kDict) {
+        best = match_len(i, (size_t)c2, 2, max_len);
+        lens[np] = (uint32_t)best; dists[np++] = (uint32_t)(i - (size_t)c2 - 1);
+      }
+      if (max_len >= 3 && best < max_len) {
+        const int32_t c3 = head3_[lzm::h3(src_ + i)];
+        if (c3 >= 0 && c3 != c2 && i - (size_t)c3 <= lzm::kDict && src_[c3] == src_[i] && src_[c3 + 1] == src_[i + 1] && src_[c3 + 2] == src_[i + 2]) {
+          const size_t l = match_len(i, (size_t)c3, 3, max_len);
+          if (l > best) { best = l; lens[np] = (uint32_t)l; dists[np++] = (uint32_t)(i - (size_t)c3 - 1); }
+        }
+      }
+      if (max_len >= 4 && best < max_len) {
+        int32_t c = head4_[lzm::h4(src_ + i)];
+        for (int depth = 0; c >= 0 && depth < lzm::kDepth; depth++, c = chain_[c]) {
+          const size_t dist = i - (size_t)c;
+          if (dist > lzm::kDict) break;
+          if (src_[c + best] != src_[i + best] || src_[c] != src_[i]) continue;
+          const size_t l = match_len(i, (size_t)c, 0, max_len);
+          if (l > best) {
+            best = l; lens[np] = (uint32_t)l; dists[np++] = (uint32_t)(dist - 1);
+            if (l == max_len) break;
+          }
+        }
+      }
+    }
+    insert(i);
+    mf_pos_ = i + 1;
+    last_i_ = i; last_np_ = np;
+    for (int q = 0; q < np; q++) { last_lens_[q] = lens[q]; last_dists_[q] = dists[q]; }
+    return np;
+  }
+
+ private:
+  void insert(size_t i) {
+    if (i + 2 <= n_) head2_[lzm::key2(src_ + i)] = (int32_t)i;
+    if (i + 3 <= n_) head3_[lzm::h3(src_ + i)] = (int32_t)i;
+    if (i + 4 <= n_) { const uint32_t h = lzm::h4(src_ + i); chain_[i] = head4_[h]; head4_[h] = (int32_t)i; }
+  }
+  size_t match_len(size_t a, size_t b, size_t from, size_t max_len) const {  // a > b
+    size_t l = from;
+    while (l < max_len && src_[a + l] == src_[b + l]) l++;
+    return l;
+  }
+  const uint8_t *src_;
+  size_t n_, mf_pos_ = 0;
+  std::vector<int32_t> head2_, head3_, head4_, chain_;
+  size_t last_i_ = (size_t)-1;
+  int last_np_ = 0;
+  uint32_t last_lens_[lzm::kMaxPairs], last_dists_[lzm::kMaxPairs];
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // The coder: LZMA-alone with lc/lp/pb as LZCompress sets them (SetLcLpPb(8,0,2), end marker on: extern.pas:429-430), priced optimal
 // parsing.  LZMA/ULZMAEncoder.pas (the Pascal port of the LZMA SDK the reference links) chooses its literals / matches / repeated matches by
 // dynamic programming over bit prices; round 1's greedy parser left 12 % on the table on the reference's own command streams.  This one
 // restates that scheme in its own structure:
-//  * match finder: exact 2-byte table, 3-byte and 4-byte hashes with a chain on the latter; per position the list of (length, nearest
-//    distance) pairs of strictly increasing length;
+//  * match lists: per position the (length, nearest distance) pairs of strictly increasing length, from a source -- the incremental
+//    finder above, or a table somebody made by the same rule (the device finder, tm_lz_matches.hip);
 //  * prices in 1/16 bit from the live probabilities (bit prices tabulated per 16 probability steps); length and distance price tables
 //    refreshed every 64 lengths / 128 matches, literal and choice prices read directly;
 //  * a window of up to 4096 positions: every node keeps the cheapest way to reach it with the state and the four repeat distances that
@@ -77,8 +149,8 @@ struct LenCoder {
 // reference's own command stream, is gone.)
 class LzmaOptEncoder {
  public:
-  static constexpr int kLc = 8, kLp = 0, kPb = 2, kNice = 128, kOpts = 4096, kDepth = 96;
-  static constexpr uint32_t kDict = 1u << 22, kInf = 1u << 30;
+  static constexpr int kLc = 8, kLp = 0, kPb = 2, kNice = 128, kOpts = 4096;
+  static constexpr uint32_t kDict = lzm::kDict, kInf = 1u << 30;
 
   explicit LzmaOptEncoder(std::vector<uint8_t> &out) : rc_(out), lit_((size_t)0x300 << (kLc + kLp), 1024), opt_(kOpts) {
     for (auto &r : is_match_) for (auto &p : r) p = 1024;
@@ -96,13 +168,11 @@ class LzmaOptEncoder {
     }
   }
 
-  void encode(const uint8_t *src, size_t n) {
-    src_ = src; n_ = n;
-    head2_.assign(1 << 16, -1); head3_.assign(1 << 16, -1); head4_.assign(1 << 20, -1); chain_.assign(n ? n : 1, -1);
+  void encode(const uint8_t *src, size_t n, lzm::MatchSource *source) {
+    src_ = src; n_ = n; source_ = source;
     fill_len_prices(len_, len_prices_); fill_len_prices(rep_len_, rep_len_prices_);
     fill_dist_prices(); fill_align_prices();
     len_counter_ = rep_len_counter_ = 64; match_counter_ = 0; align_counter_ = 0;
-    mf_pos_ = 0;
     size_t pos = 0;
     while (pos < n) {
       const int nsteps = optimum(pos);
@@ -209,62 +279,13 @@ class LzmaOptEncoder {
   static uint32_t st_rep(uint32_t s) { return s < 7 ? 8 : 11; }
   static uint32_t st_shortrep(uint32_t s) { return s < 7 ? 9 : 11; }
 
-  // ---- match finder
-  static uint32_t h3(const uint8_t *p) { return (uint32_t)((p[0] | (p[1] << 8) | (p[2] << 16)) * 2654435761u) >> 16; }
-  static uint32_t h4(const uint8_t *p) { return (uint32_t)((p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24)) * 2654435761u) >> 12; }
-  void mf_insert(size_t i) {
-    if (i + 2 <= n_) head2_[src_[i] | (src_[i + 1] << 8)] = (int32_t)i;
-    if (i + 3 <= n_) head3_[h3(src_ + i)] = (int32_t)i;
-    if (i + 4 <= n_) { const uint32_t h = h4(src_ + i); chain_[i] = head4_[h]; head4_[h] = (int32_t)i; }
-  }
+  // ---- match finder: the lists come from the source (tm_lz_matches.h); every position at most once, in order
   size_t match_len(size_t a, size_t b, size_t from, size_t max_len) const {  // a > b
     size_t l = from;
     while (l < max_len && src_[a + l] == src_[b + l]) l++;
     return l;
   }
-  // (length, distance - 1) pairs at position i, lengths strictly increasing; inserts i.  Positions must come in order.
-  int mf_find(size_t i, uint32_t *lens, uint32_t *dists) {
-    if (mf_pos_ == i + 1 && last_i_ == i) {  // asked again for the position a parse ended on: the lists it got then
-      for (int q = 0; q < last_np_; q++) { lens[q] = last_lens_[q]; dists[q] = last_dists_[q]; }
-      return last_np_;
-    }
-    while (mf_pos_ < i) mf_insert(mf_pos_++);
-    const size_t max_len = std::min<size_t>(273, n_ - i);
-    int np = 0;
-    size_t best = 1;
-    if (max_len >= 2) {
-      const int32_t c2 = head2_[src_[i] | (src_[i + 1] << 8)];
-      if (c2 >= 0 && i - (size_t)c2 <= kDict) {
-        best = match_len(i, (size_t)c2, 2, max_len);
-        lens[np] = (uint32_t)best; dists[np++] = (uint32_t)(i - (size_t)c2 - 1);
-      }
-      if (max_len >= 3 && best < max_len) {
-        const int32_t c3 = head3_[h3(src_ + i)];
-        if (c3 >= 0 && c3 != c2 && i - (size_t)c3 <= kDict && src_[c3] == src_[i] && src_[c3 + 1] == src_[i + 1] && src_[c3 + 2] == src_[i + 2]) {
-          const size_t l = match_len(i, (size_t)c3, 3, max_len);
-          if (l > best) { best = l; lens[np] = (uint32_t)l; dists[np++] = (uint32_t)(i - (size_t)c3 - 1); }
-        }
-      }
-      if (max_len >= 4 && best < max_len) {
-        int32_t c = head4_[h4(src_ + i)];
-        for (int depth = 0; c >= 0 && depth < kDepth; depth++, c = chain_[c]) {
-          const size_t dist = i - (size_t)c;
-          if (dist > kDict) break;
-          if (src_[c + best] != src_[i + best] || src_[c] != src_[i]) continue;
-          const size_t l = match_len(i, (size_t)c, 0, max_len);
-          if (l > best) {
-            best = l; lens[np] = (uint32_t)l; dists[np++] = (uint32_t)(dist - 1);
-            if (l == max_len) break;
-          }
-        }
-      }
-    }
-    mf_insert(i);
-    mf_pos_ = i + 1;
-    last_i_ = i; last_np_ = np;
-    for (int q = 0; q < np; q++) { last_lens_[q] = lens[q]; last_dists_[q] = dists[q]; }
-    return np;
-  }
+  int mf_find(size_t i, uint32_t *lens, uint32_t *dists) { return source_->find(i, lens, dists); }
 
   // ---- the parse of one stretch starting at pos: fills steps_, returns their number
   int optimum(size_t pos) {
@@ -513,26 +534,37 @@ class LzmaOptEncoder {
   uint32_t state_ = 0;
   size_t reps_[4] = {0, 0, 0, 0};
   const uint8_t *src_ = nullptr;
-  size_t n_ = 0, mf_pos_ = 0;
-  std::vector<int32_t> head2_, head3_, head4_, chain_;
+  size_t n_ = 0;
+  lzm::MatchSource *source_ = nullptr;
   std::vector<Opt> opt_;
   Step steps_[kOpts + 8], rev_[kOpts + 8];
   uint32_t bit_price_[128];
   uint32_t len_prices_[4][272], rep_len_prices_[4][272], slot_prices_[4][64], dist_prices_[4][128], align_prices_[16];
   int len_counter_ = 64, rep_len_counter_ = 64, match_counter_ = 0, align_counter_ = 0;
-  size_t last_i_ = (size_t)-1;
-  int last_np_ = 0;
-  uint32_t last_lens_[280], last_dists_[280];
 };
 
 }  // namespace
 
-void lz_compress(const std::vector<uint8_t> &raw, std::vector<uint8_t> &dst) {  // LZCompress, extern.pas:420-439
+void lz_compress_from(const uint8_t *src, size_t n, lzm::MatchSource *source, std::vector<uint8_t> &dst) {  // LZCompress, extern.pas:420-439
   dst.push_back((uint8_t)((LzmaOptEncoder::kPb * 5 + LzmaOptEncoder::kLp) * 9 + LzmaOptEncoder::kLc));  // 0x62
   for (int i = 0; i < 4; i++) dst.push_back((uint8_t)(LzmaOptEncoder::kDict >> (8 * i)));
   for (int i = 0; i < 8; i++) dst.push_back(0xFF);
+  std::unique_ptr<IncrementalFinder> own;
+  if (!source) { own = std::make_unique<IncrementalFinder>(src, n); source = own.get(); }
   auto enc = std::make_unique<LzmaOptEncoder>(dst);  // (its parse window lives in the object: not on the stack)
-  enc->encode(raw.data(), raw.size());
+  enc->encode(src, n, source);
+}
+
+void lz_compress(const std::vector<uint8_t> &raw, std::vector<uint8_t> &dst) { lz_compress_from(raw.data(), raw.size(), nullptr, dst); }
+
+void lz_matches_host(const uint8_t *src, size_t n, size_t first, size_t count, uint8_t *counts, std::vector<lzm::Pair> &pairs) {
+  IncrementalFinder finder(src, n);
+  uint32_t lens[lzm::kMaxPairs], dists[lzm::kMaxPairs];
+  for (size_t i = first; i < first + count; i++) {
+    const int np = finder.find(i, lens, dists);  // (inserts what lies below `first` on its first call)
+    counts[i - first] = (uint8_t)np;
+    for (int q = 0; q < np; q++) pairs.push_back(lzm::Pair{(uint16_t)lens[q], 0, dists[q]});
+  }
 }
 
 }  // namespace tmx
@@ -682,6 +714,41 @@ extern "C" int tm_lz_compress_host(const uint8_t *src, size_t n, uint8_t *dst, s
   tmx::lz_compress(raw, out);
   *out_n = out.size();
   if (!dst || cap < out.size()) { tmx::set_error("tm_lz_compress_host: %zu bytes needed, %zu given", out.size(), cap); return TM_E_INVAL; }
+  memcpy(dst, out.data(), out.size());
+  return TM_OK;
+}
+
+// The finder's lists of positions [first, first + count), as a forward pass would have them there: counts_u8[count], pairs in position
+// order; *npairs = pairs needed/written; TM_E_INVAL if cap_pairs is too small.
+extern "C" int tm_lz_matches_host(const uint8_t *src, size_t n, size_t first, size_t count, uint8_t *counts_u8, tm_lz_pair *pairs, size_t cap_pairs,
+                                  size_t *npairs) {
+  if ((!src && n) || !npairs || (!counts_u8 && count)) { tmx::set_error("tm_lz_matches_host: null argument"); return TM_E_INVAL; }
+  if (n >= ((size_t)1 << 31)) { tmx::set_error("tm_lz_matches_host: streams of 2^31 bytes or more are not supported"); return TM_E_UNSUPPORTED; }
+  if (first > n || count > n - first) { tmx::set_error("tm_lz_matches_host: positions [%zu,+%zu) outside the %zu bytes", first, count, n); return TM_E_INVAL; }
+  std::vector<tmx::lzm::Pair> out;
+  tmx::lz_matches_host(src, n, first, count, counts_u8, out);
+  *npairs = out.size();
+  if (out.size() > cap_pairs || (!pairs && !out.empty())) { tmx::set_error("tm_lz_matches_host: %zu pairs needed, %zu given", out.size(), cap_pairs); return TM_E_INVAL; }
+  if (!out.empty()) memcpy(pairs, out.data(), out.size() * sizeof(tmx::lzm::Pair));
+  return TM_OK;
+}
+
+// The parser and range coder on lists the caller supplies for all n positions (the capacity convention of tm_lz_compress_host).  The lists
+// are trusted to be the finder's: a pair that is no match gives a stream that decodes to other bytes.
+extern "C" int tm_lz_compress_from_matches_host(const uint8_t *src, size_t n, const uint8_t *counts_u8, const tm_lz_pair *pairs, uint8_t *dst, size_t cap,
+                                                size_t *out_n) {
+  if ((!src && n) || (!counts_u8 && n) || !out_n) { tmx::set_error("tm_lz_compress_from_matches_host: null argument"); return TM_E_INVAL; }
+  size_t total = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (counts_u8[i] > tmx::lzm::kMaxPairs) { tmx::set_error("tm_lz_compress_from_matches_host: %d pairs at position %zu", (int)counts_u8[i], i); return TM_E_INVAL; }
+    total += counts_u8[i];
+  }
+  if (total && !pairs) { tmx::set_error("tm_lz_compress_from_matches_host: null argument"); return TM_E_INVAL; }
+  tmx::lzm::TableSource table(counts_u8, reinterpret_cast<const tmx::lzm::Pair *>(pairs));
+  std::vector<uint8_t> out;
+  tmx::lz_compress_from(src, n, &table, out);
+  *out_n = out.size();
+  if (!dst || cap < out.size()) { tmx::set_error("tm_lz_compress_from_matches_host: %zu bytes needed, %zu given", out.size(), cap); return TM_E_INVAL; }
   memcpy(dst, out.data(), out.size());
   return TM_OK;
 }

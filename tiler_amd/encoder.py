@@ -454,6 +454,21 @@ class TilingEncoder:
         else:
             check(self._L.tm_save_gtm(c_void_p(self._h), os.fsencode(path)))
 
+    def SaveStats(self):
+        """What the last Save did (tm_get_save_stats): raw and compressed bytes, key frames, the parser threads and the match finder
+        ("host" or "device") that ran, and its milliseconds: the command bytes, the device finder, the parse summed over threads, the wall clock"""
+        class _Stats(ctypes.Structure):  # tm_save_stats
+            _fields_ = [("raw_bytes", c_int64), ("comp_bytes", c_int64), ("key_frames", ctypes.c_int32), ("threads", ctypes.c_int32),
+                        ("finder", ctypes.c_int32), ("reserved", ctypes.c_int32), ("ms_commands", c_double), ("ms_finder", c_double),
+                        ("ms_parse", c_double), ("ms_wall", c_double)]
+        st = _Stats()
+        self._L.tm_get_save_stats.restype = c_int
+        self._L.tm_get_save_stats.argtypes = [c_void_p, c_void_p]
+        check(self._L.tm_get_save_stats(c_void_p(self._h), ctypes.byref(st)))
+        out = {name: getattr(st, name) for name, _ in _Stats._fields_ if name != "reserved"}
+        out["finder"] = "device" if st.finder == 1 else "host"
+        return out
+
     def GenerateY4M(self, path, input=False):
         """GenerateY4M (tilingencoder.pas:2126): the rendered output frames (or the source frames) as a C444 .y4m"""
         check(self._L.tm_generate_y4m(c_void_p(self._h), os.fsencode(path), int(bool(input))))

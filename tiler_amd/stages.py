@@ -502,3 +502,36 @@ def frame_quality(a, b):
     allsum = int(tot.sum())
     clip_psnr = 10.0 * np.log10(peak * f / allsum) if allsum else float("inf")
     return dict(sse=sse, ssim_y=ssim, psnr=psnr, clip_psnr=float(clip_psnr), clip_ssim_y=_mean_in_order(s))
+
+
+LZ_PAIR = np.dtype([("len", "<u2"), ("zero", "<u2"), ("dist", "<u4")])  # tm_lz_pair: a match of `len` bytes at distance `dist` + 1
+
+
+def lz_matches(src, first=0, count=None):
+    """The LZMA coder's match lists of positions [first, first + count) of a stream, found on the device (tm_stage_lz_matches; the rule:
+    include/tilemotion.h): src = torch uint8 CUDA tensor [n] -> (counts uint8 CUDA [count], pairs numpy LZ_PAIR [sum of counts], position
+    order), pair for pair what tm_lz_matches_host returns"""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.dim() == 1 and src.is_contiguous()
+    n = src.numel()
+    count = n - first if count is None else count
+    counts = torch.zeros((max(count, 1),), dtype=torch.uint8, device=src.device)
+    need = ctypes.c_size_t()
+    rc = lib().tm_stage_lz_matches(_p(src), n, first, count, _p(counts), None, 0, ctypes.byref(need), _stream())
+    if rc == 0:  # no pairs at all
+        return counts[:count], np.zeros(0, LZ_PAIR)
+    if need.value == 0:
+        check(rc)
+    pairs = torch.zeros((need.value, 2), dtype=torch.int32, device=src.device)
+    check(lib().tm_stage_lz_matches(_p(src), n, first, count, _p(counts), _p(pairs), need.value, ctypes.byref(need), _stream()))
+    return counts[:count], pairs.cpu().numpy().view(LZ_PAIR).reshape(-1)
+
+
+def lz_compress(data):
+    """LZCompress (extern.pas:420-439) with the match lists from the device finder and the host parser behind it (tm_stage_lz_compress):
+    bytes -> bytes, exactly tm_lz_compress_host's"""
+    src = np.frombuffer(bytes(data), np.uint8)
+    cap = src.size + src.size // 4 + 64
+    dst = np.zeros(cap, np.uint8)
+    n = ctypes.c_size_t()
+    check(lib().tm_stage_lz_compress(src.ctypes.data_as(ctypes.c_void_p) if src.size else None, src.size, dst.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(n)))
+    return dst[:n.value].tobytes()

@@ -10,7 +10,7 @@ S="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
 mkdir -p "$OUT"
 "$CLANG" -O1 -g $S -Wall -I"$ROOT/include" -c "$ROOT/tests/c/player_parse.c" -o "$OUT/player_parse.o"
 objs=("$OUT/player_parse.o")
-for f in tm_player_parse tm_gtm tm_lzma tm_tables; do
+for f in tm_player_parse tm_gtm tm_lzma tm_lz_matches tm_tables; do  # (tm_lz_matches: the key frames' coder threads behind the writer)
   "$HIPCC" --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
     -c "$ROOT/tiler_amd/csrc/$f.hip" -o "$OUT/$f.o" &
   objs+=("$OUT/$f.o")
