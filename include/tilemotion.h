@@ -113,7 +113,8 @@ enum {
   TM_E_HIP = -3,       /* a HIP runtime call failed */
   TM_E_NOMEM = -4,
   TM_E_IO = -5,
-  TM_E_UNSUPPORTED = -6 /* reference feature outside the hot path */
+  TM_E_UNSUPPORTED = -6, /* reference feature outside the hot path */
+  TM_E_INTERNAL = -7     /* the library contradicted itself (a bug: the message says where); nothing was written */
 };
 
 /* TEncoderStep, tilingencoder.pas:18 */
@@ -428,6 +429,56 @@ TM_API int tm_lz_decompress_host(const uint8_t *src, size_t n, uint8_t *dst, siz
  * palettes, one 'FFBBGGRR' line per colour.  Host code (export tooling); the Y4M planes are made on the device (TM_YUV_TILER) and cross as 3 bytes a pixel. */
 TM_API int tm_generate_y4m(tm_encoder *, const char *path, int input);
 TM_API int tm_generate_pngs(tm_encoder *, int input);
+/* ---- Compressed PNG export: row filters and deflate on the device (tm_png_out.hip; the rule: tm_deflate.h) ----------
+ * level 0 (the default) writes the picture in stored blocks, the bytes GeneratePNGs has always written.  level 1 codes the filtered rows --
+ * colour type 2, 8 bits, one IDAT -- in segments of 32768 stream bytes: per position the longest match among the 32 nearest earlier
+ * positions with the same three bytes within 32768 bytes (never past the segment's end; a match of 3 further than 4096 back is dropped), a
+ * greedy parse, and per segment one dynamic-Huffman block (length-limited codes) or a stored block when that is no larger, an empty
+ * stored block between segments.  The file is a function of the pixels and the options alone: the device form (filter, key sort, match,
+ * parse, histograms, pack and compaction in kernels; the code lengths on up to min(TM_HOST_THREADS, 16) host threads, one round trip per
+ * chunk of frames) and the host twin write the same bytes.
+ *   filter: NONE = type 0 on every row; ADAPTIVE = per row the type 0..4 with the least sum of |(int8) byte| (ties to the lowest type);
+ * SMALLER = both are coded, the shorter file is kept (a tie: NONE); AUTO = NONE for the Output page, ADAPTIVE for the Input page, resolved
+ * by tm_generate_pngs -- the seams below take AUTO as NONE.
+ *   tm_set_png_options: what tm_generate_pngs writes from then on (TM_E_INVAL: null, unknown level or filter).  tm_get_export_stats: the
+ * last tm_generate_pngs (TM_E_INVAL before the first): ms_device = render, coding and read-back, ms_write = the files (at level 0 with
+ * the host's packing of the pixels into them), both inside ms_wall.
+ *   tm_png_bound_host: an upper bound of one file's size for any options (TM_E_INVAL: w or h outside 1 .. 32768, a stream of 2^31 bytes or more).
+ *   tm_stage_png_encode: nframes pictures [h][w] of 0x00RRGGBB in DEVICE memory, rows stride_px apart, frames frame_px apart (pixels), as
+ * files laid one behind the other in HOST memory host_out, file f at [offsets[f], offsets[f + 1]).  tm_png_encode_host: the same from HOST
+ * frames without a device, byte for byte.  tm_stage_zlib_compress / tm_zlib_compress_host: the stream coder alone, n bytes to one zlib
+ * stream.  Refusals, TM_E_INVAL before any device call and with nothing written: a null pointer, an unknown level or filter, w or h
+ * outside 1 .. 32768, n >= 2^31, nframes < 0, a row stride shorter than the row with more than one row, a frame stride shorter than a
+ * frame with more than one frame.  A cap too small is TM_E_INVAL too, with offsets[nframes] (or *out_n) set to the bytes needed and
+ * host_out untouched; it can only be known once the pictures are coded, and the coded files are dropped: size host_out by
+ * tm_png_bound_host (nframes times it for tm_stage_png_encode, n + 10 (n / 32768 + 1) + 6 for a stream) and the call is made once.
+ * The stage calls return synchronised.
+ *   tm_png_filter_rows_host: the stream the coder sees, h (1 + 3 w) bytes (filter NONE or ADAPTIVE).  tm_deflate_code_lengths_host: the
+ * rule's length-limited code lengths of nsym (2 .. 288) frequencies, max_bits 1 .. 15 with 2^max_bits >= nsym. */
+enum { TM_PNG_FILTER_AUTO = 0, TM_PNG_FILTER_NONE = 1, TM_PNG_FILTER_ADAPTIVE = 2, TM_PNG_FILTER_SMALLER = 3 };
+typedef struct tm_png_options {
+  int32_t level;  /* 0: stored blocks, today's bytes (default); 1: the rule above */
+  int32_t filter; /* TM_PNG_FILTER_*; level 0 ignores it */
+} tm_png_options;
+typedef struct tm_export_stats {
+  int64_t frames, file_bytes; /* files written and the sum of their sizes */
+  int32_t level, filter;      /* the options that held (level 1: AUTO resolved; level 0: the filter as set, it is not used) */
+  double ms_device;           /* render, coding and read-back of the chunks, each behind a synchronise */
+  double ms_write;            /* writing the files (level 0: packing the pixels into them too) */
+  double ms_wall;             /* the whole call */
+} tm_export_stats;
+TM_API int tm_set_png_options(tm_encoder *, const tm_png_options *opt);
+TM_API int tm_get_png_options(tm_encoder *, tm_png_options *opt);
+TM_API int tm_get_export_stats(tm_encoder *, tm_export_stats *out);
+TM_API int tm_png_bound_host(int w, int h, int64_t *bytes);
+TM_API int tm_stage_png_encode(const uint32_t *dev_frames, int64_t stride_px, int64_t frame_px, int nframes, int w, int h, const tm_png_options *opt,
+                               uint8_t *host_out, int64_t cap, int64_t *offsets /* nframes + 1 */, void *stream);
+TM_API int tm_png_encode_host(const uint32_t *frames, int64_t stride_px, int64_t frame_px, int nframes, int w, int h, const tm_png_options *opt,
+                              uint8_t *out, int64_t cap, int64_t *offsets /* nframes + 1 */);
+TM_API int tm_stage_zlib_compress(const uint8_t *dev_src, int64_t n, uint8_t *host_out, int64_t cap, int64_t *out_n, void *stream);
+TM_API int tm_zlib_compress_host(const uint8_t *src, int64_t n, uint8_t *out, int64_t cap, int64_t *out_n);
+TM_API int tm_png_filter_rows_host(const uint32_t *frame, int64_t stride_px, int w, int h, int filter, uint8_t *stream);
+TM_API int tm_deflate_code_lengths_host(const uint32_t *freq, int nsym, int max_bits, uint8_t *lens);
 /* The same pictures rendered on the device (Render :3455-3640, Output tab with the constructor's defaults; or the Input tab: input != 0):
  * frames [first_frame, first_frame+frame_count) as [frame_count][tm_h*8][tm_w*8] uint32 0x00RRGGBB (the format frames are pushed in; the
  * input render is every pushed frame cropped to tm_w*8 x tm_h*8 with alpha 0).  A predicted item is frame f-1's output at its offset,

@@ -40,6 +40,15 @@ class RenderViewDesc(ctypes.Structure):  # tm_render_view: Render's switches (32
                 ("use_gamma", ctypes.c_int32), ("palette_index", ctypes.c_int32), ("gamma", c_double)]
 
 
+class PngOptions(ctypes.Structure):  # tm_png_options
+    _fields_ = [("level", ctypes.c_int32), ("filter", ctypes.c_int32)]
+
+
+class ExportStatsDesc(ctypes.Structure):  # tm_export_stats
+    _fields_ = [("frames", c_int64), ("file_bytes", c_int64), ("level", ctypes.c_int32), ("filter", ctypes.c_int32),
+                ("ms_device", c_double), ("ms_write", c_double), ("ms_wall", c_double)]
+
+
 RENDER_PAGES = {"input": 0, "output": 1, "tiles": 2}  # TM_RENDER_PAGE_*
 
 
@@ -130,7 +139,29 @@ SIGNATURES = {
                                     c_void_p]),
     "tm_stage_lz_compress": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "tm_stage_scale_rgb32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p]),
+    "tm_set_png_options": (c_int, [c_void_p, ctypes.POINTER(PngOptions)]),
+    "tm_get_png_options": (c_int, [c_void_p, ctypes.POINTER(PngOptions)]),
+    "tm_get_export_stats": (c_int, [c_void_p, ctypes.POINTER(ExportStatsDesc)]),
+    "tm_png_bound_host": (c_int, [c_int, c_int, ctypes.POINTER(c_int64)]),
+    "tm_stage_png_encode": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, ctypes.POINTER(PngOptions), c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    "tm_png_encode_host": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, ctypes.POINTER(PngOptions), c_void_p, c_int64, ctypes.POINTER(c_int64)]),
+    "tm_stage_zlib_compress": (c_int, [c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    "tm_zlib_compress_host": (c_int, [c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(c_int64)]),
+    "tm_png_filter_rows_host": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "tm_deflate_code_lengths_host": (c_int, [c_void_p, c_int, c_int, c_void_p]),
 }
+
+
+PNG_FILTERS = {"auto": 0, "none": 1, "adaptive": 2, "smaller": 3}  # TM_PNG_FILTER_*
+
+
+def png_options(level=1, filter="auto"):
+    """tm_png_options from the keywords SetPngOptions / stages.png_encode take"""
+    if isinstance(filter, str):
+        if filter not in PNG_FILTERS:
+            raise ValueError("unknown PNG filter strategy %r (one of %s)" % (filter, " ".join(PNG_FILTERS)))
+        filter = PNG_FILTERS[filter]
+    return PngOptions(int(level), int(filter))
 
 
 SCALE_FILTERS = {"lanczos": 0, "nearest": 1}  # TM_SCALE_*

@@ -98,6 +98,9 @@ struct tm_encoder {
   double stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   tm_save_stats save_stats{};  // of the last Save (tm_get_save_stats)
   bool has_save_stats = false;
+  tm_png_options png_options{0, TM_PNG_FILTER_AUTO};  // what GeneratePNGs writes (tm_set_png_options); level 0: stored blocks
+  tm_export_stats export_stats{};                      // of the last GeneratePNGs (tm_get_export_stats)
+  bool has_export_stats = false;
   int shard_first = 0, shard_count = -1;  // query frames this process matches in Reconstruct (multi-GPU: one shard per rank)
   DevBuf pair_keys;          // the distinct pixel keys PreparePalettes' quantisation sorted out, for Dither (valid while pair_keys_n > 0:
   int64_t pair_keys_n = 0;   // every step that rewrites the global tiles zeroes it)

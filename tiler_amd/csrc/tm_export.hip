@@ -1,8 +1,10 @@
 // tm_export.hip -- what leaves the encoder as files or pictures: Save (.gtm), ReloadGTM, GenerateY4M / GeneratePNGs, and the device
 // render entry points tm_render_frames / tm_get_frame_quality (kernels in tm_render.hip).
+#include <chrono>
 #include <cmath>
 #include <fstream>
 
+#include "tm_deflate.h"
 #include "tm_encoder.h"
 #include "tm_gtm.h"
 
@@ -70,6 +72,7 @@ struct ExportFrames {
   tm_encoder *e;
   bool input;
   bool y4m = false;  // the frames come to the host as GenerateY4M's planes (Y, U, V of a frame in a row: 3 bytes a pixel), not as RGB32
+  bool keep = false; // the frames stay on the device as RGB32 (GeneratePNGs at level 1 codes them there): dev holds frames [first, first + count)
   RenderMap m{};
   RenderInput in{};
   int sw = 0, sh = 0, chunk = 0, first = 0, count = 0;
@@ -87,6 +90,7 @@ struct ExportFrames {
     const size_t fbytes = (size_t)sw * sh * 4;
     chunk = (int)std::max<size_t>(1, std::min<size_t>(32, ((size_t)256 << 20) / fbytes));  // 32 frames or 256 MB, whichever is less
     TM_TRY(dev.alloc(fbytes * chunk));
+    if (keep) return TM_OK;
     if (!y4m) { host.resize((size_t)sw * sh * chunk); return TM_OK; }
     const int64_t plane = (int64_t)sw * sh;
     TM_TRY(dev_yuv.alloc((size_t)plane * 3 * chunk));
@@ -106,12 +110,12 @@ struct ExportFrames {
       if (y4m) {
         TM_TRY(launch_rgb32_to_yuv(plan, dev.p, sw, count, yuv_dst_of(planes, 0), e->stream));
         TM_HIP(hipMemcpyAsync(host_yuv.data(), dev_yuv.p, (size_t)count * sw * sh * 3, hipMemcpyDeviceToHost, e->stream));
-      } else {
+      } else if (!keep) {
         TM_HIP(hipMemcpyAsync(host.data(), dev.p, (size_t)count * sw * sh * 4, hipMemcpyDeviceToHost, e->stream));
       }
       TM_HIP(hipStreamSynchronize(e->stream));
     }
-    if (px) *px = host.data() + (size_t)(f - first) * sw * sh;
+    if (px) *px = keep ? nullptr : host.data() + (size_t)(f - first) * sw * sh;  // (keep: the frames are in dev, none on the host)
     return TM_OK;
   }
   int frame_y4m(int f, const uint8_t **yuv) {
@@ -121,41 +125,12 @@ struct ExportFrames {
   }
 };
 
-void png_chunk(std::vector<uint8_t> &out, const char *type, const std::vector<uint8_t> &data) {
-  auto be32 = [&](uint32_t v) { out.push_back(v >> 24); out.push_back(v >> 16); out.push_back(v >> 8); out.push_back(v); };
-  be32((uint32_t)data.size());
-  const size_t at = out.size();
-  out.insert(out.end(), type, type + 4);
-  out.insert(out.end(), data.begin(), data.end());
-  be32(crc32_ieee(out.data() + at, out.size() - at));
-}
-// 24-bit RGB PNG (pf24bit, 2086) of 0x00RRGGBB pixels; the image data travels in stored deflate blocks: valid for every decoder, no codec dependency
-int write_png(const std::string &path, const uint32_t *img, int w, int h) {
-  std::vector<uint8_t> raw((size_t)h * (1 + (size_t)w * 3));
-  for (int y = 0; y < h; y++) {
-    uint8_t *row = &raw[(size_t)y * (1 + (size_t)w * 3)];
-    row[0] = 0;  // filter: none
-    for (int x = 0; x < w; x++) { const uint32_t c = img[(size_t)y * w + x]; row[1 + x * 3] = (c >> 16) & 0xff; row[2 + x * 3] = (c >> 8) & 0xff; row[3 + x * 3] = c & 0xff; }
-  }
-  std::vector<uint8_t> z = {0x78, 0x01};
-  uint32_t a = 1, b = 0;
-  for (uint8_t v : raw) { a = (a + v) % 65521u; b = (b + a) % 65521u; }
-  for (size_t off = 0; off < raw.size() || off == 0; off += 65535) {
-    const size_t n = std::min<size_t>(65535, raw.size() - off);
-    z.push_back(off + n >= raw.size() ? 1 : 0);
-    z.push_back(n & 0xff); z.push_back(n >> 8); z.push_back(~n & 0xff); z.push_back((~n >> 8) & 0xff);
-    z.insert(z.end(), raw.begin() + off, raw.begin() + off + n);
-    if (raw.empty()) break;
-  }
-  z.push_back(b >> 8); z.push_back(b); z.push_back(a >> 8); z.push_back(a);
-  std::vector<uint8_t> out = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
-  std::vector<uint8_t> ihdr = {(uint8_t)(w >> 24), (uint8_t)(w >> 16), (uint8_t)(w >> 8), (uint8_t)w, (uint8_t)(h >> 24), (uint8_t)(h >> 16), (uint8_t)(h >> 8), (uint8_t)h, 8, 2, 0, 0, 0};
-  png_chunk(out, "IHDR", ihdr);
-  png_chunk(out, "IDAT", z);
-  png_chunk(out, "IEND", {});
+// a finished PNG (pf24bit, 2086; its bytes are made by png_stored of tm_deflate.hip or on the device by tm_png_out.hip) to its file
+int write_file(const std::string &path, const std::vector<uint8_t> &bytes) {
   std::ofstream f(path, std::ios::binary);
   TM_CHECK(f.good(), TM_E_IO, "cannot write %s", path.c_str());
-  f.write((const char *)out.data(), (std::streamsize)out.size());
+  f.write((const char *)bytes.data(), (std::streamsize)bytes.size());
+  TM_CHECK(f.good(), TM_E_IO, "write to %s failed", path.c_str());
   return TM_OK;
 }
 std::string strip_ext(const std::string &p) {  // ChangeFileExt(name, '')
@@ -188,7 +163,13 @@ static int generate_y4m(tm_encoder *e, const char *path, bool input) {  // Gener
 
 static int generate_pngs(tm_encoder *e, bool input) {  // GeneratePNGs, tilingencoder.pas:2075-2124
   TM_CHECK(!e->s.OutputFileName.empty(), TM_E_INVAL, "GeneratePNGs: OutputFileName is not set");
+  const auto wall0 = std::chrono::steady_clock::now();
+  const tm_png_options opt = e->png_options;
+  // AUTO: the Output page is palettised, which the coder takes best unfiltered; the Input page is a photograph
+  const int filter = opt.filter == TM_PNG_FILTER_AUTO ? (input ? TM_PNG_FILTER_ADAPTIVE : TM_PNG_FILTER_NONE) : opt.filter;
+  e->has_export_stats = false;
   ExportFrames r{e, input};
+  r.keep = opt.level != 0;
   TM_TRY(r.init());
   const std::string base = strip_ext(e->s.OutputFileName);
   {
@@ -197,13 +178,33 @@ static int generate_pngs(tm_encoder *e, bool input) {  // GeneratePNGs, tilingen
     char line[16];
     for (int32_t c : e->palettes_host) { snprintf(line, sizeof(line), "%08X", 0xff000000u | (uint32_t)c); pf << line << "\n"; }
   }
+  // level 0: a chunk of frames comes to the host and each is written in stored blocks.  Level 1: the chunk stays on the device, is coded
+  // there (tm_png_out.hip), and only the files' bytes come back
+  tm_export_stats st{};
+  st.level = opt.level; st.filter = opt.level ? filter : opt.filter;
+  std::vector<uint8_t> file;
+  std::vector<std::vector<uint8_t>> files;
+  dfl::PngDeviceEncoder encoder;  // (its device buffers serve every chunk)
   for (int fr = 0; fr < e->nframes; fr++) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool fresh = fr >= r.first + r.count;
     const uint32_t *px = nullptr;
     TM_TRY(r.frame(fr, &px));
+    if (fresh && opt.level) TM_TRY(encoder.encode(r.dev.as<uint32_t>(), r.sw, (int64_t)r.sw * r.sh, r.count, r.sw, r.sh, filter, e->stream, files));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (!opt.level) dfl::png_stored(px, r.sw, r.sw, r.sh, file);
+    const std::vector<uint8_t> &bytes = opt.level ? files[(size_t)(fr - r.first)] : file;
     char name[32];
     snprintf(name, sizeof(name), "_%04d.png", fr);
-    TM_TRY(write_png(base + name, px, r.sw, r.sh));
+    TM_TRY(write_file(base + name, bytes));
+    const auto t2 = std::chrono::steady_clock::now();
+    st.frames++; st.file_bytes += (int64_t)bytes.size();
+    st.ms_device += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    st.ms_write += std::chrono::duration<double, std::milli>(t2 - t1).count();
   }
+  st.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  e->export_stats = st;
+  e->has_export_stats = true;
   return TM_OK;
 }
 
@@ -284,6 +285,27 @@ int tm_generate_y4m(tm_encoder *e, const char *path, int input) {
 int tm_generate_pngs(tm_encoder *e, int input) {
   TM_CHECK(e, TM_E_INVAL, "null encoder");
   return generate_pngs(e, input != 0);
+}
+
+int tm_set_png_options(tm_encoder *e, const tm_png_options *opt) {
+  TM_CHECK(e && opt, TM_E_INVAL, "null argument");
+  TM_CHECK(opt->level == 0 || opt->level == 1, TM_E_INVAL, "png options: unknown level %d (0 or 1)", opt->level);
+  TM_CHECK(opt->filter >= TM_PNG_FILTER_AUTO && opt->filter <= TM_PNG_FILTER_SMALLER, TM_E_INVAL, "png options: unknown filter %d", opt->filter);
+  e->png_options = *opt;
+  return TM_OK;
+}
+
+int tm_get_png_options(tm_encoder *e, tm_png_options *opt) {
+  TM_CHECK(e && opt, TM_E_INVAL, "null argument");
+  *opt = e->png_options;
+  return TM_OK;
+}
+
+int tm_get_export_stats(tm_encoder *e, tm_export_stats *out) {
+  TM_CHECK(e && out, TM_E_INVAL, "null argument");
+  TM_CHECK(e->has_export_stats, TM_E_INVAL, "export stats: this encoder has not written PNGs");
+  *out = e->export_stats;
+  return TM_OK;
 }
 
 int tm_save_gtm(tm_encoder *e, const char *path) {

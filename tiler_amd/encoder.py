@@ -477,6 +477,29 @@ class TilingEncoder:
         """GeneratePNGs (tilingencoder.pas:2075): <OutputFileName>_NNNN.png per frame + the palettes as <OutputFileName>.txt"""
         check(self._L.tm_generate_pngs(c_void_p(self._h), int(bool(input))))
 
+    def SetPngOptions(self, level=1, filter="auto"):
+        """How GeneratePNGs writes from now on (tm_set_png_options): level 0 = stored blocks (the default), level 1 = filtered, matched
+        and Huffman-coded on the device; filter: "auto" (none for the output frames, adaptive for the source frames), "none", "adaptive",
+        "smaller" (both coded, the shorter file kept)"""
+        from ._lib import png_options
+        check(self._L.tm_set_png_options(c_void_p(self._h), ctypes.byref(png_options(level, filter))))
+
+    def PngOptions(self):
+        from ._lib import PNG_FILTERS, PngOptions
+        opt = PngOptions()
+        check(self._L.tm_get_png_options(c_void_p(self._h), ctypes.byref(opt)))
+        return {"level": opt.level, "filter": {v: k for k, v in PNG_FILTERS.items()}[opt.filter]}
+
+    def ExportStats(self):
+        """What the last GeneratePNGs did (tm_get_export_stats): frames, the files' bytes, the level and the filter that held, and its
+        milliseconds: on the device (render, coding, read-back), writing the files, the wall clock"""
+        from ._lib import PNG_FILTERS, ExportStatsDesc
+        st = ExportStatsDesc()
+        check(self._L.tm_get_export_stats(c_void_p(self._h), ctypes.byref(st)))
+        out = {name: getattr(st, name) for name, _ in ExportStatsDesc._fields_}
+        out["filter"] = {v: k for k, v in PNG_FILTERS.items()}[st.filter]
+        return out
+
     def RenderFrames(self, first=0, count=None, input=False, device=True, size=None, filter="lanczos"):
         """The decoded frames [first, first+count) as Render (tilingencoder.pas:3455-3640) draws them with the constructor's defaults -- or
         the source frames (input=True) -- rendered on the device: [count][tm_h*8][tm_w*8] 0x00RRGGBB (the pushed frames' format, alpha 0),

@@ -535,3 +535,36 @@ def lz_compress(data):
     n = ctypes.c_size_t()
     check(lib().tm_stage_lz_compress(src.ctypes.data_as(ctypes.c_void_p) if src.size else None, src.size, dst.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(n)))
     return dst[:n.value].tobytes()
+
+
+def png_encode(frames, level=1, filter="none"):
+    """RGB32 frames on the device as PNG files (tm_stage_png_encode; the rule: include/tilemotion.h): frames = torch
+    int32 CUDA tensor [F][H][W] of 0x00RRGGBB, rows and frames at any stride -> list of F bytes objects, byte for byte what
+    tm_png_encode_host writes.  level 0: stored blocks; level 1: filtered rows (filter: "none", "adaptive", "smaller"; "auto" = "none"
+    here), matched, parsed, coded and packed on the device -- only the files' bytes come to the host"""
+    from ._lib import png_options
+    assert frames.is_cuda and frames.dtype == torch.int32 and frames.dim() == 3 and (frames.shape[2] <= 1 or frames.stride(2) == 1)
+    nf, h, w = frames.shape
+    opt = png_options(level, filter)
+    bound = ctypes.c_int64()
+    check(lib().tm_png_bound_host(w, h, ctypes.byref(bound)))
+    out = np.empty(bound.value * max(nf, 1), np.uint8)
+    offs = (ctypes.c_int64 * (nf + 1))()
+    check(lib().tm_stage_png_encode(_p(frames), frames.stride(1), frames.stride(0), nf, w, h, ctypes.byref(opt), out.ctypes.data_as(ctypes.c_void_p), out.size, offs,
+                                    _stream()))
+    return [out[offs[f]:offs[f + 1]].tobytes() for f in range(nf)]
+
+
+def zlib_compress(data):
+    """The PNG writer's stream coder alone (tm_stage_zlib_compress): data = bytes, or a torch uint8 CUDA tensor [n] -> one zlib stream,
+    exactly tm_zlib_compress_host's"""
+    if not torch.is_tensor(data):
+        raw = np.frombuffer(bytes(data), np.uint8)
+        data = torch.from_numpy(raw.copy()).cuda() if raw.size else torch.zeros(0, dtype=torch.uint8, device="cuda")
+    assert data.is_cuda and data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()
+    n = data.numel()
+    cap = n + 10 * (n // 32768 + 1) + 6
+    out = np.empty(cap, np.uint8)
+    got = ctypes.c_int64()
+    check(lib().tm_stage_zlib_compress(_p(data) if n else None, n, out.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(got), _stream()))
+    return out[:got.value].tobytes()

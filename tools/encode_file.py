@@ -1,12 +1,13 @@
 """A video file to a .gtm: python tools/encode_file.py IN OUT.gtm [--scaling S --start N --frames N --yuv auto|bt601|bt601-full|tiler|bt709|bt709-full]
-                                                               [--raw-rgb LAYOUT --size WxH --fps F [--depth D]]
+                                                               [--raw-rgb LAYOUT --size WxH --fps F [--depth D]] [--pngs]
 
 IN is a Y4M file (`ffmpeg -i clip.mp4 -f yuv4mpegpipe clip.y4m`), a .gtm stream (its frames are played on the device and encoded again;
 --scaling must stay 1) or a Format pattern naming a PNG sequence (frame_%.4d.png; key frames where a frame_NNNN.kf file exists).
 With --raw-rgb IN is a headerless file of RGB frames such as `ffmpeg -i clip.mp4 -f rawvideo -pix_fmt rgb24 clip.rgb` writes (LAYOUT: rgb24,
 bgr24, rgba, bgra, argb, abgr, rgb48, bgr48, rgba64, bgra64, rgbp, gbrp, gray; --depth D > 8: rgbp / gbrp / gray hold little-endian words of
 D bits, as gbrp10le does): it is mapped, not read, and lent to the encoder as it lies (SetFramesRGB), so --scaling applies, and --start and
---frames slice the mapping.  Prints the video as Load found it and the FrameQuality of the encode."""
+--frames slice the mapping.  --pngs: the decoded frames are also written as OUT_NNNN.png beside the stream, coded on the device
+(GeneratePNGs at level 1).  Prints the video as Load found it and the FrameQuality of the encode."""
 import argparse
 import json
 import os
@@ -29,6 +30,7 @@ ap.add_argument("--raw-rgb", choices=sorted(rgb_in.LAYOUTS), default=None)
 ap.add_argument("--size", default=None, help="WxH of a --raw-rgb file's frames")
 ap.add_argument("--fps", type=float, default=None, help="frame rate of a --raw-rgb file")
 ap.add_argument("--depth", type=int, default=None, help="bits per sample of a --raw-rgb file's 16-bit words")
+ap.add_argument("--pngs", action="store_true", help="also write the decoded frames as OUT_NNNN.png (deflate on the device)")
 args = ap.parse_args()
 enc = TilingEncoder()
 enc.LoadDefaultSettings()
@@ -53,6 +55,9 @@ else:
     enc.InputFileName, enc.StartFrame, enc.FrameCount = args.input, args.start, args.frames
     enc.InputYUV = TInputYUV(YUV.index(args.yuv))
 enc.Run()  # Load opens the input by itself (or reads the lent clip); Save follows Reindex because OutputFileName is set
+if args.pngs:
+    enc.SetPngOptions(level=1)
+    enc.GeneratePNGs()
 q = enc.FrameQuality()
 print(json.dumps(dict(video=enc.VideoInfo(), keyframes=enc.KeyFrames().tolist(), tiles=enc.counts()["tiles"], clip_psnr=q["clip_psnr"],
                       clip_ssim_y=q["clip_ssim_y"], psnr=[round(float(v), 3) for v in q["psnr"]])))

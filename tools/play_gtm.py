@@ -1,6 +1,6 @@
 """Frames of a .gtm stream, played on the device:
-python tools/play_gtm.py IN.gtm [--start N --frames N] (--info | --raw OUT.rgb | --y4m OUT.y4m [--chroma 444|422|420jpeg|420mpeg2|mono] [--yuv MODE])
-                         [--size WxH [--filter lanczos|nearest]]
+python tools/play_gtm.py IN.gtm [--start N --frames N] (--info | --raw OUT.rgb | --y4m OUT.y4m [--chroma 444|422|420jpeg|420mpeg2|mono] [--yuv MODE]
+                         | --png OUT_%04d.png [--png-level 0|1] [--png-filter none|adaptive|smaller]) [--size WxH [--filter lanczos|nearest]]
 
 --info prints what the stream says about itself (size, frames, key frames, rate, tiles, palettes, the embedded settings) as JSON;
 --raw writes frames [start, start + frames) as packed RGB24, one frame after the other (view with
@@ -8,7 +8,9 @@ python tools/play_gtm.py IN.gtm [--start N --frames N] (--info | --raw OUT.rgb |
 --y4m writes them as a Y4M file any player, FFmpeg and this library's OpenInput read: the frames are converted to YUV on the device
 (GtmPlayer.ReadYUV) and come to the host as 1 to 3 bytes a pixel.  --yuv: auto (= bt601-limited) bt601-limited bt601-full bt709-limited
 bt709-full tiler (444 and mono only); the header says XCOLORRANGE=FULL for the full-range rules and tiler.
---size WxH (with --raw and --y4m): the frames are scaled on the device to that size before they are delivered (GtmPlayer.SetOutput; --filter
+--png writes one PNG per frame, named by the pattern with the frame's number: the player's frames stay on the device and are coded there
+(stages.png_encode; --png-level 1, the default: deflate on the device, 0: stored blocks).
+--size WxH (with --raw, --y4m and --png): the frames are scaled on the device to that size before they are delivered (GtmPlayer.SetOutput; --filter
 lanczos, the default, or nearest); the Y4M header carries the output size."""
 import argparse
 import json
@@ -29,6 +31,9 @@ g = ap.add_mutually_exclusive_group(required=True)
 g.add_argument("--info", action="store_true")
 g.add_argument("--raw")
 g.add_argument("--y4m")
+g.add_argument("--png", help="a pattern with one integer field, for instance OUT_%%04d.png")
+ap.add_argument("--png-level", type=int, default=1, choices=[0, 1])
+ap.add_argument("--png-filter", default="none", choices=["none", "adaptive", "smaller"])
 ap.add_argument("--chroma", default="420jpeg", choices=["444", "422", "420jpeg", "420mpeg2", "mono"])
 ap.add_argument("--yuv", default="auto", choices=["auto", "bt601-limited", "bt601-full", "bt709-limited", "bt709-full", "tiler"])
 ap.add_argument("--size", help="WxH: the size --raw and --y4m deliver at (default: the stream's own)")
@@ -66,6 +71,20 @@ with GtmPlayer(args.input) as p:
                         if a is not None:
                             f.write(a[i].tobytes())
                 left -= planes[0].shape[0]
+    elif args.png:
+        from tiler_amd import stages
+        p.Seek(args.start)
+        left = (args.frames if args.frames > 0 else info["frames"] - args.start)
+        at = args.start
+        while left > 0:
+            fr = p.Read(min(left, 16), device=True)
+            if fr.shape[0] == 0:
+                break
+            for png in stages.png_encode(fr, level=args.png_level, filter=args.png_filter):
+                with open(args.png % at, "wb") as f:
+                    f.write(png)
+                at += 1
+            left -= fr.shape[0]
     else:
         p.Seek(args.start)
         left = (args.frames if args.frames > 0 else info["frames"] - args.start)
