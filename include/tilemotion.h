@@ -77,6 +77,8 @@
  *                           (tests: the other shards must leave their collectives at once)
  *   TM_INPUT_CHUNK_FRAMES=<n> Load reads a Y4M file, or stages a lent YUV or RGB clip, n frames at a time instead of 16 MB worth (tests: 1, so that
  *                           a small clip walks the two staging buffers many times)
+ *   TM_PNG_DECODE=host|device where the Load of a PNG sequence or of lent PNG files decodes, whatever tm_set_png_decode said;
+ *                           with `device`, TM_INPUT_CHUNK_FRAMES=<n> is also the number of files a chunk holds
  *   TM_RECON_CHUNK_FRAMES=<n> Reconstruct computes and searches its query features n frames at a time instead of 8 GiB worth (2 GiB with the
  *                           extended palette usage); the features computed ahead during PreparePalettes are then those of the first n frames
  *                           (tests: a small clip takes several chunks)
@@ -479,6 +481,72 @@ TM_API int tm_stage_zlib_compress(const uint8_t *dev_src, int64_t n, uint8_t *ho
 TM_API int tm_zlib_compress_host(const uint8_t *src, int64_t n, uint8_t *out, int64_t cap, int64_t *out_n);
 TM_API int tm_png_filter_rows_host(const uint32_t *frame, int64_t stride_px, int w, int h, int filter, uint8_t *stream);
 TM_API int tm_deflate_code_lengths_host(const uint32_t *freq, int nsym, int max_bits, uint8_t *lens);
+/* ---- PNG input on the device: inflate and unfilter (tm_png_in.hip; the rule: tm_inflate.h) -------------------------
+ * The export's mirror image.  A zlib stream (RFC 1950 / 1951: stored, fixed and dynamic blocks, Adler-32) is accepted exactly when
+ * tm_inflate_host accepts it and then yields the same bytes; a refused stream ends with a status and never with an access outside its
+ * buffers.  A stream's input is a list of spans of one blob (the IDAT payloads of a file are not joined; a span may be empty and a split may
+ * fall inside a code); its output goes to dst + dst_off, at most dst_cap bytes.  The status is per stream: code (TM_INF_*, 0 = accepted),
+ * the input byte position reached and the bytes written (0 unless accepted).
+ *   Device form: k_inflate, one wave per stream and all streams of a batch in one launch -- decode state the same in every lane; tables, a
+ * stage of input bytes and the 32 KiB window in LDS (37 KB a workgroup: four and more streams to a compute unit); a match copied LDS to LDS
+ * by the whole wave; output in 16-byte stores; Adler-32 summed as the output leaves and compared on the device.  k_png_unfilter, one wave
+ * per picture, lanes on 64 consecutive rows one pixel apart (lane l at pixel x - l): `up` and `up-left` come from lane l - 1 by a
+ * cross-lane move, the filter type is read per row, and the 0x00RRGGBB pixel -- grey replicated, alpha dropped, a palette index looked up
+ * -- is written straight into the destination frame.
+ *   tm_inflate_streams_host / tm_stage_inflate: the rule on host memory with no device call / the kernel on a batch from HOST memory into
+ * DEVICE memory dev_dst (status: HOST).  They return TM_OK whenever the batch was well formed (refusals: a null pointer, a span outside the
+ * blob, a stream's spans outside the list or 4 GiB and more in sum, a destination outside dst_bytes); what became of each stream is its status.
+ *   tm_png_decode_host / tm_stage_png_decode: nfiles PNG files in HOST memory, each of w x h, into frames [h][w] of 0x00RRGGBB, frame_px
+ * pixels apart, in HOST / DEVICE memory.  The accepted set is tm_read_png_host's: 8 bits per sample, colour types 0, 2, 3, 4, 6,
+ * non-interlaced.  What the container walk refuses (signature, CRC, IHDR, PLTE, a size other than w x h) fails the call with
+ * tm_read_png_host's code, naming the file's index, before anything is decoded; what only decoding finds is the file's status[]: a
+ * TM_INF_* code, TM_PNG_BAD_SIZE (not h (1 + row bytes) bytes of data), TM_PNG_BAD_FILTER (a row's filter type above 4), TM_PNG_BAD_INDEX
+ * (a palette index beyond PLTE) -- the first in tm_read_png_host's order: stream, then rows top to bottom, a row's type before its pixels.
+ *   tm_set_png_decode: where the Load of a PNG sequence (tm_open_input) or of lent PNG files (tm_set_frames_png) decodes.  HOST: the files
+ * are decoded by tm_read_png_host's reader on host threads and the RGB32 clip is uploaded.  DEVICE: the files' bytes and a descriptor per
+ * frame are uploaded chunk by chunk (TM_INPUT_CHUNK_FRAMES frames; otherwise as many as 2 GiB of inflated rows and 512 MiB of files hold: a stream is one wave's work) and the two kernels write the encoder's clip; a
+ * refused file fails tm_run(TM_STEP_LOAD) with the host path's code, naming the file.  AUTO is DEVICE (it was the faster on both measured
+ * sequences: DESIGN.md section 35), and HOST for pictures of 4 GiB of rows and more.  The environment variable TM_PNG_DECODE=host|device overrides what was set.
+ *   tm_set_frames_png: PNG files LENT in host memory until the next Load has returned, as tm_set_frames_rgb lends pixels: the size is the
+ * first file's (Scaling is ignored, as for a PNG sequence), a file of another size is TM_E_INVAL (at Load for all files but the first), the
+ * key frames follow the automatic rule, StartFrame and FrameCount do not apply.  tm_probe_png_clip_host: the refusals and the size with no
+ * device -- TM_E_INVAL for a null list, pointer or size, nframes < 1, fps <= 0; the first file's container refusals as tm_read_png_host
+ * makes them.
+ *   tm_get_input_stats: the last Load that read an input (TM_E_INVAL before the first): ms_read = the files into host memory (DEVICE) or
+ * read and decoded (HOST), ms_device = upload and kernels, each behind a synchronise, both inside ms_wall. */
+enum {
+  TM_INF_OK = 0, TM_INF_TOO_SHORT = 1, TM_INF_BAD_HEADER = 2, TM_INF_DICT = 3, TM_INF_TRUNCATED = 4, TM_INF_BLOCK_TYPE = 5, TM_INF_STORED_LEN = 6,
+  TM_INF_DYN_HEADER = 7, TM_INF_CL_CODE = 8, TM_INF_LENGTHS = 9, TM_INF_NO_EOB = 10, TM_INF_OVER_SUBSCRIBED = 11, TM_INF_BAD_CODE = 12,
+  TM_INF_BAD_SYMBOL = 13, TM_INF_DISTANCE = 14, TM_INF_OVERFLOW = 15, TM_INF_NO_CHECKSUM = 16, TM_INF_ADLER = 17, TM_INF_BAD_SPAN = 18,
+  TM_PNG_BAD_SIZE = 32, TM_PNG_BAD_FILTER = 33, TM_PNG_BAD_INDEX = 34
+};
+enum { TM_PNG_DECODE_AUTO = 0, TM_PNG_DECODE_HOST = 1, TM_PNG_DECODE_DEVICE = 2 };
+typedef struct tm_inflate_span { uint64_t off; uint32_t len, reserved; } tm_inflate_span;   /* bytes [off, off + len) of the blob */
+typedef struct tm_inflate_stream {
+  uint64_t dst_off;                /* where the stream's output starts in the destination */
+  uint32_t dst_cap;                /* the most it may write */
+  uint32_t first_span, span_count; /* its input: spans [first_span, + span_count) in order */
+  uint32_t reserved;
+} tm_inflate_stream;
+typedef struct tm_inflate_status { int32_t code; uint32_t in_pos, out_n; } tm_inflate_status;
+typedef struct tm_input_stats {
+  int64_t frames, file_bytes, bytes_uploaded; /* frames this Load read; the sum of their files' sizes; bytes sent to the device for them */
+  int32_t where, kind;                         /* TM_PNG_DECODE_HOST / _DEVICE (what held); TM_INPUT_PNGS or 6 for lent PNG files */
+  double ms_read, ms_device, ms_wall;
+} tm_input_stats;
+TM_API int tm_inflate_streams_host(const uint8_t *blob, size_t blob_bytes, const tm_inflate_span *spans, int nspans, const tm_inflate_stream *streams,
+                                   int nstreams, uint8_t *dst, size_t dst_bytes, tm_inflate_status *status /* nstreams */);
+TM_API int tm_stage_inflate(const uint8_t *blob, size_t blob_bytes, const tm_inflate_span *spans, int nspans, const tm_inflate_stream *streams,
+                            int nstreams, uint8_t *dev_dst, size_t dst_bytes, tm_inflate_status *status /* nstreams, host */, void *stream);
+TM_API int tm_png_decode_host(const void *const *files, const size_t *sizes, int nfiles, int w, int h, uint32_t *out, int64_t frame_px,
+                              int32_t *status /* nfiles */);
+TM_API int tm_stage_png_decode(const void *const *files, const size_t *sizes, int nfiles, int w, int h, uint32_t *dev_out, int64_t frame_px,
+                               int32_t *status /* nfiles, host */, void *stream);
+TM_API int tm_set_png_decode(tm_encoder *, int where);
+TM_API int tm_get_png_decode(tm_encoder *, int *where);
+TM_API int tm_set_frames_png(tm_encoder *, const void *const *files, const size_t *sizes, int nframes, double fps);
+TM_API int tm_probe_png_clip_host(const void *const *files, const size_t *sizes, int nframes, double fps, int *width, int *height);
+TM_API int tm_get_input_stats(tm_encoder *, tm_input_stats *out);
 /* The same pictures rendered on the device (Render :3455-3640, Output tab with the constructor's defaults; or the Input tab: input != 0):
  * frames [first_frame, first_frame+frame_count) as [frame_count][tm_h*8][tm_w*8] uint32 0x00RRGGBB (the format frames are pushed in; the
  * input render is every pushed frame cropped to tm_w*8 x tm_h*8 with alpha 0).  A predicted item is frame f-1's output at its offset,

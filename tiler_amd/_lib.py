@@ -49,6 +49,26 @@ class ExportStatsDesc(ctypes.Structure):  # tm_export_stats
                 ("ms_device", c_double), ("ms_write", c_double), ("ms_wall", c_double)]
 
 
+class InflateSpan(ctypes.Structure):  # tm_inflate_span: bytes [off, off + len) of a blob
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class InflateStream(ctypes.Structure):  # tm_inflate_stream: where a stream's output goes and which spans are its input
+    _fields_ = [("dst_off", ctypes.c_uint64), ("dst_cap", ctypes.c_uint32), ("first_span", ctypes.c_uint32), ("span_count", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class InflateStatus(ctypes.Structure):  # tm_inflate_status
+    _fields_ = [("code", ctypes.c_int32), ("in_pos", ctypes.c_uint32), ("out_n", ctypes.c_uint32)]
+
+
+class InputStatsDesc(ctypes.Structure):  # tm_input_stats
+    _fields_ = [("frames", c_int64), ("file_bytes", c_int64), ("bytes_uploaded", c_int64), ("where", ctypes.c_int32), ("kind", ctypes.c_int32),
+                ("ms_read", c_double), ("ms_device", c_double), ("ms_wall", c_double)]
+
+
+PNG_DECODE = {"auto": 0, "host": 1, "device": 2}  # TM_PNG_DECODE_*
+
 RENDER_PAGES = {"input": 0, "output": 1, "tiles": 2}  # TM_RENDER_PAGE_*
 
 
@@ -149,6 +169,15 @@ SIGNATURES = {
     "tm_zlib_compress_host": (c_int, [c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(c_int64)]),
     "tm_png_filter_rows_host": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "tm_deflate_code_lengths_host": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "tm_inflate_streams_host": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p]),
+    "tm_stage_inflate": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, c_void_p]),
+    "tm_png_decode_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "tm_stage_png_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "tm_set_png_decode": (c_int, [c_void_p, c_int]),
+    "tm_get_png_decode": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "tm_set_frames_png": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double]),
+    "tm_probe_png_clip_host": (c_int, [c_void_p, c_void_p, c_int, c_double, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "tm_get_input_stats": (c_int, [c_void_p, ctypes.POINTER(InputStatsDesc)]),
 }
 
 
@@ -162,6 +191,44 @@ def png_options(level=1, filter="auto"):
             raise ValueError("unknown PNG filter strategy %r (one of %s)" % (filter, " ".join(PNG_FILTERS)))
         filter = PNG_FILTERS[filter]
     return PngOptions(int(level), int(filter))
+
+
+def inflate_batch(streams, caps=None, dst_offs=None, src_offs=None):
+    """The arguments tm_inflate_streams_host / tm_stage_inflate take for a batch.  streams: a list whose items are bytes (one span) or a
+    list of bytes (the spans of one stream, in order; empty ones allowed); caps: the most each may write; dst_offs: where each one's
+    output starts (default: one behind the other, 16 bytes apart at least); src_offs: where each span starts in the blob (default: one
+    behind the other) -> (blob uint8 array, spans, streams, dst_bytes), the last two ctypes arrays"""
+    import numpy as np
+    lists = [[s] if isinstance(s, (bytes, bytearray)) else list(s) for s in streams]
+    flat = [bytes(p) for l in lists for p in l]
+    if src_offs is None:
+        src_offs, at = [], 0
+        for p in flat:
+            src_offs.append(at)
+            at += len(p)
+    blob = np.zeros(max([o + len(p) for o, p in zip(src_offs, flat)] + [1]), np.uint8)
+    spans = (InflateSpan * max(len(flat), 1))()
+    for j, (o, p) in enumerate(zip(src_offs, flat)):
+        blob[o:o + len(p)] = np.frombuffer(p, np.uint8)
+        spans[j] = InflateSpan(o, len(p), 0)
+    descs = (InflateStream * max(len(lists), 1))()
+    first, at = 0, 0
+    for i, l in enumerate(lists):
+        cap = int(caps[i])
+        off = int(dst_offs[i]) if dst_offs is not None else at
+        descs[i] = InflateStream(off, cap, first, len(l), 0)
+        first += len(l)
+        at = off + ((cap + 15) & ~15) + 16
+    dst_bytes = max([d.dst_off + d.dst_cap for d in descs[:len(lists)]] + [0])
+    return blob, spans, descs, dst_bytes, len(flat)
+
+
+def file_list(files):
+    """(pointer array, size array, keep-alive) of a list of bytes objects, as tm_png_decode_host and tm_set_frames_png take them"""
+    bufs = [ctypes.create_string_buffer(bytes(f), len(f)) if len(f) else ctypes.create_string_buffer(1) for f in files]
+    ptrs = (c_void_p * max(len(files), 1))(*[ctypes.addressof(b) for b in bufs])
+    sizes = (ctypes.c_size_t * max(len(files), 1))(*[len(f) for f in files])
+    return ptrs, sizes, bufs
 
 
 SCALE_FILTERS = {"lanczos": 0, "nearest": 1}  # TM_SCALE_*

@@ -15,11 +15,14 @@ namespace tmx {
 constexpr int INPUT_YUV_CLIP = 3;  // InputInfo::kind of a YUV clip lent in memory (tm_set_frames_yuv), beside TM_INPUT_Y4M / TM_INPUT_PNGS
 constexpr int INPUT_GTM = TM_INPUT_GTM;  // a .gtm stream: Load plays its frames into the device clip (tm_player.hip)
 constexpr int INPUT_RGB_CLIP = 5;  // an RGB clip lent in memory (tm_set_frames_rgb)
+constexpr int INPUT_PNG_CLIP = 6;  // PNG files lent in memory (tm_set_frames_png)
 struct InputInfo {
   int kind = 0;  // 0: RGB32 frames from memory (pushed or lent); TM_INPUT_Y4M / TM_INPUT_PNGS: from the file; INPUT_YUV_CLIP / INPUT_RGB_CLIP: a lent clip
   std::string name;
   tm_yuv_clip clip{};               // INPUT_YUV_CLIP: the descriptor as it was lent
   tm_rgb_clip rgb_clip{};           // INPUT_RGB_CLIP: the same
+  std::vector<const void *> png_files;  // INPUT_PNG_CLIP: the files as they were lent
+  std::vector<size_t> png_sizes;
   bool lent = false;                // the clip's memory is still borrowed: no Load has read it yet
   int start = 0, frames = 0, src_w = 0, src_h = 0, dst_w = 0, dst_h = 0, chroma = 0, full_range = 0;
   double fps = 0;

@@ -5,12 +5,15 @@
 // The reference opens "any file" through FFmpeg (extern.pas:780-781, 837-840), which does not exist here (DESIGN.md sections 9 and 17):
 // Y4M is the uncompressed container every FFmpeg build writes.
 #include <fcntl.h>
+#include <sys/stat.h>
 
 #include <atomic>
+#include <chrono>
 #include <mutex>
 #include <thread>
 
 #include "tm_encoder.h"
+#include "tm_inflate.h"
 
 // fn(i) for i in [0, n) on up to IN_READERS host threads (the calling one included); the first failure's code and message come back.
 // Reading a file that the page cache holds is a copy the memory system bounds, not one core: a single reader brought the 0.41 GB of the
@@ -295,19 +298,137 @@ static int convert_rgb_clip(tm_encoder *e, int a, int b) {
   return convert_staged(e, a, b, src);
 }
 
-// the PNG sequence, decoded on the host into a clip the encoder keeps until Load's chunked host-clip upload has taken it
+namespace tmx { int decode_png(const uint8_t *file, size_t n, const char *name, uint32_t *out, int64_t cap_px, int *w_out, int *h_out); }  // tm_png.hip
+
+static bool png_kind(int kind) { return kind == TM_INPUT_PNGS || kind == INPUT_PNG_CLIP; }
+// where a PNG input is decoded: TM_PNG_DECODE, else what tm_set_png_decode said.  AUTO is the device (0.33 s against
+// 0.93 s for the 720p x 300 clip), and the host for pictures whose rows the kernels' 32-bit positions cannot hold
+static int png_decode_where(const tm_encoder *e) {
+  const int w = knobs().png_decode ? knobs().png_decode : e->png_decode;
+  if (w != TM_PNG_DECODE_AUTO) return w;
+  return ((uint64_t)e->width * 4 + 1) * (uint64_t)e->height < ((uint64_t)1 << 32) ? TM_PNG_DECODE_DEVICE : TM_PNG_DECODE_HOST;
+}
+static double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+// the PNG sequence, or the lent PNG files, decoded on the host into a clip the encoder keeps until Load's chunked host-clip upload has taken it
 static int decode_pngs(tm_encoder *e) {
   InputInfo &in = e->input;
   const size_t px = (size_t)e->width * e->height;
   e->input_clip.resize(px * e->nframes);
-  return parallel_for(e->nframes, [&](int i) -> int {  // (frames are files of their own: inflate is the time, and it is one core's per file)
+  std::atomic<int64_t> file_bytes{0};
+  const int rc = parallel_for(e->nframes, [&](int i) -> int {  // (frames are files of their own: inflate is the time, and it is one core's per file)
+    int w = 0, h = 0;
+    if (in.kind == INPUT_PNG_CLIP) {
+      char name[32];
+      snprintf(name, sizeof(name), "frame %d", i);
+      const uint8_t *file = (const uint8_t *)in.png_files[(size_t)i];
+      const size_t n = in.png_sizes[(size_t)i];
+      TM_TRY(decode_png(file, n, name, nullptr, 0, &w, &h));
+      TM_CHECK(w == e->width && h == e->height, TM_E_INVAL, "%s is %dx%d, the sequence's first frame is %dx%d", name, w, h, e->width, e->height);
+      file_bytes += (int64_t)n;
+      return decode_png(file, n, name, e->input_clip.data() + px * i, (int64_t)px, &w, &h);
+    }
     std::string path;
     TM_TRY(format_pattern(in.name, (int64_t)in.start + i, &path));
-    int w = 0, h = 0;
     TM_TRY(read_png(path.c_str(), nullptr, 0, &w, &h));
     TM_CHECK(w == e->width && h == e->height, TM_E_INVAL, "%s is %dx%d, the sequence's first frame is %dx%d", path.c_str(), w, h, e->width, e->height);
+    struct stat sb;
+    if (stat(path.c_str(), &sb) == 0) file_bytes += (int64_t)sb.st_size;
     return read_png(path.c_str(), e->input_clip.data() + px * i, (int64_t)px, &w, &h);
   });
+  e->input_stats.file_bytes = file_bytes.load();
+  return rc;
+}
+
+// Frames [a, b) of the PNG sequence, or of the lent files, decoded on the device into the encoder's clip.  A chunk of
+// files is read into a page-locked buffer (the reader threads; each walks its file's chunks and checks what decode_png checks before the
+// stream), the descriptor of the chunk is written behind the files, and both go up in one copy on the copy stream; k_inflate and
+// k_png_unfilter run on the main stream while the next chunk is read.  What only decoding finds comes back as a status per frame.
+static int decode_pngs_device(tm_encoder *e, int a, int b) {
+  InputInfo &in = e->input;
+  tm_input_stats &stats = e->input_stats;
+  const bool lent = in.kind == INPUT_PNG_CLIP;
+  const int n = b - a, w = e->width, h = e->height;
+  std::vector<std::string> names((size_t)n);
+  std::vector<size_t> sizes((size_t)n);
+  for (int i = 0; i < n; i++) {
+    if (lent) {
+      names[(size_t)i] = "frame " + std::to_string(a + i);
+      sizes[(size_t)i] = in.png_sizes[(size_t)(a + i)];
+    } else {
+      TM_TRY(format_pattern(in.name, (int64_t)in.start + a + i, &names[(size_t)i]));
+      struct stat sb;
+      TM_CHECK(stat(names[(size_t)i].c_str(), &sb) == 0, TM_E_IO, "cannot open %s", names[(size_t)i].c_str());
+      sizes[(size_t)i] = (size_t)sb.st_size;
+    }
+    stats.file_bytes += (int64_t)sizes[(size_t)i];
+  }
+  // A stream is one wave's work from end to end, so a chunk should hold as many frames as the device has room for waves (four to a compute
+  // unit): as many as 2 GiB of inflated rows and 512 MiB of files allow.  The 720p x 300 clip is one chunk; in chunks of 32 frames its
+  // Load took 2.8 s, one launch of 32 waves after the other.
+  const size_t raw_frame = (((size_t)w * 4 + 1) * (size_t)h + 15) & ~(size_t)15, out_fb = (size_t)w * h * 4;
+  size_t largest = 16;
+  for (size_t sz : sizes) largest = std::max(largest, (sz + 15) & ~(size_t)15);
+  const size_t by_room = std::max<size_t>(1, std::min(((size_t)2 << 30) / raw_frame, ((size_t)512 << 20) / largest));
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, knobs().input_chunk_frames > 0 ? (size_t)knobs().input_chunk_frames : by_room));
+  size_t cap = 0;  // a chunk's files, each on 16 bytes, and the most its descriptor can take (a span per 12 bytes of file at the worst)
+  for (int f0 = 0; f0 < n; f0 += chunk) {
+    size_t files = 0;
+    const int nf = std::min(chunk, n - f0);
+    for (int i = 0; i < nf; i++) files += (sizes[(size_t)(f0 + i)] + 15) & ~(size_t)15;
+    cap = std::max(cap, files + (size_t)nf * (sizeof(inf::Stream) + sizeof(inf::Picture) + 768) + (files / 12 + (size_t)nf) * sizeof(inf::Span) + 64);
+  }
+  TM_CHECK(cap < ((size_t)1 << 32), TM_E_UNSUPPORTED, "a chunk of %d PNG files takes %zu bytes (below 4 GiB: lower TM_INPUT_CHUNK_FRAMES)", chunk, cap);
+  PinnedBuf *host = e->input_pinned;
+  DevBuf dev[2], raw, inflated, status;
+  StagingRing ring;
+  TM_TRY(ring.make());
+  for (int i = 0; i < (n > chunk ? 2 : 1); i++) { TM_TRY(host[i].alloc(cap)); TM_TRY(dev[i].alloc(cap)); }
+  TM_TRY(raw.alloc(raw_frame * chunk)); TM_TRY(inflated.alloc((size_t)n * sizeof(tm_inflate_status))); TM_TRY(status.alloc((size_t)n * 4));
+  if (!e->copy_stream) TM_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
+  inf::PngBatch batch[2];
+  std::vector<inf::PngInfo> infos((size_t)chunk);
+  std::vector<size_t> at((size_t)chunk);
+  int c = 0;
+  for (int f0 = 0; f0 < n; f0 += chunk, c++) {
+    const int nf = std::min(chunk, n - f0), s = c & 1;
+    TM_TRY(ring.host_free(s));
+    const auto t0 = std::chrono::steady_clock::now();
+    size_t files = 0;
+    for (int i = 0; i < nf; i++) { at[(size_t)i] = files; files += (sizes[(size_t)(f0 + i)] + 15) & ~(size_t)15; }
+    uint8_t *hb = (uint8_t *)host[s].p;
+    TM_TRY(parallel_for(nf, [&](int i) -> int {
+      const std::string &name = names[(size_t)(f0 + i)];
+      const size_t sz = sizes[(size_t)(f0 + i)];
+      uint8_t *to = hb + at[(size_t)i];
+      if (lent) memcpy(to, in.png_files[(size_t)(a + f0 + i)], sz);
+      else {
+        const int fd = open(name.c_str(), O_RDONLY);
+        TM_CHECK(fd >= 0, TM_E_IO, "cannot open %s", name.c_str());
+        FdCloser closer{fd};
+        TM_CHECK(pread_all(fd, to, sz, 0) == 0, TM_E_IO, "cannot read %s", name.c_str());
+      }
+      TM_TRY(inf::parse_png(to, sz, name.c_str(), &infos[(size_t)i]));
+      return inf::png_check_decodable(infos[(size_t)i], name.c_str(), w, h);
+    }));
+    batch[s].clear();
+    for (int i = 0; i < nf; i++) batch[s].add(infos[(size_t)i], at[(size_t)i]);
+    TM_CHECK(files + batch[s].desc_bytes() <= cap, TM_E_INVAL, "a PNG file changed while it was being read");
+    const size_t used = files + batch[s].write_desc(hb + files);
+    stats.ms_read += ms_since(t0);
+    stats.bytes_uploaded += (int64_t)used;
+    TM_TRY(ring.device_free(s, e->copy_stream));
+    TM_HIP(hipMemcpyAsync(dev[s].p, hb, used, hipMemcpyHostToDevice, e->copy_stream));
+    TM_TRY(ring.uploaded(s, e->copy_stream, e->stream));
+    TM_TRY(inf::png_batch_launch(batch[s], dev[s].as<uint8_t>(), used, files, raw.as<uint8_t>(), inflated.as<tm_inflate_status>() + f0, w, h,
+                                 reinterpret_cast<uint32_t *>(e->frames_owned.as<uint8_t>() + out_fb * (size_t)(a + f0)), (int64_t)w * h, status.as<int32_t>() + f0, e->stream));
+    TM_TRY(ring.worked(s, e->stream));
+  }
+  std::vector<int32_t> st((size_t)n);
+  TM_HIP(hipMemcpyAsync(st.data(), status.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  TM_HIP(hipStreamSynchronize(e->stream));  // the staging buffers go back to the pool and to the host
+  for (int i = 0; i < n; i++) TM_TRY(inf::png_status_error(st[(size_t)i], names[(size_t)i].c_str()));
+  return TM_OK;
 }
 
 // frames [a, b) of the .gtm stream, played straight into the encoder's device clip (the player writes frame i where frame i + 1 reads it)
@@ -326,13 +447,23 @@ static int play_gtm(tm_encoder *e, int a, int b) {
 // Load's first lines when the frames come from a file or from lent YUV planes: leaves the clip where tm_set_frames_device / tm_set_frames_host would have put it
 int load_from_input(tm_encoder *e) {
   InputInfo &in = e->input;
-  if (in.kind == TM_INPUT_PNGS) {
+  const bool pngs = png_kind(in.kind);
+  const auto t0 = std::chrono::steady_clock::now();
+  if (pngs && png_decode_where(e) == TM_PNG_DECODE_HOST) {
     if (in.decoded && e->frames != nullptr) return TM_OK;  // a second Run(esLoad): the device copy of the last one
+    TM_CHECK(in.kind != INPUT_PNG_CLIP || in.lent, TM_E_INVAL, "the PNG files were given back when the last Load returned: lend them again (tm_set_frames_png)");
+    e->input_stats = tm_input_stats{};
+    e->has_input_stats = false;
     TM_TRY(decode_pngs(e));
     e->frames = nullptr;
     e->frames_host = e->input_clip.data();
     e->hclip_cur = -1;
     in.decoded = true;
+    in.lent = false;
+    e->input_stats.frames = e->nframes; e->input_stats.bytes_uploaded = (int64_t)e->input_clip.size() * 4;
+    e->input_stats.where = TM_PNG_DECODE_HOST; e->input_stats.kind = in.kind;
+    e->input_stats.ms_read = e->input_stats.ms_wall = ms_since(t0);
+    e->has_input_stats = true;
     return TM_OK;
   }
   int64_t a = 0, b = e->nframes;
@@ -345,6 +476,7 @@ int load_from_input(tm_encoder *e) {
   if (in.decoded && e->frames == e->frames_owned.p && e->frames_owned.p && in.dec_first <= a && b <= in.dec_first + in.dec_count && (rgb_clip || in.dec_mode == mode))
     return TM_OK;
   const bool lent_clip = in.kind == INPUT_YUV_CLIP || rgb_clip;
+  TM_CHECK(in.kind != INPUT_PNG_CLIP || in.lent, TM_E_INVAL, "the PNG files were given back when the last Load returned: lend them again (tm_set_frames_png) for more frames");
   TM_CHECK(!rgb_clip || in.lent, TM_E_INVAL, "the RGB clip was given back when the last Load returned: lend the clip again (tm_set_frames_rgb) for more frames");
   TM_CHECK(!lent_clip || in.lent, TM_E_INVAL,
            "the YUV planes were given back when the last Load returned: lend the clip again (tm_set_frames_yuv) to convert it with another InputYUV or for more frames");
@@ -354,7 +486,21 @@ int load_from_input(tm_encoder *e) {
   e->frames_host = nullptr;
   e->hclip_cur = -1;
   in.decoded = false;
-  if (b > a) TM_TRY(rgb_clip ? convert_rgb_clip(e, (int)a, (int)b) : lent_clip ? convert_yuv_clip(e, (int)a, (int)b) : in.kind == INPUT_GTM ? play_gtm(e, (int)a, (int)b) : decode_y4m(e, (int)a, (int)b));
+  if (pngs) {
+    e->input_stats = tm_input_stats{};
+    e->has_input_stats = false;
+    int rc = TM_OK;
+    if (b > a) rc = decode_pngs_device(e, (int)a, (int)b);
+    if (rc != TM_OK) {  // as a failed host decode leaves it: no clip, and the next Load decodes again
+      (void)hipStreamSynchronize(e->stream);
+      e->frames = nullptr;
+      return rc;
+    }
+    e->input_stats.frames = b - a; e->input_stats.where = TM_PNG_DECODE_DEVICE; e->input_stats.kind = in.kind;
+    e->input_stats.ms_wall = ms_since(t0);
+    e->input_stats.ms_device = std::max(0.0, e->input_stats.ms_wall - e->input_stats.ms_read);
+    e->has_input_stats = true;
+  } else if (b > a) TM_TRY(rgb_clip ? convert_rgb_clip(e, (int)a, (int)b) : lent_clip ? convert_yuv_clip(e, (int)a, (int)b) : in.kind == INPUT_GTM ? play_gtm(e, (int)a, (int)b) : decode_y4m(e, (int)a, (int)b));
   in.lent = false;  // (a lent clip is borrowed until this Load has returned: from here on the encoder reads its own RGB32 clip)
   in.decoded = true; in.dec_first = (int)a; in.dec_count = (int)(b - a); in.dec_mode = mode;
   return TM_OK;
@@ -406,6 +552,55 @@ int tm_set_frames_rgb(tm_encoder *e, const tm_rgb_clip *clip) {  // tm_set_frame
   in.chroma = TM_CHROMA_444; in.fps = clip->fps;
   e->input = std::move(in);
   e->input_clip.clear();
+  return TM_OK;
+}
+
+int tm_probe_png_clip_host(const void *const *files, const size_t *sizes, int nframes, double fps, int *width, int *height) {
+  TM_CHECK(files && sizes && nframes >= 1 && fps > 0, TM_E_INVAL, "png clip: a null list, no frames or fps <= 0");
+  for (int i = 0; i < nframes; i++) TM_CHECK(files[i] && sizes[i], TM_E_INVAL, "png clip: frame %d is null or empty", i);
+  inf::PngInfo info;
+  TM_TRY(inf::parse_png((const uint8_t *)files[0], sizes[0], "frame 0", &info));
+  if (width) *width = info.w;
+  if (height) *height = info.h;
+  return TM_OK;
+}
+
+int tm_set_frames_png(tm_encoder *e, const void *const *files, const size_t *sizes, int nframes, double fps) {  // tm_set_frames_rgb's twin for files
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  int w = 0, h = 0;
+  TM_TRY(tm_probe_png_clip_host(files, sizes, nframes, fps, &w, &h));
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_set_frames_png(s, files, sizes, nframes, fps); });  // every shard decodes what its Load reads
+  TM_TRY(tm_set_video(e, w, h, fps, nframes));
+  InputInfo in;
+  in.kind = INPUT_PNG_CLIP;
+  in.png_files.assign(files, files + nframes);
+  in.png_sizes.assign(sizes, sizes + nframes);
+  in.lent = true;
+  in.frames = nframes; in.src_w = in.dst_w = w; in.src_h = in.dst_h = h;
+  in.chroma = TM_CHROMA_444; in.fps = fps;
+  e->input = std::move(in);
+  e->input_clip.clear();
+  return TM_OK;
+}
+
+int tm_set_png_decode(tm_encoder *e, int where) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_CHECK(where >= TM_PNG_DECODE_AUTO && where <= TM_PNG_DECODE_DEVICE, TM_E_INVAL, "bad PNG decode place %d", where);
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_set_png_decode(s, where); });
+  e->png_decode = where;
+  return TM_OK;
+}
+
+int tm_get_png_decode(tm_encoder *e, int *where) {
+  TM_CHECK(e && where, TM_E_INVAL, "null argument");
+  *where = e->png_decode;
+  return TM_OK;
+}
+
+int tm_get_input_stats(tm_encoder *e, tm_input_stats *out) {
+  TM_CHECK(e && out, TM_E_INVAL, "null argument");
+  TM_CHECK(e->has_input_stats, TM_E_INVAL, "no Load has read a PNG input yet");
+  *out = e->input_stats;
   return TM_OK;
 }
 

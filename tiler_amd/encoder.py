@@ -295,6 +295,45 @@ class TilingEncoder:
         self._yuv_ref = [frames]
         return self.VideoInfo()
 
+    def SetFramesPNG(self, files, fps):
+        """PNG files lent in memory (tm_set_frames_png): files = a list of bytes objects, one per frame -- an archive's members, a capture, a
+        socket.  The size is the first file's (Scaling is ignored, as for a PNG sequence); a file of another size fails the Load.  The key
+        frames follow the automatic rule.  Decoded where SetPngDecode says.  The files are borrowed (and kept alive here) until the Run that
+        loads them has returned.  Returns VideoInfo()."""
+        from ._lib import file_list
+        files = [bytes(f) for f in files]
+        ptrs, sizes, keep = file_list(files)
+        check(self._L.tm_set_frames_png(c_void_p(self._h), ptrs, sizes, len(files), float(fps)))
+        self._yuv_ref = [ptrs, sizes, keep]
+        return self.VideoInfo()
+
+    def SetPngDecode(self, where="auto"):
+        """Where the Load of a PNG sequence or of lent PNG files decodes (tm_set_png_decode): "host" (the reader on host threads, the RGB32
+        clip uploaded), "device" (the files' bytes uploaded, inflate and unfilter in kernels), "auto" (the device: DESIGN.md section 35 has the
+        measurement).  The environment variable TM_PNG_DECODE=host|device overrides."""
+        from ._lib import PNG_DECODE
+        if isinstance(where, str):
+            if where not in PNG_DECODE:
+                raise ValueError("unknown PNG decode place %r (one of %s)" % (where, " ".join(PNG_DECODE)))
+            where = PNG_DECODE[where]
+        check(self._L.tm_set_png_decode(c_void_p(self._h), int(where)))
+
+    def PngDecode(self):
+        from ._lib import PNG_DECODE
+        v = c_int()
+        check(self._L.tm_get_png_decode(c_void_p(self._h), ctypes.byref(v)))
+        return {n: k for k, n in PNG_DECODE.items()}[v.value]
+
+    def InputStats(self):
+        """What the last Load of a PNG input did (tm_get_input_stats): frames, the files' bytes, the bytes uploaded for them, where they
+        were decoded ("host" / "device"), and its milliseconds: reading (host: reading and decoding), the device, the wall clock"""
+        from ._lib import PNG_DECODE, InputStatsDesc
+        st = InputStatsDesc()
+        check(self._L.tm_get_input_stats(c_void_p(self._h), ctypes.byref(st)))
+        out = {name: getattr(st, name) for name, _ in InputStatsDesc._fields_}
+        out["where"] = {n: k for k, n in PNG_DECODE.items()}[st.where]
+        return out
+
     def SaveSettings(self, path):
         self._L.tm_save_settings_ini.restype = c_int
         self._L.tm_save_settings_ini.argtypes = [c_void_p, c_char_p]

@@ -568,3 +568,31 @@ def zlib_compress(data):
     got = ctypes.c_int64()
     check(lib().tm_stage_zlib_compress(_p(data) if n else None, n, out.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(got), _stream()))
     return out[:got.value].tobytes()
+
+
+def inflate(streams, caps, dst_offs=None, src_offs=None, guard=0):
+    """A batch of zlib streams in host memory inflated on the device in one launch (tm_stage_inflate; the rule: tm_inflate.h, DESIGN.md
+    section 35).  streams: a list whose items are bytes or a list of bytes (a stream's spans); caps: the most each may write; dst_offs:
+    where each one's output starts in the destination (default: one behind the other); src_offs: where each span starts in the blob;
+    guard: bytes of 0xA5 kept behind the last destination -> (dst uint8 CUDA tensor, filled with 0xA5 before the launch, [(code, in_pos,
+    out_n)] per stream)"""
+    from ._lib import InflateStatus, inflate_batch
+    blob, spans, descs, dst_bytes, nspans = inflate_batch(streams, caps, dst_offs, src_offs)
+    dst = torch.full((dst_bytes + guard,), 0xA5, dtype=torch.uint8, device="cuda")
+    status = (InflateStatus * max(len(streams), 1))()
+    check(lib().tm_stage_inflate(blob.ctypes.data_as(ctypes.c_void_p), blob.size if nspans else 0, spans, nspans, descs, len(streams), _p(dst), dst_bytes, status, _stream()))
+    return dst, [(s.code, s.in_pos, s.out_n) for s in status[:len(streams)]]
+
+
+def png_decode(files, w, h, frame_px=None):
+    """A batch of PNG file images in host memory decoded on the device (tm_stage_png_decode: k_inflate, k_png_unfilter).  files: a list of
+    bytes, every one a w x h picture; frame_px: pixels from one frame of the destination to the next (default w h) -> (int32 CUDA tensor
+    [len(files)][frame_px] filled with -1 before the launch: frame f's pixels are its first w h entries, 0x00RRGGBB; status per file)"""
+    from ._lib import file_list
+    frame_px = w * h if frame_px is None else int(frame_px)
+    ptrs, sizes, keep = file_list(files)
+    out = torch.full((max(len(files), 1), frame_px), -1, dtype=torch.int32, device="cuda")
+    status = (ctypes.c_int32 * max(len(files), 1))()
+    check(lib().tm_stage_png_decode(ptrs, sizes, len(files), w, h, _p(out), frame_px, status, _stream()))
+    del keep
+    return out[:len(files)], list(status[:len(files)])

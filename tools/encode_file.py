@@ -1,5 +1,6 @@
 """A video file to a .gtm: python tools/encode_file.py IN OUT.gtm [--scaling S --start N --frames N --yuv auto|bt601|bt601-full|tiler|bt709|bt709-full]
                                                                [--raw-rgb LAYOUT --size WxH --fps F [--depth D]] [--pngs]
+                                                               [--png-decode host|device]
 
 IN is a Y4M file (`ffmpeg -i clip.mp4 -f yuv4mpegpipe clip.y4m`), a .gtm stream (its frames are played on the device and encoded again;
 --scaling must stay 1) or a Format pattern naming a PNG sequence (frame_%.4d.png; key frames where a frame_NNNN.kf file exists).
@@ -7,7 +8,7 @@ With --raw-rgb IN is a headerless file of RGB frames such as `ffmpeg -i clip.mp4
 bgr24, rgba, bgra, argb, abgr, rgb48, bgr48, rgba64, bgra64, rgbp, gbrp, gray; --depth D > 8: rgbp / gbrp / gray hold little-endian words of
 D bits, as gbrp10le does): it is mapped, not read, and lent to the encoder as it lies (SetFramesRGB), so --scaling applies, and --start and
 --frames slice the mapping.  --pngs: the decoded frames are also written as OUT_NNNN.png beside the stream, coded on the device
-(GeneratePNGs at level 1).  Prints the video as Load found it and the FrameQuality of the encode."""
+(GeneratePNGs at level 1).  --png-decode: where a PNG sequence is decoded (SetPngDecode; the default is the library's).  Prints the video as Load found it and the FrameQuality of the encode."""
 import argparse
 import json
 import os
@@ -31,11 +32,14 @@ ap.add_argument("--size", default=None, help="WxH of a --raw-rgb file's frames")
 ap.add_argument("--fps", type=float, default=None, help="frame rate of a --raw-rgb file")
 ap.add_argument("--depth", type=int, default=None, help="bits per sample of a --raw-rgb file's 16-bit words")
 ap.add_argument("--pngs", action="store_true", help="also write the decoded frames as OUT_NNNN.png (deflate on the device)")
+ap.add_argument("--png-decode", choices=["host", "device"], default=None, help="where a PNG sequence is decoded")
 args = ap.parse_args()
 enc = TilingEncoder()
 enc.LoadDefaultSettings()
 enc.OutputFileName = args.output
 enc.Scaling = args.scaling
+if args.png_decode:
+    enc.SetPngDecode(args.png_decode)
 if args.raw_rgb:
     import numpy as np
     if not args.size or not args.fps:

@@ -1,6 +1,6 @@
 """Wall time of Load from a Y4M file against Load of the same clip as RGB32 in page-locked host memory, and of the same clip lent as YUV planes.
 
-    python tools/time_file_load.py [--mode file|host|both|yuv|rgb|all] [--frames 300 --width 1280 --height 720] [--scaling 1.0] [--passes 7] [--dir /dev/shm]
+    python tools/time_file_load.py [--mode file|host|both|yuv|rgb|png|all] [--frames 300 --width 1280 --height 720] [--scaling 1.0] [--passes 7] [--dir /dev/shm]
 
 The clip is bench.py's (SURVEY.md 8d's generator).  `file`: it is written as a 4:2:0 Y4M into --dir (memory-backed by default, so that the
 figure is the pipeline's and not a disk's) and every pass is OpenInput + Run(esLoad).  `host`: the RGB32 clip sits in pinned memory and every
@@ -9,7 +9,10 @@ script times an older build of the library.  `yuv` (`all`: every leg): the plane
 Run(esLoad) -- (d) planar 4:2:0 in page-locked host memory, (e) NV12 in device memory, (f) P010 in device memory (the bytes in the high
 bits of 10-bit samples).  `rgb` (and `all`): the clip is lent with SetFramesRGB and every pass is SetFramesRGB + Run(esLoad) -- rgb24 and bgra in
 page-locked host memory, rgb24 and gbrp 10-bit in device memory, rgb24 in device memory at Scaling 0.5; the device legs also time the
-conversion alone (stages.rgb_to_rgb32) between two events.  One warm-up pass, then the median of --passes passes with their spread; one JSON line."""
+conversion alone (stages.rgb_to_rgb32) between two events.  `png` (not part of `all`): the clip is written into --dir as a PNG sequence, once by
+Pillow at its defaults and once by this library's level-1 export, and every pass is OpenInput + Run(esLoad) under TM_PNG_DECODE=host and
+=device; with --png-keep the sequences stay in --dir for the next call (an older build of the library, loaded with TM_LIB_VARIANT, reads them
+under `host` alone: --png-where host).  One warm-up pass, then the median of --passes passes with their spread; one JSON line."""
 import argparse
 import json
 import os
@@ -40,13 +43,15 @@ def stats(ms):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["file", "host", "both", "yuv", "rgb", "all"], default="both")
+    ap.add_argument("--mode", choices=["file", "host", "both", "yuv", "rgb", "png", "all"], default="both")
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=720)
     ap.add_argument("--scaling", type=float, default=1.0)
     ap.add_argument("--passes", type=int, default=7)
     ap.add_argument("--dir", default="/dev/shm")
+    ap.add_argument("--png-where", default="host,device", help="the TM_PNG_DECODE settings --mode png times")
+    ap.add_argument("--png-keep", action="store_true", help="--mode png: leave the sequences in --dir, and use those that are there")
     args = ap.parse_args()
     import torch
     from bench import synth_clip
@@ -132,6 +137,51 @@ def main():
                     kms.append(e0.elapsed_time(e1))
                 out[name]["convert_events"] = stats(kms[1:])
                 del dst
+
+    if args.mode == "png":
+        from PIL import Image
+        for writer in ("pillow", "own"):
+            stem = os.path.join(args.dir, "time_png_load_%s_%dx%dx%d" % (writer, W, H, F))
+            names = ["%s_%04d.png" % (stem, i) for i in range(F)]
+            try:
+                if not all(os.path.exists(n) for n in names):
+                    if writer == "pillow":
+                        for i in range(F):
+                            fr = clip[i]
+                            Image.fromarray(np.stack([(fr >> 16) & 255, (fr >> 8) & 255, fr & 255], -1).astype(np.uint8), "RGB").save(names[i], "PNG")
+                    else:
+                        enc = TilingEncoder()
+                        enc.LoadDefaultSettings()
+                        enc.OutputFileName = stem + ".gtm"
+                        enc.SetVideo(W, H, 24.0, F)
+                        enc.SetFramesHost(host)
+                        enc.Run(S.esLoad)
+                        enc.SetPngOptions(level=1)
+                        enc.GeneratePNGs(input=True)
+                        enc.close()
+                leg = dict(file_bytes=sum(os.path.getsize(n) for n in names))
+                for where in args.png_where.split(","):
+                    os.environ["TM_PNG_DECODE"] = where
+                    enc = TilingEncoder()
+                    enc.LoadDefaultSettings()
+                    enc.InputFileName = stem + "_%.4d.png"
+                    ms = []
+                    for p in range(args.passes + 1):
+                        t0 = time.perf_counter()
+                        info = enc.OpenInput()
+                        enc.Run(S.esLoad)
+                        ms.append((time.perf_counter() - t0) * 1e3)
+                    leg[where] = dict(stats(ms[1:]), video=info)
+                    if hasattr(enc._L, "tm_get_input_stats"):
+                        leg[where]["input_stats"] = enc.InputStats()
+                    enc.close()
+                out["load_png_" + writer] = leg
+            finally:
+                os.environ.pop("TM_PNG_DECODE", None)
+                if not args.png_keep:
+                    for n in names + [stem + ".txt"]:
+                        if os.path.exists(n):
+                            os.remove(n)
 
     if args.mode in ("file", "both", "all"):
         path = os.path.join(args.dir, "time_file_load_%d.y4m" % os.getpid())
