@@ -34,6 +34,10 @@
  *                           its entries' smallest bound, and ended at the first entry no query can want; A/B runs and tests)
  *   TM_KNN_FIRST_CHUNK=0    the scan runs every listed block's whole chain (default: a block is judged on its 32 widest columns first and
  *                           ends there when no query of it can gain or tie; A/B runs and tests)
+ *   TM_KNN_CURVE=morton|hilbert the order both sides of a KNN search (nearest neighbour and k nearest) are sorted in before they are cut into
+ *                           tiles: the Hilbert index of a row's four quantised coordinates, or their interleaved bits.  The results are the same
+ *                           either way; the boxes, and with them the work, are not (A/B runs and tests).  Not set: Hilbert,
+ *                           except for the sampled rows the k-nearest search estimates its first thresholds from, which stay in Morton order
  *   TM_KNN_ARENA_ENTRIES=<n> first size of the scan's tile-list arena (tests: a tiny one, so that a search is repeated with the counted size)
  *   TM_TOPK_BRUTE           the k-nearest search by the VALU brute force (tests compare the pruned scan with it)
  *   TM_EPU_TABLE_GIB=<x>    above this size the (tile, palette) feature table is not built, the pairs asked for are (default 6)
@@ -921,6 +925,11 @@ TM_API int tm_knn_last_plan(int *ht, int *hq, int *topk, int64_t *arena_retries)
 TM_API int tm_knn_index_row_order(tm_knn_index *, void *out_rows_u32, void *stream);
 /* ... and the step that orders them, on its own: every run of 32 entries of perm (device memory, uint32 [n]) into ascending order, in place */
 TM_API int tm_stage_knn_tile_order(void *perm_u32, int64_t n, void *stream);
+/* ... and the key both sides of a search are sorted by, on its own (k_curve_keys' arithmetic: curve_key, tm_knn_kernel.h): n cells of four
+ * quantised coordinates (device memory, uint32 [n][4], coordinate d below 2^bits[d]) into keys (device memory, uint32 [n]).  kind 0: the
+ * coordinates' bits interleaved (Morton order; the bits sum to 32 at most); kind 1: the Hilbert index on a grid of max(bits) bits per
+ * axis, an axis with fewer bits shifted up (every bits[d] 8 at most).  bits: HOST memory, int [4]. */
+TM_API int tm_stage_curve_keys(const void *coords_u32, int64_t n, const int *bits, int kind, void *keys_u32, void *stream);
 
 /* Render (:3455-3640) of nframes frames from their tile maps, on device pointers: tile_idx / pal_idx i32 [nframes][tm_h*tm_w],
  * item_flags u8 (bit 0 H mirror, bit 1 V mirror, bit 2 predicted), px / py int8 (PredictedX / PredictedY), pal_px u8 [ntiles][64],

@@ -114,6 +114,7 @@ SIGNATURES = {
     "tm_knn_index_last_chunk_counts": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     "tm_knn_index_row_order": (c_int, [c_void_p, c_void_p, c_void_p]),
     "tm_stage_knn_tile_order": (c_int, [c_void_p, c_int64, c_void_p]),
+    "tm_stage_curve_keys": (c_int, [c_void_p, c_int64, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p]),
     "tm_knn_last_plan": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int64)]),
     "tm_stage_dedup": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
     "tm_stage_kmeans": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int),

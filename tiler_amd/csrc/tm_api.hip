@@ -17,7 +17,7 @@ int tm_device_count(void) {
 }
 
 // the trailing token names the build of the KNN scan kernel: PMC passes under profiles/ are keyed by it (bench.py reads `traffic` from them)
-const char *tm_version(void) { return "tilemotion-mi355x 0.3 (gfx950) knn-scan3-r11"; }
+const char *tm_version(void) { return "tilemotion-mi355x 0.3 (gfx950) knn-scan3-r15"; }
 
 int tm_stage_load(const void *frames, int nframes, int img_w, int img_h, int tm_w, int tm_h, void *tiles, void *flags,
                   void *lab_means, void *stream) {
@@ -177,6 +177,21 @@ int tm_stage_knn_tile_order(void *perm_u32, int64_t n, void *stream) {
   TM_TRY(require_device());
   TM_CHECK(perm_u32 != nullptr && n >= 0, TM_E_INVAL, "knn tile order: null rows or a negative count");
   return launch_tile_order((uint32_t *)perm_u32, n, (hipStream_t)stream);
+}
+
+int tm_stage_curve_keys(const void *coords_u32, int64_t n, const int *bits, int kind, void *keys_u32, void *stream) {
+  TM_TRY(require_device());
+  TM_CHECK(n >= 0 && bits != nullptr && (n == 0 || (coords_u32 != nullptr && keys_u32 != nullptr)), TM_E_INVAL, "curve keys: null argument or a negative count");
+  TM_CHECK(kind == 0 || kind == 1, TM_E_INVAL, "curve keys: kind %d is neither 0 (Morton) nor 1 (Hilbert)", kind);
+  int sum = 0, most = 0;
+  for (int d = 0; d < 4; d++) {
+    TM_CHECK(bits[d] >= 1 && bits[d] <= 16, TM_E_INVAL, "curve keys: %d bits for dimension %d (1..16)", bits[d], d);
+    sum += bits[d];
+    most = std::max(most, bits[d]);
+  }
+  TM_CHECK(kind == 0 ? sum <= 32 : most <= 8, TM_E_UNSUPPORTED, "curve keys: bits %d %d %d %d do not fit a 32-bit key (Morton: their sum, Hilbert: four times the largest)",
+           bits[0], bits[1], bits[2], bits[3]);
+  return launch_curve_keys((const uint32_t *)coords_u32, n, bits, kind, (uint32_t *)keys_u32, (hipStream_t)stream);
 }
 
 int tm_knn_last_plan(int *ht, int *hq, int *topk, int64_t *arena_retries) {

@@ -52,6 +52,8 @@ struct Knobs {
        comm_force_dist = false, features_plain = false, km_launches = false, kmodes_binwise = false, kmodes_fast_always = false, pp_sharded = false, window_dcts_by_tile = false, km_resident_fail = false, features_by_tile = false, motion_pack_separate = false, motion_force_flag = false;
   bool knn_first_chunk = true;  // TM_KNN_FIRST_CHUNK=0: the scan runs every listed block's whole chain (A/B runs, tests)
   bool knn_list_order = true;  // TM_KNN_LIST_ORDER=0: the scan's tile lists stay in run order and are consumed to their ends (A/B runs, tests)
+  int knn_curve = -1;  // TM_KNN_CURVE=morton|hilbert: the order both sides of every KNN search are sorted in (CURVE_MORTON 0, CURVE_HILBERT 1, tm_knn_kernel.h; A/B runs, tests);
+                       // -1, not set: Hilbert, and Morton for the sample index of the k-nearest search's estimate (knn_index_search_topk)
   bool km_first_look = true;  // TM_KM_FIRST_LOOK=0: the plain iterations of the tile k-means score every point with the double-precision chain (A/B runs, tests)
   int topk_estimate = -1;  // TM_TOPK_ESTIMATE: the k-nearest search's first thresholds from a sample of the database: -1 by size, 0 never, 1 whenever possible
   double epu_table_gib = 6.0, comm_timeout_s = 120.0;

@@ -62,6 +62,8 @@ int knn_index_row_order(tm_knn_index_impl *ix, void *out_rows, hipStream_t strea
 // tm_knn_prepare.hip: every run of 32 entries of perm (device, [n]) into ascending order, in place (what a built index does to its curve order;
 // pack: the database's pack, whose tiles' last 128 bytes take the ordered indices)
 int launch_tile_order(uint32_t *perm, int64_t n, hipStream_t stream, uint8_t *pack = nullptr, int tile_bytes = 0);
+// tm_knn_prepare.hip: curve_key (tm_knn_kernel.h) of n cells (device, [n][4], cell d below 2^bits[d]) into keys (device, [n]); kind: CURVE_MORTON 0, CURVE_HILBERT 1
+int launch_curve_keys(const uint32_t *cells, int64_t n, const int bits[4], int kind, uint32_t *keys, hipStream_t stream);
 // the last search's three kernels on their own: ms of seeds / lists / consume; pairs evaluated by seeds / consume, matrix instructions the consume kernel issued
 void knn_index_kernel_split(tm_knn_index_impl *ix, double ms[3], int64_t pairs[3]);
 // grp_off / grp_members (optional): the index was built over DISTINCT rows; results are expanded to the original rows (member lists

@@ -51,6 +51,7 @@ struct tm_knn_index_impl {
   DevBuf qperm, qkey, skey, skey2, sidx, sort_tmp;  // queries sorted along the curve
   DevBuf rrange, tradial, qradial;                  // radial coordinate of the rows (curve key) and its range
   CurveSpec curve;
+  int curve_kind = CURVE_HILBERT;                   // the order an index takes where TM_KNN_CURVE is not set (choose_curve)
   DevBuf counters;                                  // one K3Counters (tm_knn3_kernel.h)
   DevBuf tccol, qccol;                              // the rows' three curve columns (k_row_radial -> k_curve_keys)
   DevBuf qmeta;                                     // per query sub-tile: box, home tile, high-chunk mask

@@ -1,4 +1,4 @@
-// tm_knn_prepare.hip -- what a KNN search does before its scan: both sides sorted along the Morton curve and packed into the scan's
+// tm_knn_prepare.hip -- what a KNN search does before its scan: both sides sorted along the curve (Hilbert or Morton) and packed into the scan's
 // MFMA fragment order, the database's boxes (see tm_knn.hip for the scheme, tm_knn_kernel.h for the pruning).
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -321,13 +321,13 @@ __global__ __launch_bounds__(256) void k_row_radial(const int16_t *__restrict__ 
   }
 }
 
-// Morton key, value = row index: the three widest columns at 8 bits each over the union range, plus 8 bits of the radial coordinate
-// over ITS range, so that the rows of a tile are alike in texture energy as well as in mean colour -- which is what the radial
-// box dimension needs in order to prune (30 % fewer evaluated pairs on the bench clip than a 3 x 10-bit curve of the columns alone).
+// Curve key (curve_key, tm_knn_kernel.h: Hilbert or Morton order of the cells), value = row index: the three widest columns quantised over
+// the union range, plus the radial coordinate over ITS range, so that the rows of a tile are alike in texture energy as well as in mean
+// colour -- which is what the radial box dimension needs in order to prune (30 % fewer evaluated pairs on the bench clip than a
+// 3 x 10-bit curve of the columns alone).  k_cell_keys is the key alone, on cells given (tm_stage_curve_keys: the tests' way in).
 __global__ void k_curve_keys(const uint2 *__restrict__ ccol /* k_row_radial's copy of the three curve columns */, int64_t n, CurveSpec cs, const float *__restrict__ radial,
                              uint32_t *__restrict__ key, uint32_t *__restrict__ idx) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    // per-dimension bit counts, interleaved from the top: a dimension with more bits splits first
     uint32_t q[4];
     const uint2 c3 = ccol[i];
     const int cv[3] = {(int)(int16_t)(c3.x & 0xffff), (int)(int16_t)(c3.x >> 16), (int)(int16_t)(c3.y & 0xffff)};
@@ -336,13 +336,15 @@ __global__ void k_curve_keys(const uint2 *__restrict__ ccol /* k_row_radial's co
       const float v = d < 3 ? (float)cv[d] : (cs.rlog ? log2f(radial[i] + 1.0f) : radial[i]);
       q[d] = (uint32_t)min((float)((1u << cs.bits[d]) - 1u), max(0.0f, (v - cs.off[d]) * cs.scale[d]));
     }
-    uint32_t k = 0;
-    for (int b = 15; b >= 0; b--)
-#pragma unroll
-      for (int d = 0; d < 4; d++)
-        if (cs.bits[d] > b) k = (k << 1) | ((q[d] >> b) & 1u);
-    key[i] = k;
+    key[i] = curve_key(q, cs.bits, cs.kind);
     idx[i] = (uint32_t)i;
+  }
+}
+
+__global__ void k_cell_keys(const uint32_t *__restrict__ cells /* [n][4] */, int64_t n, CurveSpec cs, uint32_t *__restrict__ key) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t q[4] = {cells[i * 4], cells[i * 4 + 1], cells[i * 4 + 2], cells[i * 4 + 3]};
+    key[i] = curve_key(q, cs.bits, cs.kind);
   }
 }
 
@@ -360,7 +362,17 @@ static int row_radial(tm_knn_index_impl *ix, const void *feat, int64_t n, DevBuf
   return TM_OK;
 }
 
-// rows sorted along the Morton curve: perm (row order) and the sorted keys
+int launch_curve_keys(const uint32_t *cells, int64_t n, const int bits[4], int kind, uint32_t *keys, hipStream_t stream) {
+  if (n <= 0) return TM_OK;
+  CurveSpec cs = {};
+  for (int d = 0; d < 4; d++) cs.bits[d] = bits[d];
+  cs.kind = kind;
+  hipLaunchKernelGGL(k_cell_keys, dim3(gridn(n)), dim3(256), 0, stream, cells, n, cs, keys);
+  TM_HIP(hipGetLastError());
+  return TM_OK;
+}
+
+// rows sorted along the curve: perm (row order) and the sorted keys
 static int sort_by_curve(tm_knn_index_impl *ix, const DevBuf &ccol, int64_t n, const DevBuf &radial, DevBuf &perm, DevBuf &keys_sorted, hipStream_t stream) {
   TM_TRY(ix->skey.alloc((size_t)n * 4)); TM_TRY(ix->sidx.alloc((size_t)n * 4));
   TM_TRY(perm.alloc((size_t)n * 4)); TM_TRY(keys_sorted.alloc((size_t)n * 4));
@@ -429,8 +441,11 @@ static int new_plan(tm_knn_index_impl *ix, const ColStats &qs, int64_t nq, hipSt
 }
 
 // The curve of an index (fixed until its plan changes): the KNN_ND widest columns of the union are the box columns, the first three
-// drive the Morton order; the radial coordinate of every database row and of this batch of queries is computed on the way, its range
+// drive the curve order; the radial coordinate of every database row and of this batch of queries is computed on the way, its range
 // scales the key's radial bits.
+#ifndef TM_KNN_CURVE_BITS
+#define TM_KNN_CURVE_BITS 8, 7, 7, 8  // (a measuring build sets another split: tools/build_variant.sh NAME -DTM_KNN_CURVE_BITS=8,8,8,8)
+#endif
 static int choose_curve(tm_knn_index_impl *ix, const void *queries, int64_t nq, const ColStats &qs, hipStream_t stream) {
   CurveSpec &cs = ix->curve;
   int order[192];
@@ -465,14 +480,16 @@ static int choose_curve(tm_knn_index_impl *ix, const void *queries, int64_t nq, 
   // isotropic cells (9, 8, 8, 6 bits, linear R): 18.6 G, 21.4 ms; columns only (10, 10, 10): 28.9 G, 30.2 ms.
   // The k-nearest scans use the same curve (measured after their kernel stopped spilling: first collection pass of the
   // extended-palette run 112 ms on this curve, 146 ms on 10, 10, 10 bits of the columns alone).
-  const int nb[4] = {8, 7, 7, 8};
+  // (Those figures are round 1's kernel on the Morton order.  DESIGN.md section 36 has the two orders on today's scan.)
+  const int nb[4] = {TM_KNN_CURVE_BITS};
   cs.rlog = 1;
+  cs.kind = knobs().knn_curve >= 0 ? knobs().knn_curve : ix->curve_kind;  // TM_KNN_CURVE: the nearest-neighbour search and the k-nearest collection share the curve and both follow it
   for (int d = 0; d < 3; d++) { cs.bits[d] = nb[d]; cs.off[d] = (float)cs.lo[d]; cs.scale[d] = (float)((1 << nb[d]) - 1) / (float)cs.range[d]; }
   cs.bits[3] = nb[3]; cs.off[3] = log2f(rlo + 1.0f);
   cs.scale[3] = ((float)(1 << nb[3]) - 0.001f) / std::max(1e-6f, log2f(rhi + 1.0f) - log2f(rlo + 1.0f));
   if (knobs().knn_debug)
-    fprintf(stderr, "[tm_knn] curve: column ranges %d %d %d, radial %.1f..%.1f -> bits %d %d %d %d (%s)\n", cs.range[0], cs.range[1], cs.range[2], rlo, rhi,
-            cs.bits[0], cs.bits[1], cs.bits[2], cs.bits[3], "own ranges, log radial");
+    fprintf(stderr, "[tm_knn] curve: column ranges %d %d %d, radial %.1f..%.1f -> bits %d %d %d %d (%s, %s order)\n", cs.range[0], cs.range[1], cs.range[2], rlo, rhi,
+            cs.bits[0], cs.bits[1], cs.bits[2], cs.bits[3], "own ranges, log radial", cs.kind == CURVE_HILBERT ? "Hilbert" : "Morton");
   return TM_OK;
 }
 

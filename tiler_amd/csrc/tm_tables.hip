@@ -157,6 +157,7 @@ void knobs_reload() {
   k.motion_valu = on("TM_MOTION_VALU"); k.pp_debug = on("TM_PP_DEBUG"); k.comm_force_dist = on("TM_COMM_FORCE_DIST"); k.features_plain = on("TM_FEATURES_PLAIN"); k.km_launches = on("TM_KM_LAUNCHES"); k.kmodes_binwise = on("TM_KMODES_BINWISE"); k.kmodes_fast_always = on("TM_KMODES_FAST_ALWAYS"); k.pp_sharded = on("TM_PP_SHARDED"); k.window_dcts_by_tile = on("TM_WINDOW_DCTS_BY_TILE"); k.km_resident_fail = on("TM_KM_RESIDENT_FAIL"); k.features_by_tile = on("TM_FEATURES_BY_TILE"); k.motion_pack_separate = on("TM_MOTION_PACK_SEPARATE"); k.motion_force_flag = on("TM_MOTION_FORCE_FLAG");
   if (const char *v = getenv("TM_KNN_FIRST_CHUNK")) k.knn_first_chunk = !(v[0] == '0' && v[1] == 0);
   if (const char *v = getenv("TM_KNN_LIST_ORDER")) k.knn_list_order = !(v[0] == '0' && v[1] == 0);
+  if (const char *v = getenv("TM_KNN_CURVE")) k.knn_curve = !strcmp(v, "morton") ? 0 : !strcmp(v, "hilbert") ? 1 : k.knn_curve;
   if (const char *v = getenv("TM_KM_FIRST_LOOK")) k.km_first_look = !(v[0] == '0' && v[1] == 0);
   if (const char *v = getenv("TM_TOPK_ESTIMATE")) k.topk_estimate = (v[0] == '0' && v[1] == 0) ? 0 : 1;
   if (const char *v = getenv("TM_EPU_TABLE_GIB")) k.epu_table_gib = atof(v);

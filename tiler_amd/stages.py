@@ -238,6 +238,15 @@ def knn_tile_order(perm):
     return perm
 
 
+def curve_keys(coords, bits, kind):
+    """the KNN searches' curve key of every cell of coords (int32 / uint32 bit patterns [n][4] on the device, coordinate d below 2^bits[d]) ->
+    int32 [n] holding uint32 bit patterns.  kind 0: Morton order (the bits interleaved), 1: Hilbert order"""
+    n = coords.shape[0]
+    keys = torch.empty((n,), dtype=torch.int32, device=coords.device)
+    check(lib().tm_stage_curve_keys(_p(coords), n, (ctypes.c_int * 4)(*[int(b) for b in bits]), kind, _p(keys), _stream()))
+    return keys
+
+
 def knn_last_plan():
     """(ht, hq, topk, arena_retries): the digit plan and mode of this thread's last scan, and the process's count of repeated scans (tests)"""
     ht, hq, tk, r = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
