@@ -1,5 +1,5 @@
-// tm_kmeans.h -- what the k-means files share (tm_kmeans.hip, tm_kmeans_tile.hip, tm_kmeans_pixel.hip, tm_palettize.hip); nobody else
-// includes it.  The callers' prototypes are in tm_internal.h.
+// tm_kmeans.h -- what the k-means files share (tm_kmeans.hip, tm_kmeans_pixel.hip, tm_palettize.hip and the three D = 192 files behind
+// tm_kmeans_tile.h); nobody else includes it.  The callers' prototypes are in tm_internal.h.
 #pragma once
 #include <cstring>
 #include <algorithm>
@@ -47,6 +47,7 @@ __device__ __forceinline__ bool better(const BestKey &a, const BestKey &b) {
 
 constexpr int KCH = 16;     // centroids scored per pass (register accumulators)
 constexpr int H_MAXK = 64;  // centroids kept in LDS by the skipping kernels
+constexpr int CU_LDS_BYTES = 160 * 1024;  // a compute unit's LDS
 
 // ---- the barrier of the resident kernels (k_h_resident: the whole grid; k_kmeans3_persistent: the workgroups of one segment) -----------
 // Arrivals are counted in eight shards (workgroup g on shard g % 8: atomics on one word take their turns, ~12 ns each); the last arrival of
@@ -119,7 +120,8 @@ int kmeans_batched(const int32_t *pts, const uint32_t *w, int d, const std::vect
 int kmeans3_persistent(const int32_t *pts, const uint32_t *w, const std::vector<int64_t> &seg_begin, const std::vector<int64_t> &seg_count, int k,
                        int max_iter, int32_t *assign, double *cent, std::vector<int> *host_kk, int *host_iters, hipStream_t stream, int *used);
 
-// ---- tm_kmeans_tile.hip: D = 192 --------------------------------------------------------------------------------------------------
+// ---- D = 192 (tm_kmeans_tile.h has the rules the three files share) -----------------------------------------------------------------
+// tm_kmeans_assign192.hip: the plain iterations' assignment step
 void launch_chunk_major(const int32_t *pts, int64_t n, int32_t *out, hipStream_t stream);  // [n][192] -> [24][n][8]
 
 // ---- the first look of the plain iterations: decide in single precision, the double-precision chain only where in doubt ----------------
@@ -133,31 +135,44 @@ void launch_chunk_major(const int32_t *pts, int64_t n, int32_t *out, hipStream_t
 //           integer rows leaves Single's normal range: a quotient of an int64 sum and a count, zero or at least 2^-64 in magnitude),
 //           computed in double and rounded up.  By the triangle inequality | |p - c^| - |p - c| | <= E(c).
 // The true distance d(c) therefore lies in [lo(c), hi(c)] = [sqrt(s(c)) (1 - FL_GAMMA) - E(c), sqrt(s(c)) (1 + FL_GAMMA) + E(c)].
-// With c* the Single argmin, a point is DECIDED iff lo(c) (1 - FL_ETA) > hi(c*) (1 + FL_ETA) for every other c: the reference's computed
+// With c* the Single argmin, a point is DECIDED iff lo(c) (1 - KM_ETA) > hi(c*) (1 + KM_ETA) for every other c: the reference's computed
 // squared distances (within 1e-13 of the true ones) are then strictly ordered the same way, no tie can occur, c* is the reference's
 // answer.  Otherwise, or when some |p_j| >= 2^24 (its conversion may round), the point is IN DOUBT and goes through the chain itself:
 // double, terms in order, ties to the lowest index, against all its centroids (those that are no contenders lie strictly behind c*, so
 // scoring them as well changes nothing).
-// Bounds for the skipping iterations: ub = hi(c*), lb = the smallest lo(c) among the others, each moved outwards by FL_ETA; the exact
+// Bounds for the skipping iterations: ub = hi(c*), lb = the smallest lo(c) among the others, each moved outwards by KM_ETA (the one margin, tm_kmeans_tile.h); the exact
 // roots with k_assign192's own margins where the chain ran.
 constexpr double FL_GAMMA = 1.0 / 65536.0;    // 2^-16
 constexpr double FL_CENT = 1.0 / 8388608.0;   // 2^-23
-constexpr double FL_ETA = 1e-9;                // the margin of the comparison, the one of the skip test (H_ETA)
 constexpr float FL_INT_EXACT = 16777216.0f;    // 2^24: below it int32 -> Single is exact
 
 // k_assign192's launch: slices of the largest segment sized so that one round of workgroups fills the chip evenly
 struct Assign192Shape { int ppt, nblk, rows, lds_delta; size_t lds; };
 Assign192Shape assign192_shape(int64_t maxcount, int nseg, int k, int cus);
-// look_stats: two counters on the device (point-scorings looked at, those that went to the chain) the launch adds to, or null; the first
-// look itself is taken unless TM_KM_FIRST_LOOK=0
-void launch_assign192(const Assign192Shape &sh, int nseg, hipStream_t stream, const int32_t *pts, const int32_t *ptsc, int64_t ntot, const uint32_t *w, Seg *ds,
-                      int k, const double *cent, int32_t *assign, u64 *sums, u64 *cnts, const int *quiet, double *ub = nullptr, double *lb = nullptr,
-                      u64 *look_stats = nullptr);
+// what a launch of k_assign192 works on.  ub, lb: where it leaves the bounds the skipping iterations start from, or null.  look_stats: two
+// counters on the device (point-scorings looked at, those that went to the chain) the launch adds to, or null; the first look itself is taken
+// unless TM_KM_FIRST_LOOK=0
+struct Assign192Args {
+  const int32_t *pts, *ptsc;  // rows, and the same chunk-major
+  int64_t ntot;
+  const uint32_t *w;
+  Seg *ds;
+  int k;
+  const double *cent;
+  int32_t *assign;
+  u64 *sums, *cnts;
+  const int *quiet;
+  double *ub = nullptr, *lb = nullptr;
+  u64 *look_stats = nullptr;
+};
+void launch_assign192(const Assign192Shape &sh, int nseg, hipStream_t stream, const Assign192Args &a);
 
+// ---- tm_kmeans_resident.hip
 // Would one segment of n points and k centroids go through k_h_resident on a device of `cus` compute units?  rounds == 0: no.
 struct ResidentPlan { int grid, rounds; size_t lds; };
 ResidentPlan resident_plan(int64_t n, int k, int cus);
 
+// ---- tm_kmeans_skip.hip
 // One clustering of one D = 192 segment with at most H_MAXK centroids, as kmeans_batched hands it to the skipping iterations: after
 // H_WARM plain iterations the assignment step only touches the points whose bounds do not prove their assignment.
 constexpr int H_WARM = 5;
@@ -177,10 +192,11 @@ struct TileRun {
   // the skipping iterations' own state (tile_skip_setup)
   DevBuf ub, lb, cent_t, move, half, need, cnt;
   int kt;        // row pitch of the transposed centroids (cent_t)
-  size_t l_lds;  // k_assign192_list4's
+  Assign192Args assign192_args(double *ub_out = nullptr, double *lb_out = nullptr) const { return {pts, ptsc, n, w, ds, k, cent, assign, sums, cnts, quiet, ub_out, lb_out, look}; }
 };
 int tile_skip_setup(TileRun &t);
 void tile_skip_iteration(TileRun &t, int iter, int *pin_dev);  // iteration `iter` (plain below H_WARM) and its update
+// tm_kmeans_resident.hip again, on a TileRun:
 enum class Resident { done, gave_up, not_applicable };
 // the H_WARM plain iterations, then all skipping iterations in one launch of k_h_resident; done: *iters is set
 int tile_resident(TileRun &t, const ResidentPlan &plan, Resident *verdict, int *iters);

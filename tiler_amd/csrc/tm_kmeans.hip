@@ -12,8 +12,8 @@
 // Callers: tm_stage_kmeans (one segment), run_palettize (DoPalettization, tilingencoder.pas:4105-4245, D = 192) and
 // run_quantize_palettes (QuantizeUsingYakmo + DoQuantization, 4434-4564, D = 3, one segment per palette, run on the
 // (G,R,B)-sorted colour histogram of each palette's pixels).
-// The D = 192 kernels are in tm_kmeans_tile.hip, the resident D = 3 clustering in tm_kmeans_pixel.hip, PreparePalettes' use of all of it in
-// tm_palettize.hip; tm_kmeans.h is what the four share.
+// The D = 192 kernels are in tm_kmeans_assign192.hip, tm_kmeans_skip.hip and tm_kmeans_resident.hip (their own rules: tm_kmeans_tile.h), the resident
+// D = 3 clustering in tm_kmeans_pixel.hip, PreparePalettes' use of all of it in tm_palettize.hip; tm_kmeans.h is what all of them share.
 #include <type_traits>
 #include <chrono>
 #include <cstdlib>
@@ -518,7 +518,7 @@ static int km_launches(KmRun &r, int *iters) {
           hipLaunchKernelGGL(k_accumulate<3>, dim3(nblk), dim3(256), lds_acc, stream, t.pts, t.w, t.ds, k, t.assign, t.sums, t.cnts, t.quiet);
         }
       } else {
-        launch_assign192(t.a192, nseg, stream, t.pts, t.ptsc, t.n, t.w, t.ds, k, t.cent, t.assign, t.sums, t.cnts, t.quiet, nullptr, nullptr, t.look);
+        launch_assign192(t.a192, nseg, stream, t.assign192_args());
       }
       hipLaunchKernelGGL(k_update_all, dim3(1), dim3(1024), 0, stream, t.ds, nseg, k, d, (d == 192 || fuse3) ? 1 : 0, t.sums, t.cnts, t.cent, issued, t.quiet, pin_dev);
     }

@@ -478,8 +478,7 @@ int run_palettize_dist(const void *feat_local, const void *use_local, int64_t n,
   const Assign192Shape a192 = assign192_shape(n1, 1, k, cu_count());
   for (int it = 0; it < max_iter; it++) {
     if (n > 0)
-      launch_assign192(a192, 1, stream, pts, ptsc.as<int32_t>(), n, w, dsegs.as<Seg>(), k, cent.as<double>(), assign.as<int32_t>(), sums.as<u64>(), cnts.as<u64>(),
-                       quiet.as<int>());
+      launch_assign192(a192, 1, stream, {pts, ptsc.as<int32_t>(), n, w, dsegs.as<Seg>(), k, cent.as<double>(), assign.as<int32_t>(), sums.as<u64>(), cnts.as<u64>(), quiet.as<int>()});
     hipLaunchKernelGGL(k_kmd_pack, dim3(32), dim3(256), 0, stream, sums.as<u64>(), cnts.as<u64>(), dsegs.as<Seg>(), k, red.as<u64>());
     TM_HIP(hipGetLastError());
     TM_TRY(co.allreduce_sum_i64(red.p, (int64_t)k * d + k + 1));

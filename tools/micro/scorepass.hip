@@ -1,4 +1,4 @@
-// development aid: what the pieces of one scoring pass of k_h_resident (tm_kmeans_tile.hip) cost, on a single workgroup: a kernel repeats the pass REPS
+// development aid: what the pieces of one scoring pass of k_h_resident (tm_kmeans_resident.hip) cost, on a single workgroup: a kernel repeats the pass REPS
 // times with pieces switched on by template flags (1 chain, 2 merge, 4 results + moved list, 8 the two barriers + moved rows), timed from the host.
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off scorepass.hip -o scorepass && ./scorepass
 #include <hip/hip_runtime.h>
