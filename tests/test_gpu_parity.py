@@ -259,7 +259,11 @@ def _rand_features(rng, n, spread):
     return f.astype(np.int16)
 
 
-@pytest.mark.parametrize("nq,nt,spread", [(70, 100, 90), (1, 1, 90), (33, 31, 1200), (300, 1000, 600), (64, 2049, 100), (700, 5000, 300)])
+# (65 queries x 224 .. 257 rows: three sub-tiles, the last with one real query, against seven, eight, eight and nine database tiles -- the
+# seed window's clamp, database tiles - seeds scored per group, below, at and above zero: where the seed kernel and the list kernel must
+# agree on which tiles the seeds took)
+@pytest.mark.parametrize("nq,nt,spread", [(70, 100, 90), (1, 1, 90), (33, 31, 1200), (300, 1000, 600), (64, 2049, 100), (700, 5000, 300),
+                                          (65, 224, 90), (65, 255, 90), (65, 256, 90), (65, 257, 90)])
 def test_knn_exact(oracle, nq, nt, spread):
     from tiler_amd import stages
     rng = np.random.default_rng(nq * 1000 + nt)

@@ -1,5 +1,6 @@
 // tm_knn.h -- what the KNN stage's host files share (tm_knn.hip, tm_knn_plan.hip, tm_knn_prepare.hip, tm_knn_topk.hip); nobody else
-// includes it.  The callers' prototypes are in tm_internal.h, the kernels' argument structs in tm_knn_kernel.h and tm_knn3_kernel.h.
+// includes it.  The callers' prototypes are in tm_internal.h, the kernels' argument structs and the layouts both sides agree on in
+// tm_knn_kernel.h and tm_knn3.h (the packed tile: knn_pack_bytes and its parts).
 #pragma once
 #include <cstring>
 
@@ -10,7 +11,7 @@
 #include "tm_common.h"
 #include "tm_internal.h"
 #include "tm_knn_kernel.h"
-#include "tm_knn3_kernel.h"
+#include "tm_knn3.h"
 
 namespace tmx {
 
@@ -24,11 +25,6 @@ struct KnnPlan {
   int tscale = 1;         // database digits are those of tscale * (t - c): 2 lets the scan's chain deliver 2 X without a final doubling
 };
 inline int knn_kbytes(const KnnPlan &p) { return 192 + 32 * (p.ht + p.hq + std::min(p.ht, p.hq)); }  // K of the distance GEMM
-
-// a packed tile of 32 rows: the operand chunks, 32 row terms (norms), the box (database side), 32 row terms over the first chunk's columns,
-// the rows' 32 original indices (database side)
-__host__ __device__ constexpr int knn_tile_bytes(int hch, int with_box) { return (6 + hch) * 1024 + 128 + (with_box ? 64 : 0) + 128 + (with_box ? 128 : 0); }
-static_assert(knn_tile_bytes(5, 1) == k3_t_bytes(11) && knn_tile_bytes(4, 0) == k3_q_bytes(10), "the scan kernels' view of the packs");
 
 // what the last nearest-neighbour search's counters said (K3Counters, read once per attempt)
 struct KnnCounts {
@@ -52,7 +48,7 @@ struct tm_knn_index_impl {
   DevBuf rrange, tradial, qradial;                  // radial coordinate of the rows (curve key) and its range
   CurveSpec curve;
   int curve_kind = CURVE_HILBERT;                   // the order an index takes where TM_KNN_CURVE is not set (choose_curve)
-  DevBuf counters;                                  // one K3Counters (tm_knn3_kernel.h)
+  DevBuf counters;                                  // one K3Counters (tm_knn3.h)
   DevBuf tccol, qccol;                              // the rows' three curve columns (k_row_radial -> k_curve_keys)
   DevBuf qmeta;                                     // per query sub-tile: box, home tile, high-chunk mask
   // third scan shape: what the seed kernel leaves for the other two (bests, bounds) and the groups' tile lists
@@ -98,8 +94,10 @@ int ensure_list_buffers(tm_knn_index_impl *ix, Knn3Args *a);
 int ensure_arena(tm_knn_index_impl *ix, double factor, Knn3Args *a);
 int arena_overflowed(tm_knn_index_impl *ix, unsigned long long cursor, int attempt);
 int scan_grid_blocks(int64_t units);
+int launch_collect(tm_knn_index_impl *ix, const Knn3Args &a, hipStream_t stream);
+
+// tm_knn3_lists.hip: the lists kernel and the collection mode's bounds
 int launch_tau_bounds(const Knn3Args &a, hipStream_t stream);
 int launch_lists(const Knn3Args &a, hipStream_t stream);
-int launch_collect(tm_knn_index_impl *ix, const Knn3Args &a, hipStream_t stream);
 
 }  // namespace tmx

@@ -19,10 +19,10 @@
 //   tiny kernel puts (index, error) back in the caller's order.
 //
 // Files: tm_knn_plan.hip (column ranges, digit plan), tm_knn_prepare.hip (curve order, packs, boxes), this file (the index, the scan's
-// host side, the nearest-neighbour search), tm_knn_topk.hip (the k nearest rows); tm_knn.h is what the four share.
+// host side, the nearest-neighbour search), tm_knn_topk.hip (the k nearest rows); tm_knn.h is what the four share.  The scan's kernels:
+// tm_knn3.h (what they share with the host), tm_knn3_lists.hip and tm_knn3_k<HT>.hip.
 #include <atomic>
 
-#define TM_KNN3_WITH_LISTS  // k_knn_lists and k_knn_tau_bounds are defined here and launched by launch_lists / launch_tau_bounds
 #include "tm_knn.h"
 
 namespace tmx {
@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void k_knn_refine(int64_t nq, const uint32_t *
                                                     const int *__restrict__ best_key, const int *__restrict__ best_idx,
                                                     int *__restrict__ out_idx, uint32_t *__restrict__ out_err) {
   for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < nq; p += (int64_t)gridDim.x * blockDim.x) {
-    const uint32_t nqv = reinterpret_cast<const uint32_t *>(qpack + (p >> 5) * (int64_t)q_bytes + q_bytes - 256)[p & 31];
+    const uint32_t nqv = reinterpret_cast<const uint32_t *>(qpack + (p >> 5) * (int64_t)q_bytes + knn_pack_row_terms_of(q_bytes))[p & 31];
     const int64_t q = qperm[p];
     out_idx[q] = best_idx[p];
     out_err[q] = (uint32_t)best_key[p] + (nqv & 1u);
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void k_knn_qmeta(const uint32_t *__restrict__ 
     const uint32_t k0 = qkey[st * 32];  // last tile whose first key <= the sub-tile's first key
     int64_t lo = 0, hi = n_ttiles;
     while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (bx.tkey[mid] <= k0) lo = mid + 1; else hi = mid; }
-    qmeta[st * 16 + 7] = (int)max((int64_t)0, lo - 1);
+    qmeta[qmeta_at(st, QMETA_HOME)] = (int)max((int64_t)0, lo - 1);
   }
 }
 
@@ -74,7 +74,7 @@ int knn_index_create(const void *db, int64_t nt, hipStream_t stream, tm_knn_inde
 void knn_index_destroy(tm_knn_index_impl *ix) { delete ix; }
 
 // ---------------------------------------------------------------------------------------------------------------
-// host side: the third scan shape (tm_knn3_kernel.h): seeds -> lists -> consume, all queued on the caller's stream
+// host side: the third scan shape (tm_knn3.h): seeds -> lists -> consume, all queued on the caller's stream
 
 #define TM_KNN3_BY_HT(FN)                                          \
   switch (ht) {                                                      \
@@ -136,7 +136,7 @@ int launch_qmeta(tm_knn_index_impl *ix, int64_t nqt, int64_t ntt, const KnnBoxes
 // collection: no_seeds, split, the thresholds and the candidate lists) and grid_blocks is the caller's (scan_grid_blocks).
 int scan_args(tm_knn_index_impl *ix, int64_t nq, int ns, Knn3Args *out) {
   const int64_t nqt = knn_tiles(nq), ntt = knn_tiles(ix->nt);
-  TM_CHECK(ntt < (1 << 24), TM_E_UNSUPPORTED, "knn: %lld database tiles exceed the list entries' 24-bit tile index", (long long)ntt);
+  TM_CHECK(ntt < K3_ENTRY_TILES, TM_E_UNSUPPORTED, "knn: %lld database tiles exceed the list entries' 24-bit tile index", (long long)ntt);
   Knn3Args &a = *out;
   memset(&a, 0, sizeof(a));
   a.tpack = ix->tpack.as<uint8_t>(); a.n_ttiles = ntt; a.nt_rows = ix->nt;
@@ -194,18 +194,6 @@ static void note_list_entries(unsigned long long cursor, int64_t n_groups) {
   const double per = 1.3 * (double)cursor / (double)std::max<int64_t>(1, n_groups);
   double cur = g_list_entries_per_group.load();
   while (per > cur && !g_list_entries_per_group.compare_exchange_weak(cur, per)) {}
-}
-
-int launch_tau_bounds(const Knn3Args &a, hipStream_t stream) {
-  hipLaunchKernelGGL(k_knn_tau_bounds, dim3((unsigned)std::min<int64_t>((a.n_qtiles + 7) / 8, 2048)), dim3(256), 0, stream, a.tau, a.nq, a.n_qtiles, a.gsmax);
-  TM_HIP(hipGetLastError());
-  return TM_OK;
-}
-
-int launch_lists(const Knn3Args &a, hipStream_t stream) {
-  hipLaunchKernelGGL(k_knn_lists, dim3((unsigned)a.n_groups), dim3(K3_LIST_NT), 0, stream, a);
-  TM_HIP(hipGetLastError());
-  return TM_OK;
 }
 
 int launch_collect(tm_knn_index_impl *ix, const Knn3Args &a, hipStream_t stream) {
@@ -324,7 +312,7 @@ static int search_attempt(tm_knn_index_impl *ix, int64_t nq, void *out_idx, void
   TM_HIP(hipEventRecord(ix->ev0, stream));
   TM_TRY(launch_scan3(ix, nq, prune, stream));
   TM_HIP(hipEventRecord(ix->ev1, stream));
-  hipLaunchKernelGGL(k_knn_refine, dim3(gridn(nq)), dim3(256), 0, stream, nq, ix->qperm.as<uint32_t>(), ix->qpack.as<uint8_t>(), knn_tile_bytes(ix->plan.hq, 0),
+  hipLaunchKernelGGL(k_knn_refine, dim3(gridn(nq)), dim3(256), 0, stream, nq, ix->qperm.as<uint32_t>(), ix->qpack.as<uint8_t>(), knn_pack_bytes(6 + ix->plan.hq, 0),
                      ix->best_key.as<int>(), ix->best_tile.as<int>(), (int *)out_idx, (uint32_t *)out_err);
   TM_HIP(hipGetLastError());
   return TM_OK;

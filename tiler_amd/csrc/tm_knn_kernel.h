@@ -1,4 +1,4 @@
-// tm_knn_kernel.h -- what the KNN stage's kernels and its host code share (see tm_knn.hip for the scheme, tm_knn3_kernel.h for the scan).
+// tm_knn_kernel.h -- what the KNN stage's kernels and its host code share (see tm_knn.hip for the scheme, tm_knn3.h for the scan).
 #pragma once
 #include <climits>
 #include <cstdint>

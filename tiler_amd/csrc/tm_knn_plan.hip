@@ -92,7 +92,7 @@ static int make_plan_scaled(const ColStats &ts, const ColStats &qs, KnnPlan *pla
   const bool a = costA <= costB;
   const bool *inner = a ? qb : tb;
   // Inside each class the widest columns come first: a 32-row tile whose values all stay within one digit on a chunk of 32 columns has
-  // an all-zero high-digit chunk there, and the scan skips the products with it (tm_knn3_kernel.h) -- with the wide columns (the DC terms,
+  // an all-zero high-digit chunk there, and the scan skips the products with it (k3_chain, tm_knn3_block.h) -- with the wide columns (the DC terms,
   // the lowest frequencies) packed into the first chunks, the later chunks are empty for most tiles.
   int order[192];
   for (int c = 0; c < 192; c++) order[c] = c;

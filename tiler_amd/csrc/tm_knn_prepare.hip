@@ -10,13 +10,13 @@ namespace tmx {
 // Pack n rows into MFMA fragment order: per 32-row tile [kc][64 lanes][16 B] (lane = half*32 + row) followed by
 // 32 u32 norms.  negate=1 (query side): digits of (c - v) and norm >> 1; negate=0 (database): digits of (v - c).
 // Rows >= n replicate row n-1 (database side: the tile's box and the row terms over the first chunk's columns follow the norms, and the
-// tile's last 128 bytes, the rows' original indices, are k_knn_tile_order's: knn_tile_bytes).  err_flag is set if a digit overflows int8.
+// tile's last 128 bytes, the rows' original indices, are k_knn_tile_order's: the packed tile of tm_knn3.h).  err_flag is set if a digit overflows int8.
 // scale (database side, KnnPlan::tscale): the digits are those of scale * (v - c); the norms stay those of v - c.
 __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ feat, int64_t n, int64_t ntiles, int hch, int negate, int scale,
                                                   const int16_t *__restrict__ centre, const int16_t *__restrict__ perm,
                                                   const uint32_t *__restrict__ rowperm, int with_box, CurveSpec cs,
                                                   int *__restrict__ box_lo, int *__restrict__ box_hi, uint8_t *__restrict__ out,
-                                                  int *__restrict__ err_flag, int *__restrict__ qmeta /* query side: [ntiles][16] box, home tile, high-chunk mask */,
+                                                  int *__restrict__ err_flag, int *__restrict__ qmeta /* query side: [ntiles][QMETA_INTS] box, home tile, high-chunk mask */,
                                                   uint8_t *__restrict__ hmask /* database side: [ntiles] which high-digit chunks of the tile hold a non-zero digit */) {
   __shared__ __attribute__((aligned(16))) int16_t s_c[192];  // centre of the column at packed position p
   __shared__ int16_t s_inv[192];                             // source column -> packed position
@@ -26,7 +26,7 @@ __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ fe
   __shared__ __attribute__((aligned(16))) int16_t s_perm[32][200];  // the tile's rows, raw values in PACKED column order (pitch 400 B)
   for (int i = threadIdx.x; i < 192; i += 256) { s_c[i] = centre[perm[i]]; s_inv[perm[i]] = (int16_t)i; }
   __syncthreads();
-  const int kch = 6 + hch, tile_bytes = knn_tile_bytes(hch, with_box);
+  const int kch = 6 + hch, tile_bytes = knn_pack_bytes(kch, with_box);
   // The 32 rows of a tile come in as 16-byte vectors (three per thread: the column permutation would otherwise turn the read into 6 144
   // two-byte loads per tile) and go into LDS already permuted, two bytes at a time to places the thread knows for good (its vectors cover the
   // same columns of every tile); digits and norms are then made from 16-byte reads of the permuted rows.  (A copy in memory order, a second,
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ fe
         for (int d = 0; d < KNN_NC; d++) { lo[d] = min(lo[d], __shfl_xor(lo[d], o)); hi[d] = max(hi[d], __shfl_xor(hi[d], o)); }
       if (r == 0)
 #pragma unroll
-        for (int d = 0; d < KNN_NC; d++) { qmeta[tile * 16 + d] = lo[d]; qmeta[tile * 16 + 8 + d] = hi[d]; }
+        for (int d = 0; d < KNN_NC; d++) { qmeta[qmeta_at(tile, QMETA_LO + d)] = lo[d]; qmeta[qmeta_at(tile, QMETA_HI + d)] = hi[d]; }
     }
     uint8_t *obase = out + tile * (int64_t)tile_bytes;
     bool bad = false;
@@ -153,18 +153,18 @@ __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ fe
       sqp += __shfl_xor(sqp, 1); sqp += __shfl_xor(sqp, 2); sqp += __shfl_xor(sqp, 4);
       // what the pack keeps per row is what the scan's chain starts from (k3_chain's `cin`): the query side's |q-c|^2 (the kernel drops its
       // parity), the database side's |t-c|^2 where its digits are those of 2 (t - c), and |t-c|^2 >> 1 where not -- the parities then go
-      // into the tile's box (word 14)
+      // into the tile's box (word KNN_PACK_BOX_PARITY)
       // ... and the same over the first chunk's columns, in the same form (the query side's whole), behind the box
       if (part == 0) {
         s_norm[r] = sq;
-        reinterpret_cast<uint32_t *>(obase + kch * 1024)[r] = (with_box && scale == 1) ? sq >> 1 : sq;
-        reinterpret_cast<uint32_t *>(obase + kch * 1024 + 128 + (with_box ? 64 : 0))[r] = (with_box && scale == 1) ? sqp >> 1 : sqp;
+        reinterpret_cast<uint32_t *>(knn_pack_row_terms(kch, obase))[r] = (with_box && scale == 1) ? sq >> 1 : sq;
+        reinterpret_cast<uint32_t *>(knn_pack_first_terms(kch, with_box, obase))[r] = (with_box && scale == 1) ? sqp >> 1 : sqp;
       }
     }
     __syncthreads();
     if (threadIdx.x == 0) {  // (rows >= n replicate row n - 1: they add no digit the real rows do not have)
       if (hmask) hmask[tile] = (uint8_t)s_hm;
-      if (qmeta) qmeta[tile * 16 + 15] = (int)s_hm;
+      if (qmeta) qmeta[qmeta_at(tile, QMETA_HMASK)] = (int)s_hm;
     }
     if (qmeta && threadIdx.x < 32) {  // the radial dimension of the sub-tile's box (the columns' part was done beside the centring phase)
       const int r = threadIdx.x;
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ fe
       int lo = max(0, (int)floor(sqrt((double)max(0ll, n2 - boxsq))) - 1);
       int hi = (int)ceil(sqrt((double)max(0ll, n2 + 1 - boxsq))) + 1;
       for (int o = 16; o > 0; o >>= 1) { lo = min(lo, __shfl_xor(lo, o)); hi = max(hi, __shfl_xor(hi, o)); }
-      if (r == 0) { qmeta[tile * 16 + KNN_NC] = lo; qmeta[tile * 16 + 8 + KNN_NC] = hi; }
+      if (r == 0) { qmeta[qmeta_at(tile, QMETA_LO + KNN_NC)] = lo; qmeta[qmeta_at(tile, QMETA_HI + KNN_NC)] = hi; }
     }
     if (threadIdx.x < 32) {
       const uint32_t s = with_box ? s_norm[threadIdx.x] : 0u;
@@ -186,9 +186,9 @@ __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ fe
         for (int o = 16; o > 0; o >>= 1) { lo = min(lo, __shfl_xor(lo, o)); hi = max(hi, __shfl_xor(hi, o)); }
         const unsigned par = (unsigned)__builtin_amdgcn_ballot_w64((s & 1u) != 0);  // (lanes 0..31: one per row)
         if (threadIdx.x == 0) {
-          int *tb = reinterpret_cast<int *>(obase + kch * 1024 + 128);
-          tb[14] = (int)par;
-          tb[15] = 0;
+          int *tb = reinterpret_cast<int *>(knn_pack_box(kch, obase));
+          tb[KNN_PACK_BOX_PARITY] = (int)par;
+          tb[KNN_PACK_BOX_PARITY + 1] = 0;
           tb[KNN_NC] = lo;
           tb[KNN_ND + KNN_NC] = hi;
           box_lo[(int64_t)KNN_NC * ntiles + tile] = lo;
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void k_knn_pack(const int16_t *__restrict__ fe
         a = min(a, v);
         b = max(b, v);
       }
-      int *tb = reinterpret_cast<int *>(obase + kch * 1024 + 128);
+      int *tb = reinterpret_cast<int *>(knn_pack_box(kch, obase));
       tb[d] = a;
       tb[KNN_ND + d] = b;
       box_lo[(int64_t)d * ntiles + tile] = a;
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void k_knn_tile_order(uint32_t *__restrict__ p
     if (row < n) perm[row] = v;
     if (pack) {
       const uint32_t last = (uint32_t)__shfl((int)v, real - 1, 32);
-      reinterpret_cast<uint32_t *>(pack + (tile + 1) * (int64_t)tile_bytes - 128)[i] = row < n ? v : last;
+      reinterpret_cast<uint32_t *>(pack + tile * (int64_t)tile_bytes + knn_pack_indices_of(tile_bytes))[i] = row < n ? v : last;
     }
   }
 }
@@ -397,9 +397,9 @@ static int run_pack(tm_knn_index_impl *ix, const void *feat, int64_t n, int nega
                     DevBuf &out, hipStream_t stream) {
   const int scale = negate ? 1 : ix->plan.tscale;
   const int64_t ntiles = (n + 31) / 32;
-  TM_TRY(out.alloc((size_t)ntiles * knn_tile_bytes(hch, with_box)));
+  TM_TRY(out.alloc((size_t)ntiles * knn_pack_bytes(6 + hch, with_box)));
   TM_TRY(ix->err_flag.alloc(sizeof(int)));
-  if (negate) TM_TRY(ix->qmeta.alloc((size_t)std::max<int64_t>(ntiles, 1) * 16 * 4));
+  if (negate) TM_TRY(ix->qmeta.alloc((size_t)std::max<int64_t>(ntiles, 1) * QMETA_INTS * 4));
   else TM_TRY(ix->thmask.alloc((size_t)std::max<int64_t>(ntiles, 1)));
   int grid = (int)std::min<int64_t>(ntiles, 4096);
   hipLaunchKernelGGL(k_knn_pack, dim3(grid), dim3(256), 0, stream, (const int16_t *)feat, n, ntiles, hch, negate, scale,
@@ -501,8 +501,8 @@ static int build_database_side(tm_knn_index_impl *ix, hipStream_t stream) {
   ix->tradial.release();
   TM_TRY(ix->tkey.alloc((size_t)ntt * 4));
   TM_HIP(hipMemcpy2DAsync(ix->tkey.p, 4, ix->skey2.p, 128, 4, (size_t)ntt, hipMemcpyDeviceToDevice, stream));  // each tile's smallest key (the sorted keys stay in curve order)
-  TM_TRY(ix->tpack.alloc((size_t)ntt * knn_tile_bytes(ix->plan.ht, 1)));  // (the pack's own allocation below finds it there)
-  TM_TRY(launch_tile_order(ix->tperm.as<uint32_t>(), ix->nt, stream, ix->tpack.as<uint8_t>(), knn_tile_bytes(ix->plan.ht, 1)));
+  TM_TRY(ix->tpack.alloc((size_t)ntt * knn_pack_bytes(6 + ix->plan.ht, 1)));  // (the pack's own allocation below finds it there)
+  TM_TRY(launch_tile_order(ix->tperm.as<uint32_t>(), ix->nt, stream, ix->tpack.as<uint8_t>(), knn_pack_bytes(6 + ix->plan.ht, 1)));
   TM_TRY(ix->box_lo.alloc((size_t)ntt * KNN_ND * 4));
   TM_TRY(ix->box_hi.alloc((size_t)ntt * KNN_ND * 4));
   TM_TRY(run_pack(ix, ix->db, ix->nt, 0, ix->plan.ht, ix->tperm, 1, ix->tpack, stream));

@@ -2,7 +2,7 @@
 //  1. k_topk_tau: every query's k-th smallest exact SSD among the TOPK_WINDOW database tiles around its position on the
 //     curve = an upper bound tau of its true k-th smallest SSD (any k rows give one).  A large search takes its first thresholds
 //     from a search of a sample of the database instead (knn_index_search_topk).
-//  2. the third scan shape in collection mode (tm_knn3_kernel.h: k_knn_tau_bounds, k_knn_lists, k_knn_consume<.., TOPK = true>) with
+//  2. the third scan shape in collection mode (tm_knn3.h: k_knn_tau_bounds, k_knn_lists, k_knn_consume<.., TOPK = true>) with
 //     those thresholds; every row with d'' <= tau lands in the query's candidate list (at most `cap` entries, the count keeps running).
 //  3. k_topk_select: exact SSD (d'' + the query norm's parity bit), original row index, rank by (SSD, index), first k out.
 //     A query whose list overflowed keeps the threshold the scan's ladder ended on (still a valid bound) and is
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(64) void k_topk_select(int64_t nq, const uint32_t *
     }
     return;
   }
-  const uint32_t parity = reinterpret_cast<const uint32_t *>(qpack + (p >> 5) * (int64_t)q_bytes + q_bytes - 256)[p & 31] & 1u;
+  const uint32_t parity = reinterpret_cast<const uint32_t *>(qpack + (p >> 5) * (int64_t)q_bytes + knn_pack_row_terms_of(q_bytes))[p & 31] & 1u;
   int n = 0;
   // (the stored candidates are asked for eight chunks of 64 at a time: a chunk per round trip to memory was most of this kernel -- the sort
   // below is 1.5 ms of the bench clip's 23)
@@ -409,7 +409,7 @@ static int topk_thresholds(tm_knn_index_impl *ix, const int16_t *feats, int64_t 
   return TM_OK;
 }
 
-// The third scan shape in collection mode (tm_knn3_kernel.h): bounds from the thresholds, tile lists judged against them (no seeds:
+// The third scan shape in collection mode (tm_knn3.h): bounds from the thresholds, tile lists judged against them (no seeds:
 // every tile goes through the lists), then the consume kernel appending every row within its query's threshold.
 static int topk_collect(tm_knn_index_impl *ix, int64_t n, int k, TopkPass &ps, hipStream_t stream) {
   const int64_t nqt = knn_tiles(n), ntt = knn_tiles(ix->nt);
@@ -451,7 +451,7 @@ static int topk_select(tm_knn_index_impl *ix, int64_t n, int k, int32_t *out_idx
   const size_t lds = (size_t)topk_pow2(ps.cap) * 8;
   if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_topk_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(k_topk_select, dim3((unsigned)n), dim3(64), lds, stream, n, ix->qperm.as<uint32_t>(), ix->qpack.as<uint8_t>(),
-                     knn_tile_bytes(ix->plan.hq, 0), ix->tperm.as<uint32_t>(), ix->nt, ps.cand.as<uint2>(), ps.cand_cnt.as<int>(), ps.cap, k, ps.tau.as<int>(), ps.tau_in.as<int>(), ps.step.as<int>(),
+                     knn_pack_bytes(6 + ix->plan.hq, 0), ix->tperm.as<uint32_t>(), ix->nt, ps.cand.as<uint2>(), ps.cand_cnt.as<int>(), ps.cap, k, ps.tau.as<int>(), ps.tau_in.as<int>(), ps.step.as<int>(),
                      ps.map_sorted.as<uint32_t>(), out_idx, out_err, ps.ovf.as<uint32_t>(), ps.counter.as<unsigned int>(), ex.grp_off, ex.grp_members,
                      0, estimated ? ps.unf.as<uint32_t>() : (uint32_t *)nullptr);
   TM_HIP(hipGetLastError());

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Development aid: builds libtilemotion with extra -D flags into tiler_amd/lib/variants/libtilemotion_<name>.so (loaded with
-# TM_LIB_VARIANT=<name>), so that kernel-shape experiments (TM_KNN_NW, TM_KNN_NQ, TM_KNN_NBUF, TM_KNN_OCC ...) can be A/B-ed in one GPU call.
+# TM_LIB_VARIANT=<name>), so that kernel-shape experiments (TM_KNN3_WAVES, TM_KNN3_SEEDS, TM_KNN3_REFRESH_EVERY, the diagnostic TM_KNN3_STAMPS ...) can be A/B-ed in one GPU call.
 set -euo pipefail
 NAME="$1"; shift
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")/../tiler_amd/csrc" && pwd)"
