@@ -551,6 +551,60 @@ TM_API int tm_get_png_decode(tm_encoder *, int *where);
 TM_API int tm_set_frames_png(tm_encoder *, const void *const *files, const size_t *sizes, int nframes, double fps);
 TM_API int tm_probe_png_clip_host(const void *const *files, const size_t *sizes, int nframes, double fps, int *width, int *height);
 TM_API int tm_get_input_stats(tm_encoder *, tm_input_stats *out);
+/* ---- JPEG input on the device (the rule: tiler_amd/csrc/tm_jpeg.h).
+ *   Accepted: baseline JPEG -- SOF0, or SOF1 with 8-bit samples; one component, or three (YCbCr) with chroma 1x1 and luma 1x1 (4:4:4), 2x1
+ * (4:2:2) or 2x2 (4:2:0); one interleaved scan with Ss 0, Se 63, Ah = Al = 0; DQT with 8- or 16-bit entries; DHT tables 0..3 per class,
+ * and a file with no DHT at all decodes with the tables of T.81 Annex K.3 (the frames of an MJPEG capture); DRI / RSTn; APPn and COM of
+ * any size and fill bytes before a marker are skipped; what follows EOI is ignored.  The EXIF orientation is ignored.
+ *   The container walk (host) refuses, naming the marker or field, before anything is decoded: TM_E_UNSUPPORTED for SOF2 (progressive),
+ * SOF3 and SOF5..SOF15, a precision other than 8, 2 or 4 components, any other sampling, more than one scan, APP14 (Adobe) transform 0 on
+ * three components (RGB), DNL or a height of 0; TM_E_IO for a file without SOI, a segment that runs past the file, a scan that names a
+ * missing table or component, a DHT whose counts over-subscribe the code space or name more than 256 symbols.
+ *   The walk cuts the scan at every RSTn into segments of restart_interval MCUs, each an independent chain; what only decoding finds is
+ * the file's status: TM_JPG_TRUNCATED (a symbol needs bits beyond its segment), TM_JPG_BAD_CODE (bits that are no code), TM_JPG_BAD_RUN (a
+ * zero run past coefficient 63), TM_JPG_BAD_MAGNITUDE (a DC category above 11, an AC category above 10), TM_JPG_BAD_RESTART (an RSTn
+ * missing or out of sequence: the file is not decoded) -- the first in segment order, then MCU order.  TM_JPG_BAD_DESC is the kernel's
+ * refusal of a descriptor that points outside what the launch was given; the entry points below never make one.
+ *   The samples: coefficient x quantiser, the "islow" integer inverse DCT (13-bit constants, columns then rows, descaled by 11 and by 18),
+ * + 128, clamped -- in wrapping 32-bit arithmetic, the same on the host and on the device; for files written from 8-bit samples these are
+ * libjpeg's planes bit for bit.  Chroma planes are ceil(w / 2) wide and, for 4:2:0, ceil(h / 2) high.
+ *   tm_probe_jpeg_host: the walk alone, no device: the size, the components, the luma sampling factors, the restart interval (0: none),
+ * the number of segments, the SOF kind (0 or 1), the TM_CHROMA_* layout of the planes (4:2:2 is sited between the luma pairs, as JFIF
+ * has it, which no public layout names: it reports TM_CHROMA_422) and status (0 or TM_JPG_BAD_RESTART).
+ *   tm_jpeg_decode_host / tm_stage_jpeg_decode: nfiles files in HOST memory into planes in HOST / DEVICE memory.  File i's planes start
+ * i frame strides into y, u, v and have the file's own size, which may be anything up to w x h: strides = {y_row, y_frame, u_row,
+ * u_frame, v_row, v_frame} in bytes (HOST array); u and v may be null when every file has one component.  The walk's refusals fail the
+ * call, naming the file's index; so do (TM_E_INVAL) a null pointer, a file larger than w x h, strides shorter than a file's planes.
+ * Otherwise they return TM_OK and what became of each file is its status; a refused file never causes an access outside its own planes,
+ * and both forms leave the same bytes in them.
+ *   tm_set_frames_jpeg: JPEG files LENT in host memory until the next Load has returned, as tm_set_frames_png lends PNG files: the size
+ * and sampling are the first file's, a file of another size or sampling is TM_E_INVAL at Load, Scaling is ignored, the key frames follow
+ * the automatic rule, StartFrame and FrameCount do not apply.  tm_probe_jpeg_clip_host: its refusals and the size with no device.
+ *   A pattern whose first file starts with FF D8 is a JPEG sequence for tm_open_input / tm_probe_input_host (kind TM_INPUT_JPEGS), with a
+ * PNG sequence's rules: 24 frames a second, files counted to the first gap, key frames where a .kf file exists, Scaling ignored.
+ *   The decoded planes become RGB32 through the YUV input rule (k_yuv_to_rgb32): JFIF is full-range BT.601, so TM_YUV_AUTO is
+ * TM_YUV_BT601_FULL; a mode set with tm_set_input_yuv is honoured.
+ *   tm_set_jpeg_decode: where Load decodes.  DEVICE: the files and a descriptor per frame go up chunk by chunk (TM_INPUT_CHUNK_FRAMES
+ * files; otherwise as many as 1 GiB of planes and 512 MiB of files hold) and k_jpeg_decode writes the planes.  HOST: the reader threads
+ * decode with the host form and the planes are uploaded.  AUTO goes by the first file, whose segments are the lanes it keeps busy:
+ * DEVICE when it has four restart segments or more, else HOST.  Measured at 720p x 300 with 1, 2, 4, 8, 16, 30 and 45 segments a file: the
+ * host is faster at 1 and 2 (138 ms against 227 ms, 142 against 150), the device from 4 on (96 ms against 142 ms; 26 against 139 at 45);
+ * three segments were not measured.  TM_JPEG_DECODE=host|device overrides.
+ * tm_get_input_stats reports kind 8 for a sequence and 12 for lent files. */
+enum { TM_JPG_TRUNCATED = 48, TM_JPG_BAD_CODE = 49, TM_JPG_BAD_RUN = 50, TM_JPG_BAD_MAGNITUDE = 51, TM_JPG_BAD_RESTART = 52, TM_JPG_BAD_DESC = 53 };
+enum { TM_INPUT_JPEGS = 8 };
+typedef struct tm_jpeg_info {
+  int32_t width, height, components, h_samp, v_samp, restart_interval, segments, sof, chroma, status;
+} tm_jpeg_info;
+TM_API int tm_probe_jpeg_host(const void *file, size_t size, tm_jpeg_info *out);
+TM_API int tm_jpeg_decode_host(const void *const *files, const size_t *sizes, int nfiles, int w, int h, uint8_t *y, uint8_t *u, uint8_t *v,
+                               const int64_t *strides /* 6 */, int32_t *status /* nfiles */);
+TM_API int tm_stage_jpeg_decode(const void *const *files, const size_t *sizes, int nfiles, int w, int h, uint8_t *dev_y, uint8_t *dev_u, uint8_t *dev_v,
+                                const int64_t *strides /* 6, host */, int32_t *status /* nfiles, host */, void *stream);
+TM_API int tm_set_jpeg_decode(tm_encoder *, int where /* TM_PNG_DECODE_* */);
+TM_API int tm_get_jpeg_decode(tm_encoder *, int *where);
+TM_API int tm_set_frames_jpeg(tm_encoder *, const void *const *files, const size_t *sizes, int nframes, double fps);
+TM_API int tm_probe_jpeg_clip_host(const void *const *files, const size_t *sizes, int nframes, double fps, int *width, int *height);
 /* The same pictures rendered on the device (Render :3455-3640, Output tab with the constructor's defaults; or the Input tab: input != 0):
  * frames [first_frame, first_frame+frame_count) as [frame_count][tm_h*8][tm_w*8] uint32 0x00RRGGBB (the format frames are pushed in; the
  * input render is every pushed frame cropped to tm_w*8 x tm_h*8 with alpha 0).  A predicted item is frame f-1's output at its offset,

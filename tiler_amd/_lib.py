@@ -67,6 +67,10 @@ class InputStatsDesc(ctypes.Structure):  # tm_input_stats
                 ("ms_read", c_double), ("ms_device", c_double), ("ms_wall", c_double)]
 
 
+class JpegInfoDesc(ctypes.Structure):  # tm_jpeg_info
+    _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "components", "h_samp", "v_samp", "restart_interval", "segments", "sof", "chroma", "status")]
+
+
 PNG_DECODE = {"auto": 0, "host": 1, "device": 2}  # TM_PNG_DECODE_*
 
 RENDER_PAGES = {"input": 0, "output": 1, "tiles": 2}  # TM_RENDER_PAGE_*
@@ -179,6 +183,13 @@ SIGNATURES = {
     "tm_set_frames_png": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double]),
     "tm_probe_png_clip_host": (c_int, [c_void_p, c_void_p, c_int, c_double, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "tm_get_input_stats": (c_int, [c_void_p, ctypes.POINTER(InputStatsDesc)]),
+    "tm_probe_jpeg_host": (c_int, [c_void_p, ctypes.c_size_t, ctypes.POINTER(JpegInfoDesc)]),
+    "tm_jpeg_decode_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tm_stage_jpeg_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tm_set_jpeg_decode": (c_int, [c_void_p, c_int]),
+    "tm_get_jpeg_decode": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "tm_set_frames_jpeg": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double]),
+    "tm_probe_jpeg_clip_host": (c_int, [c_void_p, c_void_p, c_int, c_double, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
 }
 
 
@@ -230,6 +241,14 @@ def file_list(files):
     ptrs = (c_void_p * max(len(files), 1))(*[ctypes.addressof(b) for b in bufs])
     sizes = (ctypes.c_size_t * max(len(files), 1))(*[len(f) for f in files])
     return ptrs, sizes, bufs
+
+
+def jpeg_plane_sizes(w, h, components, h_samp, v_samp):
+    """[(width, height)] of the planes a JPEG of this geometry decodes to: chroma is ceil(w / h_samp) x ceil(h / v_samp)"""
+    if components == 1:
+        return [(w, h)]
+    c = ((w + h_samp - 1) // h_samp, (h + v_samp - 1) // v_samp)
+    return [(w, h), c, c]
 
 
 SCALE_FILTERS = {"lanczos": 0, "nearest": 1}  # TM_SCALE_*

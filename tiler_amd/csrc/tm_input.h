@@ -16,13 +16,18 @@ constexpr int INPUT_YUV_CLIP = 3;  // InputInfo::kind of a YUV clip lent in memo
 constexpr int INPUT_GTM = TM_INPUT_GTM;  // a .gtm stream: Load plays its frames into the device clip (tm_player.hip)
 constexpr int INPUT_RGB_CLIP = 5;  // an RGB clip lent in memory (tm_set_frames_rgb)
 constexpr int INPUT_PNG_CLIP = 6;  // PNG files lent in memory (tm_set_frames_png)
+constexpr int INPUT_JPEG_CLIP = 12;  // JPEG files lent in memory (tm_set_frames_jpeg), beside TM_INPUT_JPEGS
+// JFIF's 4:2:2: chroma between the luma pairs.  A layout of chroma_geom for the JPEG reader's planes only: no public TM_CHROMA_* value,
+// and check_yuv_clip and the stage seams keep refusing it.
+constexpr int CHROMA_422_CENTRED = 5;
 struct InputInfo {
   int kind = 0;  // 0: RGB32 frames from memory (pushed or lent); TM_INPUT_Y4M / TM_INPUT_PNGS: from the file; INPUT_YUV_CLIP / INPUT_RGB_CLIP: a lent clip
   std::string name;
   tm_yuv_clip clip{};               // INPUT_YUV_CLIP: the descriptor as it was lent
   tm_rgb_clip rgb_clip{};           // INPUT_RGB_CLIP: the same
-  std::vector<const void *> png_files;  // INPUT_PNG_CLIP: the files as they were lent
+  std::vector<const void *> png_files;  // INPUT_PNG_CLIP, INPUT_JPEG_CLIP: the files as they were lent
   std::vector<size_t> png_sizes;
+  int jpeg_segments = 0;            // JPEG inputs: the restart segments of the first file (what AUTO decides by)
   bool lent = false;                // the clip's memory is still borrowed: no Load has read it yet
   int start = 0, frames = 0, src_w = 0, src_h = 0, dst_w = 0, dst_h = 0, chroma = 0, full_range = 0;
   double fps = 0;

@@ -14,6 +14,7 @@
 
 #include "tm_encoder.h"
 #include "tm_inflate.h"
+#include "tm_jpeg.h"
 
 // fn(i) for i in [0, n) on up to IN_READERS host threads (the calling one included); the first failure's code and message come back.
 // Reading a file that the page cache holds is a copy the memory system bounds, not one core: a single reader brought the 0.41 GB of the
@@ -431,6 +432,162 @@ static int decode_pngs_device(tm_encoder *e, int a, int b) {
   return TM_OK;
 }
 
+static bool jpeg_kind(int kind) { return kind == TM_INPUT_JPEGS || kind == INPUT_JPEG_CLIP; }
+// where a JPEG input is decoded: TM_JPEG_DECODE, else what tm_set_jpeg_decode said.  AUTO goes by the first file:
+// a file's segments are the lanes it keeps busy.  The 720p x 300 clip on the device against the host's reader threads: 227 ms against
+// 138 ms with one segment a file, 150 against 142 with two, 96 against 142 with four, 26 against 139 with 45.  Three were not measured
+// and stay with the host.
+constexpr int JPEG_AUTO_DEVICE_SEGMENTS = 4;
+static int jpeg_decode_where(const tm_encoder *e) {
+  const int w = knobs().jpeg_decode ? knobs().jpeg_decode : e->jpeg_decode;
+  if (w != TM_PNG_DECODE_AUTO) return w;
+  return e->input.jpeg_segments >= JPEG_AUTO_DEVICE_SEGMENTS ? TM_PNG_DECODE_DEVICE : TM_PNG_DECODE_HOST;
+}
+
+// Frames [a, b) of the JPEG sequence, or of the lent files, into the encoder's clip.  The reader threads bring a
+// chunk's files into memory and walk them.  DEVICE: the files lie in the page-locked buffer, the chunk's descriptor is written behind
+// them, both go up in one copy on the copy stream and k_jpeg_decode writes the chunk's planes.  HOST: the reader threads decode with the
+// host form into the page-locked buffer and the planes go up.  Either way the planes -- MCU-padded, with the true size and a row stride
+// handed on -- are converted by k_yuv_to_rgb32 on the main stream while the next chunk is read.
+static int decode_jpegs(tm_encoder *e, int a, int b) {
+  InputInfo &in = e->input;
+  tm_input_stats &stats = e->input_stats;
+  const bool lent = in.kind == INPUT_JPEG_CLIP, on_device = jpeg_decode_where(e) == TM_PNG_DECODE_DEVICE;
+  const int n = b - a, w = e->width, h = e->height, layout = in.chroma;
+  std::vector<std::string> names((size_t)n);
+  std::vector<size_t> sizes((size_t)n);
+  for (int i = 0; i < n; i++) {
+    if (lent) {
+      names[(size_t)i] = "frame " + std::to_string(a + i);
+      sizes[(size_t)i] = in.png_sizes[(size_t)(a + i)];
+    } else {
+      TM_TRY(format_pattern(in.name, (int64_t)in.start + a + i, &names[(size_t)i]));
+      struct stat sb;
+      TM_CHECK(stat(names[(size_t)i].c_str(), &sb) == 0, TM_E_IO, "cannot open %s", names[(size_t)i].c_str());
+      sizes[(size_t)i] = (size_t)sb.st_size;
+    }
+    stats.file_bytes += (int64_t)sizes[(size_t)i];
+  }
+  InputTables &tables = e->input_tables;
+  TM_TRY(build_input_tables(w, h, layout, w, h, &tables, e->stream));
+  const int mode = resolve_yuv_mode(e->input_yuv, in.full_range);
+  // the planes of a frame, whole MCUs: an MCU is 8 hs x 8 vs luma samples (8 x 8 for a single component)
+  const bool mono = layout == TM_CHROMA_MONO;
+  const uint32_t hs = (mono || layout == TM_CHROMA_444) ? 1 : 2, vs = layout == TM_CHROMA_420JPEG ? 2 : 1;
+  const uint32_t ypw = ((uint32_t)w + 8 * hs - 1) / (8 * hs) * (8 * hs), yph = ((uint32_t)h + 8 * vs - 1) / (8 * vs) * (8 * vs);
+  const uint32_t cpw = mono ? 0 : ypw / hs, cph = mono ? 0 : yph / vs;
+  const size_t yb = (size_t)ypw * yph, cb = (size_t)cpw * cph, fb = yb + 2 * cb, out_fb = (size_t)w * h * 4;
+  const size_t mcus = (size_t)(ypw / (8 * hs)) * (yph / (8 * vs));
+  // A file without restart markers is one lane's work from end to end, so a chunk should hold as many frames as the device has room for
+  // (the PNG path's rule): as many as 1 GiB of planes and 512 MiB of files allow.
+  size_t largest = 16;
+  for (size_t sz : sizes) largest = std::max(largest, (sz + 15) & ~(size_t)15);
+  const size_t by_room = std::max<size_t>(1, std::min(((size_t)1 << 30) / fb, ((size_t)512 << 20) / largest));
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, knobs().input_chunk_frames > 0 ? (size_t)knobs().input_chunk_frames : by_room));
+  size_t cap = fb * (size_t)chunk;  // HOST: a chunk's planes.  DEVICE: its files, each on 16 bytes, and the most its descriptor can take (a segment per MCU)
+  if (on_device) {
+    cap = 0;
+    for (int f0 = 0; f0 < n; f0 += chunk) {
+      size_t files = 0;
+      const int nf = std::min(chunk, n - f0);
+      for (int i = 0; i < nf; i++) files += (sizes[(size_t)(f0 + i)] + 15) & ~(size_t)15;
+      cap = std::max(cap, files + (size_t)nf * (sizeof(jpg::Frame) + sizeof(jpg::TableSet) + mcus * sizeof(jpg::Seg)) + 64);
+    }
+    TM_CHECK(cap < ((size_t)1 << 32), TM_E_UNSUPPORTED, "a chunk of %d JPEG files takes %zu bytes (below 4 GiB: lower TM_INPUT_CHUNK_FRAMES)", chunk, cap);
+  }
+  PinnedBuf *host = e->input_pinned;
+  DevBuf dev[2], planes, status;
+  StagingRing ring;
+  TM_TRY(ring.make());
+  for (int i = 0; i < (n > chunk ? 2 : 1); i++) { TM_TRY(host[i].alloc(cap)); TM_TRY(dev[i].alloc(cap)); }
+  if (on_device) { TM_TRY(planes.alloc(fb * (size_t)chunk)); TM_TRY(status.alloc((size_t)n * 4)); }
+  if (!e->copy_stream) TM_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
+  jpg::JpegBatch batch[2];
+  std::vector<jpg::JpegInfo> infos((size_t)chunk);
+  std::vector<size_t> at((size_t)chunk);
+  auto layout_of = [&](int i) {  // frame i of a chunk: its offset in the Y planes, in the U planes, in the V planes
+    jpg::PlaneLayout pl;
+    pl.off[0] = yb * (size_t)i; pl.stride[0] = ypw; pl.w[0] = ypw; pl.h[0] = yph;
+    for (int c = 1; c < (mono ? 1 : 3); c++) { pl.off[c] = cb * (size_t)i; pl.stride[c] = cpw; pl.w[c] = cpw; pl.h[c] = cph; }
+    return pl;
+  };
+  auto check_like_first = [&](const jpg::JpegInfo &info, const std::string &name) -> int {
+    TM_CHECK(info.w == w && info.h == h, TM_E_INVAL, "%s is %dx%d, the sequence's first frame is %dx%d", name.c_str(), info.w, info.h, w, h);
+    TM_CHECK(info.layout() == layout, TM_E_INVAL, "%s has %d component(s) sampled %dx%d, which is not the sampling of the sequence's first frame", name.c_str(), info.ncomp,
+             info.hs, info.vs);
+    return (int)TM_OK;
+  };
+  int c = 0;
+  for (int f0 = 0; f0 < n; f0 += chunk, c++) {
+    const int nf = std::min(chunk, n - f0), s = c & 1;
+    TM_TRY(ring.host_free(s));
+    const auto t0 = std::chrono::steady_clock::now();
+    uint8_t *hb = (uint8_t *)host[s].p;
+    size_t used = 0, files = 0;
+    if (on_device) {
+      for (int i = 0; i < nf; i++) { at[(size_t)i] = files; files += (sizes[(size_t)(f0 + i)] + 15) & ~(size_t)15; }
+      TM_TRY(parallel_for(nf, [&](int i) -> int {
+        const std::string &name = names[(size_t)(f0 + i)];
+        const size_t sz = sizes[(size_t)(f0 + i)];
+        uint8_t *to = hb + at[(size_t)i];
+        if (lent) memcpy(to, in.png_files[(size_t)(a + f0 + i)], sz);
+        else {
+          const int fd = open(name.c_str(), O_RDONLY);
+          TM_CHECK(fd >= 0, TM_E_IO, "cannot open %s", name.c_str());
+          FdCloser closer{fd};
+          TM_CHECK(pread_all(fd, to, sz, 0) == 0, TM_E_IO, "cannot read %s", name.c_str());
+        }
+        TM_TRY(jpg::parse_jpeg(to, sz, name.c_str(), &infos[(size_t)i]));
+        return check_like_first(infos[(size_t)i], name);
+      }));
+      batch[s].clear();
+      for (int i = 0; i < nf; i++) batch[s].add(infos[(size_t)i], at[(size_t)i], layout_of(i));
+      TM_CHECK(files + batch[s].desc_bytes() <= cap, TM_E_INVAL, "a JPEG file changed while it was being read");
+      used = files + batch[s].write_desc(hb + files);
+    } else {
+      uint8_t *const pl3[3] = {hb, hb + yb * (size_t)nf, hb + (yb + cb) * (size_t)nf};
+      TM_TRY(parallel_for(nf, [&](int i) -> int {
+        const std::string &name = names[(size_t)(f0 + i)];
+        const size_t sz = sizes[(size_t)(f0 + i)];
+        std::vector<uint8_t> mine;
+        const uint8_t *file = lent ? (const uint8_t *)in.png_files[(size_t)(a + f0 + i)] : nullptr;
+        if (!lent) {
+          mine.resize(sz);
+          const int fd = open(name.c_str(), O_RDONLY);
+          TM_CHECK(fd >= 0, TM_E_IO, "cannot open %s", name.c_str());
+          FdCloser closer{fd};
+          TM_CHECK(pread_all(fd, mine.data(), sz, 0) == 0, TM_E_IO, "cannot read %s", name.c_str());
+          file = mine.data();
+        }
+        jpg::JpegInfo info;
+        TM_TRY(jpg::parse_jpeg(file, sz, name.c_str(), &info));
+        TM_TRY(check_like_first(info, name));
+        return jpg::jpeg_status_error(jpg::jpeg_decode_one_host(info, file, sz, layout_of(i), pl3), name.c_str());
+      }));
+      used = fb * (size_t)nf;
+    }
+    stats.ms_read += ms_since(t0);
+    stats.bytes_uploaded += (int64_t)used;
+    TM_TRY(ring.device_free(s, e->copy_stream));
+    TM_HIP(hipMemcpyAsync(dev[s].p, hb, used, hipMemcpyHostToDevice, e->copy_stream));
+    TM_TRY(ring.uploaded(s, e->copy_stream, e->stream));
+    uint8_t *py = on_device ? planes.as<uint8_t>() : dev[s].as<uint8_t>();
+    uint8_t *pu = mono ? nullptr : py + yb * (size_t)nf, *pv = mono ? nullptr : pu + cb * (size_t)nf;
+    if (on_device) {
+      const uint64_t plane_bytes[3] = {yb * (uint64_t)nf, cb * (uint64_t)nf, cb * (uint64_t)nf};
+      TM_TRY(jpg::jpeg_batch_launch(batch[s], dev[s].as<uint8_t>(), used, files, py, pu, pv, plane_bytes, status.as<int32_t>() + f0, e->stream));
+    }
+    const int64_t strides[6] = {(int64_t)ypw, (int64_t)yb, (int64_t)cpw, (int64_t)cb, (int64_t)cpw, (int64_t)cb};
+    TM_TRY(launch_yuv_to_rgb32(tables, py, pu, pv, strides, SampleFmt(), nf, mode, e->frames_owned.as<uint8_t>() + out_fb * (size_t)(a + f0), e->stream));
+    TM_TRY(ring.worked(s, e->stream));
+  }
+  std::vector<int32_t> st((size_t)n, 0);
+  if (on_device) TM_HIP(hipMemcpyAsync(st.data(), status.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  TM_HIP(hipStreamSynchronize(e->stream));  // the staging buffers go back to the pool and to the host
+  for (int i = 0; i < n; i++) TM_TRY(jpg::jpeg_status_error(st[(size_t)i], names[(size_t)i].c_str()));
+  return TM_OK;
+}
+
 // frames [a, b) of the .gtm stream, played straight into the encoder's device clip (the player writes frame i where frame i + 1 reads it)
 static int play_gtm(tm_encoder *e, int a, int b) {
   const InputInfo &in = e->input;
@@ -476,6 +633,9 @@ int load_from_input(tm_encoder *e) {
   if (in.decoded && e->frames == e->frames_owned.p && e->frames_owned.p && in.dec_first <= a && b <= in.dec_first + in.dec_count && (rgb_clip || in.dec_mode == mode))
     return TM_OK;
   const bool lent_clip = in.kind == INPUT_YUV_CLIP || rgb_clip;
+  const bool jpegs = jpeg_kind(in.kind);
+  TM_CHECK(in.kind != INPUT_JPEG_CLIP || in.lent, TM_E_INVAL,
+           "the JPEG files were given back when the last Load returned: lend them again (tm_set_frames_jpeg) to convert them with another InputYUV or for more frames");
   TM_CHECK(in.kind != INPUT_PNG_CLIP || in.lent, TM_E_INVAL, "the PNG files were given back when the last Load returned: lend them again (tm_set_frames_png) for more frames");
   TM_CHECK(!rgb_clip || in.lent, TM_E_INVAL, "the RGB clip was given back when the last Load returned: lend the clip again (tm_set_frames_rgb) for more frames");
   TM_CHECK(!lent_clip || in.lent, TM_E_INVAL,
@@ -486,17 +646,17 @@ int load_from_input(tm_encoder *e) {
   e->frames_host = nullptr;
   e->hclip_cur = -1;
   in.decoded = false;
-  if (pngs) {
+  if (pngs || jpegs) {
     e->input_stats = tm_input_stats{};
     e->has_input_stats = false;
     int rc = TM_OK;
-    if (b > a) rc = decode_pngs_device(e, (int)a, (int)b);
+    if (b > a) rc = pngs ? decode_pngs_device(e, (int)a, (int)b) : decode_jpegs(e, (int)a, (int)b);
     if (rc != TM_OK) {  // as a failed host decode leaves it: no clip, and the next Load decodes again
       (void)hipStreamSynchronize(e->stream);
       e->frames = nullptr;
       return rc;
     }
-    e->input_stats.frames = b - a; e->input_stats.where = TM_PNG_DECODE_DEVICE; e->input_stats.kind = in.kind;
+    e->input_stats.frames = b - a; e->input_stats.where = pngs ? (int)TM_PNG_DECODE_DEVICE : jpeg_decode_where(e); e->input_stats.kind = in.kind;
     e->input_stats.ms_wall = ms_since(t0);
     e->input_stats.ms_device = std::max(0.0, e->input_stats.ms_wall - e->input_stats.ms_read);
     e->has_input_stats = true;
@@ -583,6 +743,51 @@ int tm_set_frames_png(tm_encoder *e, const void *const *files, const size_t *siz
   return TM_OK;
 }
 
+int tm_probe_jpeg_clip_host(const void *const *files, const size_t *sizes, int nframes, double fps, int *width, int *height) {
+  TM_CHECK(files && sizes && nframes >= 1 && fps > 0, TM_E_INVAL, "jpeg clip: a null list, no frames or fps <= 0");
+  for (int i = 0; i < nframes; i++) TM_CHECK(files[i] && sizes[i], TM_E_INVAL, "jpeg clip: frame %d is null or empty", i);
+  jpg::JpegInfo info;
+  TM_TRY(jpg::parse_jpeg((const uint8_t *)files[0], sizes[0], "frame 0", &info));
+  if (width) *width = info.w;
+  if (height) *height = info.h;
+  return TM_OK;
+}
+
+int tm_set_frames_jpeg(tm_encoder *e, const void *const *files, const size_t *sizes, int nframes, double fps) {  // tm_set_frames_png's twin
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  int w = 0, h = 0;
+  TM_TRY(tm_probe_jpeg_clip_host(files, sizes, nframes, fps, &w, &h));
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_set_frames_jpeg(s, files, sizes, nframes, fps); });  // every shard decodes what its Load reads
+  jpg::JpegInfo info;
+  TM_TRY(jpg::parse_jpeg((const uint8_t *)files[0], sizes[0], "frame 0", &info));
+  TM_TRY(tm_set_video(e, w, h, fps, nframes));
+  InputInfo in;
+  in.kind = INPUT_JPEG_CLIP;
+  in.png_files.assign(files, files + nframes);
+  in.png_sizes.assign(sizes, sizes + nframes);
+  in.lent = true;
+  in.frames = nframes; in.src_w = in.dst_w = w; in.src_h = in.dst_h = h;
+  in.chroma = info.layout(); in.full_range = 1; in.fps = fps;  // (JFIF: full-range BT.601)
+  in.jpeg_segments = (int)info.nsegs;
+  e->input = std::move(in);
+  e->input_clip.clear();
+  return TM_OK;
+}
+
+int tm_set_jpeg_decode(tm_encoder *e, int where) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_CHECK(where >= TM_PNG_DECODE_AUTO && where <= TM_PNG_DECODE_DEVICE, TM_E_INVAL, "bad JPEG decode place %d", where);
+  if (e->grp) return group_each(e, [=](tm_encoder *s) { return tm_set_jpeg_decode(s, where); });
+  e->jpeg_decode = where;
+  return TM_OK;
+}
+
+int tm_get_jpeg_decode(tm_encoder *e, int *where) {
+  TM_CHECK(e && where, TM_E_INVAL, "null argument");
+  *where = e->jpeg_decode;
+  return TM_OK;
+}
+
 int tm_set_png_decode(tm_encoder *e, int where) {
   TM_CHECK(e, TM_E_INVAL, "null encoder");
   TM_CHECK(where >= TM_PNG_DECODE_AUTO && where <= TM_PNG_DECODE_DEVICE, TM_E_INVAL, "bad PNG decode place %d", where);
@@ -599,7 +804,7 @@ int tm_get_png_decode(tm_encoder *e, int *where) {
 
 int tm_get_input_stats(tm_encoder *e, tm_input_stats *out) {
   TM_CHECK(e && out, TM_E_INVAL, "null argument");
-  TM_CHECK(e->has_input_stats, TM_E_INVAL, "no Load has read a PNG input yet");
+  TM_CHECK(e->has_input_stats, TM_E_INVAL, "no Load has read a PNG or JPEG input yet");
   *out = e->input_stats;
   return TM_OK;
 }

@@ -6,6 +6,7 @@
 
 #include "tm_gtm.h"
 #include "tm_input.h"
+#include "tm_jpeg.h"
 
 namespace tmx {
 
@@ -146,6 +147,26 @@ static bool has_gtm_magic(const std::string &name) {
   return n == 4 && gtm_has_magic(m, GTM_HEADER_MAGIC);
 }
 
+static bool starts_with_soi(const std::string &name) {
+  FILE *f = fopen(name.c_str(), "rb");
+  if (!f) return false;
+  uint8_t m[2] = {0, 0};
+  const size_t n = fread(m, 1, 2, f);
+  fclose(f);
+  return n == 2 && m[0] == 0xff && m[1] == 0xd8;
+}
+static int read_whole(const std::string &name, std::vector<uint8_t> *out) {
+  FILE *f = fopen(name.c_str(), "rb");
+  TM_CHECK(f, TM_E_IO, "cannot open %s", name.c_str());
+  struct Closer { FILE *f; ~Closer() { fclose(f); } } closer{f};
+  fseek(f, 0, SEEK_END);
+  const long n = ftell(f);
+  fseek(f, 0, SEEK_SET);
+  out->resize(n > 0 ? (size_t)n : 0);
+  TM_CHECK(fread(out->data(), 1, out->size(), f) == out->size(), TM_E_IO, "cannot read %s", name.c_str());
+  return TM_OK;
+}
+
 // what tm_open_input finds out, without a device: the kind of input, its sizes, rate, frame range
 int probe_input(const std::string &name, int start_frame, int frame_count, double scaling, InputInfo *in) {
   *in = InputInfo();
@@ -185,7 +206,16 @@ int probe_input(const std::string &name, int start_frame, int frame_count, doubl
   TM_TRY(format_pattern(name, start_frame, &path));
   TM_CHECK(cnt > 0 && file_exists(path), TM_E_IO, "input: %s does not exist", path.c_str());
   in->frames = cnt;
-  TM_TRY(read_png(path.c_str(), nullptr, 0, &in->src_w, &in->src_h));  // the size comes from the first file (1813-1814)
+  if (starts_with_soi(path)) {  // a JPEG sequence: the size and the sampling are the first file's
+    std::vector<uint8_t> file;
+    TM_TRY(read_whole(path, &file));
+    jpg::JpegInfo info;
+    TM_TRY(jpg::parse_jpeg(file.data(), file.size(), path.c_str(), &info));
+    in->kind = TM_INPUT_JPEGS;
+    in->src_w = info.w; in->src_h = info.h; in->chroma = info.layout(); in->full_range = 1;  // (JFIF: full-range BT.601)
+    in->jpeg_segments = (int)info.nsegs;
+  } else
+    TM_TRY(read_png(path.c_str(), nullptr, 0, &in->src_w, &in->src_h));  // the size comes from the first file (1813-1814)
   in->dst_w = in->src_w; in->dst_h = in->src_h;                         // Scaling plays no part on this path (3347-3348)
   // manual key frames (FindKeyFrames(AManualMode), 3380-3384): frame i where Format(ChangeFileExt(name, '.kf'), [i + StartFrame]) exists
   const std::string kf = change_ext(name, ".kf");
@@ -213,6 +243,6 @@ extern "C" int tm_probe_input_host(const char *name, int start_frame, int frame_
   if (dst_height) *dst_height = in.dst_h;
   if (fps) *fps = in.fps;
   if (frames) *frames = in.frames;
-  if (chroma) *chroma = in.chroma;
+  if (chroma) *chroma = in.chroma == CHROMA_422_CENTRED ? (int)TM_CHROMA_422 : in.chroma;
   return TM_OK;
 }

@@ -304,7 +304,7 @@ static int step_load(tm_encoder *e) {  // Load, tilingencoder.pas:1741-1841 (fra
   TM_TRY(dcorrel.alloc((size_t)e->nframes * 12));
   e->h_fflags.clear();  // fetched lazily by tm_get_tilemap
   e->kf_lo_thres = e->s.ShotTransCorrelLoThres; e->kf_min_s = e->s.ShotTransMinSecondsPerKF; e->kf_max_s = e->s.ShotTransMaxSecondsPerKF; e->kf_fps = e->fps;
-  e->kf_manual = e->input.kind == TM_INPUT_PNGS;
+  e->kf_manual = e->input.kind == TM_INPUT_PNGS || e->input.kind == TM_INPUT_JPEGS;
   e->kf_manual_list = e->kf_manual ? e->input.manual_kf : std::vector<int32_t>();
   if (e->load_sharded) {
     const int64_t f0 = e->load_first, f1 = f0 + e->load_count, lo = std::max<int64_t>(f0 - 1, 0);

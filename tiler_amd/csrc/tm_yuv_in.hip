@@ -15,6 +15,7 @@ int chroma_geom(int chroma, int w, int h, ChromaGeom *g) {
     case TM_CHROMA_420JPEG: *g = {2, 2, 1, 1, (w + 1) / 2, (h + 1) / 2}; break;
     case TM_CHROMA_420MPEG2: *g = {2, 2, 0, 1, (w + 1) / 2, (h + 1) / 2}; break;
     case TM_CHROMA_MONO: *g = {1, 1, 0, 0, 0, 0}; break;
+    case CHROMA_422_CENTRED: *g = {2, 1, 1, 0, (w + 1) / 2, h}; break;
     default: set_error("bad chroma layout %d", chroma); return TM_E_INVAL;
   }
   return TM_OK;
@@ -252,6 +253,7 @@ int tm_stage_yuv_to_rgb32(const void *y, const void *u, const void *v, const int
   knobs_reload();
   TM_TRY(require_device());
   ChromaGeom g;
+  TM_CHECK(chroma >= TM_CHROMA_444 && chroma <= TM_CHROMA_MONO, TM_E_INVAL, "bad chroma layout %d", chroma);
   TM_TRY(chroma_geom(chroma, src_w, src_h, &g));
   const bool has_c = chroma != TM_CHROMA_MONO;
   TM_CHECK(y && out_rgb32 && strides && (!has_c || (u && v)) && nframes >= 0 && src_w > 0 && src_h > 0 && dst_w > 0 && dst_h > 0, TM_E_INVAL, "yuv_to_rgb32: bad arguments");

@@ -307,6 +307,36 @@ class TilingEncoder:
         self._yuv_ref = [ptrs, sizes, keep]
         return self.VideoInfo()
 
+    def SetFramesJPEG(self, files, fps):
+        """JPEG files lent in memory (tm_set_frames_jpeg): files = a list of bytes objects, one per frame -- camera stills, the frames of an
+        MJPEG capture.  Baseline files only (include/tilemotion.h lists what is read).  The size and the sampling are the first file's
+        (Scaling is ignored); a file of another size or sampling fails the Load.  The key frames follow the automatic rule.  Decoded where
+        SetJpegDecode says, converted by the InputYUV rule (auto: full-range BT.601).  The files are borrowed (and kept alive here) until
+        the Run that loads them has returned.  Returns VideoInfo()."""
+        from ._lib import file_list
+        files = [bytes(f) for f in files]
+        ptrs, sizes, keep = file_list(files)
+        check(self._L.tm_set_frames_jpeg(c_void_p(self._h), ptrs, sizes, len(files), float(fps)))
+        self._yuv_ref = [ptrs, sizes, keep]
+        return self.VideoInfo()
+
+    def SetJpegDecode(self, where="auto"):
+        """Where the Load of a JPEG sequence or of lent JPEG files decodes (tm_set_jpeg_decode): "host" (the host form of the decoder on
+        the reader threads, the planes uploaded), "device" (the files' bytes uploaded, k_jpeg_decode), "auto" (the device when the first file has
+        four restart segments or more, else the host: DESIGN.md section 39.3 has the measurement).  The environment variable TM_JPEG_DECODE=host|device overrides."""
+        from ._lib import PNG_DECODE
+        if isinstance(where, str):
+            if where not in PNG_DECODE:
+                raise ValueError("unknown JPEG decode place %r (one of %s)" % (where, " ".join(PNG_DECODE)))
+            where = PNG_DECODE[where]
+        check(self._L.tm_set_jpeg_decode(c_void_p(self._h), int(where)))
+
+    def JpegDecode(self):
+        from ._lib import PNG_DECODE
+        v = c_int()
+        check(self._L.tm_get_jpeg_decode(c_void_p(self._h), ctypes.byref(v)))
+        return {n: k for k, n in PNG_DECODE.items()}[v.value]
+
     def SetPngDecode(self, where="auto"):
         """Where the Load of a PNG sequence or of lent PNG files decodes (tm_set_png_decode): "host" (the reader on host threads, the RGB32
         clip uploaded), "device" (the files' bytes uploaded, inflate and unfilter in kernels), "auto" (the device: DESIGN.md section 35 has the
@@ -325,7 +355,7 @@ class TilingEncoder:
         return {n: k for k, n in PNG_DECODE.items()}[v.value]
 
     def InputStats(self):
-        """What the last Load of a PNG input did (tm_get_input_stats): frames, the files' bytes, the bytes uploaded for them, where they
+        """What the last Load of a PNG or JPEG input did (tm_get_input_stats): frames, the files' bytes, the bytes uploaded for them, where they
         were decoded ("host" / "device"), and its milliseconds: reading (host: reading and decoding), the device, the wall clock"""
         from ._lib import PNG_DECODE, InputStatsDesc
         st = InputStatsDesc()

@@ -605,3 +605,61 @@ def png_decode(files, w, h, frame_px=None):
     check(lib().tm_stage_png_decode(ptrs, sizes, len(files), w, h, _p(out), frame_px, status, _stream()))
     del keep
     return out[:len(files)], list(status[:len(files)])
+
+
+def jpeg_probe(file):
+    """What the container walk finds of one JPEG file, with no device (tm_probe_jpeg_host): a dict of width, height, components, h_samp,
+    v_samp (the luma sampling factors), restart_interval, segments, sof, chroma (TM_CHROMA_*) and status (0, or TM_JPG_BAD_RESTART).  The
+    walk's refusals raise."""
+    from ._lib import JpegInfoDesc
+    info = JpegInfoDesc()
+    buf = bytes(file)
+    check(lib().tm_probe_jpeg_host(buf, len(buf), ctypes.byref(info)))
+    return {name: getattr(info, name) for name, _ in JpegInfoDesc._fields_}
+
+
+def _jpeg_decode(files, w, h, guard, host):
+    import numpy as np
+    from ._lib import file_list
+    files = [bytes(f) for f in files]
+    n = len(files)
+    ptrs, sizes, keep = file_list(files)
+    # every plane's slot holds w x h samples on rows of w rounded up to 8 bytes, with `guard` bytes of 0xA5 before, between and behind
+    row = (w + 7) & ~7
+    frame = (row * h + guard + 7) & ~7
+    total = guard + frame * max(n, 1)
+    if host:
+        planes = [np.full(total, 0xA5, np.uint8) for _ in range(3)]
+        base = [p.ctypes.data + guard for p in planes]
+    else:
+        planes = [torch.full((total,), 0xA5, dtype=torch.uint8, device="cuda") for _ in range(3)]
+        base = [p.data_ptr() + guard for p in planes]
+    strides = (ctypes.c_int64 * 6)(row, frame, row, frame, row, frame)
+    status = (ctypes.c_int32 * max(n, 1))()
+    if host:
+        check(lib().tm_jpeg_decode_host(ptrs, sizes, n, w, h, base[0], base[1], base[2], strides, status))
+    else:
+        check(lib().tm_stage_jpeg_decode(ptrs, sizes, n, w, h, base[0], base[1], base[2], strides, status, _stream()))
+    del keep
+    return planes, list(status[:n]), {"row": row, "frame": frame, "first": guard}
+
+
+def jpeg_decode(files, w=None, h=None, guard=64):
+    """A batch of JPEG file images in host memory decoded on the device (tm_stage_jpeg_decode: k_jpeg_decode).  files: a list of bytes;
+    w, h: the size of a plane's slot (default: the largest file's) -> ([Y, U, V] uint8 CUDA tensors filled with 0xA5 before the launch,
+    status per file, layout): file i's plane starts at layout["first"] + i layout["frame"], rows layout["row"] apart, at the file's own
+    size; `guard` bytes lie before the first slot and behind every slot's h rows."""
+    if w is None or h is None:
+        infos = [jpeg_probe(f) for f in files]
+        w = max([i["width"] for i in infos] + [1])
+        h = max([i["height"] for i in infos] + [1])
+    return _jpeg_decode(files, int(w), int(h), int(guard), False)
+
+
+def jpeg_decode_host(files, w=None, h=None, guard=64):
+    """jpeg_decode's host twin (tm_jpeg_decode_host), no device: the same arguments and layout, numpy arrays"""
+    if w is None or h is None:
+        infos = [jpeg_probe(f) for f in files]
+        w = max([i["width"] for i in infos] + [1])
+        h = max([i["height"] for i in infos] + [1])
+    return _jpeg_decode(files, int(w), int(h), int(guard), True)

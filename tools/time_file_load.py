@@ -1,6 +1,6 @@
 """Wall time of Load from a Y4M file against Load of the same clip as RGB32 in page-locked host memory, and of the same clip lent as YUV planes.
 
-    python tools/time_file_load.py [--mode file|host|both|yuv|rgb|png|all] [--frames 300 --width 1280 --height 720] [--scaling 1.0] [--passes 7] [--dir /dev/shm]
+    python tools/time_file_load.py [--mode file|host|both|yuv|rgb|png|jpeg|all] [--frames 300 --width 1280 --height 720] [--scaling 1.0] [--passes 7] [--dir /dev/shm]
 
 The clip is bench.py's (SURVEY.md 8d's generator).  `file`: it is written as a 4:2:0 Y4M into --dir (memory-backed by default, so that the
 figure is the pipeline's and not a disk's) and every pass is OpenInput + Run(esLoad).  `host`: the RGB32 clip sits in pinned memory and every
@@ -12,7 +12,9 @@ page-locked host memory, rgb24 and gbrp 10-bit in device memory, rgb24 in device
 conversion alone (stages.rgb_to_rgb32) between two events.  `png` (not part of `all`): the clip is written into --dir as a PNG sequence, once by
 Pillow at its defaults and once by this library's level-1 export, and every pass is OpenInput + Run(esLoad) under TM_PNG_DECODE=host and
 =device; with --png-keep the sequences stay in --dir for the next call (an older build of the library, loaded with TM_LIB_VARIANT, reads them
-under `host` alone: --png-where host).  One warm-up pass, then the median of --passes passes with their spread; one JSON line."""
+under `host` alone: --png-where host).  `jpeg` (not part of `all`): the clip is written into --dir by Pillow as a JPEG sequence (quality 90, 4:2:0), once
+without restart markers and once with an interval of one MCU row, and the passes alternate between TM_JPEG_DECODE=device and =host, every
+pass OpenInput + Run(esLoad); --jpeg-blocks N,M,... times sequences with restart intervals of N, M, ... MCUs instead.  One warm-up pass, then the median of --passes passes with their spread; one JSON line."""
 import argparse
 import json
 import os
@@ -43,7 +45,7 @@ def stats(ms):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["file", "host", "both", "yuv", "rgb", "png", "all"], default="both")
+    ap.add_argument("--mode", choices=["file", "host", "both", "yuv", "rgb", "png", "jpeg", "all"], default="both")
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=720)
@@ -51,6 +53,7 @@ def main():
     ap.add_argument("--passes", type=int, default=7)
     ap.add_argument("--dir", default="/dev/shm")
     ap.add_argument("--png-where", default="host,device", help="the TM_PNG_DECODE settings --mode png times")
+    ap.add_argument("--jpeg-blocks", default="", help="--mode jpeg: time these restart intervals (MCUs, comma separated) instead of the two standard sequences")
     ap.add_argument("--png-keep", action="store_true", help="--mode png: leave the sequences in --dir, and use those that are there")
     args = ap.parse_args()
     import torch
@@ -182,6 +185,41 @@ def main():
                     for n in names + [stem + ".txt"]:
                         if os.path.exists(n):
                             os.remove(n)
+
+    if args.mode == "jpeg":
+        from PIL import Image
+        legs = [("plain", {}), ("restart_rows", {"restart_marker_rows": 1})]
+        if args.jpeg_blocks:  # further legs: a restart interval of so many MCUs
+            legs = [("restart_%s_mcus" % b, {"restart_marker_blocks": int(b)}) for b in args.jpeg_blocks.split(",")]
+        for name, opts in legs:
+            stem = os.path.join(args.dir, "time_jpeg_load_%s_%d_%dx%dx%d" % (name, os.getpid(), W, H, F))
+            names = ["%s_%04d.jpg" % (stem, i) for i in range(F)]
+            try:
+                for i in range(F):
+                    fr = clip[i]
+                    Image.fromarray(np.stack([(fr >> 16) & 255, (fr >> 8) & 255, fr & 255], -1).astype(np.uint8), "RGB").save(names[i], "JPEG", quality=90, subsampling=2, **opts)
+                leg = dict(file_bytes=sum(os.path.getsize(n) for n in names))
+                encs, ms, info = {}, {"device": [], "host": []}, None
+                for where in ms:
+                    encs[where] = TilingEncoder()
+                    encs[where].LoadDefaultSettings()
+                    encs[where].InputFileName = stem + "_%.4d.jpg"
+                for p in range(args.passes + 1):
+                    for where in ms:  # alternating, so that a drift of the machine falls on both
+                        os.environ["TM_JPEG_DECODE"] = where
+                        t0 = time.perf_counter()
+                        info = encs[where].OpenInput()
+                        encs[where].Run(S.esLoad)
+                        ms[where].append((time.perf_counter() - t0) * 1e3)
+                for where in ms:
+                    leg[where] = dict(stats(ms[where][1:]), video=info, input_stats=encs[where].InputStats())
+                    encs[where].close()
+                out["load_jpeg_" + name] = leg
+            finally:
+                os.environ.pop("TM_JPEG_DECODE", None)
+                for n in names:
+                    if os.path.exists(n):
+                        os.remove(n)
 
     if args.mode in ("file", "both", "all"):
         path = os.path.join(args.dir, "time_file_load_%d.y4m" % os.getpid())
