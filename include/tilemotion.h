@@ -605,6 +605,56 @@ TM_API int tm_set_jpeg_decode(tm_encoder *, int where /* TM_PNG_DECODE_* */);
 TM_API int tm_get_jpeg_decode(tm_encoder *, int *where);
 TM_API int tm_set_frames_jpeg(tm_encoder *, const void *const *files, const size_t *sizes, int nframes, double fps);
 TM_API int tm_probe_jpeg_clip_host(const void *const *files, const size_t *sizes, int nframes, double fps, int *width, int *height);
+/* ---- JPEG export on the device: forward DCT and Huffman coding; MJPEG (tm_jpeg_out.hip; the rule: tm_jpeg_out.h) ----
+ * The input's mirror image.  The files are libjpeg's baseline files byte for byte: quantisers = the Annex K.1 tables scaled by quality
+ * (scale = q < 50 ? 5000 / q : 200 - 2 q; clamp((base scale + 50) / 100, 1, 255)); JFIF's YCbCr in 16-bit fixed point; chroma box-averaged
+ * with libjpeg's alternating bias, edges repeated; the "islow" integer forward DCT; quantisation by integer division; the Huffman tables
+ * of Annex K.3 (not optimised); SOI, APP0 JFIF 1.01, DQT per table, SOF0, DHT per table (DC0, AC0, DC1, AC1), DRI, SOS, the scan, EOI.
+ * The file is a function of the pixels and the options alone: the device form (transform, bit counts, scans, bit packing, byte stuffing
+ * and compaction in kernels; only file bytes cross to the host, one size read-back and one copy per chunk of frames) and the host twin
+ * write the same bytes.
+ *   quality 1 .. 100 (default 90); sampling TM_JPEG_420 (default), _422, _444 or _GREY (Y alone); restart_rows: 0 = no DRI, one entropy
+ * segment; n > 0 = a restart interval of n MCU rows (default 1: the file tm_open_input decodes on the device, section 39.3).
+ *   tm_set_jpeg_options: what tm_generate_jpegs / tm_generate_mjpeg write from then on (TM_E_INVAL: null, quality outside 1 .. 100,
+ * unknown sampling, restart_rows < 0, restart_rows times the MCUs of a row above 65535 is refused by the call that learns the width).
+ *   tm_generate_jpegs: <OutputFileName without extension>_NNNN.jpg, one per frame, of the frames tm_generate_pngs writes (the Output page
+ * with the constructor's defaults, or the source frames: input != 0); no .txt.  tm_generate_mjpeg: the same files one behind another in
+ * `path`.  Both refuse what tm_generate_pngs refuses and, in a device group, read shard 0.  tm_get_jpeg_export_stats: the last of either
+ * (TM_E_INVAL before the first), with tm_export_stats' meanings; tm_export_stats and tm_get_export_stats are not touched by them.
+ *   tm_jpeg_bound_host: an upper bound of one file's size for any pixels.  tm_jpeg_quant_tables_host: the two quantiser tables of a
+ * quality in natural (row-major) order.
+ *   tm_stage_jpeg_encode: nframes pictures [h][w] of 0x00RRGGBB in DEVICE memory, rows stride_px apart, frames frame_px apart (pixels), as
+ * files laid one behind the other in HOST memory host_out, file f at [offsets[f], offsets[f + 1]).  tm_jpeg_encode_host: the same from
+ * HOST frames without a device, byte for byte.  Refusals, TM_E_INVAL before any device call and with nothing written: a null pointer,
+ * options tm_set_jpeg_options refuses, w or h outside 1 .. 32768, a restart interval above 65535 MCUs, nframes < 0, a row stride shorter
+ * than the row with more than one row, a frame stride shorter than a frame with more than one frame.  A cap too small is TM_E_INVAL too,
+ * with offsets[nframes] set to the bytes needed and host_out untouched: size host_out by nframes times tm_jpeg_bound_host and the call is
+ * made once.  The stage call returns synchronised. */
+enum { TM_JPEG_420 = 0, TM_JPEG_422 = 1, TM_JPEG_444 = 2, TM_JPEG_GREY = 3 };
+typedef struct tm_jpeg_options {
+  int32_t quality;      /* 1 .. 100 (default 90) */
+  int32_t sampling;     /* TM_JPEG_* (default TM_JPEG_420) */
+  int32_t restart_rows; /* 0: none; n: RSTn every n MCU rows (default 1) */
+} tm_jpeg_options;
+typedef struct tm_jpeg_export_stats {
+  int64_t frames, file_bytes;               /* pictures written and the sum of their sizes */
+  int32_t quality, sampling, restart_rows;  /* the options that held */
+  int32_t reserved;
+  double ms_device;                         /* render, coding and read-back of the chunks, each behind a synchronise */
+  double ms_write;                          /* writing the files */
+  double ms_wall;                           /* the whole call */
+} tm_jpeg_export_stats;
+TM_API int tm_set_jpeg_options(tm_encoder *, const tm_jpeg_options *opt);
+TM_API int tm_get_jpeg_options(tm_encoder *, tm_jpeg_options *opt);
+TM_API int tm_generate_jpegs(tm_encoder *, int input);
+TM_API int tm_generate_mjpeg(tm_encoder *, const char *path, int input);
+TM_API int tm_get_jpeg_export_stats(tm_encoder *, tm_jpeg_export_stats *out);
+TM_API int tm_jpeg_bound_host(int w, int h, const tm_jpeg_options *opt, int64_t *bytes);
+TM_API int tm_jpeg_quant_tables_host(int quality, uint16_t *luma /* 64 */, uint16_t *chroma /* 64 */);
+TM_API int tm_stage_jpeg_encode(const uint32_t *dev_frames, int64_t stride_px, int64_t frame_px, int nframes, int w, int h, const tm_jpeg_options *opt,
+                                uint8_t *host_out, int64_t cap, int64_t *offsets /* nframes + 1 */, void *stream);
+TM_API int tm_jpeg_encode_host(const uint32_t *frames, int64_t stride_px, int64_t frame_px, int nframes, int w, int h, const tm_jpeg_options *opt,
+                               uint8_t *out, int64_t cap, int64_t *offsets /* nframes + 1 */);
 /* The same pictures rendered on the device (Render :3455-3640, Output tab with the constructor's defaults; or the Input tab: input != 0):
  * frames [first_frame, first_frame+frame_count) as [frame_count][tm_h*8][tm_w*8] uint32 0x00RRGGBB (the format frames are pushed in; the
  * input render is every pushed frame cropped to tm_w*8 x tm_h*8 with alpha 0).  A predicted item is frame f-1's output at its offset,

@@ -71,6 +71,15 @@ class JpegInfoDesc(ctypes.Structure):  # tm_jpeg_info
     _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "components", "h_samp", "v_samp", "restart_interval", "segments", "sof", "chroma", "status")]
 
 
+class JpegOptions(ctypes.Structure):  # tm_jpeg_options
+    _fields_ = [("quality", ctypes.c_int32), ("sampling", ctypes.c_int32), ("restart_rows", ctypes.c_int32)]
+
+
+class JpegExportStatsDesc(ctypes.Structure):  # tm_jpeg_export_stats
+    _fields_ = [("frames", c_int64), ("file_bytes", c_int64), ("quality", ctypes.c_int32), ("sampling", ctypes.c_int32), ("restart_rows", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("ms_device", c_double), ("ms_write", c_double), ("ms_wall", c_double)]
+
+
 PNG_DECODE = {"auto": 0, "host": 1, "device": 2}  # TM_PNG_DECODE_*
 
 RENDER_PAGES = {"input": 0, "output": 1, "tiles": 2}  # TM_RENDER_PAGE_*
@@ -190,6 +199,15 @@ SIGNATURES = {
     "tm_get_jpeg_decode": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "tm_set_frames_jpeg": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double]),
     "tm_probe_jpeg_clip_host": (c_int, [c_void_p, c_void_p, c_int, c_double, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "tm_generate_jpegs": (c_int, [c_void_p, c_int]),
+    "tm_generate_mjpeg": (c_int, [c_void_p, c_char_p, c_int]),
+    "tm_set_jpeg_options": (c_int, [c_void_p, ctypes.POINTER(JpegOptions)]),
+    "tm_get_jpeg_options": (c_int, [c_void_p, ctypes.POINTER(JpegOptions)]),
+    "tm_get_jpeg_export_stats": (c_int, [c_void_p, ctypes.POINTER(JpegExportStatsDesc)]),
+    "tm_jpeg_bound_host": (c_int, [c_int, c_int, ctypes.POINTER(JpegOptions), ctypes.POINTER(c_int64)]),
+    "tm_jpeg_quant_tables_host": (c_int, [c_int, c_void_p, c_void_p]),
+    "tm_stage_jpeg_encode": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, ctypes.POINTER(JpegOptions), c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    "tm_jpeg_encode_host": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, ctypes.POINTER(JpegOptions), c_void_p, c_int64, ctypes.POINTER(c_int64)]),
 }
 
 
@@ -203,6 +221,18 @@ def png_options(level=1, filter="auto"):
             raise ValueError("unknown PNG filter strategy %r (one of %s)" % (filter, " ".join(PNG_FILTERS)))
         filter = PNG_FILTERS[filter]
     return PngOptions(int(level), int(filter))
+
+
+JPEG_SAMPLINGS = {"420": 0, "422": 1, "444": 2, "grey": 3}  # TM_JPEG_*
+
+
+def jpeg_options(quality=90, sampling="420", restart_rows=1):
+    """tm_jpeg_options from the keywords SetJpegOptions / stages.jpeg_encode take"""
+    if isinstance(sampling, str):
+        if sampling not in JPEG_SAMPLINGS:
+            raise ValueError("unknown JPEG sampling %r (one of %s)" % (sampling, " ".join(JPEG_SAMPLINGS)))
+        sampling = JPEG_SAMPLINGS[sampling]
+    return JpegOptions(int(quality), int(sampling), int(restart_rows))
 
 
 def inflate_batch(streams, caps=None, dst_offs=None, src_offs=None):

@@ -101,6 +101,9 @@ struct tm_encoder {
   tm_png_options png_options{0, TM_PNG_FILTER_AUTO};  // what GeneratePNGs writes (tm_set_png_options); level 0: stored blocks
   tm_export_stats export_stats{};                      // of the last GeneratePNGs (tm_get_export_stats)
   bool has_export_stats = false;
+  tm_jpeg_options jpeg_options{90, TM_JPEG_420, 1};    // what GenerateJPEGs / GenerateMJPEG write (tm_set_jpeg_options)
+  tm_jpeg_export_stats jpeg_export_stats{};            // of the last of them (tm_get_jpeg_export_stats)
+  bool has_jpeg_export_stats = false;
   int jpeg_decode = TM_PNG_DECODE_AUTO; // where a JPEG input is decoded (tm_set_jpeg_decode); TM_JPEG_DECODE overrides
   int png_decode = TM_PNG_DECODE_AUTO;  // where a PNG input is decoded (tm_set_png_decode); TM_PNG_DECODE overrides
   tm_input_stats input_stats{};          // of the last Load that read a PNG input (tm_get_input_stats)

@@ -1,4 +1,4 @@
-// tm_export.hip -- what leaves the encoder as files or pictures: Save (.gtm), ReloadGTM, GenerateY4M / GeneratePNGs, and the device
+// tm_export.hip -- what leaves the encoder as files or pictures: Save (.gtm), ReloadGTM, GenerateY4M / GeneratePNGs / GenerateJPEGs, and the device
 // render entry points tm_render_frames / tm_get_frame_quality (kernels in tm_render.hip).
 #include <chrono>
 #include <cmath>
@@ -7,6 +7,7 @@
 #include "tm_deflate.h"
 #include "tm_encoder.h"
 #include "tm_gtm.h"
+#include "tm_jpeg_out.h"
 
 int save_to(tm_encoder *e, const char *path) {  // Save, tilingencoder.pas:2040-2058 -> SaveStream, 5177
   TM_TRY(need(e, TM_STEP_REINDEX, "Reindex"));
@@ -208,6 +209,56 @@ static int generate_pngs(tm_encoder *e, bool input) {  // GeneratePNGs, tilingen
   return TM_OK;
 }
 
+// GenerateJPEGs / GenerateMJPEG: the frames GeneratePNGs writes, kept on the device a chunk at a time and coded there
+// (tm_jpeg_out.hip); only the files' bytes come back.  path: the one file they go to behind one another, or null: a file per frame next
+// to OutputFileName.
+static int generate_jpegs(tm_encoder *e, const char *path, bool input) {
+  const char *who = path ? "GenerateMJPEG" : "GenerateJPEGs";
+  TM_CHECK(!path || *path, TM_E_INVAL, "GenerateMJPEG: no file name");
+  TM_CHECK(path || !e->s.OutputFileName.empty(), TM_E_INVAL, "GenerateJPEGs: OutputFileName is not set");
+  const auto wall0 = std::chrono::steady_clock::now();
+  const tm_jpeg_options opt = e->jpeg_options;
+  e->has_jpeg_export_stats = false;
+  ExportFrames r{e, input};
+  r.keep = true;
+  TM_TRY(r.init());
+  TM_TRY(jpo::jpeg_out_check(who, r.dev.p, r.sw, (int64_t)r.sw * r.sh, e->nframes, r.sw, r.sh, &opt));
+  const std::string base = strip_ext(e->s.OutputFileName);
+  std::ofstream all;
+  if (path) {
+    all.open(path, std::ios::binary);
+    TM_CHECK(all.good(), TM_E_IO, "cannot write %s", path);
+  }
+  tm_jpeg_export_stats st{};
+  st.quality = opt.quality; st.sampling = opt.sampling; st.restart_rows = opt.restart_rows;
+  std::vector<std::vector<uint8_t>> files;
+  jpo::JpegDeviceEncoder encoder;  // (its device buffers serve every chunk)
+  for (int fr = 0; fr < e->nframes; fr++) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool fresh = fr >= r.first + r.count;
+    TM_TRY(r.frame(fr, nullptr));
+    if (fresh) TM_TRY(encoder.encode(r.dev.as<uint32_t>(), r.sw, (int64_t)r.sw * r.sh, r.count, r.sw, r.sh, opt, e->stream, files));
+    const auto t1 = std::chrono::steady_clock::now();
+    const std::vector<uint8_t> &bytes = files[(size_t)(fr - r.first)];
+    if (path) {
+      all.write((const char *)bytes.data(), (std::streamsize)bytes.size());
+      TM_CHECK(all.good(), TM_E_IO, "write to %s failed", path);
+    } else {
+      char name[32];
+      snprintf(name, sizeof(name), "_%04d.jpg", fr);
+      TM_TRY(write_file(base + name, bytes));
+    }
+    const auto t2 = std::chrono::steady_clock::now();
+    st.frames++; st.file_bytes += (int64_t)bytes.size();
+    st.ms_device += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    st.ms_write += std::chrono::duration<double, std::milli>(t2 - t1).count();
+  }
+  st.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  e->jpeg_export_stats = st;
+  e->has_jpeg_export_stats = true;
+  return TM_OK;
+}
+
 extern "C" {
 
 int tm_reload_gtm(tm_encoder *e, const char *path) {  // ReloadGTM, tilingencoder.pas:2059 -> LoadStream, 4880-5175
@@ -305,6 +356,37 @@ int tm_get_export_stats(tm_encoder *e, tm_export_stats *out) {
   TM_CHECK(e && out, TM_E_INVAL, "null argument");
   TM_CHECK(e->has_export_stats, TM_E_INVAL, "export stats: this encoder has not written PNGs");
   *out = e->export_stats;
+  return TM_OK;
+}
+
+int tm_generate_jpegs(tm_encoder *e, int input) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  return generate_jpegs(e, nullptr, input != 0);
+}
+
+int tm_generate_mjpeg(tm_encoder *e, const char *path, int input) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_CHECK(path, TM_E_INVAL, "GenerateMJPEG: no file name");
+  return generate_jpegs(e, path, input != 0);
+}
+
+int tm_set_jpeg_options(tm_encoder *e, const tm_jpeg_options *opt) {
+  TM_CHECK(e && opt, TM_E_INVAL, "null argument");
+  TM_TRY(jpo::jpeg_options_check("jpeg options", opt));
+  e->jpeg_options = *opt;
+  return TM_OK;
+}
+
+int tm_get_jpeg_options(tm_encoder *e, tm_jpeg_options *opt) {
+  TM_CHECK(e && opt, TM_E_INVAL, "null argument");
+  *opt = e->jpeg_options;
+  return TM_OK;
+}
+
+int tm_get_jpeg_export_stats(tm_encoder *e, tm_jpeg_export_stats *out) {
+  TM_CHECK(e && out, TM_E_INVAL, "null argument");
+  TM_CHECK(e->has_jpeg_export_stats, TM_E_INVAL, "jpeg export stats: this encoder has not written JPEGs");
+  *out = e->jpeg_export_stats;
   return TM_OK;
 }
 

@@ -546,6 +546,36 @@ class TilingEncoder:
         """GeneratePNGs (tilingencoder.pas:2075): <OutputFileName>_NNNN.png per frame + the palettes as <OutputFileName>.txt"""
         check(self._L.tm_generate_pngs(c_void_p(self._h), int(bool(input))))
 
+    def GenerateJPEGs(self, input=False):
+        """<OutputFileName>_NNNN.jpg per frame (tm_generate_jpegs): the frames GeneratePNGs writes, coded on the device as SetJpegOptions says"""
+        check(self._L.tm_generate_jpegs(c_void_p(self._h), int(bool(input))))
+
+    def GenerateMJPEG(self, path, input=False):
+        """The same files one behind another in `path` (tm_generate_mjpeg)"""
+        check(self._L.tm_generate_mjpeg(c_void_p(self._h), os.fsencode(path), int(bool(input))))
+
+    def SetJpegOptions(self, quality=90, sampling="420", restart_rows=1):
+        """How GenerateJPEGs / GenerateMJPEG write from now on (tm_set_jpeg_options): quality 1 .. 100; sampling "420", "422", "444" or
+        "grey"; restart_rows: 0 = no restart markers, n = one every n MCU rows (1, the default, is the file Load decodes on the device)"""
+        from ._lib import jpeg_options
+        check(self._L.tm_set_jpeg_options(c_void_p(self._h), ctypes.byref(jpeg_options(quality, sampling, restart_rows))))
+
+    def JpegOptions(self):
+        from ._lib import JPEG_SAMPLINGS, JpegOptions
+        opt = JpegOptions()
+        check(self._L.tm_get_jpeg_options(c_void_p(self._h), ctypes.byref(opt)))
+        return {"quality": opt.quality, "sampling": {v: k for k, v in JPEG_SAMPLINGS.items()}[opt.sampling], "restart_rows": opt.restart_rows}
+
+    def JpegExportStats(self):
+        """What the last GenerateJPEGs / GenerateMJPEG did (tm_get_jpeg_export_stats): frames, the files' bytes, the options that held, and
+        its times in ms (ms_device, ms_write, ms_wall, as ExportStats has them)"""
+        from ._lib import JPEG_SAMPLINGS, JpegExportStatsDesc
+        st = JpegExportStatsDesc()
+        check(self._L.tm_get_jpeg_export_stats(c_void_p(self._h), ctypes.byref(st)))
+        out = {name: getattr(st, name) for name, _ in JpegExportStatsDesc._fields_ if name != "reserved"}
+        out["sampling"] = {v: k for k, v in JPEG_SAMPLINGS.items()}[st.sampling]
+        return out
+
     def SetPngOptions(self, level=1, filter="auto"):
         """How GeneratePNGs writes from now on (tm_set_png_options): level 0 = stored blocks (the default), level 1 = filtered, matched
         and Huffman-coded on the device; filter: "auto" (none for the output frames, adaptive for the source frames), "none", "adaptive",

@@ -663,3 +663,56 @@ def jpeg_decode_host(files, w=None, h=None, guard=64):
         w = max([i["width"] for i in infos] + [1])
         h = max([i["height"] for i in infos] + [1])
     return _jpeg_decode(files, int(w), int(h), int(guard), True)
+
+
+def jpeg_bound(w, h, quality=90, sampling="420", restart_rows=1):
+    """An upper bound of one JPEG file's size for any pixels (tm_jpeg_bound_host), no device"""
+    from ._lib import jpeg_options
+    opt = jpeg_options(quality, sampling, restart_rows)
+    bound = ctypes.c_int64()
+    check(lib().tm_jpeg_bound_host(int(w), int(h), ctypes.byref(opt), ctypes.byref(bound)))
+    return bound.value
+
+
+def jpeg_quant_tables(quality):
+    """The luma and chroma quantisers of a quality in natural order (tm_jpeg_quant_tables_host), no device -> two uint16 arrays [64]"""
+    luma, chroma = np.zeros(64, np.uint16), np.zeros(64, np.uint16)
+    check(lib().tm_jpeg_quant_tables_host(int(quality), luma.ctypes.data_as(ctypes.c_void_p), chroma.ctypes.data_as(ctypes.c_void_p)))
+    return luma, chroma
+
+
+def _jpeg_encode(call, ptr, stride_px, frame_px, nf, w, h, opt, cap, guard, full, extra):
+    if cap is None:
+        bound = ctypes.c_int64()
+        check(lib().tm_jpeg_bound_host(w, h, ctypes.byref(opt), ctypes.byref(bound)))
+        cap = bound.value * max(nf, 1)
+    buf = np.full(cap + 2 * guard, 0xA5, np.uint8)
+    offs = (ctypes.c_int64 * (nf + 1))(*([-1] * (nf + 1)))
+    rc = call(ptr, stride_px, frame_px, nf, w, h, ctypes.byref(opt), ctypes.c_void_p(buf.ctypes.data + guard) if cap else None, cap, offs, *extra)
+    if not full:
+        check(rc)
+    files = [buf[guard + offs[f]:guard + offs[f + 1]].tobytes() for f in range(nf)] if rc == 0 else None
+    return dict(rc=rc, files=files, buffer=buf, offsets=list(offs), guard=guard) if full else files
+
+
+def jpeg_encode(frames, quality=90, sampling="420", restart_rows=1, cap=None, guard=0, full=False):
+    """RGB32 frames on the device as baseline JPEG files (tm_stage_jpeg_encode; the rule: include/tilemotion.h):
+    frames = torch int32 CUDA tensor [F][H][W] of 0x00RRGGBB, rows and frames at any stride -> list of F bytes objects, byte for byte what
+    tm_jpeg_encode_host (and libjpeg) writes; only the files' bytes come to the host.  cap: the room given (default: F times
+    jpeg_bound); guard: bytes of 0xA5 kept before and behind that room; full=True: nothing raises, and the result is a dict of rc, files
+    (None when refused), buffer (guards included), offsets and guard"""
+    from ._lib import jpeg_options
+    assert frames.is_cuda and frames.dtype == torch.int32 and frames.dim() == 3 and (frames.shape[2] <= 1 or frames.stride(2) == 1)
+    nf, h, w = frames.shape
+    return _jpeg_encode(lib().tm_stage_jpeg_encode, _p(frames), frames.stride(1), frames.stride(0), nf, w, h, jpeg_options(quality, sampling, restart_rows), cap,
+                        guard, full, (_stream(),))
+
+
+def jpeg_encode_host(frames, quality=90, sampling="420", restart_rows=1, cap=None, guard=0, full=False):
+    """jpeg_encode's host twin (tm_jpeg_encode_host), no device: frames = numpy uint32 or int32 array [F][H][W], rows and frames at any
+    stride (a multiple of 4 bytes; pixels contiguous)"""
+    from ._lib import jpeg_options
+    assert frames.dtype in (np.uint32, np.int32) and frames.ndim == 3 and (frames.shape[2] <= 1 or frames.strides[2] == 4)
+    nf, h, w = frames.shape
+    return _jpeg_encode(lib().tm_jpeg_encode_host, ctypes.c_void_p(frames.ctypes.data), frames.strides[1] // 4, frames.strides[0] // 4, nf, w, h,
+                        jpeg_options(quality, sampling, restart_rows), cap, guard, full, ())

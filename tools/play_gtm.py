@@ -1,6 +1,8 @@
 """Frames of a .gtm stream, played on the device:
 python tools/play_gtm.py IN.gtm [--start N --frames N] (--info | --raw OUT.rgb | --y4m OUT.y4m [--chroma 444|422|420jpeg|420mpeg2|mono] [--yuv MODE]
-                         | --png OUT_%04d.png [--png-level 0|1] [--png-filter none|adaptive|smaller]) [--size WxH [--filter lanczos|nearest]]
+                         | --png OUT_%04d.png [--png-level 0|1] [--png-filter none|adaptive|smaller]
+                         | --jpeg OUT_%04d.jpg | --mjpeg OUT.mjpeg [--jpeg-quality 90] [--jpeg-sampling 420|422|444|grey] [--jpeg-restart-rows 1])
+                         [--size WxH [--filter lanczos|nearest]]
 
 --info prints what the stream says about itself (size, frames, key frames, rate, tiles, palettes, the embedded settings) as JSON;
 --raw writes frames [start, start + frames) as packed RGB24, one frame after the other (view with
@@ -10,7 +12,10 @@ python tools/play_gtm.py IN.gtm [--start N --frames N] (--info | --raw OUT.rgb |
 bt709-full tiler (444 and mono only); the header says XCOLORRANGE=FULL for the full-range rules and tiler.
 --png writes one PNG per frame, named by the pattern with the frame's number: the player's frames stay on the device and are coded there
 (stages.png_encode; --png-level 1, the default: deflate on the device, 0: stored blocks).
---size WxH (with --raw, --y4m and --png): the frames are scaled on the device to that size before they are delivered (GtmPlayer.SetOutput; --filter
+--jpeg writes one baseline JPEG per frame, --mjpeg the same files one behind another in one file that any player opens: the frames stay on
+the device and are coded there (stages.jpeg_encode: libjpeg's bytes; --jpeg-restart-rows 1, the default, writes the restart markers that
+let this library's Load decode the files on the device, 0 none).
+--size WxH (with --raw, --y4m, --png, --jpeg and --mjpeg): the frames are scaled on the device to that size before they are delivered (GtmPlayer.SetOutput; --filter
 lanczos, the default, or nearest); the Y4M header carries the output size."""
 import argparse
 import json
@@ -32,6 +37,11 @@ g.add_argument("--info", action="store_true")
 g.add_argument("--raw")
 g.add_argument("--y4m")
 g.add_argument("--png", help="a pattern with one integer field, for instance OUT_%%04d.png")
+g.add_argument("--jpeg", help="a pattern with one integer field, for instance OUT_%%04d.jpg")
+g.add_argument("--mjpeg")
+ap.add_argument("--jpeg-quality", type=int, default=90)
+ap.add_argument("--jpeg-sampling", default="420", choices=["420", "422", "444", "grey"])
+ap.add_argument("--jpeg-restart-rows", type=int, default=1)
 ap.add_argument("--png-level", type=int, default=1, choices=[0, 1])
 ap.add_argument("--png-filter", default="none", choices=["none", "adaptive", "smaller"])
 ap.add_argument("--chroma", default="420jpeg", choices=["444", "422", "420jpeg", "420mpeg2", "mono"])
@@ -85,6 +95,26 @@ with GtmPlayer(args.input) as p:
                     f.write(png)
                 at += 1
             left -= fr.shape[0]
+    elif args.jpeg or args.mjpeg:
+        from tiler_amd import stages
+        p.Seek(args.start)
+        left = (args.frames if args.frames > 0 else info["frames"] - args.start)
+        at = args.start
+        one = open(args.mjpeg, "wb") if args.mjpeg else None
+        while left > 0:
+            fr = p.Read(min(left, 16), device=True)
+            if fr.shape[0] == 0:
+                break
+            for jpg in stages.jpeg_encode(fr, quality=args.jpeg_quality, sampling=args.jpeg_sampling, restart_rows=args.jpeg_restart_rows):
+                if one:
+                    one.write(jpg)
+                else:
+                    with open(args.jpeg % at, "wb") as f:
+                        f.write(jpg)
+                at += 1
+            left -= fr.shape[0]
+        if one:
+            one.close()
     else:
         p.Seek(args.start)
         left = (args.frames if args.frames > 0 else info["frames"] - args.start)

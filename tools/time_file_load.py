@@ -54,6 +54,8 @@ def main():
     ap.add_argument("--dir", default="/dev/shm")
     ap.add_argument("--png-where", default="host,device", help="the TM_PNG_DECODE settings --mode png times")
     ap.add_argument("--jpeg-blocks", default="", help="--mode jpeg: time these restart intervals (MCUs, comma separated) instead of the two standard sequences")
+    ap.add_argument("--jpeg-writer", default="pillow", choices=["pillow", "library"],
+                    help="--mode jpeg: who writes the sequences: Pillow, or this library's exporter on the device (stages.jpeg_encode: the same bytes; restart_rows 0 and 1 only)")
     ap.add_argument("--png-keep", action="store_true", help="--mode png: leave the sequences in --dir, and use those that are there")
     args = ap.parse_args()
     import torch
@@ -195,10 +197,17 @@ def main():
             stem = os.path.join(args.dir, "time_jpeg_load_%s_%d_%dx%dx%d" % (name, os.getpid(), W, H, F))
             names = ["%s_%04d.jpg" % (stem, i) for i in range(F)]
             try:
-                for i in range(F):
+                for i in range(F if args.jpeg_writer == "pillow" else 0):
                     fr = clip[i]
                     Image.fromarray(np.stack([(fr >> 16) & 255, (fr >> 8) & 255, fr & 255], -1).astype(np.uint8), "RGB").save(names[i], "JPEG", quality=90, subsampling=2, **opts)
-                leg = dict(file_bytes=sum(os.path.getsize(n) for n in names))
+                for i in range(0, F if args.jpeg_writer == "library" else 0, 16):
+                    import torch
+                    from tiler_amd import stages
+                    dev = torch.from_numpy(np.ascontiguousarray(clip[i:i + 16]).view(np.int32)).cuda()
+                    for k, data in enumerate(stages.jpeg_encode(dev, 90, "420", opts.get("restart_marker_rows", 0))):
+                        with open(names[i + k], "wb") as fh:
+                            fh.write(data)
+                leg = dict(file_bytes=sum(os.path.getsize(n) for n in names), writer=args.jpeg_writer)
                 encs, ms, info = {}, {"device": [], "host": []}, None
                 for where in ms:
                     encs[where] = TilingEncoder()
