@@ -1020,6 +1020,12 @@ TM_API int tm_knn_index_last_list_counts(tm_knn_index *, int64_t *listed, int64_
 /* diagnostics (tests): listed blocks (tile x 32 queries) the last search judged on their first chunk of columns, and how many of them ended
  * there (both 0 with TM_KNN_FIRST_CHUNK=0) */
 TM_API int tm_knn_index_last_chunk_counts(tm_knn_index *, int64_t *looked, int64_t *stopped);
+/* diagnostics (tests): the survivor queue of the last search's consume kernel -- tiles popped and looked at, those of them none of whose blocks
+ * got past its look (never loaded beyond their first chunk), survivor entries pushed to the queue, and entries the full queue turned away
+ * (their chains ran in the looking wave), tiles loaded whole (chain tasks run: pushed + ring_full with the look, every tile without) and
+ * the consume kernel's blocks that ran to completion; no_survivor, pushed and ring_full are 0 with TM_KNN_FIRST_CHUNK=0 */
+TM_API int tm_knn_index_last_survivor_counts(tm_knn_index *, int64_t *tiles, int64_t *no_survivor, int64_t *pushed, int64_t *ring_full, int64_t *whole,
+                                             int64_t *completed);
 /* diagnostics (tests): the digit plan of the calling thread's last scan -- 32-column chunks that carry a high digit on the database / query
  * side, 0..6 each, and whether it was the k-nearest collection: together they name the instantiation of the scan's kernels that ran -- and
  * how often a scan of this process has been repeated with a larger tile-list arena (TM_KNN_ARENA_ENTRIES sets the first size) */

@@ -125,6 +125,7 @@ SIGNATURES = {
     "tm_knn_index_last_stats": (c_int, [c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_int), ctypes.POINTER(c_int64)]),
     "tm_knn_index_last_list_counts": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     "tm_knn_index_last_chunk_counts": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
+    "tm_knn_index_last_survivor_counts": (c_int, [c_void_p] + [ctypes.POINTER(c_int64)] * 6),
     "tm_knn_index_row_order": (c_int, [c_void_p, c_void_p, c_void_p]),
     "tm_stage_knn_tile_order": (c_int, [c_void_p, c_int64, c_void_p]),
     "tm_stage_curve_keys": (c_int, [c_void_p, c_int64, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p]),

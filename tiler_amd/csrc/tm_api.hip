@@ -17,7 +17,7 @@ int tm_device_count(void) {
 }
 
 // the trailing token names the build of the KNN scan kernel: PMC passes under profiles/ are keyed by it (bench.py reads `traffic` from them)
-const char *tm_version(void) { return "tilemotion-mi355x 0.3 (gfx950) knn-scan3-r15"; }
+const char *tm_version(void) { return "tilemotion-mi355x 0.3 (gfx950) knn-scan3-r18"; }
 
 int tm_stage_load(const void *frames, int nframes, int img_w, int img_h, int tm_w, int tm_h, void *tiles, void *flags,
                   void *lab_means, void *stream) {
@@ -165,6 +165,12 @@ int tm_knn_index_last_list_counts(tm_knn_index *ix, int64_t *listed, int64_t *po
 int tm_knn_index_last_chunk_counts(tm_knn_index *ix, int64_t *looked, int64_t *stopped) {
   TM_CHECK(ix != nullptr, TM_E_INVAL, "null index");
   knn_index_chunk_counts(reinterpret_cast<tm_knn_index_impl *>(ix), looked, stopped);
+  return TM_OK;
+}
+
+int tm_knn_index_last_survivor_counts(tm_knn_index *ix, int64_t *tiles, int64_t *no_survivor, int64_t *pushed, int64_t *ring_full, int64_t *whole, int64_t *completed) {
+  TM_CHECK(ix != nullptr, TM_E_INVAL, "null index");
+  knn_index_survivor_counts(reinterpret_cast<tm_knn_index_impl *>(ix), tiles, no_survivor, pushed, ring_full, whole, completed);
   return TM_OK;
 }
 

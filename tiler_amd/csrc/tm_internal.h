@@ -56,6 +56,7 @@ int knn_index_search(tm_knn_index_impl *ix, const void *queries, int64_t nq, voi
 void knn_index_stats(tm_knn_index_impl *ix, double *ms, int *kbytes, int64_t *pairs);
 void knn_index_list_counts(tm_knn_index_impl *ix, int64_t *listed, int64_t *popped);
 void knn_index_chunk_counts(tm_knn_index_impl *ix, int64_t *looked, int64_t *stopped);
+void knn_index_survivor_counts(tm_knn_index_impl *ix, int64_t *tiles, int64_t *no_survivor, int64_t *pushed, int64_t *ring_full, int64_t *whole, int64_t *completed);
 void knn_last_plan(int *ht, int *hq, int *topk, long long *arena_retries);
 // diagnostics for the tests: the database's row order as the scan sees it (host, [nt]: tile t holds rows out[32 t ..]), of an index that has searched
 int knn_index_row_order(tm_knn_index_impl *ix, void *out_rows, hipStream_t stream);

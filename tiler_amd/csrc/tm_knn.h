@@ -32,6 +32,7 @@ struct KnnCounts {
   unsigned long long seed_blocks = 0, seed_tiles = 0, seed_pairs = 0;  // the seed kernel's, summed over its stripes
   unsigned long long listed = 0, popped = 0, cursor = 0;         // list entries written / taken off / asked of the arena
   unsigned long long stopped = 0, stopped_pairs = 0;             // blocks the first-chunk look stopped, and their pairs
+  unsigned long long nosurv = 0, pushed = 0, ringfull = 0, whole = 0;      // popped tiles none of whose blocks got past its look; survivor entries queued / turned away by the full ring
   unsigned long long mfma = 0, guard = 0;
   unsigned long long stamps[6] = {}, stamps_in[3] = {}, seed_stamps[7] = {};  // a diagnostic build's (TM_KNN3_STAMPS)
 };
@@ -61,6 +62,7 @@ struct tm_knn_index_impl {
   double last_ms = 0;
   int last_kbytes = 0;
   int64_t last_pairs = 0, last_seed_pairs = 0, last_mfma = 0;
+  int64_t last_consume_tiles = 0, last_no_survivor = 0, last_pushed = 0, last_ring_full = 0, last_whole = 0, last_completed = 0;  // the consume kernel's survivor queue (tm_knn3.h)
   int64_t last_chunk_looked = 0, last_chunk_stopped = 0, last_stopped_pairs = 0;  // listed blocks judged on their first chunk, and those it stopped
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   K3Counters *dev_counters() const { return counters.as<K3Counters>(); }  // (a device address: only its members' addresses are taken on the host)

@@ -251,6 +251,7 @@ static int read_counts(tm_knn_index_impl *ix, KnnCounts *n, int *flag, hipStream
   n->blocks = c.stats[K3S_BLOCKS]; n->tiles = c.stats[K3S_TILES]; n->pairs = c.stats[K3S_PAIRS];
   n->listed = c.stats[K3S_LISTED]; n->popped = c.stats[K3S_POPPED]; n->cursor = c.stats[K3S_CURSOR];
   n->stopped = c.stats[K3S_STOPPED]; n->stopped_pairs = c.stats[K3S_STOPPED_PAIRS];
+  n->nosurv = c.stats[K3S_NOSURV]; n->pushed = c.stats[K3S_PUSHED]; n->ringfull = c.stats[K3S_RINGFULL]; n->whole = c.stats[K3S_WHOLE];
   n->mfma = c.stats[K3S_MFMA]; n->guard = c.stats[K3S_GUARD];
   for (int i = 0; i < 64; i++) { n->seed_blocks += c.seed[i][K3SEED_BLOCKS]; n->seed_tiles += c.seed[i][K3SEED_TILES]; n->seed_pairs += c.seed[i][K3SEED_PAIRS]; }
   for (int i = 0; i < 6; i++) n->stamps[i] = c.stats[K3S_STAMPS + i];
@@ -277,14 +278,17 @@ static int record_counts(tm_knn_index_impl *ix, const KnnCounts &n, int prune) {
   ix->last_mfma = (int64_t)n.mfma;
   ix->last_blocks = (int64_t)(n.blocks + n.seed_blocks); ix->last_loads = (int64_t)(n.tiles + n.seed_tiles);
   ix->last_listed = (int64_t)n.listed; ix->last_popped = (int64_t)n.popped;
+  ix->last_consume_tiles = (int64_t)n.tiles; ix->last_no_survivor = (int64_t)n.nosurv; ix->last_pushed = (int64_t)n.pushed; ix->last_ring_full = (int64_t)n.ringfull; ix->last_whole = (int64_t)n.whole; ix->last_completed = (int64_t)n.blocks;
   ix->last_chunk_stopped = (int64_t)n.stopped; ix->last_chunk_looked = prune && knobs().knn_first_chunk ? (int64_t)(n.blocks + n.stopped) : 0;
   return TM_OK;
 }
 
 static void print_counts(const tm_knn_index_impl *ix, const KnnCounts &n, int64_t nq, int64_t groups) {
   const int64_t ntt = knn_tiles(ix->nt);
-  fprintf(stderr, "[tm_knn] first chunk: %lld of %lld listed blocks stopped (%.1f %%)\n", (long long)ix->last_chunk_stopped, (long long)ix->last_chunk_looked,
-          100.0 * (double)ix->last_chunk_stopped / (double)std::max<int64_t>(1, ix->last_chunk_looked));
+  fprintf(stderr, "[tm_knn] first chunk: %lld of %lld listed blocks stopped (%.1f %%); %llu of %llu popped tiles with no block past its look (%.1f %%)\n", (long long)ix->last_chunk_stopped,
+          (long long)ix->last_chunk_looked, 100.0 * (double)ix->last_chunk_stopped / (double)std::max<int64_t>(1, ix->last_chunk_looked), n.nosurv, n.tiles,
+          100.0 * (double)n.nosurv / (double)std::max<unsigned long long>(1, n.tiles));
+  fprintf(stderr, "[tm_knn] survivor queue: %llu entries pushed, %llu more run in place (ring full), %llu tiles loaded whole; %llu blocks completed\n", n.pushed, n.ringfull, n.whole, n.blocks);
   fprintf(stderr, "[tm_knn] seeds %.3f ms, lists %.3f ms (%.1f entries per group, arena %.0f %% full), consume %.3f ms, %.2f of %d matrix instructions per block\n", ix->last_seed_ms, ix->last_lists_ms,
           (double)n.cursor / (double)groups, 100.0 * (double)n.cursor / (double)std::max<uint64_t>(1, ix->arena_cap), ix->last_consume_ms,
           (double)n.mfma / (double)std::max<unsigned long long>(1, n.blocks + n.stopped), knn_kbytes(ix->plan) / 32);
@@ -373,6 +377,15 @@ void knn_index_stats(tm_knn_index_impl *ix, double *ms, int *kbytes, int64_t *pa
   if (ms) *ms = ix->last_ms;
   if (kbytes) *kbytes = ix->last_kbytes;
   if (pairs) *pairs = ix->last_pairs;
+}
+
+void knn_index_survivor_counts(tm_knn_index_impl *ix, int64_t *tiles, int64_t *no_survivor, int64_t *pushed, int64_t *ring_full, int64_t *whole, int64_t *completed) {
+  if (whole) *whole = ix->last_whole;
+  if (completed) *completed = ix->last_completed;
+  if (tiles) *tiles = ix->last_consume_tiles;
+  if (no_survivor) *no_survivor = ix->last_no_survivor;
+  if (pushed) *pushed = ix->last_pushed;
+  if (ring_full) *ring_full = ix->last_ring_full;
 }
 
 void knn_index_chunk_counts(tm_knn_index_impl *ix, int64_t *looked, int64_t *stopped) {

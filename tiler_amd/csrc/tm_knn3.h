@@ -14,12 +14,15 @@
 //                    No MFMA, no query operands: small workgroups, many per CU, whose global loads hide behind each other.  Lists go to an
 //                    arena in HBM in segments of <= K3_LCAP entries, each sorted by its entries' smallest bound.
 //   3. k_knn_consume (tm_knn3_consume.h) persistent workgroups (one per CU, 16 waves): a group's query operands and its seeds' bests into LDS,
-//                    then one list segment after the other: copied into LDS, consumed by the waves on their own exactly as in the second
-//                    shape (pop an entry, re-judge it against the sub-tiles' bounds AS THEY ARE NOW, tile into registers, one MFMA chain per
-//                    sub-tile that wants it).  An entry judged with the seeds' bound instead of a later, tighter one costs one pop, not a
-//                    block; a sorted segment ends at the first entry whose smallest bound lies above every sub-tile's bound.  A block is
-//                    judged on its first chunk of columns, the 32 widest, before its chain runs, and ends there nine times in ten
-//                    (k3_chunk_look).
+//                    then one list segment after the other: copied into LDS, consumed by the waves on their own (pop an entry, re-judge it
+//                    against the sub-tiles' bounds AS THEY ARE NOW, one MFMA chain per sub-tile that wants the tile).  An entry judged with
+//                    the seeds' bound instead of a later, tighter one costs one pop, not a block; a sorted segment ends at the first entry
+//                    whose smallest bound lies above every sub-tile's bound.  A block is judged on its first chunk of columns, the 32
+//                    widest, before its chain runs, and ends there nine times in ten (k3_chunk_look).  The two jobs
+//                    are two tasks: a wave either LOOKS -- the popped tile's chunk 0 only, two sub-tiles at a time,
+//                    the next tile's chunk 0 asked for before -- or RUNS THE CHAINS of a tile some look let through, taken from a survivor
+//                    queue in LDS and loaded whole then; nine popped tiles in ten never are.  The collection mode keeps the one loop that
+//                    loads every popped tile whole.
 // The device pieces the three are made of are in tm_knn3_block.h; tm_knn3_kernels.h is what a tm_knn3_k<HT>.hip includes.
 // Arithmetic, operands, boxes, curve and the exactness argument are those of the earlier shapes: a pair is skipped only when its lower
 // bound exceeds the sub-tile's largest best + 1 (both sides of the 16-bit compare rounded the safe way), the minimum VALUE is exact, and
@@ -114,12 +117,19 @@ constexpr unsigned K3_LB_NONE = 0xFFFFu; // a list entry's slot for a sub-tile t
 // ------------------------------------------------------------------------------------------------------------------ LDS budget
 // (per sub-tile: operands, norms, bests, box, the norms over the first chunk's columns; per wave: its tile's 32 row terms over them and its
 // 32 original indices)
-constexpr int k3_lds_bytes(int ns, int kq) { return ns * (kq * 1024 + 576) + 64 + 64 + 64 + K3_NW * (128 + 128) + K3_LCAP * (4 + 2 * ((ns + 1) & ~1)); }
+// ... and the survivor queue between the consume kernel's looks and its chains: a ring of 8-byte entries
+constexpr int K3_RING = 128;             // entries (a power of two)
+constexpr int K3_RING_BYTES = K3_RING * 8;
+constexpr int K3_CTL_HEAD = 4, K3_CTL_TAIL = 5;  // the ring's tickets: words of the kernel's s_ctl (taken / handed out; they only grow)
+constexpr int k3_lds_bytes(int ns, int kq) {
+  return ns * (kq * 1024 + 576) + 64 + 64 + 64 + K3_NW * (128 + 128) + K3_LCAP * (4 + 2 * ((ns + 1) & ~1)) + K3_RING_BYTES;
+}
 constexpr int k3_ns(int kq) {  // sub-tiles per query group
   int ns = 16;
   while (ns > 1 && k3_lds_bytes(ns, kq) > K3_LDS) ns--;
   return ns;
 }
+static_assert(K3_NW != 16 || k3_ns(10) == 12, "the bench's plan <5, 4> keeps its 12 sub-tiles per group beside the ring");
 constexpr int k3_ns_topk(int kq) { return k3_ns(kq) > 1 ? k3_ns(kq) - 1 : 1; }  // collection mode: one fewer pays for the ladder's counters
 
 // ------------------------------------------------------------------------------------------------------------------ arguments
@@ -177,7 +187,11 @@ enum K3Stat {
   K3S_GUARD = 27,          // consume: a tile index or a segment out of range (0: none)
   K3S_POPPED = 28,         // entries the waves took off their lists: short of K3S_LISTED by what the stops left behind
   K3S_STOPPED = 29,        // blocks the first chunk stopped
-  K3S_COUNT = 30
+  K3S_NOSURV = 30,         // popped tiles none of whose blocks got past its first-chunk look
+  K3S_PUSHED = 31,         // survivor entries pushed to the ring: tiles with a block past its look, loaded whole by whoever took the entry
+  K3S_RINGFULL = 32,       // ... and those the queue turned away (the ring full, or the tail lost to another wave's push): the looker ran their chains itself
+  K3S_WHOLE = 33,          // chain tasks run: tiles loaded whole (= pushed + turned away: the queue loses and doubles nothing)
+  K3S_COUNT = 34
 };
 enum K3SeedStat { K3SEED_BLOCKS = 0, K3SEED_TILES = 1, K3SEED_PAIRS = 2, K3SEED_WORDS = 4 };  // a stripe of the seed kernel's counters (the fourth word is spare)
 struct K3Counters {
@@ -186,7 +200,7 @@ struct K3Counters {
   unsigned long long seed[64][K3SEED_WORDS];  // the seed kernel's, striped by workgroup
   unsigned *tickets() { return reinterpret_cast<unsigned *>(stats + K3S_TICKETS); }
 };
-static_assert(offsetof(K3Counters, stats) == 16 && offsetof(K3Counters, seed) == 256 && sizeof(K3Counters) == 2304, "the counter block's layout");
+static_assert(offsetof(K3Counters, stats) == 16 && offsetof(K3Counters, seed) == 288 && sizeof(K3Counters) == 2336, "the counter block's layout");
 
 // ------------------------------------------------------------------------------------------------------------------ launches
 // one per HT, defined in tm_knn3_k<HT>.hip (tm_knn3_kernels.h)

@@ -202,9 +202,10 @@ __device__ __forceinline__ void k3_load_tile_masked(const uint8_t *tb, int lane,
 }
 
 // ... in two parts for the first-chunk look (k3_chunk_look): chunk 0's low and high digits and row r = lane & 31's term over the chunk's
-// columns (`rowp`; behind the tile's box in the pack) are all the look reads; the other nine KB and the full row terms are asked for right behind
-// them, so that the look need not wait for them.  (Asked for only when a block of the tile gets past its look, as a phase of its own in front of
-// the block loop: 127 registers, 136 bytes of scratch, 12.5 against 8.2 ms -- DESIGN 23.)
+// columns (`rowp`; behind the tile's box in the pack) are all the look reads, and all k_knn_consume's look task asks for.  The rest of the
+// tile is loaded by the chain task (k3_load_tile_masked, the whole tile again) when a block got past its look, which on the bench clip is one
+// popped tile in nine.  (The same loads as a phase of the one block loop, look and chain registers live together: 127 registers,
+// 136 bytes of scratch, 12.5 against 8.2 ms -- DESIGN 23.)
 template <int KT>
 __device__ __forceinline__ void k3_load_tile_chunk0(const uint8_t *tb, int lane, unsigned tm, v4i (&T)[KT], unsigned &rowp) {
   T[0] = *reinterpret_cast<const v4i *>(tb + lane * 16);
@@ -214,18 +215,6 @@ __device__ __forceinline__ void k3_load_tile_chunk0(const uint8_t *tb, int lane,
   }
   rowp = *reinterpret_cast<const unsigned *>(tb + knn_pack_first_terms(KT, 1) + (lane & 31) * 4);
 }
-template <int KT>
-__device__ __forceinline__ void k3_load_tile_rest(const uint8_t *tb, int lane, int half, unsigned tm, v4i (&T)[KT], v16i &cin, unsigned &pwh) {
-#pragma unroll
-  for (int kc = 1; kc < 6; kc++) T[kc] = *reinterpret_cast<const v4i *>(tb + (kc * 64 + lane) * 16);
-#pragma unroll
-  for (int kc = 7; kc < KT; kc++) {
-    T[kc] = v4i{0, 0, 0, 0};
-    if ((tm >> (kc - 6)) & 1u) T[kc] = *reinterpret_cast<const v4i *>(tb + (kc * 64 + lane) * 16);
-  }
-  k3_load_rows<KT>(tb, half, cin, pwh);
-}
-
 // the minimum of the chain's sixteen values of a lane: a tree of three-way minima (five, two, one: eight instructions; pairs first cost ten)
 __device__ __forceinline__ int k3_min3(int a, int b, int c) { return min(min(a, b), c); }
 __device__ __forceinline__ int k3_min16(const int (&t)[16]) {
@@ -311,6 +300,68 @@ __device__ __forceinline__ bool k3_chunk_look(const v4i (&T)[6 + HT], const uint
   const unsigned qnp = (unsigned)*qnp_p;  // (asked for behind the shifts: a register fewer across them)
   const unsigned look = (unsigned)k3_first_look<TD>(acc) + qnp;  // the SSD over the chunk (without TD: at most one below it, -1 at the least)
   return k3_within<TD>(look, bound);
+}
+// Two blocks of one tile judged at once: sub-tiles A and B (`qa`, `qb`: their operands) against the same chunk 0 and the same row terms,
+// k3_chunk_look's arithmetic for each.  A look is one chain of dependent steps -- operand read, product, shift, product ... minimum -- and a
+// wave that looks (k_knn_consume's look task) holds so little of the tile that a second accumulator fits: the two chains stand in ONE
+// basic block and each fills the other's waits.  For that the products run whatever the masks say: a chunk its mask calls empty is all
+// zeros, the tile's by k3_load_tile_chunk0 and the queries' in the pack, so the product adds nothing and the values are k3_chunk_look's.
+template <int HT, int HQ, bool TD>
+__device__ __forceinline__ void k3_chunk_look2(const v4i (&T)[6 + HT], const uint8_t *rows, int half, const uint8_t *qa, const uint8_t *qb, const int *qnpa_p,
+                                               const int *qnpb_p, unsigned bounda, unsigned boundb, bool &ina, bool &inb) {
+  constexpr int HM = HT < HQ ? HT : HQ;
+  const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  auto opd = [](const uint8_t *q, int kc) { return *reinterpret_cast<const v4i *>(q + kc * 1024); };
+  auto term = [&](int q4) { return *reinterpret_cast<const v4i *>(rows + (q4 * 8 + half * 4) * 4); };  // (k3_load_rows' order)
+  const v4i la = opd(qa, 0), lb = opd(qb, 0);  // Q_L0 of either sub-tile
+  const v4i r0 = term(0), r1 = term(1), r2 = term(2), r3 = term(3);
+  v16i a, b;
+  if constexpr (HT + HQ > 0) {
+    if constexpr (HM > 0) {
+      const v4i ha = opd(qa, 6), hb = opd(qb, 6);  // Q_H0
+      a = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[6], ha, zero, 0, 0, 0);
+      b = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[6], hb, zero, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 16; r++) a[r] = (int)((unsigned)a[r] << 8);
+      a = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[6], la, a, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 16; r++) b[r] = (int)((unsigned)b[r] << 8);
+      b = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[6], lb, b, 0, 0, 0);
+      a = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[0], ha, a, 0, 0, 0);
+      b = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[0], hb, b, 0, 0, 0);
+    } else if constexpr (HT > 0) {  // no high digits on the query side: T_H0 . Q_L0
+      a = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[6], la, zero, 0, 0, 0);
+      b = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[6], lb, zero, 0, 0, 0);
+    } else {  // none on the database side: T_L0 . Q_H0
+      a = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[0], opd(qa, 6), zero, 0, 0, 0);
+      b = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[0], opd(qb, 6), zero, 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      a[i] = (int)(((unsigned)a[i] << 8) + (unsigned)r0[i]); a[4 + i] = (int)(((unsigned)a[4 + i] << 8) + (unsigned)r1[i]);
+      a[8 + i] = (int)(((unsigned)a[8 + i] << 8) + (unsigned)r2[i]); a[12 + i] = (int)(((unsigned)a[12 + i] << 8) + (unsigned)r3[i]);
+    }
+    a = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[0], la, a, 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      b[i] = (int)(((unsigned)b[i] << 8) + (unsigned)r0[i]); b[4 + i] = (int)(((unsigned)b[4 + i] << 8) + (unsigned)r1[i]);
+      b[8 + i] = (int)(((unsigned)b[8 + i] << 8) + (unsigned)r2[i]); b[12 + i] = (int)(((unsigned)b[12 + i] << 8) + (unsigned)r3[i]);
+    }
+    b = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[0], lb, b, 0, 0, 0);
+  } else {
+    v16i c;
+#pragma unroll
+    for (int i = 0; i < 4; i++) { c[i] = r0[i]; c[4 + i] = r1[i]; c[8 + i] = r2[i]; c[12 + i] = r3[i]; }
+    a = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[0], la, c, 0, 0, 0);
+    b = __builtin_amdgcn_mfma_i32_32x32x32_i8(T[0], lb, c, 0, 0, 0);
+  }
+  const unsigned qnpa = (unsigned)*qnpa_p, qnpb = (unsigned)*qnpb_p;
+  ina = k3_within<TD>((unsigned)k3_first_look<TD>(a) + qnpa, bounda);
+  inb = k3_within<TD>((unsigned)k3_first_look<TD>(b) + qnpb, boundb);
+}
+template <int HT, int HQ>
+__device__ __forceinline__ constexpr int k3_chunk_look2_products() {  // ... of either block
+  return HT + HQ == 0 ? 1 : ((HT < HQ ? HT : HQ) > 0 ? 4 : 2);
 }
 // matrix instructions k3_chunk_look issues for a block with these masks
 template <int HT, int HQ>
@@ -407,6 +458,47 @@ __device__ __forceinline__ unsigned k3_tile_idx_staged(const unsigned *p) {
                : "v"((unsigned)(size_t)(const __attribute__((address_space(3))) unsigned *)p)
                : "memory");
   return v;
+}
+
+// The survivor queue of k_knn_consume: a ring of K3_RING entries in LDS between the waves that look and the waves that run
+// chains.  An entry is one 64-bit word, (ticket + 1) << 32 | list index << 16 | mask of the sub-tiles whose looks the tile got past (never
+// empty: no entry's low word is 0); `head` and `tail` count the tickets taken and handed out and only grow.  A pusher claims ticket t by a
+// compare-and-swap on the tail while t - head < K3_RING -- the slot's last tenant, ticket t - K3_RING, is then taken, and whoever took it
+// read it before the swap that took it -- and writes the word with one store.  A popper reads the head h and the slot's word, and takes the
+// entry by a compare-and-swap on the head only if the word carries ticket h: a slot not yet written, or written for another lap, reads as
+// an empty queue, and a swap that fails (another wave was faster; the slot may have a new tenant by now) leaves the word read unused.
+// NOBODY WAITS FOR ANOTHER WAVE.  A push is tried once: a full ring, or a tail another wave moved first, turns the entry away, and the
+// pusher runs its chains itself, which costs nothing (it would as likely have popped the entry itself).  A pop is tried again only while
+// an entry stands READY at the head -- every failed swap is another wave's entry taken, so the tries end with the entries (and at
+// K3_RING_TRIES whatever happens); what a popper missed is picked up behind the segment's barrier.  Lane 0 acts, every lane gets the answer.
+__device__ __forceinline__ unsigned k3_surv_make(int j, unsigned surv) { return ((unsigned)j << 16) | surv; }
+__device__ __forceinline__ unsigned k3_surv_entry(unsigned e) { return e >> 16; }
+__device__ __forceinline__ unsigned k3_surv_mask(unsigned e) { return e & 0xFFFFu; }
+static_assert(K3_LCAP <= 1 << 16 && (K3_RING & (K3_RING - 1)) == 0, "a survivor entry's fields; the ring's slots by a mask");
+constexpr int K3_RING_TRIES = 64;
+__device__ __forceinline__ bool k3_ring_push(unsigned long long *ring, int *head, int *tail, unsigned e, int lane) {
+  int ok = 0;
+  if (lane == 0) {
+    const unsigned t = k3_peek(reinterpret_cast<unsigned *>(tail)), h = k3_peek(reinterpret_cast<unsigned *>(head));
+    // (t - h >= K3_RING: full -- or the two reads straddled other waves' work, which is taken for full)
+    if (t - h < (unsigned)K3_RING && atomicCAS(reinterpret_cast<unsigned *>(tail), t, t + 1u) == t) {
+      __hip_atomic_store(&ring[t & (K3_RING - 1)], ((unsigned long long)(t + 1u) << 32) | e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      ok = 1;
+    }
+  }
+  return __builtin_amdgcn_readfirstlane(ok) != 0;
+}
+__device__ __forceinline__ unsigned k3_ring_pop(const unsigned long long *ring, int *head, int lane) {  // 0: nothing ready
+  unsigned got = 0;
+  if (lane == 0) {
+    for (int tries = 0; tries < K3_RING_TRIES && !got; tries++) {
+      const unsigned h = k3_peek(reinterpret_cast<unsigned *>(head));
+      const unsigned long long w = __hip_atomic_load(&ring[h & (K3_RING - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if ((unsigned)(w >> 32) != h + 1u) break;  // empty, or claimed and not yet written
+      if (atomicCAS(reinterpret_cast<unsigned *>(head), h, h + 1u) == h) got = (unsigned)w;
+    }
+  }
+  return (unsigned)__builtin_amdgcn_readfirstlane((int)got);
 }
 
 // A block's epilogue: the row minimum of each query (lane & 31; the two half-waves hold 16 rows each) against its running best in LDS.

@@ -287,6 +287,13 @@ class KnnIndex:
         check(lib().tm_knn_index_last_chunk_counts(ctypes.c_void_p(self.h), ctypes.byref(looked), ctypes.byref(stopped)))
         return looked.value, stopped.value
 
+    def last_survivor_counts(self):
+        """(tiles popped, those with no block past its look, survivor entries queued, entries the full queue turned away, tiles loaded
+        whole, blocks run to completion) of the last search's consume kernel"""
+        v = [ctypes.c_int64() for _ in range(6)]
+        check(lib().tm_knn_index_last_survivor_counts(ctypes.c_void_p(self.h), *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def row_order(self):
         """the database's row order as the scan sees it (numpy uint32 [nt]; tile t = rows [32 t, 32 t + 32)), after a search"""
         out = np.empty((self.db.shape[0],), dtype=np.uint32)
