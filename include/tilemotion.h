@@ -605,6 +605,77 @@ TM_API int tm_set_jpeg_decode(tm_encoder *, int where /* TM_PNG_DECODE_* */);
 TM_API int tm_get_jpeg_decode(tm_encoder *, int *where);
 TM_API int tm_set_frames_jpeg(tm_encoder *, const void *const *files, const size_t *sizes, int nframes, double fps);
 TM_API int tm_probe_jpeg_clip_host(const void *const *files, const size_t *sizes, int nframes, double fps, int *width, int *height);
+/* ---- GIF input on the device (the rule: tiler_amd/csrc/tm_gif.h).
+ *   An existing file that starts with GIF87a / GIF89a is an animated GIF for tm_open_input / tm_probe_input_host (kind TM_INPUT_GIF): the
+ * size is the logical screen's, the rate the file's, StartFrame and FrameCount apply (the frames before StartFrame are decoded and
+ * composited, not delivered), the key frames follow the automatic rule, Scaling != 1 is TM_E_UNSUPPORTED.
+ *   The container walk (host) refuses before anything is decoded: TM_E_UNSUPPORTED for a file without the signature or of 4 GiB or more;
+ * TM_E_IO for a block or sub-block that runs past the end of the file, an unknown block introducer, a file with no image, a screen or a
+ * rectangle of width or height 0, a minimum code size outside 2..8 (1 is refused, not read as 2: Pillow reads such a file with a
+ * two-symbol alphabet at two bits, so data written for 2 comes out differently there and there is no one reading to agree with), an
+ * image with neither a local nor a global colour table.  Graphic
+ * control (disposal, transparent index, delay; for the next image only) and the NETSCAPE2.0 loop count are read; every other extension is
+ * skipped sub-block by sub-block; what follows the trailer is ignored; a file that ends without a trailer behind a whole image is read.
+ *   LZW: codes LSB first from min + 1 bits, clear = 1 << min, eoi = clear + 1, first free entry clear + 2, wider when the next free entry
+ * reaches 1 << width, up to 12; a full table goes on at 12 bits and adds nothing; a clear resets; the code behind a clear adds no entry; a
+ * missing initial clear is accepted; decoding stops at w x h indices (eoi is not required, what follows is not looked at).  Per image:
+ * TM_GIF_TRUNCATED (the data or an eoi ends it early), TM_GIF_BAD_CODE (a code above the next free entry, or a non-literal behind a clear).
+ * TM_GIF_BAD_DESC is the kernel's refusal of a descriptor that points outside what the launch was given; the entry points never make one.
+ *   Frames: the canvas is the logical screen, filled with bg = the caller's colour, else the global table's entry at the background index
+ * when that index lies in the table, else 0x000000.  Before frame i > 0 the rectangle of frame i - 1 (clipped to the screen) is set to bg
+ * (disposal 2) or to what the canvas held before frame i - 1 was drawn (disposal 3); any other disposal leaves it.  Then frame i's
+ * indices other than its transparent index are drawn through its local table, else the global one (an index past the table: 0x000000);
+ * a rectangle that leaves the screen is clipped; interlaced rows are stored in the four-pass order.  The canvas is the frame, 0x00RRGGBB.
+ *   Rate: a delay (1/100 s) of 0 or 1 counts as 10; fps = 100 n / sum of the delays of all n frames; uniform_delay: all equal.  Frames are
+ * never repeated or dropped.
+ *   tm_probe_gif_host / tm_gif_frames_host: the walk alone (no device); *nframes is the file's count, at most cap entries are written.
+ *   tm_gif_lzw_streams_host / tm_stage_gif_lzw: the LZW rule on a batch.  Stream s reads the sub-block chain (length bytes included) at
+ * [src_off, src_off + src_bytes) of blob (HOST) and writes at most npix indices at dst_off of dst (HOST / DEVICE); the end of the span ends
+ * the data like a terminator.  TM_E_INVAL for a stream outside blob or dst or a min_code_size outside 2..8; otherwise TM_OK and a status
+ * per stream: {code, payload bytes of the codes read, indices written}.  A refused stream writes only inside its own npix.
+ *   tm_gif_decode_host / tm_stage_gif_decode: frames [first, first + count) of a file in HOST memory as [count] frames of frame_px pixels in
+ * HOST / DEVICE memory; background -1: the file's.  status: first + count entries (HOST), one per image from image 0 on.  The walk's
+ * refusals fail the call; otherwise TM_OK, and nothing is delivered from the first image with a status on.  The device form goes chunk by
+ * chunk (TM_INPUT_CHUNK_FRAMES images, otherwise what 1 GiB of stored indices holds); where the chunks end changes no byte.
+ *   tm_set_frames_gif: one GIF file LENT in host memory until the next Load has returned; fps <= 0: the file's.  Scaling, StartFrame and
+ * FrameCount do not apply.  tm_probe_gif_clip_host: its refusals, size, frames and rate with no device.
+ *   tm_set_gif_decode: where Load decodes (TM_PNG_DECODE_*; TM_GIF_DECODE=host|device overrides).  HOST: the reader threads run the LZW
+ * image by image, the frames are composited on the host and the RGB32 clip is uploaded.  DEVICE: the file and a descriptor per chunk go up,
+ * k_gif_lzw (a wave per image) and k_gif_compose (a lane per four canvas pixels) write the encoder's clip.  AUTO is DEVICE.  Measured on
+ * two clips of 480 x 270 x 120 written by Pillow, OpenInput + Load from a memory-backed directory, median of 7 passes (range): the bench
+ * clip in 256 colours 24.4 ms (24.3 - 25.0) on the device against 32.8 ms (31.7 - 35.6) on the host, a flat 16-colour one 2.19 ms (2.16 -
+ * 2.24) against 24.5 ms (24.3 - 24.7); the ranges meet on neither.
+ * tm_set_gif_background: -1 (the file's) or 0x00RRGGBB.  tm_get_input_stats reports kind 16 for a file and 20 for a lent file. */
+enum { TM_GIF_TRUNCATED = 64, TM_GIF_BAD_CODE = 65, TM_GIF_BAD_DESC = 66 };
+enum { TM_INPUT_GIF = 16 };
+typedef struct tm_gif_info {
+  int32_t width, height, frames, uniform_delay, loop_count /* -1: no loop extension */, global_table_size, background_index, version /* 87, 89 */;
+  uint32_t background; /* resolved, 0x00RRGGBB */
+  int32_t reserved;
+  double fps;
+} tm_gif_info;
+typedef struct tm_gif_frame {
+  int32_t left, top, width, height, delay /* 1/100 s, as stored */, disposal, transparent /* index, or -1 */, interlaced;
+  int32_t table_size, local_table /* 1: its own table */, min_code_size, reserved;
+  uint64_t data_off, data_bytes; /* the sub-block chain in the file, terminator included */
+} tm_gif_frame;
+typedef struct tm_gif_stream { uint64_t src_off, dst_off; uint32_t src_bytes, npix, min_code_size, reserved; } tm_gif_stream;
+typedef struct tm_gif_status { int32_t code; uint32_t in_pos, out_n; } tm_gif_status;
+TM_API int tm_probe_gif_host(const void *file, size_t size, tm_gif_info *out);
+TM_API int tm_gif_frames_host(const void *file, size_t size, tm_gif_frame *out, int cap, int *nframes);
+TM_API int tm_gif_lzw_streams_host(const uint8_t *blob, size_t blob_bytes, const tm_gif_stream *streams, int nstreams, uint8_t *dst, size_t dst_bytes, tm_gif_status *status);
+TM_API int tm_stage_gif_lzw(const uint8_t *blob, size_t blob_bytes, const tm_gif_stream *streams, int nstreams, uint8_t *dev_dst, size_t dst_bytes,
+                            tm_gif_status *status /* host */, void *stream);
+TM_API int tm_gif_decode_host(const void *file, size_t size, int first, int count, int background /* -1: the file's */, uint32_t *out, int64_t frame_px,
+                              int32_t *status /* first + count */);
+TM_API int tm_stage_gif_decode(const void *file, size_t size, int first, int count, int background, uint32_t *dev_out, int64_t frame_px,
+                               int32_t *status /* first + count, host */, void *stream);
+TM_API int tm_set_gif_decode(tm_encoder *, int where /* TM_PNG_DECODE_* */);
+TM_API int tm_get_gif_decode(tm_encoder *, int *where);
+TM_API int tm_set_gif_background(tm_encoder *, int background /* -1, or 0x00RRGGBB */);
+TM_API int tm_get_gif_background(tm_encoder *, int *background);
+TM_API int tm_set_frames_gif(tm_encoder *, const void *file, size_t size, double fps /* <= 0: the file's */);
+TM_API int tm_probe_gif_clip_host(const void *file, size_t size, double fps, int *width, int *height, int *frames, double *out_fps);
 /* ---- JPEG export on the device: forward DCT and Huffman coding; MJPEG (tm_jpeg_out.hip; the rule: tm_jpeg_out.h) ----
  * The input's mirror image.  The files are libjpeg's baseline files byte for byte: quantisers = the Annex K.1 tables scaled by quality
  * (scale = q < 50 ? 5000 / q : 200 - 2 q; clamp((base scale + 50) / 100, 1, 255)); JFIF's YCbCr in 16-bit fixed point; chroma box-averaged

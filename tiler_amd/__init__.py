@@ -8,3 +8,4 @@ importing works anywhere, calling a compute entry point without the library or a
 from ._lib import lib, TileMotionError, lib_path, check  # noqa: F401
 from . import stages  # noqa: F401
 from .player import GtmPlayer  # noqa: F401
+from .stages import probe_gif, gif_frames  # noqa: F401

@@ -80,6 +80,25 @@ class JpegExportStatsDesc(ctypes.Structure):  # tm_jpeg_export_stats
                 ("reserved", ctypes.c_int32), ("ms_device", c_double), ("ms_write", c_double), ("ms_wall", c_double)]
 
 
+class GifInfoDesc(ctypes.Structure):  # tm_gif_info
+    _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "frames", "uniform_delay", "loop_count", "global_table_size", "background_index", "version")] + [
+        ("background", ctypes.c_uint32), ("reserved", ctypes.c_int32), ("fps", c_double)]
+
+
+class GifFrameDesc(ctypes.Structure):  # tm_gif_frame
+    _fields_ = [(n, ctypes.c_int32) for n in ("left", "top", "width", "height", "delay", "disposal", "transparent", "interlaced", "table_size", "local_table",
+                                              "min_code_size", "reserved")] + [("data_off", ctypes.c_uint64), ("data_bytes", ctypes.c_uint64)]
+
+
+class GifStreamDesc(ctypes.Structure):  # tm_gif_stream
+    _fields_ = [("src_off", ctypes.c_uint64), ("dst_off", ctypes.c_uint64), ("src_bytes", ctypes.c_uint32), ("npix", ctypes.c_uint32), ("min_code_size", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class GifStatusDesc(ctypes.Structure):  # tm_gif_status
+    _fields_ = [("code", ctypes.c_int32), ("in_pos", ctypes.c_uint32), ("out_n", ctypes.c_uint32)]
+
+
 PNG_DECODE = {"auto": 0, "host": 1, "device": 2}  # TM_PNG_DECODE_*
 
 RENDER_PAGES = {"input": 0, "output": 1, "tiles": 2}  # TM_RENDER_PAGE_*
@@ -200,6 +219,18 @@ SIGNATURES = {
     "tm_get_jpeg_decode": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "tm_set_frames_jpeg": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double]),
     "tm_probe_jpeg_clip_host": (c_int, [c_void_p, c_void_p, c_int, c_double, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "tm_probe_gif_host": (c_int, [c_void_p, ctypes.c_size_t, ctypes.POINTER(GifInfoDesc)]),
+    "tm_gif_frames_host": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "tm_gif_lzw_streams_host": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p]),
+    "tm_stage_gif_lzw": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, c_void_p]),
+    "tm_gif_decode_host": (c_int, [c_void_p, ctypes.c_size_t, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p]),
+    "tm_stage_gif_decode": (c_int, [c_void_p, ctypes.c_size_t, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
+    "tm_set_gif_decode": (c_int, [c_void_p, c_int]),
+    "tm_get_gif_decode": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "tm_set_gif_background": (c_int, [c_void_p, c_int]),
+    "tm_get_gif_background": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "tm_set_frames_gif": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_double]),
+    "tm_probe_gif_clip_host": (c_int, [c_void_p, ctypes.c_size_t, c_double, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_double)]),
     "tm_generate_jpegs": (c_int, [c_void_p, c_int]),
     "tm_generate_mjpeg": (c_int, [c_void_p, c_char_p, c_int]),
     "tm_set_jpeg_options": (c_int, [c_void_p, ctypes.POINTER(JpegOptions)]),

@@ -62,6 +62,7 @@ struct Knobs {
   int recon_chunk_frames = 0;  // TM_RECON_CHUNK_FRAMES: frames per chunk of Reconstruct's query features (0: 8 GiB worth, 2 GiB with the extended palette usage; tests: small, so that a clip takes several chunks)
   bool player_no_worker = false;  // TM_PLAYER_NO_WORKER: the player decodes the next key frame on the calling thread, when the last one has been played
   int player_chunk_frames = 0;    // TM_PLAYER_CHUNK_FRAMES: frames per chunk of the player's record upload (0: 8 MB worth, at most 16)
+  int gif_decode = 0;  // TM_GIF_DECODE=host|device: the same for a GIF input and tm_set_gif_decode
   int jpeg_decode = 0; // TM_JPEG_DECODE=host|device: the same for a JPEG input and tm_set_jpeg_decode
   int png_decode = 0;  // TM_PNG_DECODE=host|device: where a PNG input is decoded, whatever tm_set_png_decode said (0: not set; else TM_PNG_DECODE_*)
   int group_fail_shard = -1;  // TM_GROUP_FAIL_SHARD: that shard of a device group fails at the start of its next step (tests)

@@ -16,6 +16,7 @@ constexpr int INPUT_YUV_CLIP = 3;  // InputInfo::kind of a YUV clip lent in memo
 constexpr int INPUT_GTM = TM_INPUT_GTM;  // a .gtm stream: Load plays its frames into the device clip (tm_player.hip)
 constexpr int INPUT_RGB_CLIP = 5;  // an RGB clip lent in memory (tm_set_frames_rgb)
 constexpr int INPUT_PNG_CLIP = 6;  // PNG files lent in memory (tm_set_frames_png)
+constexpr int INPUT_GIF_CLIP = 20;  // one GIF file lent in memory (tm_set_frames_gif), beside TM_INPUT_GIF
 constexpr int INPUT_JPEG_CLIP = 12;  // JPEG files lent in memory (tm_set_frames_jpeg), beside TM_INPUT_JPEGS
 // JFIF's 4:2:2: chroma between the luma pairs.  A layout of chroma_geom for the JPEG reader's planes only: no public TM_CHROMA_* value,
 // and check_yuv_clip and the stage seams keep refusing it.
@@ -25,7 +26,7 @@ struct InputInfo {
   std::string name;
   tm_yuv_clip clip{};               // INPUT_YUV_CLIP: the descriptor as it was lent
   tm_rgb_clip rgb_clip{};           // INPUT_RGB_CLIP: the same
-  std::vector<const void *> png_files;  // INPUT_PNG_CLIP, INPUT_JPEG_CLIP: the files as they were lent
+  std::vector<const void *> png_files;  // INPUT_PNG_CLIP, INPUT_JPEG_CLIP, INPUT_GIF_CLIP (one file): the files as they were lent
   std::vector<size_t> png_sizes;
   int jpeg_segments = 0;            // JPEG inputs: the restart segments of the first file (what AUTO decides by)
   bool lent = false;                // the clip's memory is still borrowed: no Load has read it yet
@@ -40,6 +41,7 @@ struct InputInfo {
 // tm_input_probe.hip (host only)
 int probe_input(const std::string &name, int start_frame, int frame_count, double scaling, InputInfo *in);
 int format_pattern(const std::string &pat, int64_t i, std::string *out);  // Pascal's Format(pattern, [i])
+int read_whole(const std::string &name, std::vector<uint8_t> *out);         // a file's bytes
 int scaled_size(int w, int h, double scaling, int *dst_w, int *dst_h);    // Round(W * Scaling) x Round(H * Scaling); refuses an eightfold shrink
 
 // ---- files and staging

@@ -6,6 +6,7 @@
 
 #include "tm_gtm.h"
 #include "tm_input.h"
+#include "tm_gif.h"
 #include "tm_jpeg.h"
 
 namespace tmx {
@@ -155,7 +156,15 @@ static bool starts_with_soi(const std::string &name) {
   fclose(f);
   return n == 2 && m[0] == 0xff && m[1] == 0xd8;
 }
-static int read_whole(const std::string &name, std::vector<uint8_t> *out) {
+static bool starts_with_gif(const std::string &name) {
+  FILE *f = fopen(name.c_str(), "rb");
+  if (!f) return false;
+  char m[6] = {0};
+  const size_t n = fread(m, 1, 6, f);
+  fclose(f);
+  return n == 6 && (!memcmp(m, "GIF87a", 6) || !memcmp(m, "GIF89a", 6));
+}
+int read_whole(const std::string &name, std::vector<uint8_t> *out) {
   FILE *f = fopen(name.c_str(), "rb");
   TM_CHECK(f, TM_E_IO, "cannot open %s", name.c_str());
   struct Closer { FILE *f; ~Closer() { fclose(f); } } closer{f};
@@ -183,6 +192,17 @@ int probe_input(const std::string &name, int start_frame, int frame_count, doubl
     TM_TRY(frame_range(name, total, "frames", start_frame, frame_count, &in->frames));
     in->dst_w = in->src_w; in->dst_h = in->src_h;
     return TM_OK;
+  }
+  if (file_exists(name) && starts_with_gif(name)) {  // an animated GIF: its frames are decoded and composited into the clip (decode_gif, tm_input.hip)
+    TM_CHECK(scaling == 1.0, TM_E_UNSUPPORTED, "%s: Scaling %g with a GIF input (only Scaling = 1 is read)", name.c_str(), scaling);
+    std::vector<uint8_t> file;
+    TM_TRY(read_whole(name, &file));
+    gif::GifInfo info;
+    TM_TRY(gif::parse_gif(file.data(), file.size(), name.c_str(), &info));
+    in->kind = TM_INPUT_GIF;
+    in->chroma = TM_CHROMA_444;
+    in->src_w = in->dst_w = info.w; in->src_h = in->dst_h = info.h; in->fps = info.fps;
+    return frame_range(name, (int64_t)info.images.size(), "frames", start_frame, frame_count, &in->frames);
   }
   if (file_exists(name)) {
     TM_TRY(parse_y4m(name, in));

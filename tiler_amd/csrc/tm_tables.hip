@@ -169,6 +169,7 @@ void knobs_reload() {
   if (const char *v = getenv("TM_RECON_CHUNK_FRAMES")) k.recon_chunk_frames = std::max(0, atoi(v));
   k.player_no_worker = on("TM_PLAYER_NO_WORKER");
   if (const char *v = getenv("TM_PLAYER_CHUNK_FRAMES")) k.player_chunk_frames = std::max(0, atoi(v));
+  if (const char *v = getenv("TM_GIF_DECODE")) k.gif_decode = !strcmp(v, "device") ? TM_PNG_DECODE_DEVICE : !strcmp(v, "host") ? TM_PNG_DECODE_HOST : 0;
   if (const char *v = getenv("TM_JPEG_DECODE")) k.jpeg_decode = !strcmp(v, "device") ? TM_PNG_DECODE_DEVICE : !strcmp(v, "host") ? TM_PNG_DECODE_HOST : 0;
   if (const char *v = getenv("TM_PNG_DECODE")) k.png_decode = !strcmp(v, "device") ? TM_PNG_DECODE_DEVICE : !strcmp(v, "host") ? TM_PNG_DECODE_HOST : 0;
   t_knobs = k;

@@ -337,6 +337,43 @@ class TilingEncoder:
         check(self._L.tm_get_jpeg_decode(c_void_p(self._h), ctypes.byref(v)))
         return {n: k for k, n in PNG_DECODE.items()}[v.value]
 
+    def SetFramesGIF(self, data, fps=None):
+        """One animated GIF file lent in memory (tm_set_frames_gif): data = the file's bytes.  The size is the logical screen's, every
+        image is a frame (drawn over what the frames before it left, under its disposal rule), the rate is the file's unless fps is given.
+        Scaling, StartFrame and FrameCount do not apply; the key frames follow the automatic rule.  Decoded where SetGifDecode says.  The
+        file is borrowed (and kept alive here) until the Run that loads it has returned.  Returns VideoInfo()."""
+        data = bytes(data)
+        check(self._L.tm_set_frames_gif(c_void_p(self._h), data, len(data), float(fps) if fps else 0.0))
+        self._yuv_ref = [data]
+        return self.VideoInfo()
+
+    def SetGifDecode(self, where="auto"):
+        """Where the Load of a GIF file decodes (tm_set_gif_decode): "host" (the LZW on the reader threads, the frames composited on the
+        host, the RGB32 clip uploaded), "device" (the file's bytes uploaded, k_gif_lzw and k_gif_compose), "auto" (the device: DESIGN.md
+        section 42.3 has the measurement).  The environment variable TM_GIF_DECODE=host|device overrides."""
+        from ._lib import PNG_DECODE
+        if isinstance(where, str):
+            if where not in PNG_DECODE:
+                raise ValueError("unknown GIF decode place %r (one of %s)" % (where, " ".join(PNG_DECODE)))
+            where = PNG_DECODE[where]
+        check(self._L.tm_set_gif_decode(c_void_p(self._h), int(where)))
+
+    def GifDecode(self):
+        from ._lib import PNG_DECODE
+        v = c_int()
+        check(self._L.tm_get_gif_decode(c_void_p(self._h), ctypes.byref(v)))
+        return {n: k for k, n in PNG_DECODE.items()}[v.value]
+
+    def SetGifBackground(self, colour=None):
+        """The colour a GIF's canvas starts with and disposal 2 restores (tm_set_gif_background): 0x00RRGGBB, or None for the file's (the
+        global table's entry at the background index, else black)"""
+        check(self._L.tm_set_gif_background(c_void_p(self._h), -1 if colour is None else int(colour)))
+
+    def GifBackground(self):
+        v = c_int()
+        check(self._L.tm_get_gif_background(c_void_p(self._h), ctypes.byref(v)))
+        return None if v.value < 0 else v.value
+
     def SetPngDecode(self, where="auto"):
         """Where the Load of a PNG sequence or of lent PNG files decodes (tm_set_png_decode): "host" (the reader on host threads, the RGB32
         clip uploaded), "device" (the files' bytes uploaded, inflate and unfilter in kernels), "auto" (the device: DESIGN.md section 35 has the

@@ -723,3 +723,92 @@ def jpeg_encode_host(frames, quality=90, sampling="420", restart_rows=1, cap=Non
     nf, h, w = frames.shape
     return _jpeg_encode(lib().tm_jpeg_encode_host, ctypes.c_void_p(frames.ctypes.data), frames.strides[1] // 4, frames.strides[0] // 4, nf, w, h,
                         jpeg_options(quality, sampling, restart_rows), cap, guard, full, ())
+
+
+def probe_gif(file):
+    """What the container walk finds of one GIF file, with no device (tm_probe_gif_host): a dict of width, height, frames, uniform_delay,
+    loop_count (-1: none), global_table_size, background_index, version (87 / 89), background (resolved, 0x00RRGGBB) and fps.  The walk's
+    refusals raise."""
+    from ._lib import GifInfoDesc
+    info = GifInfoDesc()
+    buf = bytes(file)
+    check(lib().tm_probe_gif_host(buf, len(buf), ctypes.byref(info)))
+    return {name: getattr(info, name) for name, _ in GifInfoDesc._fields_ if name != "reserved"}
+
+
+def gif_frames(file):
+    """The images of one GIF file, with no device (tm_gif_frames_host): a list of dicts of left, top, width, height, delay (1/100 s, as
+    stored), disposal, transparent (index or -1), interlaced, table_size, local_table, min_code_size, data_off and data_bytes (the sub-block
+    chain in the file, terminator included)"""
+    from ._lib import GifFrameDesc
+    buf = bytes(file)
+    n = ctypes.c_int()
+    check(lib().tm_gif_frames_host(buf, len(buf), None, 0, ctypes.byref(n)))
+    out = (GifFrameDesc * max(n.value, 1))()
+    check(lib().tm_gif_frames_host(buf, len(buf), out, n.value, ctypes.byref(n)))
+    return [{name: getattr(out[i], name) for name, _ in GifFrameDesc._fields_ if name != "reserved"} for i in range(n.value)]
+
+
+def _gif_lzw(blob, streams, guard, host):
+    from ._lib import GifStreamDesc, GifStatusDesc
+    blob = bytes(blob)
+    n = len(streams)
+    desc = (GifStreamDesc * max(n, 1))()
+    at = guard
+    offs = []
+    for i, (src_off, src_bytes, min_code, npix) in enumerate(streams):
+        desc[i] = GifStreamDesc(int(src_off), at, int(src_bytes), int(npix), int(min_code), 0)
+        offs.append(at)
+        at += int(npix) + guard
+    total = max(at, 1)
+    status = (GifStatusDesc * max(n, 1))()
+    if host:
+        dst = np.full(total, 0xA5, np.uint8)
+        check(lib().tm_gif_lzw_streams_host(blob, len(blob), desc, n, dst.ctypes.data, total, status))
+    else:
+        dst = torch.full((total,), 0xA5, dtype=torch.uint8, device="cuda")
+        check(lib().tm_stage_gif_lzw(blob, len(blob), desc, n, _p(dst), total, status, _stream()))
+    return dst, [(status[i].code, status[i].in_pos, status[i].out_n) for i in range(n)], offs
+
+
+def gif_lzw(blob, streams, guard=64):
+    """A batch of GIF image data decoded on the device (tm_stage_gif_lzw: k_gif_lzw, a wave per stream, one launch).  blob: bytes; streams:
+    a list of (src_off, src_bytes, min_code_size, npix), the sub-block chain of each with its length bytes -> (a uint8 CUDA tensor filled
+    with 0xA5 before the launch, [(code, in_pos, out_n)] per stream, [dst_off] per stream): stream i's indices start at its dst_off, with
+    `guard` bytes before the first stream and behind every stream's npix."""
+    return _gif_lzw(blob, streams, int(guard), False)
+
+
+def gif_lzw_host(blob, streams, guard=64):
+    """gif_lzw's host twin (tm_gif_lzw_streams_host), no device: the same arguments and layout, a numpy array"""
+    return _gif_lzw(blob, streams, int(guard), True)
+
+
+def _gif_decode(file, first, count, background, frame_px, fill, host):
+    buf = bytes(file)
+    info = probe_gif(buf)
+    if count is None:
+        count = info["frames"] - first
+    px = info["width"] * info["height"]
+    frame_px = px if frame_px is None else int(frame_px)
+    status = (ctypes.c_int32 * max(first + count, 1))()
+    bg = -1 if background is None else int(background)
+    if host:
+        out = np.full((max(count, 1), frame_px), fill, np.uint32)
+        check(lib().tm_gif_decode_host(buf, len(buf), first, count, bg, out.ctypes.data, frame_px, status))
+    else:
+        out = torch.full((max(count, 1), frame_px), fill, dtype=torch.int32, device="cuda")
+        check(lib().tm_stage_gif_decode(buf, len(buf), first, count, bg, _p(out), frame_px, status, _stream()))
+    return out[:count, :px].reshape(count, info["height"], info["width"]), list(status[:first + count])
+
+
+def gif_decode(file, first=0, count=None, background=None, frame_px=None, fill=0x5A5A5A5A):
+    """Frames [first, first + count) of a GIF file in host memory decoded and composited on the device (tm_stage_gif_decode: k_gif_lzw and
+    k_gif_compose per chunk of images) -> (int32 CUDA tensor [count][height][width] of 0x00RRGGBB, filled with `fill` before the call, status
+    per image 0 .. first + count - 1).  background: None (the file's) or 0x00RRGGBB."""
+    return _gif_decode(file, int(first), count, background, frame_px, int(fill), False)
+
+
+def gif_decode_host(file, first=0, count=None, background=None, frame_px=None, fill=0x5A5A5A5A):
+    """gif_decode's host twin (tm_gif_decode_host), no device: the same arguments, a numpy uint32 array"""
+    return _gif_decode(file, int(first), count, background, frame_px, int(fill), True)

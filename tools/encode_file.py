@@ -1,8 +1,9 @@
 """A video file to a .gtm: python tools/encode_file.py IN OUT.gtm [--scaling S --start N --frames N --yuv auto|bt601|bt601-full|tiler|bt709|bt709-full]
                                                                [--raw-rgb LAYOUT --size WxH --fps F [--depth D]] [--pngs]
                                                                [--png-decode host|device] [--jpeg-decode host|device]
+                                                               [--gif-decode host|device] [--gif-background RRGGBB]
 
-IN is a Y4M file (`ffmpeg -i clip.mp4 -f yuv4mpegpipe clip.y4m`), a .gtm stream (its frames are played on the device and encoded again;
+IN is a Y4M file (`ffmpeg -i clip.mp4 -f yuv4mpegpipe clip.y4m`), an animated GIF (every image a frame, at the file's rate; --scaling must stay 1), a .gtm stream (its frames are played on the device and encoded again;
 --scaling must stay 1) or a Format pattern naming a PNG or baseline JPEG sequence (frame_%.4d.png, frame_%.4d.jpg; key frames where a frame_NNNN.kf file exists).
 With --raw-rgb IN is a headerless file of RGB frames such as `ffmpeg -i clip.mp4 -f rawvideo -pix_fmt rgb24 clip.rgb` writes (LAYOUT: rgb24,
 bgr24, rgba, bgra, argb, abgr, rgb48, bgr48, rgba64, bgra64, rgbp, gbrp, gray; --depth D > 8: rgbp / gbrp / gray hold little-endian words of
@@ -34,6 +35,8 @@ ap.add_argument("--depth", type=int, default=None, help="bits per sample of a --
 ap.add_argument("--pngs", action="store_true", help="also write the decoded frames as OUT_NNNN.png (deflate on the device)")
 ap.add_argument("--png-decode", choices=["host", "device"], default=None, help="where a PNG sequence is decoded")
 ap.add_argument("--jpeg-decode", choices=["host", "device"], default=None, help="where a JPEG sequence (frame_%%.4d.jpg) is decoded")
+ap.add_argument("--gif-decode", choices=["host", "device"], default=None, help="where an animated GIF is decoded")
+ap.add_argument("--gif-background", default=None, help="the canvas colour of a GIF, RRGGBB in hex (default: the file's background colour)")
 args = ap.parse_args()
 enc = TilingEncoder()
 enc.LoadDefaultSettings()
@@ -43,6 +46,10 @@ if args.png_decode:
     enc.SetPngDecode(args.png_decode)
 if args.jpeg_decode:
     enc.SetJpegDecode(args.jpeg_decode)
+if args.gif_decode:
+    enc.SetGifDecode(args.gif_decode)
+if args.gif_background:
+    enc.SetGifBackground(int(args.gif_background, 16))
 if args.raw_rgb:
     import numpy as np
     if not args.size or not args.fps:

@@ -1,6 +1,6 @@
 """Wall time of Load from a Y4M file against Load of the same clip as RGB32 in page-locked host memory, and of the same clip lent as YUV planes.
 
-    python tools/time_file_load.py [--mode file|host|both|yuv|rgb|png|jpeg|all] [--frames 300 --width 1280 --height 720] [--scaling 1.0] [--passes 7] [--dir /dev/shm]
+    python tools/time_file_load.py [--mode file|host|both|yuv|rgb|png|jpeg|gif|all] [--frames 300 --width 1280 --height 720] [--scaling 1.0] [--passes 7] [--dir /dev/shm]
 
 The clip is bench.py's (SURVEY.md 8d's generator).  `file`: it is written as a 4:2:0 Y4M into --dir (memory-backed by default, so that the
 figure is the pipeline's and not a disk's) and every pass is OpenInput + Run(esLoad).  `host`: the RGB32 clip sits in pinned memory and every
@@ -14,7 +14,10 @@ Pillow at its defaults and once by this library's level-1 export, and every pass
 =device; with --png-keep the sequences stay in --dir for the next call (an older build of the library, loaded with TM_LIB_VARIANT, reads them
 under `host` alone: --png-where host).  `jpeg` (not part of `all`): the clip is written into --dir by Pillow as a JPEG sequence (quality 90, 4:2:0), once
 without restart markers and once with an interval of one MCU row, and the passes alternate between TM_JPEG_DECODE=device and =host, every
-pass OpenInput + Run(esLoad); --jpeg-blocks N,M,... times sequences with restart intervals of N, M, ... MCUs instead.  One warm-up pass, then the median of --passes passes with their spread; one JSON line."""
+pass OpenInput + Run(esLoad); --jpeg-blocks N,M,... times sequences with restart intervals of N, M, ... MCUs instead.  `gif` (not part of `all`; meant for a GIF-like size such as --frames 120
+--width 480 --height 270): two animated GIFs are written into --dir by Pillow -- the clip in 256 colours, and a flat, cartoon-like one of the same
+size (plain areas, moving shapes, 16 colours) -- and the passes alternate between TM_GIF_DECODE=device and =host, every pass OpenInput + Run(esLoad).
+One warm-up pass, then the median of --passes passes with their spread; one JSON line."""
 import argparse
 import json
 import os
@@ -45,7 +48,7 @@ def stats(ms):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["file", "host", "both", "yuv", "rgb", "png", "jpeg", "all"], default="both")
+    ap.add_argument("--mode", choices=["file", "host", "both", "yuv", "rgb", "png", "jpeg", "gif", "all"], default="both")
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=720)
@@ -229,6 +232,48 @@ def main():
                 for n in names:
                     if os.path.exists(n):
                         os.remove(n)
+
+    if args.mode == "gif":
+        from PIL import Image
+        rgb = lambda fr: np.stack([(fr >> 16) & 255, (fr >> 8) & 255, fr & 255], -1).astype(np.uint8)  # noqa: E731
+        yy, xx = np.mgrid[0:H, 0:W]
+        cartoon = []
+        for i in range(F):  # plain areas and a few shapes that move: what a screen capture or a sprite sheet looks like
+            fr = np.where(yy < H // 2, 0x88CCEE, 0x55AA55).astype(np.int64)
+            for k in range(6):
+                cx, cy, r = (37 * k + (3 + k) * i) % W, (53 * k + (2 + k) * i) % H, 12 + 5 * k
+                fr[(xx - cx) ** 2 + (yy - cy) ** 2 < r * r] = (0xFF4040, 0xFFE040, 0x4040FF, 0xFFFFFF, 0x202020, 0xFF80C0)[k]
+            cartoon.append(fr)
+        for name, frames in (("bench_256", [clip[i] for i in range(F)]), ("cartoon_16", cartoon)):
+            path = os.path.join(args.dir, "time_gif_load_%s_%d_%dx%dx%d.gif" % (name, os.getpid(), W, H, F))
+            try:
+                ims = [Image.fromarray(rgb(fr), "RGB").quantize(256 if name == "bench_256" else 16, dither=Image.Dither.NONE) for fr in frames]
+                ims[0].save(path, "GIF", save_all=True, append_images=ims[1:], duration=40, loop=0)
+                leg = dict(file_bytes=os.path.getsize(path))
+                encs, ms, info = {}, {"device": [], "host": []}, None
+                for where in ms:
+                    encs[where] = TilingEncoder()
+                    encs[where].LoadDefaultSettings()
+                    encs[where].InputFileName = path
+                for p in range(args.passes + 1):
+                    for where in ms:  # alternating, so that a drift of the machine falls on both
+                        os.environ["TM_GIF_DECODE"] = where
+                        t0 = time.perf_counter()
+                        info = encs[where].OpenInput()
+                        encs[where].Run(S.esLoad)
+                        ms[where].append((time.perf_counter() - t0) * 1e3)
+                same = None
+                for where in ms:
+                    leg[where] = dict(stats(ms[where][1:]), video=info, input_stats=encs[where].InputStats())
+                    got = encs[where].RenderFrames(input=True, device=False)
+                    leg["same_frames"] = True if same is None else bool(np.array_equal(got, same))
+                    same = got
+                    encs[where].close()
+                out["load_gif_" + name] = leg
+            finally:
+                os.environ.pop("TM_GIF_DECODE", None)
+                if os.path.exists(path):
+                    os.remove(path)
 
     if args.mode in ("file", "both", "all"):
         path = os.path.join(args.dir, "time_file_load_%d.y4m" % os.getpid())
