@@ -726,6 +726,66 @@ TM_API int tm_stage_jpeg_encode(const uint32_t *dev_frames, int64_t stride_px, i
                                 uint8_t *host_out, int64_t cap, int64_t *offsets /* nframes + 1 */, void *stream);
 TM_API int tm_jpeg_encode_host(const uint32_t *frames, int64_t stride_px, int64_t frame_px, int nframes, int w, int h, const tm_jpeg_options *opt,
                                uint8_t *out, int64_t cap, int64_t *offsets /* nframes + 1 */);
+/* ---- GIF export on the device: colour tables, LZW coding in segments (tm_gif_out.hip; the rule: tm_gif_out.h) ----
+ * One animated GIF89a of the frames tm_generate_pngs writes.  A decoded frame is a paletted picture, so with PaletteCount x PaletteSize <=
+ * 256 the file is lossless.  No global table; NETSCAPE2.0 as `loop` says; per frame a graphic control (disposal 1, no transparency, the
+ * delay), an image descriptor with a local table of the next power of two >= the colours (at least 2, padded with black), the minimum
+ * code size max(2, bits of the table size), the data in sub-blocks of 255 and a last shorter one, a 0; the trailer.  The delay is delay_cs,
+ * or max(2, floor(100 / fps + 0.5)) (the reader and browsers take 0 and 1 as 10); above 65535: TM_E_INVAL.
+ *   diff 1: frame 0 whole, frame i the bounding box of the pixels whose 0x00RRGGBB differs from frame i - 1's, an unchanged frame the 1 x 1
+ * rectangle at (0, 0).  Table and indices per frame over the rectangle's pixels.  Exact (the distinct colours number <= max_colours): the
+ * distinct colours ascending, a pixel's index is its colour's rank, a reader shows the source.  Quantised (more colours under
+ * TM_GIF_COLOURS_AUTO, every frame under _QUANTISE; under _EXACT such a frame is TM_E_UNSUPPORTED): a median cut in integers over 15-bit
+ * cells (tm_gif_out.h states every tie), a pixel's index is its cell's box, no dithering.
+ *   LZW: the rectangle's indices in row order are cut into segments of segment_pixels; each is coded on its own from a clear (greedy longest
+ * match, an entry per code, a clear when the table fills), the clear that opens the next segment is written at the width its segment ended
+ * on, the last segment ends with eoi.  The file is a function of the pixels, the rate and the options alone: the device form (a wave per
+ * segment, every segment of a chunk of frames in one launch; the bits joined by a scan and a shifted copy) and the host twin write the same
+ * bytes, and where the chunks end changes no byte.
+ *   tm_set_gif_options: TM_E_INVAL for null, unknown colours, max_colours outside 2 .. 256, diff other than 0 / 1, segment_pixels other
+ * than 0 or >= 256, loop outside -1 .. 65535, delay_cs 1 or outside 0 .. 65535.  tm_generate_gif refuses what tm_generate_pngs refuses,
+ * before any file is opened, and in a device group reads shard 0.  tm_get_gif_export_stats: of the last tm_generate_gif.
+ *   tm_stage_gif_encode: nframes pictures [h][w] of 0x00RRGGBB in DEVICE memory as one file in HOST memory `out`; chunk_frames <= 0: the
+ * writer's own.  tm_gif_encode_host: the same from HOST frames with no device; canvas (or null): [nframes][h][w], what a reader shows.
+ * TM_E_INVAL before any device call: null pointers, options as above, w or h < 1, nframes < 1, strides shorter than a row / a frame, a
+ * delay above 65535; TM_E_UNSUPPORTED: a side above 65535, a frame above 2^28 pixels.  A cap too small is TM_E_INVAL with *bytes set to
+ * the bytes needed and `out` untouched; tm_gif_bound_host bounds any file of that shape.  stats may be null.
+ *   tm_stage_gif_lzw_pack / tm_gif_lzw_pack_host: n indices (DEVICE / HOST) below 1 << min_code as the payload before sub-blocks.
+ * tm_stage_gif_palettise / tm_gif_palettise_host: one frame as table (256 entries), colour count, exact-or-not and indices [h][w] (HOST). */
+enum { TM_GIF_COLOURS_AUTO = 0, TM_GIF_COLOURS_EXACT = 1, TM_GIF_COLOURS_QUANTISE = 2 };
+typedef struct tm_gif_options {
+  int32_t colours;        /* TM_GIF_COLOURS_* (default AUTO) */
+  int32_t max_colours;    /* 2 .. 256 (default 256) */
+  int32_t diff;           /* 0: whole frames; 1: the changed rectangle (default) */
+  int32_t segment_pixels; /* 0: one segment per image; else indices per segment, >= 256 (default 4096: DESIGN.md section 43.3) */
+  int32_t loop;           /* -1: no NETSCAPE block; 0: for ever (default); n: n times */
+  int32_t delay_cs;       /* 0: from the rate (default); else 1/100 s per frame */
+} tm_gif_options;
+typedef struct tm_gif_export_stats {
+  int64_t frames, frames_exact, frames_quantised, segments, file_bytes;
+  double ms_colours; /* rectangles, distinct colours and histograms on the device, their read-back */
+  double ms_tables;  /* the host: sorting, the median cut */
+  double ms_lzw;     /* mapping and coding, the bit counts' read-back */
+  double ms_emit;    /* joining the bits, the container, the bytes' read-back */
+  double ms_device;  /* render and all of the above */
+  double ms_write;   /* writing the file */
+  double ms_wall;    /* the whole call */
+} tm_gif_export_stats;
+TM_API int tm_set_gif_options(tm_encoder *, const tm_gif_options *opt);
+TM_API int tm_get_gif_options(tm_encoder *, tm_gif_options *opt);
+TM_API int tm_generate_gif(tm_encoder *, const char *path, int input);
+TM_API int tm_get_gif_export_stats(tm_encoder *, tm_gif_export_stats *out);
+TM_API int tm_gif_bound_host(int w, int h, int nframes, const tm_gif_options *opt, int64_t *bytes);
+TM_API int tm_stage_gif_encode(const uint32_t *dev_frames, int64_t stride_px, int64_t frame_px, int nframes, int w, int h, double fps, const tm_gif_options *opt,
+                               int chunk_frames, uint8_t *out, int64_t cap, int64_t *bytes, tm_gif_export_stats *stats, void *stream);
+TM_API int tm_gif_encode_host(const uint32_t *frames, int64_t stride_px, int64_t frame_px, int nframes, int w, int h, double fps, const tm_gif_options *opt,
+                              uint8_t *out, int64_t cap, int64_t *bytes, uint32_t *canvas, tm_gif_export_stats *stats);
+TM_API int tm_stage_gif_lzw_pack(const uint8_t *dev_indices, uint32_t n, int min_code, int segment_pixels, uint8_t *out, int64_t cap, int64_t *bytes, void *stream);
+TM_API int tm_gif_lzw_pack_host(const uint8_t *indices, uint32_t n, int min_code, int segment_pixels, uint8_t *out, int64_t cap, int64_t *bytes);
+TM_API int tm_stage_gif_palettise(const uint32_t *dev_frame, int64_t stride_px, int w, int h, const tm_gif_options *opt, uint32_t *table /* 256 */, int *colours,
+                                  int *exact, uint8_t *indices /* host, h * w */, void *stream);
+TM_API int tm_gif_palettise_host(const uint32_t *frame, int64_t stride_px, int w, int h, const tm_gif_options *opt, uint32_t *table /* 256 */, int *colours, int *exact,
+                                 uint8_t *indices /* h * w */);
 /* The same pictures rendered on the device (Render :3455-3640, Output tab with the constructor's defaults; or the Input tab: input != 0):
  * frames [first_frame, first_frame+frame_count) as [frame_count][tm_h*8][tm_w*8] uint32 0x00RRGGBB (the format frames are pushed in; the
  * input render is every pushed frame cropped to tm_w*8 x tm_h*8 with alpha 0).  A predicted item is frame f-1's output at its offset,

@@ -99,6 +99,27 @@ class GifStatusDesc(ctypes.Structure):  # tm_gif_status
     _fields_ = [("code", ctypes.c_int32), ("in_pos", ctypes.c_uint32), ("out_n", ctypes.c_uint32)]
 
 
+class GifOptions(ctypes.Structure):  # tm_gif_options
+    _fields_ = [(n, ctypes.c_int32) for n in ("colours", "max_colours", "diff", "segment_pixels", "loop", "delay_cs")]
+
+
+class GifExportStatsDesc(ctypes.Structure):  # tm_gif_export_stats
+    _fields_ = [(n, c_int64) for n in ("frames", "frames_exact", "frames_quantised", "segments", "file_bytes")] + [
+        (n, c_double) for n in ("ms_colours", "ms_tables", "ms_lzw", "ms_emit", "ms_device", "ms_write", "ms_wall")]
+
+
+GIF_COLOURS = {"auto": 0, "exact": 1, "quantise": 2}  # TM_GIF_COLOURS_*
+
+
+def gif_options(colours="auto", max_colours=256, diff=True, segment_pixels=4096, loop=0, delay_cs=0):
+    """tm_gif_options from the keywords SetGifOptions / stages.gif_encode take"""
+    if isinstance(colours, str):
+        if colours not in GIF_COLOURS:
+            raise ValueError("unknown GIF colours %r (one of %s)" % (colours, " ".join(GIF_COLOURS)))
+        colours = GIF_COLOURS[colours]
+    return GifOptions(int(colours), int(max_colours), int(diff), int(segment_pixels), int(loop), int(delay_cs))
+
+
 PNG_DECODE = {"auto": 0, "host": 1, "device": 2}  # TM_PNG_DECODE_*
 
 RENDER_PAGES = {"input": 0, "output": 1, "tiles": 2}  # TM_RENDER_PAGE_*
@@ -239,6 +260,20 @@ SIGNATURES = {
     "tm_jpeg_bound_host": (c_int, [c_int, c_int, ctypes.POINTER(JpegOptions), ctypes.POINTER(c_int64)]),
     "tm_jpeg_quant_tables_host": (c_int, [c_int, c_void_p, c_void_p]),
     "tm_stage_jpeg_encode": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, ctypes.POINTER(JpegOptions), c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    "tm_set_gif_options": (c_int, [c_void_p, ctypes.POINTER(GifOptions)]),
+    "tm_get_gif_options": (c_int, [c_void_p, ctypes.POINTER(GifOptions)]),
+    "tm_generate_gif": (c_int, [c_void_p, c_char_p, c_int]),
+    "tm_get_gif_export_stats": (c_int, [c_void_p, ctypes.POINTER(GifExportStatsDesc)]),
+    "tm_gif_bound_host": (c_int, [c_int, c_int, c_int, ctypes.POINTER(GifOptions), ctypes.POINTER(c_int64)]),
+    "tm_stage_gif_encode": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_double, ctypes.POINTER(GifOptions), c_int, c_void_p, c_int64,
+                                    ctypes.POINTER(c_int64), ctypes.POINTER(GifExportStatsDesc), c_void_p]),
+    "tm_gif_encode_host": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_double, ctypes.POINTER(GifOptions), c_void_p, c_int64, ctypes.POINTER(c_int64),
+                                   c_void_p, ctypes.POINTER(GifExportStatsDesc)]),
+    "tm_stage_gif_lzw_pack": (c_int, [c_void_p, ctypes.c_uint32, c_int, c_int, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    "tm_gif_lzw_pack_host": (c_int, [c_void_p, ctypes.c_uint32, c_int, c_int, c_void_p, c_int64, ctypes.POINTER(c_int64)]),
+    "tm_stage_gif_palettise": (c_int, [c_void_p, c_int64, c_int, c_int, ctypes.POINTER(GifOptions), c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p,
+                                       c_void_p]),
+    "tm_gif_palettise_host": (c_int, [c_void_p, c_int64, c_int, c_int, ctypes.POINTER(GifOptions), c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]),
     "tm_jpeg_encode_host": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, ctypes.POINTER(JpegOptions), c_void_p, c_int64, ctypes.POINTER(c_int64)]),
 }
 

@@ -104,6 +104,9 @@ struct tm_encoder {
   tm_jpeg_options jpeg_options{90, TM_JPEG_420, 1};    // what GenerateJPEGs / GenerateMJPEG write (tm_set_jpeg_options)
   tm_jpeg_export_stats jpeg_export_stats{};            // of the last of them (tm_get_jpeg_export_stats)
   bool has_jpeg_export_stats = false;
+  tm_gif_options gif_options{TM_GIF_COLOURS_AUTO, 256, 1, 4096, 0, 0};  // what GenerateGIF writes (tm_set_gif_options)
+  tm_gif_export_stats gif_export_stats{};                                // of the last GenerateGIF (tm_get_gif_export_stats)
+  bool has_gif_export_stats = false;
   int gif_decode = TM_PNG_DECODE_AUTO;  // where a GIF input is decoded (tm_set_gif_decode); TM_GIF_DECODE overrides
   int gif_background = -1;              // the canvas colour of a GIF input (tm_set_gif_background); -1: the file's
   int jpeg_decode = TM_PNG_DECODE_AUTO; // where a JPEG input is decoded (tm_set_jpeg_decode); TM_JPEG_DECODE overrides

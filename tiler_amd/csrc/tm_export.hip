@@ -6,6 +6,7 @@
 
 #include "tm_deflate.h"
 #include "tm_encoder.h"
+#include "tm_gif_out.h"
 #include "tm_gtm.h"
 #include "tm_jpeg_out.h"
 
@@ -259,7 +260,65 @@ static int generate_jpegs(tm_encoder *e, const char *path, bool input) {
   return TM_OK;
 }
 
+// GenerateGIF: the frames GeneratePNGs writes as one animated GIF, kept on the device a chunk at a time and coded
+// there (tm_gif_out.hip); only the file's bytes come back.  The file is opened once every chunk has been coded: a refused frame leaves none.
+static int generate_gif(tm_encoder *e, const char *path, bool input) {
+  TM_CHECK(path && *path, TM_E_INVAL, "GenerateGIF: no file name");
+  const auto wall0 = std::chrono::steady_clock::now();
+  const tm_gif_options opt = e->gif_options;
+  e->has_gif_export_stats = false;
+  ExportFrames r{e, input};
+  r.keep = true;
+  TM_TRY(r.init());
+  int delay;
+  TM_TRY(gfo::gif_out_check("GenerateGIF", r.dev.p, r.sw, (int64_t)r.sw * r.sh, e->nframes, r.sw, r.sh, e->fps, &opt, &delay));
+  std::vector<uint8_t> file;
+  gfo::GifDeviceEncoder encoder;  // (its device buffers serve every chunk)
+  TM_TRY(encoder.begin(r.sw, r.sh, e->fps, opt, e->stream, file));
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int fr = 0; fr < e->nframes; fr += r.count) {
+    TM_TRY(r.frame(fr, nullptr));
+    TM_TRY(encoder.chunk(r.dev.as<uint32_t>(), r.sw, (int64_t)r.sw * r.sh, r.count, file));
+  }
+  TM_TRY(encoder.end(file));
+  const auto t1 = std::chrono::steady_clock::now();
+  TM_TRY(write_file(path, file));
+  tm_gif_export_stats st = encoder.stats;
+  st.ms_device = std::chrono::duration<double, std::milli>(t1 - t0).count();
+  st.ms_write = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+  st.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  e->gif_export_stats = st;
+  e->has_gif_export_stats = true;
+  return TM_OK;
+}
+
 extern "C" {
+
+int tm_generate_gif(tm_encoder *e, const char *path, int input) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_CHECK(path, TM_E_INVAL, "GenerateGIF: no file name");
+  return generate_gif(e, path, input != 0);
+}
+
+int tm_set_gif_options(tm_encoder *e, const tm_gif_options *opt) {
+  TM_CHECK(e && opt, TM_E_INVAL, "null argument");
+  TM_TRY(gfo::gif_options_check("gif options", opt));
+  e->gif_options = *opt;
+  return TM_OK;
+}
+
+int tm_get_gif_options(tm_encoder *e, tm_gif_options *opt) {
+  TM_CHECK(e && opt, TM_E_INVAL, "null argument");
+  *opt = e->gif_options;
+  return TM_OK;
+}
+
+int tm_get_gif_export_stats(tm_encoder *e, tm_gif_export_stats *out) {
+  TM_CHECK(e && out, TM_E_INVAL, "null argument");
+  TM_CHECK(e->has_gif_export_stats, TM_E_INVAL, "gif export stats: this encoder has not written a GIF");
+  *out = e->gif_export_stats;
+  return TM_OK;
+}
 
 int tm_reload_gtm(tm_encoder *e, const char *path) {  // ReloadGTM, tilingencoder.pas:2059 -> LoadStream, 4880-5175
   TM_CHECK(e && path, TM_E_INVAL, "null argument");

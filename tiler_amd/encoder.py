@@ -591,6 +591,36 @@ class TilingEncoder:
         """The same files one behind another in `path` (tm_generate_mjpeg)"""
         check(self._L.tm_generate_mjpeg(c_void_p(self._h), os.fsencode(path), int(bool(input))))
 
+    def GenerateGIF(self, path, input=False):
+        """One animated GIF of the frames GeneratePNGs writes (tm_generate_gif), coded on the device as SetGifOptions says: lossless when
+        the frames hold at most 256 colours (PaletteCount x PaletteSize <= 256), quantised per frame otherwise"""
+        check(self._L.tm_generate_gif(c_void_p(self._h), os.fsencode(path), int(bool(input))))
+
+    def SetGifOptions(self, colours="auto", max_colours=256, diff=True, segment_pixels=4096, loop=0, delay_cs=0):
+        """How GenerateGIF writes from now on (tm_set_gif_options): colours "auto" (exact tables where a frame's colours fit, a median cut
+        where they do not), "exact" (refuse such a frame) or "quantise" (cut every frame); max_colours 2 .. 256; diff: code only the
+        rectangle that changed; segment_pixels: indices per separately coded LZW segment (0: one per image); loop: -1 none, 0 for ever, n
+        times; delay_cs: 1/100 s per frame (0: from the rate)"""
+        from ._lib import gif_options
+        check(self._L.tm_set_gif_options(c_void_p(self._h), ctypes.byref(gif_options(colours, max_colours, diff, segment_pixels, loop, delay_cs))))
+
+    def GifOptions(self):
+        from ._lib import GIF_COLOURS, GifOptions
+        opt = GifOptions()
+        check(self._L.tm_get_gif_options(c_void_p(self._h), ctypes.byref(opt)))
+        out = {name: getattr(opt, name) for name, _ in GifOptions._fields_}
+        out["colours"] = {v: k for k, v in GIF_COLOURS.items()}[opt.colours]
+        out["diff"] = bool(opt.diff)
+        return out
+
+    def GifExportStats(self):
+        """What the last GenerateGIF did (tm_get_gif_export_stats): frames, how many were coded exact and quantised, LZW segments, the
+        file's bytes, and milliseconds per stage"""
+        from ._lib import GifExportStatsDesc
+        st = GifExportStatsDesc()
+        check(self._L.tm_get_gif_export_stats(c_void_p(self._h), ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in GifExportStatsDesc._fields_}
+
     def SetJpegOptions(self, quality=90, sampling="420", restart_rows=1):
         """How GenerateJPEGs / GenerateMJPEG write from now on (tm_set_jpeg_options): quality 1 .. 100; sampling "420", "422", "444" or
         "grey"; restart_rows: 0 = no restart markers, n = one every n MCU rows (1, the default, is the file Load decodes on the device)"""

@@ -812,3 +812,110 @@ def gif_decode(file, first=0, count=None, background=None, frame_px=None, fill=0
 def gif_decode_host(file, first=0, count=None, background=None, frame_px=None, fill=0x5A5A5A5A):
     """gif_decode's host twin (tm_gif_decode_host), no device: the same arguments, a numpy uint32 array"""
     return _gif_decode(file, int(first), count, background, frame_px, int(fill), True)
+
+
+def _gif_stats(st):
+    from ._lib import GifExportStatsDesc
+    return {name: getattr(st, name) for name, _ in GifExportStatsDesc._fields_}
+
+
+def gif_bound(w, h, nframes, **options):
+    """An upper bound of a GIF file's size for any pixels (tm_gif_bound_host), no device; options: as gif_encode takes them"""
+    from ._lib import gif_options
+    opt = gif_options(**options)
+    bound = ctypes.c_int64()
+    check(lib().tm_gif_bound_host(int(w), int(h), int(nframes), ctypes.byref(opt), ctypes.byref(bound)))
+    return bound.value
+
+
+def _gif_encode(call, ptr, stride_px, frame_px, nf, w, h, fps, opt, cap, guard, full, extra_before, extra_after):
+    from ._lib import GifExportStatsDesc
+    if cap is None:
+        bound = ctypes.c_int64()
+        rc = lib().tm_gif_bound_host(w, h, max(nf, 1), ctypes.byref(opt), ctypes.byref(bound))
+        if rc != 0 and not full:
+            check(rc)
+        cap = bound.value if rc == 0 else 4096  # (what the bound refuses the call refuses too: any room will do)
+    buf = np.full(cap + 2 * guard, 0xA5, np.uint8)
+    need = ctypes.c_int64(-1)
+    st = GifExportStatsDesc()
+    rc = call(ptr, stride_px, frame_px, nf, w, h, float(fps), ctypes.byref(opt), *extra_before, ctypes.c_void_p(buf.ctypes.data + guard) if cap else None, cap,
+              ctypes.byref(need), *extra_after(st))
+    if not full:
+        check(rc)
+    file = buf[guard:guard + need.value].tobytes() if rc == 0 else None
+    return dict(rc=rc, file=file, buffer=buf, bytes=need.value, guard=guard, stats=_gif_stats(st)) if full else file
+
+
+def gif_encode(frames, fps, chunk_frames=0, cap=None, guard=0, full=False, **options):
+    """RGB32 frames on the device as one animated GIF (tm_stage_gif_encode; the rule: include/tilemotion.h): frames =
+    torch int32 CUDA tensor [F][H][W] of 0x00RRGGBB, rows and frames at any stride -> the file's bytes, byte for byte what
+    tm_gif_encode_host writes; only file bytes come to the host.  options: colours ("auto", "exact", "quantise"), max_colours, diff,
+    segment_pixels, loop, delay_cs.  chunk_frames: frames per trip through the device stages (0: the writer's own; no byte depends on
+    it).  cap: the room given (default: gif_bound); guard: bytes of 0xA5 kept before and behind that room; full=True: nothing raises, and the
+    result is a dict of rc, file (None when refused), buffer (guards included), bytes (the size, or the size needed), guard and stats."""
+    from ._lib import gif_options
+    assert frames.is_cuda and frames.dtype == torch.int32 and frames.dim() == 3 and (frames.shape[2] <= 1 or frames.stride(2) == 1)
+    nf, h, w = frames.shape
+    return _gif_encode(lib().tm_stage_gif_encode, _p(frames), frames.stride(1), frames.stride(0), nf, w, h, fps, gif_options(**options), cap, guard, full,
+                       (int(chunk_frames),), lambda st: (ctypes.byref(st), _stream()))
+
+
+def gif_encode_host(frames, fps, cap=None, guard=0, full=False, canvas=False, **options):
+    """gif_encode's host twin (tm_gif_encode_host), no device: frames = numpy uint32 or int32 array [F][H][W], rows and frames at any
+    stride (a multiple of 4 bytes; pixels contiguous).  canvas=True: -> (file, uint32 array [F][H][W] of what a reader shows)"""
+    from ._lib import gif_options
+    assert frames.dtype in (np.uint32, np.int32) and frames.ndim == 3 and (frames.shape[2] <= 1 or frames.strides[2] == 4)
+    nf, h, w = frames.shape
+    shown = np.zeros((max(nf, 1), h, w), np.uint32) if canvas else None
+    out = _gif_encode(lib().tm_gif_encode_host, ctypes.c_void_p(frames.ctypes.data), frames.strides[1] // 4, frames.strides[0] // 4, nf, w, h, fps, gif_options(**options),
+                      cap, guard, full, (), lambda st: (ctypes.c_void_p(shown.ctypes.data) if canvas else None, ctypes.byref(st)))
+    return (out, shown[:nf]) if canvas else out
+
+
+def _gif_lzw_pack(call, ptr, n, min_code, segment_pixels, extra):
+    nseg = -(-n // segment_pixels) if segment_pixels else 1
+    cap = 12 * (n + n // 4094 + 3 * nseg + 1) // 8 + 8  # every segment's bound (tm_gif_out.h)
+    buf = np.full(cap + 128, 0xA5, np.uint8)
+    need = ctypes.c_int64(-1)
+    check(call(ptr, n, int(min_code), int(segment_pixels), ctypes.c_void_p(buf.ctypes.data + 64), cap, ctypes.byref(need), *extra))
+    assert (buf[:64] == 0xA5).all() and (buf[64 + need.value:] == 0xA5).all()
+    return buf[64:64 + need.value].tobytes()
+
+
+def gif_lzw_pack(indices, min_code, segment_pixels=0):
+    """Indices on the device (a torch uint8 CUDA tensor, each below 1 << min_code) as GIF image data before sub-blocks
+    (tm_stage_gif_lzw_pack: k_gif_lzw_pack, a wave per segment, and k_gif_emit) -> bytes"""
+    assert indices.is_cuda and indices.dtype == torch.uint8 and indices.dim() == 1 and indices.is_contiguous()
+    return _gif_lzw_pack(lib().tm_stage_gif_lzw_pack, _p(indices), indices.numel(), min_code, segment_pixels, (_stream(),))
+
+
+def gif_lzw_pack_host(indices, min_code, segment_pixels=0):
+    """gif_lzw_pack's host twin (tm_gif_lzw_pack_host), no device: indices = a numpy uint8 array"""
+    indices = np.ascontiguousarray(indices, np.uint8).reshape(-1)
+    return _gif_lzw_pack(lib().tm_gif_lzw_pack_host, ctypes.c_void_p(indices.ctypes.data), indices.size, min_code, segment_pixels, ())
+
+
+def _gif_palettise(call, ptr, stride_px, w, h, opt, extra):
+    table = np.zeros(256, np.uint32)
+    idx = np.zeros((h, w), np.uint8)
+    ncol, exact = ctypes.c_int(), ctypes.c_int()
+    check(call(ptr, stride_px, w, h, ctypes.byref(opt), ctypes.c_void_p(table.ctypes.data), ctypes.byref(ncol), ctypes.byref(exact), ctypes.c_void_p(idx.ctypes.data), *extra))
+    return table[:ncol.value].copy(), bool(exact.value), idx
+
+
+def gif_palettise(frame, **options):
+    """One RGB32 frame on the device (torch int32 CUDA tensor [H][W], rows at any stride) as a colour table and indices
+    (tm_stage_gif_palettise: k_gif_colours, k_gif_hist for a frame to quantise, k_gif_map) -> (table uint32 [colours], exact, uint8 [H][W])"""
+    from ._lib import gif_options
+    assert frame.is_cuda and frame.dtype == torch.int32 and frame.dim() == 2 and (frame.shape[1] <= 1 or frame.stride(1) == 1)
+    h, w = frame.shape
+    return _gif_palettise(lib().tm_stage_gif_palettise, _p(frame), frame.stride(0), w, h, gif_options(**options), (_stream(),))
+
+
+def gif_palettise_host(frame, **options):
+    """gif_palettise's host twin (tm_gif_palettise_host), no device: frame = numpy uint32 or int32 array [H][W]"""
+    from ._lib import gif_options
+    assert frame.dtype in (np.uint32, np.int32) and frame.ndim == 2 and (frame.shape[1] <= 1 or frame.strides[1] == 4)
+    h, w = frame.shape
+    return _gif_palettise(lib().tm_gif_palettise_host, ctypes.c_void_p(frame.ctypes.data), frame.strides[0] // 4, w, h, gif_options(**options), ())

@@ -1,7 +1,8 @@
 """Frames of a .gtm stream, played on the device:
 python tools/play_gtm.py IN.gtm [--start N --frames N] (--info | --raw OUT.rgb | --y4m OUT.y4m [--chroma 444|422|420jpeg|420mpeg2|mono] [--yuv MODE]
                          | --png OUT_%04d.png [--png-level 0|1] [--png-filter none|adaptive|smaller]
-                         | --jpeg OUT_%04d.jpg | --mjpeg OUT.mjpeg [--jpeg-quality 90] [--jpeg-sampling 420|422|444|grey] [--jpeg-restart-rows 1])
+                         | --jpeg OUT_%04d.jpg | --mjpeg OUT.mjpeg [--jpeg-quality 90] [--jpeg-sampling 420|422|444|grey] [--jpeg-restart-rows 1]
+                         | --gif OUT.gif [--gif-colours auto|exact|quantise --gif-max-colours 256 --gif-segment 4096 --gif-no-diff])
                          [--size WxH [--filter lanczos|nearest]]
 
 --info prints what the stream says about itself (size, frames, key frames, rate, tiles, palettes, the embedded settings) as JSON;
@@ -15,7 +16,9 @@ bt709-full tiler (444 and mono only); the header says XCOLORRANGE=FULL for the f
 --jpeg writes one baseline JPEG per frame, --mjpeg the same files one behind another in one file that any player opens: the frames stay on
 the device and are coded there (stages.jpeg_encode: libjpeg's bytes; --jpeg-restart-rows 1, the default, writes the restart markers that
 let this library's Load decode the files on the device, 0 none).
---size WxH (with --raw, --y4m, --png, --jpeg and --mjpeg): the frames are scaled on the device to that size before they are delivered (GtmPlayer.SetOutput; --filter
+--gif writes one animated GIF at the stream's rate (stages.gif_encode: exact colour tables where a frame holds at most --gif-max-colours
+colours -- a stream of 16 palettes of 16 always does, and the file is lossless -- a median cut where it holds more).
+--size WxH (with --raw, --y4m, --png, --jpeg, --mjpeg and --gif): the frames are scaled on the device to that size before they are delivered (GtmPlayer.SetOutput; --filter
 lanczos, the default, or nearest); the Y4M header carries the output size."""
 import argparse
 import json
@@ -39,6 +42,11 @@ g.add_argument("--y4m")
 g.add_argument("--png", help="a pattern with one integer field, for instance OUT_%%04d.png")
 g.add_argument("--jpeg", help="a pattern with one integer field, for instance OUT_%%04d.jpg")
 g.add_argument("--mjpeg")
+g.add_argument("--gif")
+ap.add_argument("--gif-colours", default="auto", choices=["auto", "exact", "quantise"])
+ap.add_argument("--gif-max-colours", type=int, default=256)
+ap.add_argument("--gif-segment", type=int, default=4096, help="indices per separately coded LZW segment; 0: one per image")
+ap.add_argument("--gif-no-diff", action="store_true", help="code whole frames, not the rectangle that changed")
 ap.add_argument("--jpeg-quality", type=int, default=90)
 ap.add_argument("--jpeg-sampling", default="420", choices=["420", "422", "444", "grey"])
 ap.add_argument("--jpeg-restart-rows", type=int, default=1)
@@ -115,6 +123,21 @@ with GtmPlayer(args.input) as p:
             left -= fr.shape[0]
         if one:
             one.close()
+    elif args.gif:
+        import torch
+        from tiler_amd import stages
+        p.Seek(args.start)
+        left = (args.frames if args.frames > 0 else info["frames"] - args.start)
+        parts = []
+        while left > 0:
+            fr = p.Read(min(left, 16), device=True)
+            if fr.shape[0] == 0:
+                break
+            parts.append(fr.clone())
+            left -= fr.shape[0]
+        with open(args.gif, "wb") as f:  # one file: the frames wait on the device (4 bytes a pixel) and are coded there in the writer's chunks
+            f.write(stages.gif_encode(torch.cat(parts), info["fps"], colours=args.gif_colours, max_colours=args.gif_max_colours, segment_pixels=args.gif_segment,
+                                      diff=not args.gif_no_diff))
     else:
         p.Seek(args.start)
         left = (args.frames if args.frames > 0 else info["frames"] - args.start)
