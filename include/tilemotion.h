@@ -786,6 +786,61 @@ TM_API int tm_stage_gif_palettise(const uint32_t *dev_frame, int64_t stride_px, 
                                   int *exact, uint8_t *indices /* host, h * w */, void *stream);
 TM_API int tm_gif_palettise_host(const uint32_t *frame, int64_t stride_px, int w, int h, const tm_gif_options *opt, uint32_t *table /* 256 */, int *colours, int *exact,
                                  uint8_t *indices /* h * w */);
+/* ---- WebP export on the device: lossless VP8L frames, one animated file (tm_webp_out.hip; the rule: tm_webp_out.h) ----
+ * One animated WebP of the frames tm_generate_pngs writes, every frame a lossless VP8L image: exact at any number of colours.  RIFF / WEBP
+ * with VP8X (animation flag only), ANIM (background 0, `loop`), and per frame an ANMF (x / 2, y / 2, width - 1, height - 1, the duration,
+ * flags 0x02: no blending, no disposal) holding one VP8L chunk.  The duration is duration_ms, or max(1, floor(1000 / fps + 0.5)); above
+ * 2^24 - 1: TM_E_INVAL.
+ *   diff 1: frame 0 whole, frame i the bounding box of the pixels whose 0x00RRGGBB differs from frame i - 1's with its left and top lowered
+ * to even, an unchanged frame the 1 x 1 rectangle at (0, 0).  Per frame over the rectangle's pixels: with at most 256 distinct colours
+ * under TM_WEBP_PALETTE_AUTO a colour-indexing transform (the distinct colours ascending, a pixel's index is its colour's rank, 8 / 4 / 2
+ * / 1 indices to a coded pixel for <= 2 / 4 / 16 / more colours, lowest bits first; the table coded as differences with literals only),
+ * otherwise the subtract-green transform.  The coded pixels (alpha 0xFF) in row order are cut into segments of segment_pixels.
+ *   LZ77, greedy from a segment's first pixel: the candidates of a position are the earlier positions of the image whose three pixels hash
+ * alike, nearest first, at most 8 visited, none further than 2^20 - 120 back; the length is the common run capped at min(4096, what is
+ * left of the segment); the longest wins, the nearest among equals; below 3, or 3 and further than 512 back: no match, a literal.  A
+ * match never crosses its segment's end; its source may lie anywhere before it.  A distance d is written as the code d + 120.
+ *   One group of five prefix codes per image from the histograms of its tokens: lengths by tm_deflate_code_lengths_host (15 bits; 7 for
+ * the code of the lengths, whose zero runs use 17 and 18); an alphabet with at most two used symbols, all below 256, is a simple code.
+ * No colour cache, no predictor or colour transform, no meta codes, no alpha.  The file is a function of the pixels, the rate and the
+ * options alone: the device form and the host twin write the same bytes, and where the chunks end changes no byte.
+ *   tm_set_webp_options: TM_E_INVAL for null, diff or lz77 other than 0 / 1, an unknown palette, segment_pixels < 0, loop outside 0 ..
+ * 65535, duration_ms outside 0 .. 2^24 - 1.  tm_generate_webp refuses what tm_generate_pngs refuses, before any file is opened, and in a
+ * device group reads shard 0.  tm_get_webp_export_stats: of the last tm_generate_webp.
+ *   tm_stage_webp_encode: nframes pictures [h][w] of 0x00RRGGBB in DEVICE memory as one file in HOST memory `out`; chunk_frames <= 0: the
+ * writer's own (at most 32).  tm_webp_encode_host: the same from HOST frames with no device; canvas (or null): [nframes][h][w], what a
+ * reader shows.  TM_E_INVAL before any device call: null pointers, options as above, w or h < 1, nframes < 1, strides shorter than a row /
+ * a frame, a rate that gives no duration; TM_E_UNSUPPORTED: a side above 16384.  A cap too small is TM_E_INVAL with *bytes set to the
+ * bytes needed and `out` untouched; tm_webp_bound_host bounds any file of that shape.  stats may be null. */
+enum { TM_WEBP_PALETTE_AUTO = 0, TM_WEBP_PALETTE_OFF = 1 };
+typedef struct tm_webp_options {
+  int32_t diff;           /* 0: whole frames; 1: the changed rectangle (default) */
+  int32_t palette;        /* TM_WEBP_PALETTE_* (default AUTO) */
+  int32_t lz77;           /* 0: literals only; 1: matches (default) */
+  int32_t segment_pixels; /* 0: one segment per image; else coded pixels per segment (default 4096: DESIGN.md section 44.3) */
+  int32_t loop;           /* 0: for ever (default); n: n times */
+  int32_t duration_ms;    /* 0: from the rate (default); else ms per frame */
+} tm_webp_options;
+typedef struct tm_webp_export_stats {
+  int64_t frames, frames_indexed, segments, tokens, matches, file_bytes;
+  double ms_colours; /* rectangles and distinct colours on the device, their read-back, the host's tables */
+  double ms_match;   /* coded pixels, the key sort and the links */
+  double ms_parse;   /* the parse, the histograms and their read-back */
+  double ms_codes;   /* the host: code lengths and every image's header bits */
+  double ms_emit;    /* packing and joining the bits, the container, the bytes' read-back */
+  double ms_device;  /* render and all of the above */
+  double ms_write;   /* writing the file */
+  double ms_wall;    /* the whole call */
+} tm_webp_export_stats;
+TM_API int tm_set_webp_options(tm_encoder *, const tm_webp_options *opt);
+TM_API int tm_get_webp_options(tm_encoder *, tm_webp_options *opt);
+TM_API int tm_generate_webp(tm_encoder *, const char *path, int input);
+TM_API int tm_get_webp_export_stats(tm_encoder *, tm_webp_export_stats *out);
+TM_API int tm_webp_bound_host(int w, int h, int nframes, const tm_webp_options *opt, int64_t *bytes);
+TM_API int tm_stage_webp_encode(const uint32_t *dev_frames, int64_t stride_px, int64_t frame_px, int nframes, int w, int h, double fps, const tm_webp_options *opt,
+                                int chunk_frames, uint8_t *out, int64_t cap, int64_t *bytes, tm_webp_export_stats *stats, void *stream);
+TM_API int tm_webp_encode_host(const uint32_t *frames, int64_t stride_px, int64_t frame_px, int nframes, int w, int h, double fps, const tm_webp_options *opt,
+                               uint8_t *out, int64_t cap, int64_t *bytes, uint32_t *canvas, tm_webp_export_stats *stats);
 /* The same pictures rendered on the device (Render :3455-3640, Output tab with the constructor's defaults; or the Input tab: input != 0):
  * frames [first_frame, first_frame+frame_count) as [frame_count][tm_h*8][tm_w*8] uint32 0x00RRGGBB (the format frames are pushed in; the
  * input render is every pushed frame cropped to tm_w*8 x tm_h*8 with alpha 0).  A predicted item is frame f-1's output at its offset,

@@ -120,6 +120,27 @@ def gif_options(colours="auto", max_colours=256, diff=True, segment_pixels=4096,
     return GifOptions(int(colours), int(max_colours), int(diff), int(segment_pixels), int(loop), int(delay_cs))
 
 
+class WebpOptions(ctypes.Structure):  # tm_webp_options
+    _fields_ = [(n, ctypes.c_int32) for n in ("diff", "palette", "lz77", "segment_pixels", "loop", "duration_ms")]
+
+
+class WebpExportStatsDesc(ctypes.Structure):  # tm_webp_export_stats
+    _fields_ = [(n, c_int64) for n in ("frames", "frames_indexed", "segments", "tokens", "matches", "file_bytes")] + [
+        (n, c_double) for n in ("ms_colours", "ms_match", "ms_parse", "ms_codes", "ms_emit", "ms_device", "ms_write", "ms_wall")]
+
+
+WEBP_PALETTE = {"auto": 0, "off": 1}  # TM_WEBP_PALETTE_*
+
+
+def webp_options(diff=True, palette="auto", lz77=True, segment_pixels=4096, loop=0, duration_ms=0):
+    """tm_webp_options from the keywords SetWebpOptions / stages.webp_encode take"""
+    if isinstance(palette, str):
+        if palette not in WEBP_PALETTE:
+            raise ValueError("unknown WebP palette %r (one of %s)" % (palette, " ".join(WEBP_PALETTE)))
+        palette = WEBP_PALETTE[palette]
+    return WebpOptions(int(diff), int(palette), int(lz77), int(segment_pixels), int(loop), int(duration_ms))
+
+
 PNG_DECODE = {"auto": 0, "host": 1, "device": 2}  # TM_PNG_DECODE_*
 
 RENDER_PAGES = {"input": 0, "output": 1, "tiles": 2}  # TM_RENDER_PAGE_*
@@ -269,6 +290,15 @@ SIGNATURES = {
                                     ctypes.POINTER(c_int64), ctypes.POINTER(GifExportStatsDesc), c_void_p]),
     "tm_gif_encode_host": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_double, ctypes.POINTER(GifOptions), c_void_p, c_int64, ctypes.POINTER(c_int64),
                                    c_void_p, ctypes.POINTER(GifExportStatsDesc)]),
+    "tm_set_webp_options": (c_int, [c_void_p, ctypes.POINTER(WebpOptions)]),
+    "tm_get_webp_options": (c_int, [c_void_p, ctypes.POINTER(WebpOptions)]),
+    "tm_generate_webp": (c_int, [c_void_p, c_char_p, c_int]),
+    "tm_get_webp_export_stats": (c_int, [c_void_p, ctypes.POINTER(WebpExportStatsDesc)]),
+    "tm_webp_bound_host": (c_int, [c_int, c_int, c_int, ctypes.POINTER(WebpOptions), ctypes.POINTER(c_int64)]),
+    "tm_stage_webp_encode": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_double, ctypes.POINTER(WebpOptions), c_int, c_void_p, c_int64,
+                                     ctypes.POINTER(c_int64), ctypes.POINTER(WebpExportStatsDesc), c_void_p]),
+    "tm_webp_encode_host": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_double, ctypes.POINTER(WebpOptions), c_void_p, c_int64, ctypes.POINTER(c_int64),
+                                    c_void_p, ctypes.POINTER(WebpExportStatsDesc)]),
     "tm_stage_gif_lzw_pack": (c_int, [c_void_p, ctypes.c_uint32, c_int, c_int, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
     "tm_gif_lzw_pack_host": (c_int, [c_void_p, ctypes.c_uint32, c_int, c_int, c_void_p, c_int64, ctypes.POINTER(c_int64)]),
     "tm_stage_gif_palettise": (c_int, [c_void_p, c_int64, c_int, c_int, ctypes.POINTER(GifOptions), c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p,

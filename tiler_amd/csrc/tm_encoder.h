@@ -107,6 +107,9 @@ struct tm_encoder {
   tm_gif_options gif_options{TM_GIF_COLOURS_AUTO, 256, 1, 4096, 0, 0};  // what GenerateGIF writes (tm_set_gif_options)
   tm_gif_export_stats gif_export_stats{};                                // of the last GenerateGIF (tm_get_gif_export_stats)
   bool has_gif_export_stats = false;
+  tm_webp_options webp_options{1, TM_WEBP_PALETTE_AUTO, 1, 4096, 0, 0};  // what GenerateWebP writes (tm_set_webp_options)
+  tm_webp_export_stats webp_export_stats{};                              // of the last GenerateWebP (tm_get_webp_export_stats)
+  bool has_webp_export_stats = false;
   int gif_decode = TM_PNG_DECODE_AUTO;  // where a GIF input is decoded (tm_set_gif_decode); TM_GIF_DECODE overrides
   int gif_background = -1;              // the canvas colour of a GIF input (tm_set_gif_background); -1: the file's
   int jpeg_decode = TM_PNG_DECODE_AUTO; // where a JPEG input is decoded (tm_set_jpeg_decode); TM_JPEG_DECODE overrides

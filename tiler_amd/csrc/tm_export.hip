@@ -7,6 +7,7 @@
 #include "tm_deflate.h"
 #include "tm_encoder.h"
 #include "tm_gif_out.h"
+#include "tm_webp_out.h"
 #include "tm_gtm.h"
 #include "tm_jpeg_out.h"
 
@@ -292,7 +293,66 @@ static int generate_gif(tm_encoder *e, const char *path, bool input) {
   return TM_OK;
 }
 
+// GenerateWebP: the frames GeneratePNGs writes as one animated lossless WebP, kept on the device a chunk at a time and
+// coded there (tm_webp_out.hip); only the file's bytes come back.  The file is opened once every chunk has been coded.
+static int generate_webp(tm_encoder *e, const char *path, bool input) {
+  TM_CHECK(path && *path, TM_E_INVAL, "GenerateWebP: no file name");
+  const auto wall0 = std::chrono::steady_clock::now();
+  const tm_webp_options opt = e->webp_options;
+  e->has_webp_export_stats = false;
+  ExportFrames r{e, input};
+  r.keep = true;
+  TM_TRY(r.init());
+  int duration;
+  TM_TRY(wpo::webp_out_check("GenerateWebP", r.dev.p, r.sw, (int64_t)r.sw * r.sh, e->nframes, r.sw, r.sh, e->fps, &opt, &duration));
+  std::vector<uint8_t> file;
+  wpo::WebpDeviceEncoder encoder;  // (its device buffers serve every chunk)
+  TM_TRY(encoder.begin(r.sw, r.sh, e->fps, opt, e->stream, file));
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int fr = 0; fr < e->nframes; fr += r.count) {
+    TM_TRY(r.frame(fr, nullptr));
+    for (int f0 = 0; f0 < r.count; f0 += wpo::kMaxChunk)
+      TM_TRY(encoder.chunk(r.dev.as<uint32_t>() + (int64_t)f0 * r.sw * r.sh, r.sw, (int64_t)r.sw * r.sh, std::min((int)wpo::kMaxChunk, r.count - f0), file));
+  }
+  TM_TRY(encoder.end(file));
+  const auto t1 = std::chrono::steady_clock::now();
+  TM_TRY(write_file(path, file));
+  tm_webp_export_stats st = encoder.stats;
+  st.ms_device = std::chrono::duration<double, std::milli>(t1 - t0).count();
+  st.ms_write = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+  st.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  e->webp_export_stats = st;
+  e->has_webp_export_stats = true;
+  return TM_OK;
+}
+
 extern "C" {
+
+int tm_generate_webp(tm_encoder *e, const char *path, int input) {
+  TM_CHECK(e, TM_E_INVAL, "null encoder");
+  TM_CHECK(path, TM_E_INVAL, "GenerateWebP: no file name");
+  return generate_webp(e, path, input != 0);
+}
+
+int tm_set_webp_options(tm_encoder *e, const tm_webp_options *opt) {
+  TM_CHECK(e && opt, TM_E_INVAL, "null argument");
+  TM_TRY(wpo::webp_options_check("webp options", opt));
+  e->webp_options = *opt;
+  return TM_OK;
+}
+
+int tm_get_webp_options(tm_encoder *e, tm_webp_options *opt) {
+  TM_CHECK(e && opt, TM_E_INVAL, "null argument");
+  *opt = e->webp_options;
+  return TM_OK;
+}
+
+int tm_get_webp_export_stats(tm_encoder *e, tm_webp_export_stats *out) {
+  TM_CHECK(e && out, TM_E_INVAL, "null argument");
+  TM_CHECK(e->has_webp_export_stats, TM_E_INVAL, "webp export stats: this encoder has not written a WebP");
+  *out = e->webp_export_stats;
+  return TM_OK;
+}
 
 int tm_generate_gif(tm_encoder *e, const char *path, int input) {
   TM_CHECK(e, TM_E_INVAL, "null encoder");

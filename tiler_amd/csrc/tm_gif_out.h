@@ -197,6 +197,28 @@ inline void image_header(const Rect &r, const uint32_t *table, uint32_t colours,
 }
 inline uint64_t sub_blocked_bytes(uint64_t payload) { return payload + (payload + 254) / 255 + 1; }  // length bytes and the terminator
 
+// ---- where a chunk's bits go (k_gif_emit, k_gif_blob)
+struct SegPlace { uint64_t bit_off, bits, word_off; };
+struct ImagePlace {
+  uint64_t payload, pos, word0;  // payload bytes, where the data starts in the chunk's bytes, its first word among the chunk's payload words
+  uint32_t seg0, nseg;
+};
+struct Piece { uint64_t from, to; uint32_t n, pad; };
+
+#if defined(__HIPCC__)
+// The launches the WebP writer shares (tm_webp_out.hip), on `stream`, unchanged for this writer.  k_gif_rect: dev_raw[4 f ..] = min x, min y,
+// min (65535 - x), min (65535 - y) of frame f's changed pixels, each from 0x7f7f7f7f (the caller fills it); k_gif_colours: per frame the
+// open-addressed table of its rectangle's distinct colours (kHashSlots of kEmpty before) and their count, which stops above max_colours;
+// k_gif_emit: the segments' bits joined into every image's payload (sub: GIF sub-blocks); k_gif_blob: host-made pieces to their places.
+void launch_rect_raw(const uint32_t *dev_frames, int64_t stride_px, int64_t frame_px, int nframes, const uint32_t *dev_prev, int has_prev, int w, int h, int32_t *dev_raw,
+                     hipStream_t stream);
+void launch_colours(const uint32_t *dev_frames, int64_t stride_px, int64_t frame_px, int nframes, int w, int h, const Rect *dev_rects, uint32_t *dev_tabs, uint32_t *dev_counts,
+                    uint32_t max_colours, hipStream_t stream);
+void launch_emit(const ImagePlace *dev_images, uint32_t nimages, const SegPlace *dev_segs, const uint32_t *dev_words, uint64_t nwords, uint64_t total_words, uint8_t *dev_out,
+                 uint64_t out_bytes, int sub, hipStream_t stream);
+void launch_blob(const Piece *dev_pieces, uint32_t npieces, const uint8_t *dev_blob, uint64_t blob_bytes, uint8_t *dev_out, uint64_t out_bytes, hipStream_t stream);
+#endif
+
 int gif_options_check(const char *who, const tm_gif_options *opt);
 // every refusal of the writer that needs no pixel, and the delay (1/100 s) the frames get
 int gif_out_check(const char *who, const void *frames, int64_t stride_px, int64_t frame_px, int nframes, int w, int h, double fps, const tm_gif_options *opt, int *delay);

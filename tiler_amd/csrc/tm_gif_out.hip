@@ -45,12 +45,6 @@ struct SegJob {
   uint64_t idx_off, word_off;
   uint32_t n, min_code, first, last, cap_words, pad;
 };
-struct SegPlace { uint64_t bit_off, bits, word_off; };
-struct ImagePlace {
-  uint64_t payload, pos, word0;  // payload bytes, where the data starts in the chunk's bytes, its first word among the chunk's payload words
-  uint32_t seg0, nseg;
-};
-struct Piece { uint64_t from, to; uint32_t n, pad; };
 
 inline unsigned blocks_of(uint64_t n, unsigned most) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, most)); }
 inline double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
@@ -282,6 +276,28 @@ __global__ __launch_bounds__(256) void k_gif_blob(const Piece *__restrict__ piec
   for (uint32_t k = threadIdx.x; k < p.n; k += 256)
     if (p.from + k < blob_bytes && p.to + k < out_bytes) out[p.to + k] = blob[p.from + k];
 }
+
+}  // namespace
+
+// ---- the launches another writer shares (tm_gif_out.h)
+void launch_rect_raw(const uint32_t *dev_frames, int64_t stride_px, int64_t frame_px, int nframes, const uint32_t *dev_prev, int has_prev, int w, int h, int32_t *dev_raw,
+                     hipStream_t stream) {
+  hipLaunchKernelGGL(k_gif_rect, dim3(blocks_of((uint64_t)w * h, 1024), (unsigned)nframes), dim3(256), 0, stream, dev_frames, stride_px, frame_px, dev_prev, has_prev, w, h, dev_raw);
+}
+void launch_colours(const uint32_t *dev_frames, int64_t stride_px, int64_t frame_px, int nframes, int w, int h, const Rect *dev_rects, uint32_t *dev_tabs, uint32_t *dev_counts,
+                    uint32_t max_colours, hipStream_t stream) {
+  hipLaunchKernelGGL(k_gif_colours, dim3(blocks_of((uint64_t)w * h, 1024), (unsigned)nframes), dim3(256), 0, stream, dev_frames, stride_px, frame_px, dev_rects, dev_tabs, dev_counts,
+                     max_colours);
+}
+void launch_emit(const ImagePlace *dev_images, uint32_t nimages, const SegPlace *dev_segs, const uint32_t *dev_words, uint64_t nwords, uint64_t total_words, uint8_t *dev_out,
+                 uint64_t out_bytes, int sub, hipStream_t stream) {
+  hipLaunchKernelGGL(k_gif_emit, dim3(blocks_of(total_words, 16384)), dim3(256), 0, stream, dev_images, nimages, dev_segs, dev_words, nwords, total_words, dev_out, out_bytes, sub);
+}
+void launch_blob(const Piece *dev_pieces, uint32_t npieces, const uint8_t *dev_blob, uint64_t blob_bytes, uint8_t *dev_out, uint64_t out_bytes, hipStream_t stream) {
+  hipLaunchKernelGGL(k_gif_blob, dim3(npieces), dim3(256), 0, stream, dev_pieces, dev_blob, blob_bytes, dev_out, out_bytes);
+}
+
+namespace {
 
 // ---- what both forms share on the host
 struct Palette {

@@ -613,6 +613,34 @@ class TilingEncoder:
         out["diff"] = bool(opt.diff)
         return out
 
+    def GenerateWebP(self, path, input=False):
+        """One animated lossless WebP of the frames GeneratePNGs writes (tm_generate_webp), coded on the device as SetWebpOptions says:
+        exact at any PaletteCount x PaletteSize.  The file carries the clip's rate.  input=True: the Input tab's frames."""
+        check(self._L.tm_generate_webp(c_void_p(self._h), os.fsencode(path), int(bool(input))))
+
+    def SetWebpOptions(self, diff=True, palette="auto", lz77=True, segment_pixels=4096, loop=0, duration_ms=0):
+        """How GenerateWebP writes from now on (tm_set_webp_options): diff (the changed rectangle, not the whole frame), palette "auto" (a
+        colour-indexing transform where a frame holds at most 256 colours, subtract-green otherwise) or "off", lz77, segment_pixels (coded
+        pixels per separately parsed segment; 0: one per image), loop (0: for ever), duration_ms (0: from the clip's rate)."""
+        from ._lib import webp_options
+        check(self._L.tm_set_webp_options(c_void_p(self._h), ctypes.byref(webp_options(diff, palette, lz77, segment_pixels, loop, duration_ms))))
+
+    def WebpOptions(self):
+        from ._lib import WEBP_PALETTE, WebpOptions
+        opt = WebpOptions()
+        check(self._L.tm_get_webp_options(c_void_p(self._h), ctypes.byref(opt)))
+        out = {name: getattr(opt, name) for name, _ in WebpOptions._fields_}
+        out["palette"] = {v: k for k, v in WEBP_PALETTE.items()}[opt.palette]
+        return out
+
+    def WebpExportStats(self):
+        """What the last GenerateWebP did (tm_get_webp_export_stats): frames, how many were colour-indexed, segments, tokens, matches, the
+        file's bytes and ms per stage."""
+        from ._lib import WebpExportStatsDesc
+        st = WebpExportStatsDesc()
+        check(self._L.tm_get_webp_export_stats(c_void_p(self._h), ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in WebpExportStatsDesc._fields_}
+
     def GifExportStats(self):
         """What the last GenerateGIF did (tm_get_gif_export_stats): frames, how many were coded exact and quantised, LZW segments, the
         file's bytes, and milliseconds per stage"""

@@ -873,6 +873,61 @@ def gif_encode_host(frames, fps, cap=None, guard=0, full=False, canvas=False, **
     return (out, shown[:nf]) if canvas else out
 
 
+def webp_bound(w, h, nframes, **options):
+    """An upper bound of a WebP file's size for any pixels (tm_webp_bound_host), no device; options: as webp_encode takes them"""
+    from ._lib import webp_options
+    opt = webp_options(**options)
+    bound = ctypes.c_int64()
+    check(lib().tm_webp_bound_host(int(w), int(h), int(nframes), ctypes.byref(opt), ctypes.byref(bound)))
+    return bound.value
+
+
+def _webp_encode(call, ptr, stride_px, frame_px, nf, w, h, fps, opt, cap, guard, full, extra_before, extra_after):
+    from ._lib import WebpExportStatsDesc
+    if cap is None:
+        bound = ctypes.c_int64()
+        rc = lib().tm_webp_bound_host(w, h, max(nf, 1), ctypes.byref(opt), ctypes.byref(bound))
+        if rc != 0 and not full:
+            check(rc)
+        cap = bound.value if rc == 0 else 4096  # (what the bound refuses the call refuses too: any room will do)
+    buf = np.full(cap + 2 * guard, 0xA5, np.uint8)
+    need = ctypes.c_int64(-1)
+    st = WebpExportStatsDesc()
+    rc = call(ptr, stride_px, frame_px, nf, w, h, float(fps), ctypes.byref(opt), *extra_before, ctypes.c_void_p(buf.ctypes.data + guard) if cap else None, cap,
+              ctypes.byref(need), *extra_after(st))
+    if not full:
+        check(rc)
+    file = buf[guard:guard + need.value].tobytes() if rc == 0 else None
+    stats = {name: getattr(st, name) for name, _ in WebpExportStatsDesc._fields_}
+    return dict(rc=rc, file=file, buffer=buf, bytes=need.value, guard=guard, stats=stats) if full else file
+
+
+def webp_encode(frames, fps, chunk_frames=0, cap=None, guard=0, full=False, **options):
+    """RGB32 frames on the device as one animated lossless WebP (tm_stage_webp_encode; the rule: include/tilemotion.h, DESIGN.md section
+    44): frames = torch int32 CUDA tensor [F][H][W] of 0x00RRGGBB, rows and frames at any stride -> the file's bytes, byte for byte what
+    tm_webp_encode_host writes; only file bytes come to the host.  options: diff, palette ("auto", "off"), lz77, segment_pixels, loop,
+    duration_ms.  chunk_frames: frames per trip through the device stages (0: the writer's own; no byte depends on it).  cap: the room
+    given (default: webp_bound); guard: bytes of 0xA5 kept before and behind that room; full=True: nothing raises, and the result is a dict
+    of rc, file (None when refused), buffer (guards included), bytes (the size, or the size needed), guard and stats."""
+    from ._lib import webp_options
+    assert frames.is_cuda and frames.dtype == torch.int32 and frames.dim() == 3 and (frames.shape[2] <= 1 or frames.stride(2) == 1)
+    nf, h, w = frames.shape
+    return _webp_encode(lib().tm_stage_webp_encode, _p(frames), frames.stride(1), frames.stride(0), nf, w, h, fps, webp_options(**options), cap, guard, full,
+                        (int(chunk_frames),), lambda st: (ctypes.byref(st), _stream()))
+
+
+def webp_encode_host(frames, fps, cap=None, guard=0, full=False, canvas=False, **options):
+    """webp_encode's host twin (tm_webp_encode_host), no device: frames = numpy uint32 or int32 array [F][H][W], rows and frames at any
+    stride (a multiple of 4 bytes; pixels contiguous).  canvas=True: -> (file, uint32 array [F][H][W] of what a reader shows)"""
+    from ._lib import webp_options
+    assert frames.dtype in (np.uint32, np.int32) and frames.ndim == 3 and (frames.shape[2] <= 1 or frames.strides[2] == 4)
+    nf, h, w = frames.shape
+    shown = np.zeros((max(nf, 1), h, w), np.uint32) if canvas else None
+    out = _webp_encode(lib().tm_webp_encode_host, ctypes.c_void_p(frames.ctypes.data), frames.strides[1] // 4, frames.strides[0] // 4, nf, w, h, fps, webp_options(**options),
+                       cap, guard, full, (), lambda st: (ctypes.c_void_p(shown.ctypes.data) if canvas else None, ctypes.byref(st)))
+    return (out, shown[:nf]) if canvas else out
+
+
 def _gif_lzw_pack(call, ptr, n, min_code, segment_pixels, extra):
     nseg = -(-n // segment_pixels) if segment_pixels else 1
     cap = 12 * (n + n // 4094 + 3 * nseg + 1) // 8 + 8  # every segment's bound (tm_gif_out.h)

@@ -2,7 +2,8 @@
 python tools/play_gtm.py IN.gtm [--start N --frames N] (--info | --raw OUT.rgb | --y4m OUT.y4m [--chroma 444|422|420jpeg|420mpeg2|mono] [--yuv MODE]
                          | --png OUT_%04d.png [--png-level 0|1] [--png-filter none|adaptive|smaller]
                          | --jpeg OUT_%04d.jpg | --mjpeg OUT.mjpeg [--jpeg-quality 90] [--jpeg-sampling 420|422|444|grey] [--jpeg-restart-rows 1]
-                         | --gif OUT.gif [--gif-colours auto|exact|quantise --gif-max-colours 256 --gif-segment 4096 --gif-no-diff])
+                         | --gif OUT.gif [--gif-colours auto|exact|quantise --gif-max-colours 256 --gif-segment 4096 --gif-no-diff]
+                         | --webp OUT.webp [--webp-no-diff --webp-palette auto|off --webp-segment 4096])
                          [--size WxH [--filter lanczos|nearest]]
 
 --info prints what the stream says about itself (size, frames, key frames, rate, tiles, palettes, the embedded settings) as JSON;
@@ -18,7 +19,8 @@ the device and are coded there (stages.jpeg_encode: libjpeg's bytes; --jpeg-rest
 let this library's Load decode the files on the device, 0 none).
 --gif writes one animated GIF at the stream's rate (stages.gif_encode: exact colour tables where a frame holds at most --gif-max-colours
 colours -- a stream of 16 palettes of 16 always does, and the file is lossless -- a median cut where it holds more).
---size WxH (with --raw, --y4m, --png, --jpeg, --mjpeg and --gif): the frames are scaled on the device to that size before they are delivered (GtmPlayer.SetOutput; --filter
+--webp writes one animated lossless WebP at the stream's rate (stages.webp_encode: a VP8L image per frame, exact at any number of colours).
+--size WxH (with --raw, --y4m, --png, --jpeg, --mjpeg, --gif and --webp): the frames are scaled on the device to that size before they are delivered (GtmPlayer.SetOutput; --filter
 lanczos, the default, or nearest); the Y4M header carries the output size."""
 import argparse
 import json
@@ -43,6 +45,10 @@ g.add_argument("--png", help="a pattern with one integer field, for instance OUT
 g.add_argument("--jpeg", help="a pattern with one integer field, for instance OUT_%%04d.jpg")
 g.add_argument("--mjpeg")
 g.add_argument("--gif")
+g.add_argument("--webp")
+ap.add_argument("--webp-no-diff", action="store_true", help="code whole frames, not the rectangle that changed")
+ap.add_argument("--webp-palette", default="auto", choices=["auto", "off"])
+ap.add_argument("--webp-segment", type=int, default=4096, help="coded pixels per separately parsed segment; 0: one per image")
 ap.add_argument("--gif-colours", default="auto", choices=["auto", "exact", "quantise"])
 ap.add_argument("--gif-max-colours", type=int, default=256)
 ap.add_argument("--gif-segment", type=int, default=4096, help="indices per separately coded LZW segment; 0: one per image")
@@ -123,7 +129,7 @@ with GtmPlayer(args.input) as p:
             left -= fr.shape[0]
         if one:
             one.close()
-    elif args.gif:
+    elif args.gif or args.webp:
         import torch
         from tiler_amd import stages
         p.Seek(args.start)
@@ -135,9 +141,12 @@ with GtmPlayer(args.input) as p:
                 break
             parts.append(fr.clone())
             left -= fr.shape[0]
-        with open(args.gif, "wb") as f:  # one file: the frames wait on the device (4 bytes a pixel) and are coded there in the writer's chunks
-            f.write(stages.gif_encode(torch.cat(parts), info["fps"], colours=args.gif_colours, max_colours=args.gif_max_colours, segment_pixels=args.gif_segment,
-                                      diff=not args.gif_no_diff))
+        with open(args.gif or args.webp, "wb") as f:  # one file: the frames wait on the device (4 bytes a pixel) and are coded there in the writer's chunks
+            if args.webp:
+                f.write(stages.webp_encode(torch.cat(parts), info["fps"], diff=not args.webp_no_diff, palette=args.webp_palette, segment_pixels=args.webp_segment))
+            else:
+                f.write(stages.gif_encode(torch.cat(parts), info["fps"], colours=args.gif_colours, max_colours=args.gif_max_colours, segment_pixels=args.gif_segment,
+                                          diff=not args.gif_no_diff))
     else:
         p.Seek(args.start)
         left = (args.frames if args.frames > 0 else info["frames"] - args.start)
