@@ -1257,6 +1257,15 @@ TM_API int tm_stage_dither(const void *tiles, const void *flags, const void *pal
 TM_API int tm_stage_dedup(const void *rows, int64_t n, int row_bytes, const void *use_in,
                           void *remap, void *order, void *use_out, int64_t *host_n_unique, void *stream);
 
+/* The grouping Reconstruct puts its database rows through (test seam): the distinct rows of n rows of `row_bytes` (a multiple of 16, compared
+ * as dwords) in ascending order of their first occurrence.  remap i32 [n] (position of each row's first occurrence in `order`), order i32 [n]
+ * (first *n_unique entries: the first occurrences, ascending), use_out u32 [n] (first *n_unique: rows per group).  Blocking. */
+TM_API int tm_stage_dedup_by_index(const void *rows, int64_t n, int row_bytes, void *remap, void *order, void *use_out,
+                                   int64_t *host_n_unique, void *stream);
+/* How often the library has made the host wait for a stream so far in PreparePalettes and the dedup (its small read-backs anywhere, and the
+ * stream synchronisations of those stages), over all threads of the process: tests hold a step's number of round trips with it. */
+TM_API long long tm_host_waits(void);
+
 /* A9/A10: the build's deterministic k-means (farthest-first init, exact integer sums); pts i32 [n][d],
  * weights u32 [n] or NULL.  assign i32 [n], centroids f64 [k][d] (device).  Returns live centroid count in *host_k. */
 TM_API int tm_stage_kmeans(const void *pts_i32, const void *weights, int64_t n, int d, int k, int max_iter,

@@ -192,6 +192,8 @@ SIGNATURES = {
     "tm_stage_curve_keys": (c_int, [c_void_p, c_int64, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p]),
     "tm_knn_last_plan": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int64)]),
     "tm_stage_dedup": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
+    "tm_stage_dedup_by_index": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
+    "tm_host_waits": (ctypes.c_longlong, []),
     "tm_stage_kmeans": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int),
                                 ctypes.POINTER(c_int), c_void_p]),
     "tm_stage_kmeans_seeded": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int),

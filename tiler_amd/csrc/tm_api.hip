@@ -229,6 +229,13 @@ int tm_stage_dedup(const void *rows, int64_t n, int row_bytes, const void *use_i
   return run_dedup(rows, n, row_bytes, use_in, remap, order, use_out, host_n_unique, (hipStream_t)stream);
 }
 
+int tm_stage_dedup_by_index(const void *rows, int64_t n, int row_bytes, void *remap, void *order, void *use_out, int64_t *host_n_unique, void *stream) {
+  knobs_reload();
+  return run_dedup_ex(rows, n, row_bytes, nullptr, remap, order, use_out, host_n_unique, 1, (hipStream_t)stream);
+}
+
+long long tm_host_waits(void) { return host_waits(); }
+
 int tm_stage_kmeans(const void *pts_i32, const void *weights, int64_t n, int d, int k, int max_iter, void *assign, void *centroids,
                     int *host_k, int *host_iters, void *stream) {
   knobs_reload();

@@ -127,6 +127,12 @@ inline int with_temp(DevBuf &tmp, const char *what, Call &&call) {
   return (e == hipErrorOutOfMemory) ? TM_E_NOMEM : TM_E_HIP;
 }
 
+// A wait of the host for a stream that is counted (host_waits, exported as tm_host_waits): HostRead::wait, and the plain stream
+// synchronisations of PreparePalettes and the dedup (tm_steps, tm_palettize, tm_kmeans*, tm_dedup), so that a test can hold the number of
+// round trips of a step.  The count is the process's, over all threads.
+hipError_t host_sync(hipStream_t s);
+long long host_waits();
+
 // Small read-backs (counts, flags, a handful of sums) through page-locked memory: a device-to-host copy into pageable memory -- a stack
 // variable -- takes the runtime's staging path and costs 27 us behind a small kernel where the same copy into pinned memory costs 15
 // (tools/micro/readback.hip; a step holds 50-100 of them).  Scoped: the destinations must outlive the object; copies queued and not

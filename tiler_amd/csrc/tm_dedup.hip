@@ -16,7 +16,8 @@
 //      and slow; TM_DEDUP_PLAIN=1 asks for it outright).  Use counts add up with integer atomics (order free).
 //   2. ORDER the distinct rows: by content (a radix sort of 8-byte prefixes, whole rows only where prefixes tie; the comparator merge
 //      sort where they tie in long runs or the rows are few), then a stable radix sort on ~UseCount.  A caller that keeps only the
-//      first rows of the order (exact_first) has only the rows that can be among them sorted (k_po_*).
+//      first rows of the order (exact_first) has only the rows that can be among them sorted (k_po_*).  The by-index form ranks by row
+//      number, which the table's list of distinct rows is in already: nothing is sorted then.
 //   3. NUMBER the rows: every row's position is its representative's.
 // rocPRIM supplies the sort and scan primitives; the hash, table, comparator, run detection, merge bookkeeping and ranking kernels
 // are ours.
@@ -477,7 +478,9 @@ int read_groups(Dedup &d, bool *collision) {
 // The three grouping front ends share one contract: rep, use_rep, uniq and nu are filled (uniq in index order after the table, in hash order
 // after the hash sort, in content order after the plain sort); *collision says that two different rows shared a hash: what was filled is then not to be used.
 
-// the table (see k_dd_insert): no sort; cuse and clead come with it
+// the table (see k_dd_insert): no sort; cuse and clead come with it.
+// The table leaves uniq in ascending row order: a group's representative is its lowest row (k_dd_resolve: min(owner, mindup)), head marks
+// exactly the representatives, and k_dd_compact writes uniq[head_excl[i]] = i with head_excl the exclusive scan of the marks.
 int group_by_table(Dedup &d, bool *collision) {
   const int64_t n = d.n;
   int64_t slots = 1024;
@@ -671,14 +674,15 @@ int rank(Dedup &d, unsigned long long *live) {
   return hr.wait();
 }
 
-// ord2 -> the caller's arrays: a live row's position, its use count, and every row's position through its representative
-int finish(Dedup &d, int64_t live, void *remap, void *order, void *use_out) {
+// the final order (ord2, or uniq where it already is that order) -> the caller's arrays: a live row's position, its use count, and every
+// row's position through its representative
+int finish(Dedup &d, const DevBuf &final_order, int64_t live, void *remap, void *order, void *use_out) {
   TM_HIP(hipMemsetAsync(d.pos.p, 0xff, d.n * 4, d.stream));
-  hipLaunchKernelGGL(k_scatter_pos, dim3(gridn(live)), dim3(256), 0, d.stream, d.ord2.as<uint32_t>(), live, d.use_rep.as<uint32_t>(), d.pos.as<int32_t>(), (uint32_t *)use_out);
+  hipLaunchKernelGGL(k_scatter_pos, dim3(gridn(live)), dim3(256), 0, d.stream, final_order.as<uint32_t>(), live, d.use_rep.as<uint32_t>(), d.pos.as<int32_t>(), (uint32_t *)use_out);
   hipLaunchKernelGGL(k_remap, dim3(gridn(d.n)), dim3(256), 0, d.stream, d.rep.as<uint32_t>(), d.pos.as<int32_t>(), d.n, (int32_t *)remap);
-  TM_HIP(hipMemcpyAsync(order, d.ord2.p, (size_t)live * 4, hipMemcpyDeviceToDevice, d.stream));
+  TM_HIP(hipMemcpyAsync(order, final_order.p, (size_t)live * 4, hipMemcpyDeviceToDevice, d.stream));
   TM_HIP(hipGetLastError());
-  TM_HIP(hipStreamSynchronize(d.stream));  // the scratch DevBufs die with the caller's frame
+  TM_HIP(host_sync(d.stream));  // the scratch DevBufs die with the caller's frame
   return TM_OK;
 }
 
@@ -712,18 +716,20 @@ int run_dedup_ex(const void *rows, int64_t n, int row_bytes, const void *use_in,
   }
   // 2. order.  The partial order wants groups that are not in content order yet, plain use counts and a cut inside the distinct rows.  Else
   //    the content order (the plain grouping left it; the by-index form ranks by row number alone: any order of the distinct rows will do),
-  //    then the ranking sort.
+  //    then the ranking sort.  By index from the table there is nothing to rank: uniq is in ascending row order already (group_by_table's
+  //    contract) and every distinct row is live; the sorting front ends leave uniq in hash or content order and keep the sort.
   bool ordered = false;
+  const bool uniq_is_final = front == FRONT_TABLE && by_index;
   unsigned long long live = 0;
   if (front != FRONT_PLAIN && !by_index && !use_in && exact_first > 0 && exact_first < d.nu && !knobs().dedup_full_order)
     TM_TRY(order_candidates(d, front == FRONT_TABLE, exact_first, &ordered));
-  if (ordered) live = (unsigned long long)d.nu;
+  if (ordered || uniq_is_final) live = (unsigned long long)d.nu;
   else {
     if (front != FRONT_PLAIN && !by_index) TM_TRY(content_order(d));
     TM_TRY(rank(d, &live));
   }
   // 3. number
-  TM_TRY(finish(d, (int64_t)live, remap, order, use_out));
+  TM_TRY(finish(d, uniq_is_final ? d.uniq : d.ord2, (int64_t)live, remap, order, use_out));
   if (host_n_unique) *host_n_unique = (int64_t)live;
   return TM_OK;
 }

@@ -236,14 +236,17 @@ int run_kmeans(const void *pts, const void *weights, int64_t n, int d, int k, in
 // the same Lloyd iterations from the caller's own initial centres (k point indices, -1 = none) instead of the farthest-first picks
 int run_kmeans_seeded(const void *pts, const void *weights, int64_t n, int d, int k, const int64_t *host_init_idx, int max_iter, void *assign, void *centroids,
                       int *host_k, int *host_iters, hipStream_t stream);
-// keep_keys / keep_n (optional): the sorted distinct pixel keys palette << 24 | G << 16 | R << 8 | B the quantisation found, for Dither
+// keep_keys / keep_n (optional): the sorted distinct pixel keys palette << 24 | G << 16 | R << 8 | B the quantisation found, for Dither (u64 each)
+// host_palettes (optional): the palettes go to this host array [npal][pal_size] INSTEAD of out_palettes (which may then be null): no upload, and
+// the call does not wait for one
 struct DevBuf;
 int run_quantize_palettes(const void *tiles, const void *pal_idx, int64_t n, int npal, int pal_size, int max_iter, void *out_palettes,
-                          hipStream_t stream, DevBuf *keep_keys = nullptr, int64_t *keep_n = nullptr);
+                          hipStream_t stream, DevBuf *keep_keys = nullptr, int64_t *keep_n = nullptr, int32_t *host_palettes = nullptr);
 // the same for the palettes p with p % pal_world == pal_rank only (independent tasks, one thread per palette in the reference:
 // tilingencoder.pas:1864); the other palettes' rows come back as zeros, so that an all-reduce(SUM) assembles the set
 int run_quantize_palettes_part(const void *tiles, const void *pal_idx, int64_t n, int npal, int pal_size, int max_iter, void *out_palettes,
-                               int pal_rank, int pal_world, hipStream_t stream, DevBuf *keep_keys = nullptr, int64_t *keep_n = nullptr);
+                               int pal_rank, int pal_world, hipStream_t stream, DevBuf *keep_keys = nullptr, int64_t *keep_n = nullptr,
+                               int32_t *host_palettes = nullptr);
 int run_palettize(const void *feat, const void *use, int64_t n, int npal, int max_iter, void *out_pal_idx, hipStream_t stream);
 // the seeding of that clustering alone: the k picked indices to the host (-1 beyond the centres found), *out_kk = centres found
 int run_pp_seeds(const void *feat, const void *use, int64_t n, int k, int64_t *out_seeds_host, int *out_kk, hipStream_t stream);

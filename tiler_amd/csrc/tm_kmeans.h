@@ -111,14 +111,17 @@ inline int cu_count() {  // compute units of the current device
 // tm_kmeans.hip: batched k-means over nseg contiguous segments.  seg_begin / seg_count are host arrays.  Outputs assign (global point
 // order), cent [nseg][k][d], host_kk[nseg] live centroid counts.  init_idx / dev_init_idx (optional, host / device): the caller's own
 // initial centres instead of the farthest-first picks, k point indices per segment (relative to the segment), -1 = none.
+// host_cent (optional, host, [nseg][k][d]): the centroids come to the host with the clustering's own read-back; where the clustering holds
+// them on the host already (the resident pixel launch) the device copy `cent` is then NOT written: no upload, no wait for one.
 int kmeans_batched(const int32_t *pts, const uint32_t *w, int d, const std::vector<int64_t> &seg_begin, const std::vector<int64_t> &seg_count, int k,
                    int max_iter, int32_t *assign, double *cent, std::vector<int> *host_kk, int *host_iters, hipStream_t stream,
-                   const int64_t *init_idx = nullptr, const long long *dev_init_idx = nullptr);
+                   const int64_t *init_idx = nullptr, const long long *dev_init_idx = nullptr, double *host_cent = nullptr);
 
 // tm_kmeans_pixel.hip: the whole D = 3 clustering in resident launches; *used = 0 when the shape does not fit (the caller then takes the
-// launches-per-iteration path)
+// launches-per-iteration path).  host_cent: as above.
 int kmeans3_persistent(const int32_t *pts, const uint32_t *w, const std::vector<int64_t> &seg_begin, const std::vector<int64_t> &seg_count, int k,
-                       int max_iter, int32_t *assign, double *cent, std::vector<int> *host_kk, int *host_iters, hipStream_t stream, int *used);
+                       int max_iter, int32_t *assign, double *cent, std::vector<int> *host_kk, int *host_iters, hipStream_t stream, int *used,
+                       double *host_cent = nullptr);
 
 // ---- D = 192 (tm_kmeans_tile.h has the rules the three files share) -----------------------------------------------------------------
 // tm_kmeans_assign192.hip: the plain iterations' assignment step
@@ -198,7 +201,8 @@ int tile_skip_setup(TileRun &t);
 void tile_skip_iteration(TileRun &t, int iter, int *pin_dev);  // iteration `iter` (plain below H_WARM) and its update
 // tm_kmeans_resident.hip again, on a TileRun:
 enum class Resident { done, gave_up, not_applicable };
-// the H_WARM plain iterations, then all skipping iterations in one launch of k_h_resident; done: *iters is set
-int tile_resident(TileRun &t, const ResidentPlan &plan, Resident *verdict, int *iters);
+// the H_WARM plain iterations, then all skipping iterations in one launch of k_h_resident; done: *iters is set.  host_seg / host_look
+// (optional): the segment's table entry and the first look's two counters as the launch leaves them, fetched with the launch's own read-back
+int tile_resident(TileRun &t, const ResidentPlan &plan, Resident *verdict, int *iters, Seg *host_seg = nullptr, u64 *host_look = nullptr);
 
 }  // namespace tmx

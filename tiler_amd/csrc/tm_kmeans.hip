@@ -553,7 +553,7 @@ static int km_launches(KmRun &r, int *iters) {
 
 int kmeans_batched(const int32_t *pts, const uint32_t *w, int d, const std::vector<int64_t> &seg_begin, const std::vector<int64_t> &seg_count, int k,
                    int max_iter, int32_t *assign, double *cent, std::vector<int> *host_kk, int *host_iters, hipStream_t stream, const int64_t *init_idx,
-                   const long long *dev_init_idx) {
+                   const long long *dev_init_idx, double *host_cent) {
   TM_CHECK(d == 3 || d == 192, TM_E_INVAL, "kmeans: only d = 3 (pixels) or 192 (tile features) are built");
   TM_CHECK(k >= 1 && k <= 65536, TM_E_INVAL, "kmeans: k out of range");
   const int nseg = (int)seg_begin.size();
@@ -563,7 +563,7 @@ int kmeans_batched(const int32_t *pts, const uint32_t *w, int d, const std::vect
   if (nseg == 0) return TM_OK;
   if (d == 3 && !init_idx && !dev_init_idx) {  // the whole clustering in one launch when its workgroups fit the chip together
     int used = 0;
-    TM_TRY(kmeans3_persistent(pts, w, seg_begin, seg_count, k, max_iter, assign, cent, host_kk, host_iters, stream, &used));
+    TM_TRY(kmeans3_persistent(pts, w, seg_begin, seg_count, k, max_iter, assign, cent, host_kk, host_iters, stream, &used, host_cent));
     if (used) { kmeans_run_stats().resident = 1; return TM_OK; }
   }
   for (bool allow_resident = true;; allow_resident = false) {  // a resident launch that gave up: once more, from the seeds, without it
@@ -572,10 +572,11 @@ int kmeans_batched(const int32_t *pts, const uint32_t *w, int d, const std::vect
     r.t.pts = pts; r.t.ptsc = nullptr; r.t.w = w; r.t.k = k; r.t.max_iter = max_iter; r.t.assign = assign; r.t.cent = cent; r.t.stream = stream;
     TM_TRY(km_setup(r, seg_begin, seg_count, init_idx, dev_init_idx));
     int it = 0;
+    u64 look[2] = {0, 0};
     Resident leg = Resident::not_applicable;
     if (r.skipping && allow_resident && !knobs().km_launches && max_iter > H_WARM) {
       const ResidentPlan plan = resident_plan(r.t.n, k, cu_count());
-      if (plan.rounds) TM_TRY(tile_resident(r.t, plan, &leg, &it));
+      if (plan.rounds) TM_TRY(tile_resident(r.t, plan, &leg, &it, r.hs.data(), look));  // (r.skipping: one segment)
     }
     if (leg == Resident::gave_up) {
       fprintf(stderr, "[tm_kmeans] the resident tile k-means gave up at its barrier; repeating the clustering with one launch per step\n");
@@ -585,11 +586,14 @@ int kmeans_batched(const int32_t *pts, const uint32_t *w, int d, const std::vect
     else kmeans_run_stats().resident = 1;
     TM_HIP(hipGetLastError());
     if (host_iters) *host_iters = it;
-    u64 look[2] = {0, 0};
-    {
+    const bool have_state = leg == Resident::done;  // the resident leg's read-back brought the segment and the look's counters along
+    if (!have_state || host_cent) {
       HostRead hr_(stream);
-      TM_TRY(hr_.get(r.hs.data(), r.dsegs.p, sizeof(Seg) * nseg));
-      TM_TRY(hr_.get(look, r.look.p, 16));
+      if (!have_state) {
+        TM_TRY(hr_.get(r.hs.data(), r.dsegs.p, sizeof(Seg) * nseg));
+        TM_TRY(hr_.get(look, r.look.p, 16));
+      }
+      if (host_cent) TM_TRY(hr_.get(host_cent, cent, sizeof(double) * (size_t)nseg * k * d));
       TM_TRY(hr_.wait());
     }
     if (d == 192) {

@@ -365,7 +365,8 @@ __global__ __launch_bounds__(P3_NT, P3_WGS) void k_kmeans3_persistent(const int3
 
 // host side of the above; *used = 0 when the shape does not fit one resident launch (the caller then takes the multi-launch path)
 int kmeans3_persistent(const int32_t *pts, const uint32_t *w, const std::vector<int64_t> &seg_begin, const std::vector<int64_t> &seg_count, int k,
-                              int max_iter, int32_t *assign, double *cent, std::vector<int> *host_kk, int *host_iters, hipStream_t stream, int *used) {
+                              int max_iter, int32_t *assign, double *cent, std::vector<int> *host_kk, int *host_iters, hipStream_t stream, int *used,
+                              double *host_cent) {
   *used = 0;
   const int nseg = (int)seg_begin.size();
   if (k > P3_MAXK) return TM_OK;
@@ -459,11 +460,16 @@ int kmeans3_persistent(const int32_t *pts, const uint32_t *w, const std::vector<
 #endif
   }
   if (host_iters) *host_iters = iters;
-  // centroids back in the caller's [nseg][k][3] layout (device)
+  // centroids back in the caller's [nseg][k][3] layout: on the host where the caller goes on there (no upload, nothing to wait for), else on the device
+  if (host_cent) {
+    std::fill(host_cent, host_cent + (size_t)nseg * k * 3, 0.0);
+    for (size_t i = 0; i < hs.size(); i++) memcpy(host_cent + (size_t)which[i] * k * 3, &hcent[i * (size_t)k * 3], sizeof(double) * k * 3);
+    return TM_OK;
+  }
   std::vector<double> full((size_t)nseg * k * 3, 0.0);
   for (size_t i = 0; i < hs.size(); i++) memcpy(&full[(size_t)which[i] * k * 3], &hcent[i * (size_t)k * 3], sizeof(double) * k * 3);
   TM_HIP(hipMemcpyAsync(cent, full.data(), full.size() * 8, hipMemcpyHostToDevice, stream));
-  TM_HIP(hipStreamSynchronize(stream));
+  TM_HIP(host_sync(stream));  // full, the upload's source, is on this frame: the copy must have read it before the frame goes
   return TM_OK;
 }
 

@@ -433,7 +433,7 @@ ResidentPlan resident_plan(int64_t n, int k, int cus) {
 }
 
 // Should a workgroup not become resident (another process holding CUs with a resident launch of its own) the barrier gives up: gave_up.
-int tile_resident(TileRun &t, const ResidentPlan &plan, Resident *verdict, int *iters) {
+int tile_resident(TileRun &t, const ResidentPlan &plan, Resident *verdict, int *iters, Seg *host_seg, u64 *host_look) {
   DevBuf hstate;
   TM_TRY(hstate.alloc(sizeof(HrState)));
   TM_HIP(hipMemsetAsync(hstate.p, 0, sizeof(HrState), t.stream));
@@ -456,6 +456,8 @@ int tile_resident(TileRun &t, const ResidentPlan &plan, Resident *verdict, int *
     HostRead hr_(t.stream);
     TM_TRY(hr_.get(&q, t.quiet, 4));
     TM_TRY(hr_.get(&timed_out, &hs_dev->timeout, 4));
+    if (host_seg) TM_TRY(hr_.get(host_seg, t.ds, sizeof(Seg)));  // (what the caller would read straight behind this: one round trip for both)
+    if (host_look && t.look) TM_TRY(hr_.get(host_look, t.look, 16));
 #if TM_KMR_STAMPS
     TM_TRY(hr_.get(stamps.data(), hs_dev->stamps, stamps.size() * 8));
     TM_TRY(hr_.get(hlog.data(), hs_dev->log, hlog.size() * 4));

@@ -257,6 +257,24 @@ __global__ void k_apply_lut(const int32_t *__restrict__ assign, int64_t n, const
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = lut[assign[i]];
 }
 
+// the ranking of up to RANK_DEV_MAX counts by one workgroup: lut[i] = the number of j with cnt[j] > cnt[i], or cnt[j] == cnt[i] and j < i --
+// descending, ties in the initial order, which is the position a stable sort gives i
+constexpr int RANK_DEV_MAX = 1024;
+__global__ __launch_bounds__(RANK_DEV_MAX) void k_rank_counts(const u64 *__restrict__ cnt, int npal, int32_t *__restrict__ lut) {
+  __shared__ u64 s_c[RANK_DEV_MAX];
+  const int i = threadIdx.x;
+  if (i < npal) s_c[i] = cnt[i];
+  __syncthreads();
+  if (i >= npal) return;
+  const u64 c = s_c[i];
+  int before = 0;
+  for (int j = 0; j < npal; j++) {
+    const u64 o = s_c[j];
+    before += (o > c || (o == c && j < i)) ? 1 : 0;
+  }
+  lut[i] = before;
+}
+
 // palettes ranked by number of tiles (over all processes when `co` is given), descending (tilingencoder.pas:4229-4234); ties keep the initial order
 static int rank_palettes(const int32_t *assign, int64_t n, int npal, const Collectives *co, int32_t *out_pal_idx, hipStream_t stream) {
   DevBuf cnt, lut;
@@ -264,6 +282,12 @@ static int rank_palettes(const int32_t *assign, int64_t n, int npal, const Colle
   TM_HIP(hipMemsetAsync(cnt.p, 0, (size_t)npal * 8, stream));
   if (n > 0)
     hipLaunchKernelGGL(k_count_assign, dim3((int)std::min<int64_t>((n + 255) / 256, 512)), dim3(256), npal <= 8192 ? (size_t)npal * 4 : 0, stream, assign, n, npal, cnt.as<u64>());
+  if (!co && npal <= RANK_DEV_MAX) {  // the host is not asked: no read, no upload, nothing to wait for (cnt and lut go back to the pool, stream-ordered)
+    hipLaunchKernelGGL(k_rank_counts, dim3(1), dim3(RANK_DEV_MAX), 0, stream, cnt.as<u64>(), npal, lut.as<int32_t>());
+    if (n > 0) hipLaunchKernelGGL(k_apply_lut, dim3((int)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), 0, stream, assign, n, lut.as<int32_t>(), out_pal_idx);
+    TM_HIP(hipGetLastError());
+    return TM_OK;
+  }
   if (co) {
     TM_HIP(hipGetLastError());
     TM_TRY(co->allreduce_sum_i64(cnt.p, npal));
@@ -281,7 +305,7 @@ static int rank_palettes(const int32_t *assign, int64_t n, int npal, const Colle
   TM_HIP(hipMemcpyAsync(lut.p, hl.data(), (size_t)npal * 4, hipMemcpyHostToDevice, stream));
   if (n > 0) hipLaunchKernelGGL(k_apply_lut, dim3((int)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), 0, stream, assign, n, lut.as<int32_t>(), out_pal_idx);
   TM_HIP(hipGetLastError());
-  TM_HIP(hipStreamSynchronize(stream));
+  TM_HIP(host_sync(stream));  // hl, the upload's source, is on this frame: the copy must have read it before the frame goes
   return TM_OK;
 }
 
@@ -432,7 +456,7 @@ int run_palettize_dist(const void *feat_local, const void *use_local, int64_t n,
     h0.rng = PP_SEED;
     TM_HIP(hipMemcpyAsync(ppstate.p, &h0, sizeof(h0), hipMemcpyHostToDevice, stream));
     TM_HIP(hipMemsetAsync(bsum.p, 0, sizeof(PpSum) * (size_t)nb, stream));
-    TM_HIP(hipStreamSynchronize(stream));  // h0 is on the stack
+    TM_HIP(host_sync(stream));  // h0 is on the stack
   }
   FfCand *cd = cand.as<FfCand>();
   for (int c = 0; c < k; c++) {
@@ -496,30 +520,72 @@ int run_palettize_dist(const void *feat_local, const void *use_local, int64_t n,
 
 // ---- QuantizeUsingYakmo + DoQuantization -----------------------------------------------------------------------
 // pixel key = palette << 24 | G << 16 | R << 8 | B  (CompareDSPixel: G, then R, then B; tilingencoder.pas:1046-1056)
-__global__ void k_pixel_keys(const uint32_t *__restrict__ tiles, const int32_t *__restrict__ pal_idx, int64_t n, u64 *__restrict__ keys) {
+#ifndef TM_PP_WIDE_KEYS
+#define TM_PP_WIDE_KEYS 0  // 1 (tools/build_variant.sh NAME -DTM_PP_WIDE_KEYS=1): 64-bit keys at every PaletteCount, to measure the key width alone
+#endif
+// Key: uint32_t while the palette number fits the 8 bits above the colour (PaletteCount <= 256), else u64.  Every pass over the keys -- this
+// kernel's writes, the sort's histogram and passes, the run lengths -- is bound by their bytes.  A palette number outside 0..npal-1 (negative
+// ones included) raises *bad: a 32-bit key would carry it modulo 256.
+template <class Key>
+__global__ void k_pixel_keys(const uint32_t *__restrict__ tiles, const int32_t *__restrict__ pal_idx, int64_t n, int npal, Key *__restrict__ keys, int *__restrict__ bad) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n * 64; i += (int64_t)gridDim.x * blockDim.x) {
     const uint32_t c = tiles[i];
-    const u64 p = (u64)(uint32_t)pal_idx[i >> 6];
-    keys[i] = (p << 24) | ((u64)((c >> 8) & 0xff) << 16) | ((u64)(c & 0xff) << 8) | (u64)((c >> 16) & 0xff);
+    const uint32_t p = (uint32_t)pal_idx[i >> 6];
+    if (p >= (uint32_t)npal) *bad = 1;
+    keys[i] = (Key)((Key)p << 24) | (Key)(((c >> 8) & 0xff) << 16 | (c & 0xff) << 8 | ((c >> 16) & 0xff));
   }
 }
-__global__ void k_palette_bounds(const u64 *__restrict__ ukeys, int64_t nu, int npal, long long *__restrict__ lb) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;  // lb[p] = first unique key whose palette field is >= p; lb[npal] = first >= npal
+// head[p] = first unique key whose palette field is >= p, for p = 0..npal (head[npal]: first >= npal); the number of unique keys is read
+// from the device (the low word of head[npal + 1], where the run-length pass left it)
+template <class Key>
+__global__ void k_palette_bounds(const Key *__restrict__ ukeys, int npal, long long *__restrict__ head) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p > npal) return;
-  int64_t lo = 0, hi = nu;
+  int64_t lo = 0, hi = (int64_t)*reinterpret_cast<const unsigned int *>(head + npal + 1);
   while (lo < hi) {
     const int64_t mid = (lo + hi) >> 1;
     if ((long long)(ukeys[mid] >> 24) < (long long)p) lo = mid + 1; else hi = mid;
   }
-  lb[p] = lo;
+  head[p] = lo;
 }
-__global__ void k_unpack_colours(const u64 *__restrict__ ukeys, int64_t nu, int32_t *__restrict__ pts) {
+// the unique keys as points (R, G, B) and, where Dither is to have them (wide != null), as the u64 list palette << 24 | colour it reads
+template <class Key>
+__global__ void k_unpack_colours(const Key *__restrict__ ukeys, int64_t nu, int32_t *__restrict__ pts, u64 *__restrict__ wide) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nu; i += (int64_t)gridDim.x * blockDim.x) {
-    const u64 kx = ukeys[i];
+    const Key kx = ukeys[i];
     pts[i * 3 + 0] = (int32_t)((kx >> 8) & 0xff);   // R
     pts[i * 3 + 1] = (int32_t)((kx >> 16) & 0xff);  // G
     pts[i * 3 + 2] = (int32_t)(kx & 0xff);          // B
+    if (wide) wide[i] = (u64)kx;
   }
+}
+
+// The colour keys of all pixels, sorted and run-length-encoded, and the palettes' bounds in them: everything in front of the one read.
+// head (device): lb[0..npal], then the number of unique keys and the bad-palette flag, a long long each.
+struct ColourRuns { DevBuf ukeys, ucnt, head; };
+template <class Key>
+static int colour_runs(const uint32_t *tiles, const int32_t *pal_idx, int64_t n, int npal, int key_bits, hipStream_t stream, ColourRuns &r) {
+  const int64_t npx = n * 64;
+  DevBuf keys, keys2, tmp;  // (back to the pool at the return: what is queued on this stream after them is ordered behind their last use)
+  TM_TRY(keys.alloc(npx * sizeof(Key))); TM_TRY(keys2.alloc(npx * sizeof(Key))); TM_TRY(r.ukeys.alloc(npx * sizeof(Key))); TM_TRY(r.ucnt.alloc(npx * 4));
+  TM_TRY(r.head.alloc((size_t)(npal + 3) * 8));
+  long long *head = r.head.as<long long>();
+  TM_HIP(hipMemsetAsync(head + npal + 1, 0, 16, stream));
+  hipLaunchKernelGGL(k_pixel_keys<Key>, dim3((int)std::min<int64_t>((npx + 255) / 256, 4096)), dim3(256), 0, stream, tiles, pal_idx, n, npal, keys.as<Key>(),
+                     reinterpret_cast<int *>(head + npal + 2));
+  TM_TRY(with_temp(tmp, "palettes: radix sort of the pixel keys", [&](void *t, size_t &b) {
+    return rocprim::radix_sort_keys(t, b, keys.as<Key>(), keys2.as<Key>(), (size_t)npx, 0, key_bits, stream);
+  }));
+  TM_TRY(with_temp(tmp, "palettes: run lengths of the pixel keys", [&](void *t, size_t &b) {
+    return rocprim::run_length_encode(t, b, keys2.as<Key>(), (unsigned int)npx, r.ukeys.as<Key>(), r.ucnt.as<uint32_t>(), reinterpret_cast<unsigned int *>(head + npal + 1), stream);
+  }));
+  hipLaunchKernelGGL(k_palette_bounds<Key>, dim3((npal + 1 + 63) / 64), dim3(64), 0, stream, r.ukeys.as<Key>(), npal, head);
+  TM_HIP(hipGetLastError());
+  return TM_OK;
+}
+template <class Key>
+static void unpack_colours(const ColourRuns &r, int64_t nu, int32_t *pts, u64 *wide, hipStream_t stream) {
+  hipLaunchKernelGGL(k_unpack_colours<Key>, dim3((int)std::min<int64_t>((nu + 255) / 256, 4096)), dim3(256), 0, stream, r.ukeys.as<Key>(), nu, pts, wide);
 }
 
 static int muldiv_win(int a, int b, int c) {  // Windows MulDiv: round half away from zero
@@ -542,80 +608,64 @@ static void rgb_to_hsv_bytes(int rr, int gg, int bb, int &h, int &s, int &v) {  
 }
 
 int run_quantize_palettes(const void *tiles, const void *pal_idx, int64_t n, int npal, int pal_size, int max_iter, void *out_palettes,
-                          hipStream_t stream, DevBuf *keep_keys, int64_t *keep_n) {
-  return run_quantize_palettes_part(tiles, pal_idx, n, npal, pal_size, max_iter, out_palettes, 0, 1, stream, keep_keys, keep_n);
+                          hipStream_t stream, DevBuf *keep_keys, int64_t *keep_n, int32_t *host_palettes) {
+  return run_quantize_palettes_part(tiles, pal_idx, n, npal, pal_size, max_iter, out_palettes, 0, 1, stream, keep_keys, keep_n, host_palettes);
 }
 
 int run_quantize_palettes_part(const void *tiles, const void *pal_idx, int64_t n, int npal, int pal_size, int max_iter, void *out_palettes,
-                               int pal_rank, int pal_world, hipStream_t stream, DevBuf *keep_keys, int64_t *keep_n) {
+                               int pal_rank, int pal_world, hipStream_t stream, DevBuf *keep_keys, int64_t *keep_n, int32_t *host_palettes) {
   TM_TRY(require_device());
+  TM_CHECK(out_palettes || host_palettes, TM_E_INVAL, "quantize: no destination for the palettes");
   if (keep_n) *keep_n = 0;
   TM_CHECK(pal_world >= 1 && pal_rank >= 0 && pal_rank < pal_world, TM_E_INVAL, "quantize: bad palette share %d of %d", pal_rank, pal_world);
   TM_CHECK(npal >= 1 && npal <= 65536, TM_E_INVAL, "PaletteCount %d outside 1..65536", npal);
   TM_CHECK(pal_size >= 2 && pal_size <= 64, TM_E_INVAL, "PaletteSize %d outside 2..64 (tilingencoder.pas:2965)", pal_size);
   std::vector<int32_t> hpal((size_t)npal * pal_size, TM_NULL_COLOR);  // unused slots: cDitheringNullColor (4557-4558)
   if (n > 0) {
-    const int64_t npx = n * 64;
-    DevBuf keys, keys2, ukeys, ucnt, nruns, tmp, pts, assign, cent;
-    TM_TRY(keys.alloc(npx * 8)); TM_TRY(keys2.alloc(npx * 8)); TM_TRY(ukeys.alloc(npx * 8)); TM_TRY(ucnt.alloc(npx * 4));
-    TM_TRY(nruns.alloc(8));
-    hipLaunchKernelGGL(k_pixel_keys, dim3((int)std::min<int64_t>((npx + 255) / 256, 4096)), dim3(256), 0, stream, (const uint32_t *)tiles,
-                       (const int32_t *)pal_idx, n, keys.as<u64>());
+    const bool dbg = knobs().pp_debug;
+    if (dbg) (void)hipStreamSynchronize(stream);
+    const auto t_km = std::chrono::steady_clock::now();
     int key_bits = 25;  // 24 bits of colour + the palette number's: every 8 bits less is a pass over all pixels less
     while (key_bits < 41 && (1ll << (key_bits - 24)) < npal) key_bits++;
-    TM_TRY(with_temp(tmp, "palettes: radix sort of the pixel keys", [&](void *t, size_t &b) {
-      return rocprim::radix_sort_keys(t, b, keys.as<u64>(), keys2.as<u64>(), (size_t)npx, 0, key_bits, stream);
-    }));
-    TM_TRY(with_temp(tmp, "palettes: run lengths of the pixel keys", [&](void *t, size_t &b) {
-      return rocprim::run_length_encode(t, b, keys2.as<u64>(), (unsigned int)npx, ukeys.as<u64>(), ucnt.as<uint32_t>(), nruns.as<unsigned int>(), stream);
-    }));
-    unsigned int nu = 0;
+    const bool narrow = key_bits <= 32 && !TM_PP_WIDE_KEYS;  // PaletteCount <= 256: 32-bit keys
+    ColourRuns runs;
+    DevBuf pts, assign, cent, wide;
+    TM_TRY(narrow ? colour_runs<uint32_t>((const uint32_t *)tiles, (const int32_t *)pal_idx, n, npal, key_bits, stream, runs)
+                  : colour_runs<u64>((const uint32_t *)tiles, (const int32_t *)pal_idx, n, npal, key_bits, stream, runs));
+    // the one read: the palettes' bounds in the unique keys, their number, and the flag of a palette number out of range
+    std::vector<long long> lb((size_t)npal + 3);
     {
       HostRead hr_(stream);
-      TM_TRY(hr_.get(&nu, nruns.p, 4));
+      TM_TRY(hr_.get(lb.data(), runs.head.p, lb.size() * 8));
       TM_TRY(hr_.wait());
     }
-    // segment boundaries per palette: lower bound of each palette number in the sorted unique keys, found on the device
-    DevBuf dlb;
-    TM_TRY(dlb.alloc((size_t)(npal + 1) * 8));
-    hipLaunchKernelGGL(k_palette_bounds, dim3((npal + 1 + 63) / 64), dim3(64), 0, stream, ukeys.as<u64>(), (int64_t)nu, npal, dlb.as<long long>());
-    std::vector<long long> lb((size_t)npal + 1);
-    {
-      HostRead hr_(stream);
-      TM_TRY(hr_.get(lb.data(), dlb.p, lb.size() * 8));
-      TM_TRY(hr_.wait());
-    }
+    const unsigned int nu = (unsigned int)lb[(size_t)npal + 1];
+    TM_CHECK(lb[(size_t)npal + 2] == 0 && lb[npal] == (long long)nu, TM_E_INVAL, "quantize: a tile names palette >= PaletteCount");
     std::vector<int64_t> sb(npal, 0), sc(npal, 0);
-    {
-      for (int p = 0; p < npal; p++) { sb[p] = lb[p]; sc[p] = p % pal_world == pal_rank ? lb[p + 1] - lb[p] : 0; }  // other processes' palettes: empty segments
-      TM_CHECK(lb[npal] == (long long)nu, TM_E_INVAL, "quantize: a tile names palette >= PaletteCount");
-    }
+    for (int p = 0; p < npal; p++) { sb[p] = lb[p]; sc[p] = p % pal_world == pal_rank ? lb[p + 1] - lb[p] : 0; }  // other processes' palettes: empty segments
     TM_TRY(pts.alloc((size_t)std::max<unsigned>(nu, 1) * 12));
     TM_TRY(assign.alloc((size_t)std::max<unsigned>(nu, 1) * 4));
     TM_TRY(cent.alloc((size_t)npal * pal_size * 3 * 8));
-    hipLaunchKernelGGL(k_unpack_colours, dim3((int)std::min<int64_t>(((int64_t)nu + 255) / 256, 4096)), dim3(256), 0, stream,
-                       ukeys.as<u64>(), (int64_t)nu, pts.as<int32_t>());
+    const bool keep = keep_keys && keep_n;
+    if (narrow) {  // Dither reads u64 keys: the unpacking pass, which reads every unique key anyway, writes them out as such
+      if (keep) TM_TRY(wide.alloc((size_t)std::max<unsigned>(nu, 1) * 8));
+      unpack_colours<uint32_t>(runs, (int64_t)nu, pts.as<int32_t>(), keep ? wide.as<u64>() : nullptr, stream);
+    } else {
+      unpack_colours<u64>(runs, (int64_t)nu, pts.as<int32_t>(), nullptr, stream);
+    }
     std::vector<int> kk;
     int iters = 0;
-    const bool dbg = knobs().pp_debug;
-    const auto t_km = std::chrono::steady_clock::now();
-    if (dbg) (void)hipStreamSynchronize(stream);
     const auto t_km0 = std::chrono::steady_clock::now();
     kmeans_run_stats().pixel_colour_iters = 0;
-    TM_TRY(kmeans_batched(pts.as<int32_t>(), ucnt.as<uint32_t>(), 3, sb, sc, pal_size, max_iter, assign.as<int32_t>(), cent.as<double>(),
-                          &kk, &iters, stream));
+    std::vector<double> hc((size_t)npal * pal_size * 3);  // the centroids come to the host with the clustering's own read and stay here
+    TM_TRY(kmeans_batched(pts.as<int32_t>(), runs.ucnt.as<uint32_t>(), 3, sb, sc, pal_size, max_iter, assign.as<int32_t>(), cent.as<double>(),
+                          &kk, &iters, stream, nullptr, nullptr, hc.data()));
     kmeans_run_stats().pixel_iters = iters;  // (pixel_colour_iters: summed by the persistent launch, reset before it below)
     kmeans_run_stats().pixel_colours = (int64_t)nu;
     kmeans_run_stats().pixels = n * 64;
     if (dbg) fprintf(stderr, "[tm_pp]   colour keys + sort + runs %7.3f ms, k-means of %u colours %7.3f ms (%d iterations)\n",
                      std::chrono::duration<double, std::milli>(t_km0 - t_km).count() , nu,
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_km0).count(), iters);
-    std::vector<double> hc((size_t)npal * pal_size * 3);
-    {
-      HostRead hr_(stream);
-      TM_TRY(hr_.get(hc.data(), cent.p, hc.size() * 8));
-      TM_TRY(hr_.wait());
-    }
     // host tail (P x PaletteSize colours): Round, clamp, Posterize(.,255) = identity, sort by (Val, Sat, Hue)
     // -- tilingencoder.pas:4513-4558, utils.pas:526-534, 741-748
     struct Item { int v, s, h, r, g, b, idx; };
@@ -642,14 +692,18 @@ int run_quantize_palettes_part(const void *tiles, const void *pal_idx, int64_t n
       });
       for (size_t i = 0; i < items.size(); i++) hpal[(size_t)p * pal_size + i] = (items[i].b << 16) | (items[i].g << 8) | items[i].r;
     }
-    if (keep_keys && keep_n) { *keep_keys = std::move(ukeys); *keep_n = (int64_t)nu; }
+    if (keep) { *keep_keys = std::move(narrow ? wide : runs.ukeys); *keep_n = (int64_t)nu; }
   }
   if (pal_world > 1)
     for (int p = 0; p < npal; p++)
       if (p % pal_world != pal_rank)
         for (int i = 0; i < pal_size; i++) hpal[(size_t)p * pal_size + i] = 0;
+  if (host_palettes) {  // the caller goes on with the palettes on the host: nothing to upload, nothing to wait for
+    memcpy(host_palettes, hpal.data(), hpal.size() * 4);
+    return TM_OK;
+  }
   TM_HIP(hipMemcpyAsync(out_palettes, hpal.data(), hpal.size() * 4, hipMemcpyHostToDevice, stream));
-  TM_HIP(hipStreamSynchronize(stream));
+  TM_HIP(host_sync(stream));  // hpal, the upload's source, is on this frame: the copy must have read it before the frame goes
   return TM_OK;
 }
 

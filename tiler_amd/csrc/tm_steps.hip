@@ -259,7 +259,7 @@ static int step_load(tm_encoder *e) {  // Load, tilingencoder.pas:1741-1841 (fra
       for (int i = 0; i < 2; i++)
         if (!e->hclip[i].pending && (slot < 0 || i != e->hclip_cur)) slot = i;
       if (slot < 0) slot = e->hclip[0].seq < e->hclip[1].seq ? 0 : 1;
-      TM_HIP(hipStreamSynchronize(e->stream));       // the destination may have been handed out by the pool a moment ago
+      TM_HIP(host_sync(e->stream));       // the destination may have been handed out by the pool a moment ago
       TM_TRY(queue_host_clip(e, slot, e->frames_host));
     }
     tm_encoder::HostClip &hc = e->hclip[slot];
@@ -314,7 +314,7 @@ static int step_load(tm_encoder *e) {  // Load, tilingencoder.pas:1741-1841 (fra
     if (lo < f0) TM_HIP(hipMemsetAsync(dcorrel.as<uint8_t>() + lo * 12, 0, 12, e->stream));
     TM_TRY(e->co.allreduce_sum_i32(dcorrel.p, (int64_t)e->nframes * 3));  // owner holds the float, everyone else +0.0: exact
     TM_TRY(e->co.allreduce_sum_i32(e->fflags.p, (e->q + 3) / 4));
-    TM_HIP(hipStreamSynchronize(e->stream));
+    TM_HIP(host_sync(e->stream));
     e->load_tail_pending = true;
     TM_TRY(load_tail(e, e->stream));  // (the sums sit behind the encoder's own stream here)
   } else {
@@ -336,7 +336,7 @@ static int step_load(tm_encoder *e) {  // Load, tilingencoder.pas:1741-1841 (fra
   TM_HIP(hipMemsetAsync(e->tm_err.p, 0xff, (size_t)e->q * 4, e->stream));
   e->t = 0;
   e->has_pal_px = e->reconstructed = e->has_pm = false;
-  TM_HIP(hipStreamSynchronize(e->stream));  // Run(esLoad) is blocking for everything but the correlation above (and the stage times stay the stages')
+  TM_HIP(host_sync(e->stream));  // Run(esLoad) is blocking for everything but the correlation above (and the stage times stay the stages')
   std::vector<uint32_t>().swap(e->input_clip);  // (a PNG sequence's host copy: the device holds it now)
   progress(e, TM_STEP_LOAD, 3, 3);
   return TM_OK;
@@ -376,7 +376,7 @@ static int step_predict_motion(tm_encoder *e) {
     for (int f = sn; f < e->nframes; f++)
       if ((f & 15) == 15) progress(e, TM_STEP_PREDICT_MOTION, f, e->nframes);
   if (e->dist()) TM_TRY(merge_items(e, TMA_PM_ERR | TMA_PX | TMA_PY));
-  TM_HIP(hipStreamSynchronize(e->stream));
+  TM_HIP(host_sync(e->stream));
   e->has_pm = true;
   e->reconstructed = false;
   progress(e, TM_STEP_PREDICT_MOTION, e->nframes, e->nframes);
@@ -432,20 +432,21 @@ static int step_prepare_palettes(tm_encoder *e) {  // PreparePalettes, tilingenc
     lap("tile -> palette (192-D, data-parallel)");
   }
   progress(e, TM_STEP_PREPARE_PALETTES, 1, 3);
+  e->palettes_host.resize((size_t)e->s.PaletteCount * e->s.PaletteSize);
   if (e->dist()) {
     TM_TRY(run_quantize_palettes_part(e->gtiles.p, e->gpal_idx.p, e->t, e->s.PaletteCount, e->s.PaletteSize, 300, e->palettes_dev.p, e->co.rank, e->co.world, e->stream));
     TM_TRY(e->co.allreduce_sum_i32(e->palettes_dev.p, (int64_t)e->s.PaletteCount * e->s.PaletteSize));
     lap("palette colours (3-D, own palettes)");
-  } else {
-    TM_TRY(run_quantize_palettes(e->gtiles.p, e->gpal_idx.p, e->t, e->s.PaletteCount, e->s.PaletteSize, 300, e->palettes_dev.p, e->stream, &e->pair_keys, &e->pair_keys_n));
-    e->km_stats = kmeans_run_stats();
-    lap("palette colours (3-D)");
-  }
-  e->palettes_host.resize((size_t)e->s.PaletteCount * e->s.PaletteSize);
-  {
     HostRead hr_(e->stream);
     TM_TRY(hr_.get(e->palettes_host.data(), e->palettes_dev.p, e->palettes_host.size() * 4));
     TM_TRY(hr_.wait());
+  } else {
+    // the quantisation ends on the host and OptimizePalettes goes on there: the palettes stay in palettes_host, and palettes_dev is written
+    // once, below
+    TM_TRY(run_quantize_palettes(e->gtiles.p, e->gpal_idx.p, e->t, e->s.PaletteCount, e->s.PaletteSize, 300, nullptr, e->stream, &e->pair_keys, &e->pair_keys_n,
+                                 e->palettes_host.data()));
+    e->km_stats = kmeans_run_stats();
+    lap("palette colours (3-D)");
   }
   progress(e, TM_STEP_PREPARE_PALETTES, 2, 3);
   TM_TRY(prefetch_query_features(e));  // the GPU has nothing to do while the host searches: Reconstruct's query features run now
@@ -453,8 +454,9 @@ static int step_prepare_palettes(tm_encoder *e) {  // PreparePalettes, tilingenc
   // OptimizePalettes (4309-4432): slot permutation by Powell on the host (P x PaletteSize colours)
   TM_TRY(optimize_palettes_host(e->palettes_host, e->s.PaletteCount, e->s.PaletteSize, nullptr));
   lap("OptimizePalettes (host)");
+  // (the source is an encoder member and outlives the copy; the wait ends the step: Run(esPreparePalettes) is blocking like the other steps)
   TM_HIP(hipMemcpyAsync(e->palettes_dev.p, e->palettes_host.data(), e->palettes_host.size() * 4, hipMemcpyHostToDevice, e->stream));
-  TM_HIP(hipStreamSynchronize(e->stream));
+  TM_HIP(host_sync(e->stream));
   progress(e, TM_STEP_PREPARE_PALETTES, 3, 3);
   return TM_OK;
 }
@@ -472,7 +474,7 @@ static int step_dither(tm_encoder *e) {  // Dither, tilingencoder.pas:1873-1907
                          e->gpal_px.as<uint8_t>() + t0 * 64, e->stream, &e->dither_pairs, e->pair_keys_n > 0 && !knobs().dither_own_keys ? e->pair_keys.p : nullptr,
                          e->pair_keys_n));
   if (e->dist() && e->dither_world > 1) TM_TRY(e->co.allreduce_sum_i32(e->gpal_px.p, e->t * 16));  // 64 bytes per tile = 16 words; other shares hold 0
-  TM_HIP(hipStreamSynchronize(e->stream));
+  TM_HIP(host_sync(e->stream));
   e->has_pal_px = true;
   progress(e, TM_STEP_DITHER, 2, 2);
   return TM_OK;
@@ -504,7 +506,7 @@ static int step_reindex(tm_encoder *e) {  // Reindex, tilingencoder.pas:1993-203
   TM_TRY(gather<uint8_t>(e, e->gflags.p, order.p, nu, nflags.p));
   TM_TRY(gather<int32_t>(e, e->gpal_idx.p, order.p, nu, npal_idx.p));
   TM_TRY(lookup(e, e->tm_tile.p, e->q, remap.p, ntm.p));
-  TM_HIP(hipStreamSynchronize(e->stream));
+  TM_HIP(host_sync(e->stream));
   e->pair_keys_n = 0;
   e->gtiles = std::move(ntiles); e->gflags = std::move(nflags); e->gpal_idx = std::move(npal_idx); e->gpal_px = std::move(npal_px);
   e->tm_tile = std::move(ntm);
@@ -546,7 +548,7 @@ int tm_sync_tilemap(tm_encoder *e) {  // after shards were merged: TMI^.PalIdx :
   if (e->s.FrameTilingExtendedPaletteUsage) return TM_OK;  // the item's palette is the re-rank's choice: merged like TileIdx (array 2)
   TM_HIP(hipSetDevice(e->device));
   TM_TRY(pal_from_tile(e));
-  TM_HIP(hipStreamSynchronize(e->stream));
+  TM_HIP(host_sync(e->stream));
   return TM_OK;
 }
 

@@ -1,5 +1,6 @@
 // tm_tables.hip -- constant tables of the reference + LUT construction, error state, device check.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -46,6 +47,13 @@ int *pinned_words() {
   return w;
 }
 
+static std::atomic<long long> g_host_waits{0};
+hipError_t host_sync(hipStream_t s) {
+  g_host_waits.fetch_add(1, std::memory_order_relaxed);
+  return hipStreamSynchronize(s);
+}
+long long host_waits() { return g_host_waits.load(std::memory_order_relaxed); }
+
 HostRead::HostRead(hipStream_t s) : stream(s) { t_pin.depth++; }
 HostRead::~HostRead() {
   // copies queued and never waited for (an error return between get() and wait()) may still be in flight into the thread's area: they
@@ -71,7 +79,7 @@ int HostRead::get(void *dst, const void *src, size_t bytes) {
   return TM_OK;
 }
 int HostRead::wait() {
-  TM_HIP(hipStreamSynchronize(stream));
+  TM_HIP(host_sync(stream));
   for (int i = 0; i < n; i++) memcpy(items[i].dst, t_pin.p + items[i].off, items[i].bytes);
   n = 0;
   return TM_OK;

@@ -334,6 +334,25 @@ def dedup(rows, use_in=None):
     return nu.value, remap, order[: nu.value], use[: nu.value]
 
 
+def dedup_by_index(rows):
+    """the grouping Reconstruct puts its database rows through: rows [n][row_bytes a multiple of 16] -> (n_unique, remap int32 [n] (position
+    of each row's first occurrence in order), order int32 [n_unique] (the first occurrences, ascending), use int32 [n_unique] (rows per group))"""
+    n = rows.shape[0]
+    row_bytes = rows.shape[1] * rows.element_size()
+    remap = torch.empty((n,), dtype=torch.int32, device=rows.device)
+    order = torch.empty((n,), dtype=torch.int32, device=rows.device)
+    use = torch.empty((n,), dtype=torch.int32, device=rows.device)
+    nu = ctypes.c_int64()
+    check(lib().tm_stage_dedup_by_index(_p(rows), n, row_bytes, _p(remap), _p(order), _p(use), ctypes.byref(nu), _stream()))
+    return nu.value, remap, order[: nu.value], use[: nu.value]
+
+
+def host_waits():
+    """how often the library has made the host wait for a stream so far in PreparePalettes and the dedup (small read-backs and the stream
+    synchronisations of those stages), over all threads"""
+    return int(lib().tm_host_waits())
+
+
 def kmeans(pts, weights, k, max_iter=300):
     """the build's deterministic k-means: pts int32 [n][d] -> (live_k, assign int32 [n], centroids float64 [k][d], iters)"""
     n, d = pts.shape
