@@ -1,4 +1,5 @@
-// tm_encoder.h -- the encoder object behind tm_create / tm_run, shared by tm_encoder.hip, the steps (tm_steps.h), tm_shard.hip and tm_export.hip.
+// tm_encoder.h -- the encoder object behind tm_create / tm_run, shared by tm_encoder.hip, the steps (tm_steps.h), tm_shard.hip, the input
+// side (tm_input.hip, tm_input_clip.hip, tm_input_files.hip) and what leaves the encoder (tm_gtm_api.hip, tm_render_api.hip, tm_export.hip).
 #pragma once
 #include <algorithm>
 #include <functional>
@@ -49,7 +50,7 @@ struct tm_encoder {
   // device state
   DevBuf frames_owned;
   const void *frames = nullptr;  // [nframes][height][width] RGB32
-  // the frame source "file" (tm_open_input): Load decodes InputFileName into a clip the encoder owns (tm_input.hip, tm_input.h)
+  // the frame source "file" (tm_open_input): Load decodes InputFileName into a clip the encoder owns (tm_input.hip and its two source files, tm_input.h)
   InputInfo input;
   int input_yuv = TM_YUV_AUTO;
   InputTables input_tables;
@@ -205,6 +206,19 @@ int queue_host_clip(tm_encoder *e, int slot, const void *host);
 
 // tm_input.hip
 int load_from_input(tm_encoder *e);
+// tm_input_clip.hip: frames [a, b) of a clip in memory or of a raw file into the encoder's device clip
+int decode_y4m(tm_encoder *e, int a, int b);
+int convert_yuv_clip(tm_encoder *e, int a, int b);
+int convert_rgb_clip(tm_encoder *e, int a, int b);
+int play_gtm(tm_encoder *e, int a, int b);
+// tm_input_files.hip: the same of coded files (decode_pngs: the whole sequence on the host, into input_clip), and where each kind is decoded
+int decode_pngs(tm_encoder *e);
+int decode_pngs_device(tm_encoder *e, int a, int b);
+int decode_jpegs(tm_encoder *e, int a, int b);
+int decode_gif(tm_encoder *e, int a, int b);
+int png_decode_where(const tm_encoder *e);
+int jpeg_decode_where(const tm_encoder *e);
+int gif_decode_where(const tm_encoder *e);
 
 // tm_shard.hip
 void share_of(int64_t n, int rank, int world, int64_t *lo, int64_t *hi);
@@ -215,9 +229,25 @@ void group_teardown(tm_encoder *e);
 struct Piece { int first = 0, count = 0; };
 std::vector<Piece> group_pieces(tm_encoder *e, int first, int count);
 
-// tm_export.hip
+// tm_gtm_api.hip
 int save_to(tm_encoder *e, const char *path);
-// what the device renders check and read (tm_render_frames and its kin there, the views of tm_render_view.hip); no device call
+
+// tm_render_api.hip
+// what the device renders check and read (tm_render_frames and its kin there, the exports, the views of tm_render_view.hip); no device call
 int render_range_ok(tm_encoder *e, int first, int count);
 int render_output_map(tm_encoder *e, RenderMap *m);
 int render_input_src(tm_encoder *e, int first, int count, RenderInput *in);
+// the source of a render: the source frames (input) or the decoded ones.  prepare makes the checks for frames [first, +count), draw launches
+struct RenderSource {
+  bool input = false;
+  RenderMap m{};
+  RenderInput in{};
+  int prepare(tm_encoder *e, int first, int count) { return input ? render_input_src(e, first, count, &in) : render_output_map(e, &m); }
+  int draw(int first, int nf, void *dst, hipStream_t stream) const {
+    return input ? launch_render_input(in, first, nf, dst, stream) : launch_render_output(m, first, nf, dst, stream);
+  }
+};
+// the frames a render chunk holds, of `frame_count` asked for: at most 32 frames or 256 MB of its larger frame, and at least one
+inline int render_chunk_frames(int frame_count, size_t frame_bytes) {
+  return (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(frame_count, 32), ((size_t)256 << 20) / frame_bytes));
+}

@@ -7,7 +7,7 @@
 // re-rank, OptimizePalettes, the .gtm writer and reader included); what stays outside the path is listed in DESIGN.md "Scope".
 //
 // This file: create / destroy, the settings and their INI text, the video and its frames, tm_run and the read-back views.  The steps are in
-// tm_steps.hip, tm_reduce.hip and tm_reconstruct.hip, the multi-GPU side in tm_shard.hip, Save / ReloadGTM / the exports / the device render entry points in tm_export.hip.
+// tm_steps.hip, tm_reduce.hip and tm_reconstruct.hip, the multi-GPU side in tm_shard.hip, Save / ReloadGTM in tm_gtm_api.hip, the device render entry points in tm_render_api.hip, the exports in tm_export.hip.
 #include <cmath>
 #include <fstream>
 #include <map>

@@ -183,7 +183,7 @@ int probe_input(const std::string &name, int start_frame, int frame_count, doubl
   TM_CHECK(start_frame >= 0, TM_E_INVAL, "StartFrame %d", start_frame);
   in->name = name;
   in->start = start_frame;
-  if (file_exists(name) && has_gtm_magic(name)) {  // a .gtm stream: its frames are played into the clip (play_gtm, tm_input.hip)
+  if (file_exists(name) && has_gtm_magic(name)) {  // a .gtm stream: its frames are played into the clip (play_gtm, tm_input_clip.hip)
     TM_CHECK(scaling == 1.0, TM_E_UNSUPPORTED, "%s: Scaling %g with a .gtm input (the resampler takes YUV planes; only Scaling = 1 is read)", name.c_str(), scaling);
     int total = 0;
     TM_TRY(probe_gtm(name.c_str(), &in->src_w, &in->src_h, &in->fps, &total));
@@ -193,7 +193,7 @@ int probe_input(const std::string &name, int start_frame, int frame_count, doubl
     in->dst_w = in->src_w; in->dst_h = in->src_h;
     return TM_OK;
   }
-  if (file_exists(name) && starts_with_gif(name)) {  // an animated GIF: its frames are decoded and composited into the clip (decode_gif, tm_input.hip)
+  if (file_exists(name) && starts_with_gif(name)) {  // an animated GIF: its frames are decoded and composited into the clip (decode_gif, tm_input_files.hip)
     TM_CHECK(scaling == 1.0, TM_E_UNSUPPORTED, "%s: Scaling %g with a GIF input (only Scaling = 1 is read)", name.c_str(), scaling);
     std::vector<uint8_t> file;
     TM_TRY(read_whole(name, &file));

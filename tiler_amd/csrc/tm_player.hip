@@ -7,7 +7,7 @@
 // Host side, per key frame: the stream is read, decoded and walked into fixed-size records (load_keyframe, tm_player_parse.hip).  A worker
 // thread does this for key frame k + 1 while key frame k plays (TM_PLAYER_NO_WORKER: on the calling thread, when k has been played).
 // Records go to the device in chunks of frames through two page-locked buffers on a copy stream; a StagingRing (tm_input.h) orders the
-// reuse of either, as in convert_staged (tm_input.hip).  The kernel is tm_play_frame.hip's.
+// reuse of either, as in convert_staged (tm_input_clip.hip).  The kernel is tm_play_frame.hip's.
 //
 // Memory, none of it a function of the clip's length beyond the GTMk index (28 bytes per key frame):
 //   host    the records of two key frames (playing + decoded ahead): frames_in_kf * tm_w * tm_h * 8 bytes + 64 per intra item;

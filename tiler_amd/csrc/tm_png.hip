@@ -1,5 +1,5 @@
 // tm_png.hip -- host only: the PNG reader behind a numbered PNG sequence (LoadInputVideo, tilingencoder.pas:3340-3353) and the inflate it
-// needs.  Like the LZMA coder of tm_lzma.hip and the PNG writer of tm_export.hip it links nothing: stored, fixed and dynamic Huffman
+// needs.  Like the LZMA coder of tm_lzma.hip and the PNG writer of tm_deflate.hip it links nothing: stored, fixed and dynamic Huffman
 // blocks (RFC 1951), the zlib wrapper with its Adler-32 (RFC 1950), chunk CRCs and the five row filters (PNG 1.2, sections 3, 6).
 // Every read is checked against the end of its buffer; a stream that is cut short or damaged is refused, never followed.
 #include "tm_common.h"
@@ -93,7 +93,7 @@ uint32_t be32(const uint8_t *p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] <
 
 }  // namespace
 
-// the CRC of PNG chunks (and of zip, gzip: polynomial 0xEDB88320), for the reader here and the writer in tm_export.hip
+// the CRC of PNG chunks (and of zip, gzip: polynomial 0xEDB88320), for the reader here and the writer in tm_deflate.hip
 uint32_t crc32_ieee(const uint8_t *p, size_t n) {
   struct Table { uint32_t v[256]; };
   static const Table tb = [] {

@@ -1,6 +1,6 @@
 // tm_render.hip -- the decoded frames on the device and their pixel-domain quality (PSNR, SSIM on luma) against the source.
 //
-// Render (tilingencoder.pas:3455-3640) with the constructor's defaults, the pictures GenerateY4M / GeneratePNGs export (tm_export.hip):
+// Render (tilingencoder.pas:3455-3640) with the constructor's defaults, the pictures GenerateY4M / GeneratePNGs export (tm_export.hip; handed to a caller by tm_render_api.hip):
 // a predicted item copies 8 x 8 pixels of the previous output frame at its (clamped) offset, any other item is its palette-index tile
 // (mirrored) looked up in its palette.  Pixels are 0x00RRGGBB, the format frames are pushed in.
 //

@@ -212,7 +212,7 @@ int queue_host_clip(tm_encoder *e, int slot, const void *host) {
   return TM_OK;
 }
 
-static int step_load(tm_encoder *e) {  // Load, tilingencoder.pas:1741-1841 (frames are pushed in, or decoded from InputFileName: tm_input.hip)
+static int step_load(tm_encoder *e) {  // Load, tilingencoder.pas:1741-1841 (frames are pushed in, or decoded from InputFileName: load_from_input, tm_input.hip)
   TM_TRY(load_tail(e));  // (a correlation still running reads the Lab means this Load is about to replace)
   e->drop_prefetch();  // features of the previous frame tiles
   e->q_groups = 0;
